@@ -15,6 +15,15 @@ last, longest waves, overlaps the start of the next; 1 / 2 / 3 / 4 in flight: 2 
 One-time initialisation (code-object load, APP_CLOUDS' y table, first submission on each stream, first touch of the
 framebuffers, RCCL peer set-up) happens once before the W warm-up steps and is not a step.
 
+A plain N = 1 run (`python bench.py --gpus 1 --steps K --warmup W`) does only what `value` needs: set-up, pre-roll, the W warm-up
+steps, the K timed steps, --dump-outputs if given, the line (metric, value, unit, ms_per_step, higher_is_better, dtype, config,
+kernel_ms_in_timed_region).  `--full` adds the rest of the N = 1 record below: the pipelined region, steady_state, serial, roofline
+(with its rocprofv3 passes), sustained, the CPU baselines with parity, other_configs.  The N > 1, --engine lib and --emulate-ranks
+forms are unchanged by it.
+`--dump-outputs DIR` writes the frame of the last timed step (N > 1: the assembled frame on rank 0) as DIR/frame.npy, float32
+[rows, W, 4], row 0 = bottom: all rows when the frame is at most 32 MB, else a fixed, seeded choice of whole rows, whose indices are
+DIR/frame_rows.npy (float64).  The inputs are the same in every run with the same arguments, so two builds compare file for file.
+
 N = 1 : the frame is one kernel launch.
 N > 1 : one process per GPU (torch.distributed / RCCL; `--exchange auto` = shaderbox_amd.tuning.choose_exchange: the RCCL forms — span
         exchange, whole slabs — and, where allowed, the store forms are tried on the ranks at hand within --trial-budget-s and the fastest
@@ -91,8 +100,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from sbxbench.common import (DIST_OTHER_CONFIGS, KERNEL_OF, OPS_PER_PIXEL, OTHER_CONFIGS, claim_stdout, launch_check, parity,  # noqa: E402,F401
-                             self_launch, steady_state)
+from sbxbench.common import (DIST_OTHER_CONFIGS, KERNEL_OF, OPS_PER_PIXEL, OTHER_CONFIGS, claim_stdout, frame_sample,  # noqa: E402,F401
+                             launch_check, parity, self_launch, steady_state, write_outputs)
 from sbxbench.cpu import cpu_baseline, cpu_baseline_port, cpu_baseline_speed, cpu_rows, host_cpu_facts  # noqa: E402,F401
 from sbxbench.pmc import pmc_committed, pmc_counters, rooflines, run_pmc_pass  # noqa: E402,F401
 
@@ -196,6 +205,14 @@ def main():
     ap.add_argument("--trial-budget-s", type=float, default=20.0,
                     help="N>1, --exchange auto: wall time (rank 0's clock) after which no further exchange form is tried, per config "
                          "(three configs: at most ~60 s; the first form always runs; what was cut is in exchange.notes)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: everything beside the headline — the pipelined region, the un-overlapped kernel time, the roofline "
+                         "and its rocprofv3 passes, the sustained leg, the CPU baselines and the parity rows, the other BASELINE "
+                         "configs.  Without it a run sets up, warms up, times the --steps frames and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame of the last timed step as DIR/frame.npy (float32 [rows, W, 4]: "
+                         "the whole frame, or a fixed seeded choice of whole rows when it is over 32 MB) and the row indices as "
+                         "DIR/frame_rows.npy (float64)")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -211,6 +228,8 @@ def main():
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher of N ranks (the driver's command shape at N = 1, 2, 4, 8)
         sys.exit(self_launch(args, sys.argv[1:]))
+    if args.dump_outputs and (args.engine == "lib" and args.gpus > 1 or args.emulate_ranks > 1):
+        raise SystemExit("--dump-outputs writes the frame of the N = 1 run or of the one-process-per-GPU ranks (rank 0)")
     if args.launch_check:
         claim_stdout()
         sys.exit(launch_check(args))
@@ -288,6 +307,8 @@ def main():
                 out["parity"]["oracle"] = par
                 if not (par["max_abs_diff"] <= 1e-4):
                     status = 3
+        if rank == 0 and args.dump_outputs:                # the assembled frame of the last timed step
+            write_outputs(args.dump_outputs, frame_sample(res["frame"]))
         res.pop("frame", None)
         res.pop("plans", None)
         torch.cuda.empty_cache()

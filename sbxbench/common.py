@@ -106,6 +106,30 @@ def steady_state(step_done, ns, pixels):
                     "neither the ramp-in of the first %d frames nor the drain of the last %d is in it" % (i2 - i1, i1, i2, ns, ns)}
 
 
+DUMP_BYTES = 32 << 20              # --dump-outputs: at most this much of the frame (the limit for all files is 64 MB)
+
+
+def frame_sample(frame):
+    """--dump-outputs: the rows of a [H, W, 4] float32 frame (device tensor) that are written out, on the host.  The whole frame
+    if it fits in DUMP_BYTES, else a fixed, seeded choice of whole rows (the same rows for the same W x H in every run).
+    Returns {name: float32 / float64 array}."""
+    import numpy as np
+    import torch
+    H, W = int(frame.shape[0]), int(frame.shape[1])
+    n = min(H, max(1, DUMP_BYTES // (W * 4 * 4)))
+    rows = np.arange(H) if n == H else np.sort(np.random.default_rng(0).choice(H, n, replace=False))
+    pix = frame.index_select(0, torch.as_tensor(rows, device=frame.device)).cpu().numpy().astype(np.float32)
+    return {"frame": pix, "frame_rows": rows.astype(np.float64)}
+
+
+def write_outputs(outdir, arrays):
+    """--dump-outputs DIR: DIR/<name>.npy per array"""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def parity(gpu, ref, nrows):
     import numpy as np
     both_nan = np.isnan(gpu) & np.isnan(ref)

@@ -4,7 +4,7 @@ import shutil
 import tempfile
 import time
 
-from .common import KERNEL_OF, OTHER_CONFIGS, parity, steady_state
+from .common import KERNEL_OF, OTHER_CONFIGS, frame_sample, parity, steady_state, write_outputs
 from .pmc import PMC_PASSES, pmc_committed, pmc_counters, rooflines, run_pmc_pass
 
 class GpuSampler:
@@ -196,7 +196,7 @@ def time_config(R, torch, dev, streams, app, W, H, t, steps=10, warmup=2, check_
         finally:
             shutil.rmtree(tmp, ignore_errors=True)
         if pmc:
-            pmc["source"] = "live: rocprofv3 --kernel-trace --pmc passes (instruction count, then the class counters) of `bench.py --app %s --steps 4 --warmup 1 --streams 1` in this run" % app
+            pmc["source"] = "live: rocprofv3 --kernel-trace --pmc passes (instruction count, then the class counters) of `bench.py --full --app %s --steps 4 --warmup 1 --streams 1` in this run" % app
     if not pmc and pmc_mode != "off":
         pmc = pmc_committed(app, W, H)
     roofline, _ = rooflines(app, W * H, W * H, kmean, min(k), pmc)
@@ -228,7 +228,8 @@ def bench_n1(args, R, torch, dev, streams, app, W, H, t):
       1. one launch at a time, back to back on ONE stream                -> `value`, `ms_per_step`  (SURVEY.md 8d: Mpixels/s per launch;
                                                                              the dominant kernel's time per step cannot exceed the step)
       2. --streams frames in flight (a frame's drain overlaps the next)   -> `value_pipelined`, `ms_per_step_pipelined`
-    (Until round 5 region 2 WAS `value`; its 6-9 % over region 1 is overlap credit, not kernel time: VERDICT r5 #3.)"""
+    (Until round 5 region 2 WAS `value`; its 6-9 % over region 1 is overlap credit, not kernel time: VERDICT r5 #3.)
+    A plain run ends after region 1 (and --dump-outputs); region 2 and every figure after it are --full."""
     from .cpu import cpu_baseline, cpu_baseline_port, cpu_baseline_speed
     ns = len(streams)
     status = 0
@@ -271,6 +272,28 @@ def bench_n1(args, R, torch, dev, streams, app, W, H, t):
     elapsed = time.perf_counter() - t0
     # the dominant kernel's time per step INSIDE this region: completion of frame 0 to completion of frame K - 1, over K - 1 launches
     span1 = done1[0].elapsed_time(done1[-1]) / max(args.steps - 1, 1) if args.steps > 1 else None
+    pixels = W * H
+    ms_per_step = elapsed * 1e3 / args.steps
+    value = pixels / (ms_per_step * 1e-3) / 1e6
+    out = {"metric": "Mpixels/s, APP_%s %dx%d" % (app.upper(), W, H), "value": round(value, 3),
+           "unit": "Mpixels/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong",
+           "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": "APP_%s %dx%d u_time=%g u_mouse=0 default aux, fragCoord=(x+.5,y+.5)" % (app.upper(), W, H, t),
+                      "frames_in_flight": 1, "parallelism": "1 GPU, one launch per frame, one launch at a time",
+                      "preroll": "%d untimed frames (>= %g ms) before the warm-up steps" % (preroll_frames, args.preroll_ms)},
+           "value_is": "SURVEY.md 8d: the K timed frames launched one at a time (back to back on one stream), wall clock between two "
+                       "synchronisations / K",
+           "scene": "the canonical frame rendered K times — a scene that stands still, as BASELINE's configs are; from "
+                    "the fourth launch on the library dispatches APP_CLOUDS / APP_EGG / APP_VINYL tiles by the cost "
+                    "earlier launches measured (same pixels).  A scene that MOVES: APP_CLOUDS rebuilds that table behind "
+                    "every launch (about -4 % instead of -7 %), APP_EGG keeps its own hot-first order (no gain) — "
+                    "DESIGN.md 5.1",
+           "kernel_ms_in_timed_region": round(span1, 4) if span1 else None}
+    if args.dump_outputs:                               # the frame of region 1's last step (step1 renders into frames[0])
+        write_outputs(args.dump_outputs, frame_sample(frames[0]))
+    if not args.full:                                   # a plain run: the headline only; everything below is --full
+        return out, status
     # ---- timed region 2: the same K frames with ns in flight
     for i in range(args.warmup):
         step(i)
@@ -293,37 +316,20 @@ def bench_n1(args, R, torch, dev, streams, app, W, H, t):
     R.set_timing(False)
     torch.cuda.synchronize(dev)
     kmean = sorted(kernel_ms)[len(kernel_ms) // 2]
-    pixels = W * H
-    ms_per_step = elapsed * 1e3 / args.steps
     ms_pipe = elapsed_pipe * 1e3 / args.steps
-    value = pixels / (ms_per_step * 1e-3) / 1e6
     value_pipe = pixels / (ms_pipe * 1e-3) / 1e6
     pmc = pmc_counters(args, app, W, H, t) if args.pmc != "off" else None
     roofline, roofline_hbm = rooflines(app, pixels, pixels, kmean, min(kernel_ms), pmc)
     serial = round(pixels / (kmean * 1e-3) / 1e6, 3)
-    out = {"metric": "Mpixels/s, APP_%s %dx%d" % (app.upper(), W, H), "value": round(value, 3),
-           "unit": "Mpixels/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong",
-           "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": {"workload": "APP_%s %dx%d u_time=%g u_mouse=0 default aux, fragCoord=(x+.5,y+.5)" % (app.upper(), W, H, t),
-                      "frames_in_flight": 1, "parallelism": "1 GPU, one launch per frame, one launch at a time",
-                      "preroll": "%d untimed frames (>= %g ms) before the warm-up steps" % (preroll_frames, args.preroll_ms)},
-           "value_is": "SURVEY.md 8d: the K timed frames launched one at a time (back to back on one stream), wall clock between two "
-                       "synchronisations / K",
-           "scene": "the canonical frame rendered K times — a scene that stands still, as BASELINE's configs are; from "
-                    "the fourth launch on the library dispatches APP_CLOUDS / APP_EGG / APP_VINYL tiles by the cost "
-                    "earlier launches measured (same pixels).  A scene that MOVES: APP_CLOUDS rebuilds that table behind "
-                    "every launch (about -4 % instead of -7 %), APP_EGG keeps its own hot-first order (no gain) — "
-                    "DESIGN.md 5.1",
-           # the same K frames with `frames_in_flight` launches overlapping (one framebuffer per stream: the drain of a frame's
-           # last, longest waves overlaps the start of the next frame) — a throughput figure of independent frames, NOT the metric
-           "value_pipelined": round(value_pipe, 3), "ms_per_step_pipelined": round(ms_pipe, 4), "frames_in_flight_pipelined": ns,
-           # ... and one un-overlapped launch bracketed by HIP events (median of 10 after 2 warm-ups)
-           "value_serial": serial,
-           "serial": {"value": serial, "unit": "Mpixels/s", "what": "one un-overlapped launch (HIP events), %d pixels" % pixels},
-           "kernel_ms_in_timed_region": round(span1, 4) if span1 else None,
-           "steady_state": steady_state(step_done, ns, pixels),
-           "roofline": roofline, "roofline_hbm": roofline_hbm}
+    out.update({
+        # the same K frames with `frames_in_flight` launches overlapping (one framebuffer per stream: the drain of a frame's
+        # last, longest waves overlaps the start of the next frame) — a throughput figure of independent frames, NOT the metric
+        "value_pipelined": round(value_pipe, 3), "ms_per_step_pipelined": round(ms_pipe, 4), "frames_in_flight_pipelined": ns,
+        # ... and one un-overlapped launch bracketed by HIP events (median of 10 after 2 warm-ups)
+        "value_serial": serial,
+        "serial": {"value": serial, "unit": "Mpixels/s", "what": "one un-overlapped launch (HIP events), %d pixels" % pixels},
+        "steady_state": steady_state(step_done, ns, pixels),
+        "roofline": roofline, "roofline_hbm": roofline_hbm})
     last_timed = frames[(args.steps - 1) % ns].clone() if not args.no_cpu_baseline else None
     if args.sustained_seconds > 0:
         out["sustained"] = sustained(torch, dev, step, ns, W * H, args.sustained_seconds, value_pipe, serial)

@@ -58,7 +58,7 @@ def run_pmc_pass(counters, app, W, H, t, outdir, timeout=100):
     if not os.path.exists(exe):
         return None
     cmd = [exe, "--kernel-trace", "-f", "csv", "--pmc"] + counters + ["-d", outdir, "-o", "pmc", "--", sys.executable,
-           BENCH, "--app", app, "--width", str(W), "--height", str(H), "--time", repr(t), "--steps", "4",
+           BENCH, "--full", "--app", app, "--width", str(W), "--height", str(H), "--time", repr(t), "--steps", "4",
            "--warmup", "1", "--streams", "1", "--no-cpu-baseline", "--pmc", "off", "--no-other-configs"]
     env = dict(os.environ)
     env["TMPDIR"] = "/tmp"
@@ -141,7 +141,7 @@ def pmc_counters(args, app, W, H, t):
         finally:
             shutil.rmtree(tmp, ignore_errors=True)
         if got:
-            got["source"] = "live: rocprofv3 --kernel-trace --pmc passes of `bench.py --steps 4 --warmup 1 --streams 1` in this run"
+            got["source"] = "live: rocprofv3 --kernel-trace --pmc passes of `bench.py --full --steps 4 --warmup 1 --streams 1` in this run"
             return got
         if args.pmc == "live":
             return None

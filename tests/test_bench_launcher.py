@@ -45,9 +45,26 @@ def test_under_torchrun_uses_the_given_ranks():
     assert line["n_gpus"] == 2 and line["self_launched"] is False
 
 
+def test_dump_sample_is_fixed_rows_within_the_limit():
+    """--dump-outputs of a frame over the limit: whole rows, the same ones in every run, under 32 MB; a small frame whole"""
+    import numpy as np
+    import torch
+    from sbxbench.common import DUMP_BYTES, frame_sample
+    H, W = 700, 4096
+    frame = torch.arange(H, dtype=torch.float32).view(H, 1, 1).expand(H, W, 4).contiguous()
+    a, b = frame_sample(frame), frame_sample(frame.clone())
+    rows = a["frame_rows"]
+    assert rows.dtype == np.float64 and (rows == b["frame_rows"]).all() and (np.diff(rows) > 0).all()
+    assert a["frame"].dtype == np.float32 and a["frame"].nbytes <= DUMP_BYTES and len(rows) == DUMP_BYTES // (W * 16)
+    assert (a["frame"][:, 0, 0] == rows).all() and (a["frame"] == b["frame"]).all()
+    small = frame_sample(frame[:10])
+    assert (small["frame_rows"] == np.arange(10)).all() and (small["frame"] == frame[:10].numpy()).all()
+
+
 @pytest.mark.gpu
 def test_bench_line_contract_and_parity():
-    r, line = run_bench("--steps", "10", "--warmup", "1", "--width", "640", "--height", "360", "--pmc", "off", "--cpu-row-stride", "8")
+    r, line = run_bench("--full", "--steps", "10", "--warmup", "1", "--width", "640", "--height", "360", "--pmc", "off",
+                        "--cpu-row-stride", "8")
     assert r.returncode == 0, r.stderr[-2000:]
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline", "cpu_baseline_port", "cpu_baseline_speed", "parity", "serial",
@@ -78,6 +95,27 @@ def test_bench_line_contract_and_parity():
     assert len(tier) == 1 and tier[0]["precision"] == "1e-4" and "TOLERANCE TIER" in tier[0]["workload"] and tier[0]["kernel"] == "k_atmosphere"
     assert tier[0]["parity"]["max_abs_diff"] <= 1e-4 and tier[0]["parity"]["mismatching_pixels"] > 0
     assert line["sustained"]["value"] > 0 and line["sustained"]["frames"] > 0 and "preroll" in line["config"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_frame(tmp_path):
+    """without --full: the K timed steps and the headline line only; --dump-outputs writes the frame of the last timed step"""
+    import numpy as np
+    from oracle.oracle import APP_IDS, Oracle
+    r, line = run_bench("--steps", "7", "--warmup", "2", "--width", "320", "--height", "180", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in line, k
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["unit"] == "Mpixels/s"
+    assert line["value"] == pytest.approx(320 * 180 / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+    for k in ("value_pipelined", "roofline", "cpu_baseline", "parity", "sustained", "other_configs"):
+        assert k not in line, k
+    frame, rows = np.load(tmp_path / "frame.npy"), np.load(tmp_path / "frame_rows.npy")
+    assert frame.dtype == np.float32 and frame.shape == (180, 320, 4) and rows.dtype == np.float64
+    assert (rows == np.arange(180)).all()
+    pick = [0, 90, 179]
+    ref = Oracle().render_rows(APP_IDS["clouds"], 320, 180, 0.37, pick)
+    assert (frame[pick].view(np.uint32) == ref.view(np.uint32)).all()
 
 
 @pytest.mark.gpu

@@ -1,24 +1,37 @@
 """Pin the constants this build hard-codes against the reference's source TEXT (no reference code is run).
-Only in the build container: skipped when /root/reference is absent (the GPU box)."""
+The uniforms' defaults are checked against their record (tests/golden/reference_uniform_defaults.json) everywhere; the record
+itself and the literals below are checked against the reference tree where it exists, and skipped where it does not."""
+import json
 import os
 import re
 
 import pytest
 
 REF = "/root/reference/src"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_uniform_defaults.json")
+needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
 
 
 def text(name):
     return open(os.path.join(REF, name), errors="ignore").read()
 
 
+def parse_uniform_defaults(ub):
+    got = dict((m.group(2), m.group(3)) for m in re.finditer(r"_uniform\((\w+),\s*(\w+),\s*([^)]*\)?)\)", ub))
+    got.pop("name", None)                              # (the macro's own definition line)
+    return got
+
+
+@needs_reference
+def test_recorded_uniform_defaults_are_the_reference_text():
+    assert parse_uniform_defaults(text("uniform_buffer.h")) == json.load(open(GOLDEN))["defaults"]
+
+
 def test_uniform_defaults_match_the_c_abi():
     import shaderbox_amd
     from shaderbox_amd import build
     build.build(verbose=False)
-    ub = text("uniform_buffer.h")
-    got = dict((m.group(2), m.group(3)) for m in re.finditer(r"_uniform\((\w+),\s*(\w+),\s*([^)]*\)?)\)", ub))
+    got = json.load(open(GOLDEN))["defaults"]
     a = shaderbox_amd.clouds_defaults()
     assert got["wind_dir"].replace(" ", "") == "vec3(0,0,.2)" and list(a.wind_dir)[2] == pytest.approx(.2)
     assert got["sun_dir"].replace(" ", "") == "vec3(0,0,-1)" and list(a.sun_dir) == [0.0, 0.0, -1.0]
@@ -58,6 +71,7 @@ def test_uniform_defaults_match_the_c_abi():
     ("util.h", ["const float p = 1. / 2.2;", "mod(pattern.x + pattern.y, 2.0)"]),
     ("main.h", ["fragCoord.xy / u_res.xy", "(2.0 * point_ndc - 1.0) * aspect_ratio * FOV", "vec4(linear_to_srgb(color), 1)"]),
 ])
+@needs_reference
 def test_literals_this_build_relies_on_are_in_the_reference_text(fname, needles):
     src = text(fname)
     for n in needles:

@@ -36,8 +36,8 @@ fi
 T=$OUT/streams3_trace.txt
 : > $T
 for ns in 3 1; do
-  rocprofv3 --kernel-trace --stats -f csv -d $OUT/bench_s$ns -o t -- python bench.py --steps 20 --warmup 5 --streams $ns --no-cpu-baseline --pmc off --no-other-configs --sustained-seconds 0 > $OUT/bench_s$ns.log 2>&1
-  echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 5 --streams $ns --no-cpu-baseline --pmc off --no-other-configs --sustained-seconds 0" >> $T
+  rocprofv3 --kernel-trace --stats -f csv -d $OUT/bench_s$ns -o t -- python bench.py --full --steps 20 --warmup 5 --streams $ns --no-cpu-baseline --pmc off --no-other-configs --sustained-seconds 0 > $OUT/bench_s$ns.log 2>&1
+  echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 5 --streams $ns --no-cpu-baseline --pmc off --no-other-configs --sustained-seconds 0" >> $T
   tail -1 $OUT/bench_s$ns.log | cut -c1-600 >> $T
   find $OUT/bench_s$ns -name '*kernel_stats.csv' | head -1 | xargs -r head -4 >> $T
   f=$(find $OUT/bench_s$ns -name '*kernel_trace.csv' | head -1)

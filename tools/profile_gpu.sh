@@ -6,7 +6,7 @@
 # Summaries land in gpurun_out/<tag>/summary.txt ; copy what should be judged into profiles/.
 set -u
 TAG=${1:-prof}; shift || true
-ARGS=${@:---steps 5 --warmup 1 --no-cpu-baseline}
+ARGS=${@:---full --steps 5 --warmup 1 --no-cpu-baseline}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp

@@ -9,6 +9,8 @@
 //              [--wind x,y,z] [--sun x,y,z] [--sun-color r,g,b] [--sun-power P] [--sky-radius R] [--sky-height Y]
 //              [--sigma S] [--coverage C] [--thick T] [--steps N] [--light-steps N]
 //     APP_SDF_AO aux block (:484-487):  [--fog-density D] [--fog-falloff F]
+//     app "2d" / "2d_tex": src/app_2d.h (its alpha is not 1: the .f32 frames carry it; single GPU only), the USE_TEXTURE build
+//              reading hlsltoy's default 128x128 checkerboard at t0
 //     APP_CLOUDS with USE_NOISE_TEX (app "clouds_tex"; hlsltoy's argv[2], argv[3], hlsltoy.cpp:227-238):
 //              --noise-tex shape.dds,detail.dds   (DX10 RGBA32F volume .dds as util/ddsvolgen / sbx_ddsvolgen write)
 //              --noise-tex bake:128,64            (bake the two volumes here with sbx_worley_volume)
@@ -30,8 +32,8 @@
 
 static int app_from_name(const std::string& s) {
     const char* names[] = {"planet", "clouds", "vinyl", "egg", "raytracer", "atmosphere", "sdf_ao", "clouds_best", "clouds_tex", "clouds_ue4",
-                           "clouds_sky", "vinyl_gpu", "planet_atmosphere"};
-    const int n = 13;
+                           "clouds_sky", "vinyl_gpu", "planet_atmosphere", "2d", "2d_tex"};
+    const int n = 15;
     std::string low;
     for (char c : s) low += (char)tolower(c);
     for (int i = 0; i < n; ++i)

@@ -34,7 +34,9 @@ extern "C" {
 #endif
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
- * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  A host checks
+ * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
+ * sbx_set_texture2d and sbx_checkerboard_texture: new enum values after the old ones and new entry points only, no value renumbered
+ * and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
 int sbx_abi_version(void);
@@ -75,7 +77,24 @@ typedef enum sbx_app {
        replaced by APP_ATMOSPHERE's get_incident_light (src/app_atmosphere.h:78-160) for the ray from (0, earth_radius + 1, 0)
        (:204-207) along the VIEW direction, lit by APP_ATMOSPHERE's sun (setup_scene :177-181, a function of u_time).
        No reference-held answers: PARITY UNPINNED (bit-identical to the oracle's restatement of the same definition). */
-    SBX_APP_PLANET_ATMOSPHERE = 12
+    SBX_APP_PLANET_ATMOSPHERE = 12,
+    /* not APP_* defines of the reference: the author's tunnel / road UV demo src/app_2d.h with its own mainImage (:70-111).
+       t = mod(u_time, 16) picks one of four phases with the reference's strict inequalities (:80-103): tunnel; tunnel(1) mixed
+       into road(1) with weight (t - 4) / 4; road; road(1) mixed into tunnel(1) with weight (t - 12) / 4; then
+       color *= 1 - tent_filter(2 uv.y - 1) (:106).  sample() is checkboard_pattern(uv, 2.) as (cb, cb, cb, 1) (src/util.h:95-101).
+       ALPHA IS NOT 1: the shader writes `color` straight to fragColor (:108), its alpha scaled by the tunnel's r and by the tent.
+       So the entry points that carry only R, G, B — sbx_render_split_rgb, sbx_render_split_in_place_rgb, sbx_render_span_peer,
+       sbx_render_span_peer_in_place with 3 channels, and the span exchange around them (sbx_render_span_root, sbx_assemble_spans)
+       — return SBX_ERR_UNSUPPORTED for these apps and write nothing, as does sbx_multi_render.  Four-channel forms work: rows,
+       strips, points, sbx_main_image*, ranks, splits (in place too) and their assemblies; SBX_FORMAT_RGBA8 stores unorm8(alpha).
+       THE PORT'S CHOICE, parity unpinned: at t exactly 4, 8 or 12, and for non-finite u_time, no branch runs and the reference's
+       `color` is uninitialised; the port writes (0, 0, 0, 0) times the tent.  NaN / Inf (the r = 0 pixel of an odd frame size,
+       points far outside the frame) flow through as data.  Math: DESIGN.md §3 (atan is the binary64 atan2 of the spec). */
+    SBX_APP_2D = 13,
+    /* SBX_APP_2D built with USE_TEXTURE (src/app_2d.h:3-30): sample() is u_tex0.Sample(u_sampler0, uv), the t0 texture of
+       sbx_set_texture2d (default: hlsltoy's 128x128 checkerboard, util/hlsltoy/src/hlsltoy.cpp:66-87, 217-223, bound with a
+       LINEAR / WRAP sampler :242-249, 434-437) filtered by the sbx texture-filter spec reduced to two axes and four channels. */
+    SBX_APP_2D_TEX = 14
 } sbx_app;
 
 typedef enum sbx_status {
@@ -375,6 +394,20 @@ int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream);
  * call (same stream, or an event). */
 int sbx_set_noise_volumes(sbx_ctx* ctx, int shape_size, const float* shape_rgba, int detail_size,
                           const float* detail_rgba, void* stream);
+/* The t0 texture of SBX_APP_2D_TEX (src/app_2d.h:3-30; what hlsltoy binds at t0, util/hlsltoy/src/hlsltoy.cpp:434).  `texels`:
+ * device memory, width x height texels, row-major, row 0 at v = 0; `format` SBX_FORMAT_RGBA8 (R8G8B8A8_UNORM words, R in the low
+ * byte, decoded to c / 255 correctly rounded) or SBX_FORMAT_RGBA32F (float4).  1 <= width, height <= 16384.  The call copies the
+ * texture into the context (as RGBA32F) on `stream` and returns when the copy is done; the caller's buffer is not referenced
+ * afterwards (inside a stream capture it does not wait).  texels = NULL restores the default, hlsltoy's 128x128 checkerboard.  Renders
+ * of SBX_APP_2D_TEX enqueued after the call read the new texture (same stream, or an event); earlier ones keep the old.
+ * Sampling (DESIGN.md §3 "SampleLevel", two axes): per axis u = c * size - .5, i = floor(u), f = u - i, WRAP by
+ * i - size * floor(i / size) folded into [0, size) (NaN -> texel 0), mix in x, then in y, binary32 weights.  Any coordinate reads
+ * only texels inside the texture.  SBX_ERR_ARG for a bad size or format. */
+int sbx_set_texture2d(sbx_ctx* ctx, int width, int height, int format, const void* texels, void* stream);
+/* hlsltoy's CreateTextureCheckboard (util/hlsltoy/src/hlsltoy.cpp:66-87) for a size x size texture, host only:
+ * out[y * size + x] = ((x & freq) == (y & freq)) ? 0xff000000 : 0xffffffff.  The default t0 is (128, 16). */
+void sbx_checkerboard_texture(int size, int freq, uint32_t* out);
+
 /* ---- Multi-GPU frames inside the library (SURVEY.md §8b "Ownership", §8e "Collective") -----------------------------
  * One process drives `nranks` ranks; devices[i] is the HIP device of rank i, rank 0 owns the frame.  With all devices
  * distinct the library creates its communicator with ncclCommInitAll (rccl.h:236; librccl is dlopen'ed here, not linked)

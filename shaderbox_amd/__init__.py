@@ -17,7 +17,7 @@ from . import shard  # noqa: F401  (pure-python row-block arithmetic, no GPU nee
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsbx.so")
 
-APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE = range(13)
+APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX = range(15)
 APPS = {"APP_PLANET": APP_PLANET, "APP_CLOUDS": APP_CLOUDS, "APP_VINYL": APP_VINYL, "APP_EGG": APP_EGG,
         "APP_RAYTRACER": APP_RAYTRACER, "APP_ATMOSPHERE": APP_ATMOSPHERE, "APP_SDF_AO": APP_SDF_AO,
         "APP_CLOUDS_BEST": APP_CLOUDS_BEST,    # src/app_clouds_best.h (stand-alone shader, not an APP_* define)
@@ -25,7 +25,9 @@ APPS = {"APP_PLANET": APP_PLANET, "APP_CLOUDS": APP_CLOUDS, "APP_VINYL": APP_VIN
         "APP_CLOUDS_UE4": APP_CLOUDS_UE4,      # ue4/volumetric_clouds/Shaders/app_clouds.usf (host mapping: include/sbx.h)
         "APP_CLOUDS_SKY": APP_CLOUDS_SKY,      # APP_CLOUDS + SKY_SPHERE (src/app_clouds.h:8,14-19,154-162)
         "APP_VINYL_GPU": APP_VINYL_GPU,        # APP_VINYL with the 180 march steps of its GLSL / HLSL builds (src/app_vinyl.h:411-416)
-        "APP_PLANET_ATMOSPHERE": APP_PLANET_ATMOSPHERE}   # config 5's composite: APP_PLANET with APP_ATMOSPHERE's sky as background (include/sbx.h)
+        "APP_PLANET_ATMOSPHERE": APP_PLANET_ATMOSPHERE,   # config 5's composite: APP_PLANET with APP_ATMOSPHERE's sky as background (include/sbx.h)
+        "APP_2D": APP_2D,                      # src/app_2d.h, the tunnel / road UV demo (own mainImage; alpha is not 1, include/sbx.h)
+        "APP_2D_TEX": APP_2D_TEX}              # APP_2D + USE_TEXTURE (src/app_2d.h:3-30): sample() reads t0 (Renderer.set_texture2d)
 
 SBX_OK, SBX_ERR_ARG, SBX_ERR_UNSUPPORTED, SBX_ERR_HIP, SBX_ERR_NO_DEVICE, SBX_ERR_FAULT = 0, -1, -2, -3, -4, -5
 SBX_FORMAT_RGBA32F, SBX_FORMAT_RGBA8 = 0, 1
@@ -168,6 +170,9 @@ def load_library(path=None):
     lib.sbx_multi_last_error.argtypes = [vp]
     lib.sbx_multi_last_error.restype = ctypes.c_char_p
     lib.sbx_set_noise_volumes.argtypes = [vp, ci, fp, ci, fp, vp]
+    lib.sbx_set_texture2d.argtypes = [vp, ci, ci, ci, vp, vp]
+    lib.sbx_checkerboard_texture.argtypes = [ci, ci, vp]
+    lib.sbx_checkerboard_texture.restype = None
     lib.sbx_tex3d_eval.argtypes = [vp, ci, fp, fp, fp, ctypes.c_size_t, vp]
     lib.sbx_last_error.argtypes = [vp]
     lib.sbx_last_error.restype = ctypes.c_char_p
@@ -209,6 +214,16 @@ def sdf_ao_defaults(lib=None):
     a = AuxSdfAo()
     lib.sbx_aux_sdf_ao_defaults(ctypes.byref(a))
     return a
+
+
+def checkerboard_texture(size=128, freq=16):
+    """hlsltoy's t0 (CreateTextureCheckboard, util/hlsltoy/src/hlsltoy.cpp:66-87): a numpy uint32 array [size, size] of
+    R8G8B8A8_UNORM words, ((x & freq) == (y & freq)) ? 0xff000000 : 0xffffffff.  The default texture of APP_2D_TEX is (128, 16).
+    Pure Python; include/sbx.h's sbx_checkerboard_texture is the same rule in C."""
+    import numpy as np
+    i = np.arange(int(size), dtype=np.uint32)
+    same = (i[None, :] & np.uint32(freq)) == (i[:, None] & np.uint32(freq))
+    return np.where(same, np.uint32(0xff000000), np.uint32(0xffffffff)).astype(np.uint32)
 
 
 def uniforms(width, height, time, mouse=(0.0, 0.0)):
@@ -669,6 +684,24 @@ class Renderer:
         self._check(self.lib.sbx_set_noise_volumes(self.ctx, int(shape_rgba.shape[0]), ctypes.c_void_p(shape_rgba.data_ptr()),
                                                    int(detail_rgba.shape[0]), ctypes.c_void_p(detail_rgba.data_ptr()),
                                                    self._stream()))
+
+    def set_texture2d(self, texels):
+        """Bind the t0 texture of APP_2D_TEX (sbx_set_texture2d): a CUDA tensor [height, width, 4] float32 (RGBA32F) or uint8
+        (R8G8B8A8_UNORM), or [height, width] int32 words; row 0 at v = 0.  None restores hlsltoy's 128x128 checkerboard.
+        The library copies the texels on the current stream and returns when the copy is done."""
+        if texels is None:
+            self._check(self.lib.sbx_set_texture2d(self.ctx, 0, 0, 0, None, self._stream()))
+            return
+        t = self.torch
+        assert texels.is_cuda and texels.is_contiguous()
+        if texels.dtype in (t.float32, t.uint8):
+            assert texels.dim() == 3 and texels.shape[2] == 4
+            fmt = SBX_FORMAT_RGBA32F if texels.dtype == t.float32 else SBX_FORMAT_RGBA8
+        else:
+            assert texels.dim() == 2 and texels.element_size() == 4 and not texels.is_floating_point()
+            fmt = SBX_FORMAT_RGBA8
+        self._check(self.lib.sbx_set_texture2d(self.ctx, int(texels.shape[1]), int(texels.shape[0]), fmt,
+                                               ctypes.c_void_p(texels.data_ptr()), self._stream()))
 
     def tex3d(self, rgba, xyz):
         """SampleLevel(linear, wrap, 0).r of an RGBA32F device volume at points xyz[n, 3] (the texture-filter spec)."""

@@ -68,6 +68,13 @@ struct sbx_ctx {
     unsigned* tex_scan = nullptr;    // 6 device words: min / max keys and NaN flag of the two volumes (sbx_set_noise_volumes)
     float tex_bounds[4] = {0, 0, 0, 0};   // {lo1, hi1, lo2, hi2} of the texels; valid only if tex_bounds_valid
     bool tex_bounds_valid = false;
+    // APP_2D_TEX: t0 as RGBA32F texels (sbx_set_texture2d).  tex2d_def = hlsltoy's 128x128 checkerboard, built at sbx_create;
+    // tex2d_user = the last texture bound (kept, and reused by a rebind of the same size, after a NULL reset)
+    float4* tex2d_def = nullptr;
+    float4* tex2d_user = nullptr;
+    size_t tex2d_user_cap = 0;             // texels
+    int tex2d_w = 0, tex2d_h = 0;          // of tex2d_user
+    bool tex2d_bound = false;              // false: renders read tex2d_def
     // sbx_main_image: the frames of the last MI_FRAMES distinct (app, uniforms, aux) seen, each in pinned host memory behind a
     // sequence lock — host threads that hit read their pixel WITHOUT any lock or shared write (the reference's harness calls
     // mainImage from many threads, src/def.h:7-8); only a miss takes mi_lock and renders.  `gen` is even while an entry is stable
@@ -417,8 +424,33 @@ static FrameCloudsUe4 build_clouds_ue4(const sbx_uniforms& U, const sbx_aux_clou
     return F;
 }
 
+// APP_2D / APP_2D_TEX (src/app_2d.h:70-111): what mainImage decides from the uniforms alone
+static constexpr int TEX2D_DEFAULT = 128, TEX2D_DEFAULT_FREQ = 16;   // hlsltoy's t0: CreateTextureCheckboard(dev, 128, 128, 16), hlsltoy.cpp:217
+static Frame2d build_2d(const sbx_uniforms& U) {
+    Frame2d F{};
+    F.rres_x = recip64(U.u_res[0]); F.rres_y = recip64(U.u_res[1]);
+    F.rpi = recip64(3.14159265359f);                                   // PI, src/def.h:51
+    const float t = mod_(U.u_time, 16.f);                              // :80
+    F.w = 0.f; F.time = 1.f;
+    if (t < 4.f) { F.phase = 0; F.time = U.u_time; }                   // :82
+    else if (t > 4.f && t < 8.f) { F.phase = 1; F.w = (t - 4.f) / 4.f; }     // :88
+    else if (t > 8.f && t < 12.f) { F.phase = 2; F.time = U.u_time; }        // :94
+    else if (t > 12.f) { F.phase = 3; F.w = (t - 12.f) / 4.f; }              // :99
+    else F.phase = 4;                                                  // t = 4, 8, 12 or NaN: no branch runs
+    F.omw = 1.f - F.w;
+    return F;
+}
+static bool is_app_2d(int app) { return app == SBX_APP_2D || app == SBX_APP_2D_TEX; }
+
 // ---------------------------------------------------------------------------------------------
 extern "C" {
+
+void sbx_checkerboard_texture(int size, int freq, uint32_t* out) {    // hlsltoy.cpp:66-87 (square: its buffer[y*h + x])
+    if (!out || size <= 0) return;
+    for (int y = 0; y < size; ++y)
+        for (int x = 0; x < size; ++x)
+            out[(size_t)y * size + x] = ((x & freq) == (y & freq)) ? 0xff000000u : 0xffffffffu;
+}
 
 void sbx_aux_clouds_ue4_defaults(sbx_aux_clouds_ue4* a) {              // app_clouds.usf:4-7
     if (!a) return;
@@ -469,6 +501,24 @@ int sbx_create(int device, sbx_ctx** out) {
         delete ctx;
         return SBX_ERR_HIP;
     }
+    {   // APP_2D_TEX's default t0 (256 KB): the UNORM words decoded on the host, c / 255 in binary32 as the device decode does
+        constexpr int n = TEX2D_DEFAULT * TEX2D_DEFAULT;
+        std::vector<uint32_t> words(n);
+        std::vector<float4> texels(n);
+        sbx_checkerboard_texture(TEX2D_DEFAULT, TEX2D_DEFAULT_FREQ, words.data());
+        for (int i = 0; i < n; ++i) {
+            const uint32_t w = words[i];
+            texels[i] = make_float4((float)(w & 255u) / 255.f, (float)((w >> 8) & 255u) / 255.f, (float)((w >> 16) & 255u) / 255.f,
+                                    (float)(w >> 24) / 255.f);
+        }
+        if (hipMalloc((void**)&ctx->tex2d_def, n * sizeof(float4)) != hipSuccess ||
+            hipMemcpy(ctx->tex2d_def, texels.data(), n * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess) {
+            if (ctx->tex2d_def) (void)hipFree(ctx->tex2d_def);
+            (void)hipFree(ctx->ytab);
+            delete ctx;
+            return SBX_ERR_HIP;
+        }
+    }
     *out = ctx;
     return SBX_OK;
 }
@@ -493,6 +543,8 @@ void sbx_destroy(sbx_ctx* ctx) {
     if (ctx->noise_tex) (void)hipFree(ctx->noise_tex);
     if (ctx->noise_tex2) (void)hipFree(ctx->noise_tex2);
     if (ctx->tex_scan) (void)hipFree(ctx->tex_scan);
+    if (ctx->tex2d_def) (void)hipFree(ctx->tex2d_def);
+    if (ctx->tex2d_user) (void)hipFree(ctx->tex2d_user);
     if (ctx->have_ytab_event) (void)hipEventDestroy(ctx->ytab_ready);
     for (auto& sl : ctx->slots) for (auto& u : sl.users) (void)hipEventDestroy(u.second);
     for (auto& e : ctx->event_pool) (void)hipEventDestroy(e);
@@ -639,7 +691,9 @@ static int render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const v
     if (M_in.nrows == 0) return SBX_OK;
     if (device_fault(ctx)) return fail(ctx, SBX_ERR_FAULT, fault_text(ctx));
     // argument checks come before anything is enqueued or recorded
-    if (app < SBX_APP_PLANET || app > SBX_APP_PLANET_ATMOSPHERE) return fail(ctx, SBX_ERR_UNSUPPORTED, "app is not on the accelerated path");
+    if (app < SBX_APP_PLANET || app > SBX_APP_2D_TEX) return fail(ctx, SBX_ERR_UNSUPPORTED, "app is not on the accelerated path");
+    if (is_app_2d(app) && (M_in.rgb == 1 || M_in.rgb == 3))
+        return fail(ctx, SBX_ERR_UNSUPPORTED, "APP_2D writes its own alpha: three-channel outputs cannot hold its pixels");
     sbx_aux_clouds AC;
     if (app == SBX_APP_CLOUDS || app == SBX_APP_CLOUDS_TEX || app == SBX_APP_CLOUDS_SKY) {
         if (aux) AC = *(const sbx_aux_clouds*)aux; else sbx_aux_clouds_defaults(&AC);
@@ -719,6 +773,19 @@ static int render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const v
         sbx_aux_clouds_ue4 A;
         if (aux) A = *(const sbx_aux_clouds_ue4*)aux; else sbx_aux_clouds_ue4_defaults(&A);
         launch_clouds_ue4(build_clouds_ue4(*uni, A), M, rgba, s);
+        break;
+    }
+    case SBX_APP_2D: case SBX_APP_2D_TEX: {
+        Frame2d F = build_2d(*uni);
+        const bool tex = app == SBX_APP_2D_TEX;
+        if (tex) {
+            F.tex = ctx->tex2d_bound ? ctx->tex2d_user : ctx->tex2d_def;
+            F.tw = ctx->tex2d_bound ? ctx->tex2d_w : TEX2D_DEFAULT;
+            F.th = ctx->tex2d_bound ? ctx->tex2d_h : TEX2D_DEFAULT;
+            F.ftw = (float)F.tw; F.fth = (float)F.th;
+            F.rtw = recip64(F.ftw); F.rth = recip64(F.fth);
+        }
+        (void)launch_2d(F, M, rgba, s, tex);                         // (three-channel maps were refused above)
         break;
     }
     default: break;
@@ -1300,6 +1367,7 @@ extern "C" int sbx_render_span_peer(sbx_ctx* ctx, int app, const sbx_uniforms* u
     int W, H;
     int rc = check_common(ctx, uni, rgb, W, H, 3u);
     if (rc != SBX_OK) return rc;
+    if (is_app_2d(app)) return fail(ctx, SBX_ERR_UNSUPPORTED, "APP_2D writes its own alpha: span slabs carry R, G, B only");
     if (rank < 1 || rank >= nranks) return fail(ctx, SBX_ERR_ARG, "span slabs are rendered by ranks 1 .. nranks-1");
     const int rows = sbx_split_rank_rows(H, block_rows, rank, nranks, root_rounds, rounds);
     if (rows < 0) return fail(ctx, SBX_ERR_ARG, "bad rank split");
@@ -1323,6 +1391,7 @@ extern "C" int sbx_render_span_peer_in_place(sbx_ctx* ctx, int app, const sbx_un
     if (rc != SBX_OK) return rc;
     if (rank < 1 || rank >= nranks) return fail(ctx, SBX_ERR_ARG, "sbx_render_span_peer_in_place is for ranks 1 .. nranks-1");
     if (channels != 3 && channels != 4) return fail(ctx, SBX_ERR_ARG, "channels must be 3 or 4");
+    if (is_app_2d(app) && channels == 3) return fail(ctx, SBX_ERR_UNSUPPORTED, "APP_2D writes its own alpha: three channels cannot hold it");
     const int rows = sbx_split_rank_rows(H, block_rows, rank, nranks, root_rounds, rounds);
     if (rows < 0) return fail(ctx, SBX_ERR_ARG, "bad rank split");
     if (rows == 0) return SBX_OK;
@@ -1341,6 +1410,7 @@ extern "C" int sbx_render_span_root(sbx_ctx* ctx, int app, const sbx_uniforms* u
     int rc = check_common(ctx, uni, frame, W, H);
     if (rc != SBX_OK) return rc;
     if (!split_ok(H, block_rows, nranks, root_rounds, rounds)) return fail(ctx, SBX_ERR_ARG, "bad rank split");
+    if (is_app_2d(app)) return fail(ctx, SBX_ERR_UNSUPPORTED, "APP_2D writes its own alpha: the span exchange's slabs carry R, G, B only");
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipSetDevice", e);
     const int4* dev = nullptr; int mw = 0;
@@ -1357,6 +1427,7 @@ extern "C" int sbx_assemble_spans(sbx_ctx* ctx, int app, const sbx_uniforms* uni
     int rc = check_common(ctx, uni, frame, W, H);
     if (rc != SBX_OK) return rc;
     if (!split_ok(H, block_rows, nranks, root_rounds, rounds) || stride_pixels < 0) return fail(ctx, SBX_ERR_ARG, "bad assemble arguments");
+    if (is_app_2d(app)) return fail(ctx, SBX_ERR_UNSUPPORTED, "APP_2D writes its own alpha: span slabs carry R, G, B only");
     if (nranks == 1) return SBX_OK;
     if (!peers) return fail(ctx, SBX_ERR_ARG, "NULL peers");
     hipError_t e = hipSetDevice(ctx->device);
@@ -1374,6 +1445,7 @@ extern "C" int sbx_assemble_spans(sbx_ctx* ctx, int app, const sbx_uniforms* uni
 static int render_split(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const void* aux, int block_rows, int rank, int nranks,
                         int root_rounds, int rounds, int r0, int r1, int rgb, float* rgba, void* stream) {
     int W, H;
+    if (ctx && rgb && is_app_2d(app)) return fail(ctx, SBX_ERR_UNSUPPORTED, "APP_2D writes its own alpha: sbx_render_split_rgb carries R, G, B only");
     if (ctx && uni && r0 == r1 && r0 >= 0) return SBX_OK;
     int rc = check_common(ctx, uni, rgba, W, H, rgb ? 3u : 15u);
     if (rc != SBX_OK) return rc;
@@ -1409,6 +1481,7 @@ int sbx_render_split_in_place_rgb(sbx_ctx* ctx, int app, const sbx_uniforms* uni
     int W, H;
     int rc = check_common(ctx, uni, frame, W, H);
     if (rc != SBX_OK) return rc;
+    if (is_app_2d(app)) return fail(ctx, SBX_ERR_UNSUPPORTED, "APP_2D writes its own alpha: sbx_render_split_in_place_rgb writes R, G, B only");
     const int rows = sbx_split_rank_rows(H, block_rows, rank, nranks, root_rounds, rounds);
     if (rows < 0) return fail(ctx, SBX_ERR_ARG, "bad rank split");
     if (rows == 0) return SBX_OK;
@@ -1567,6 +1640,52 @@ int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream) {
     return SBX_OK;
 }
 
+// forget the cached frames of sbx_main_image (a texture they were rendered with changed)
+static void mi_invalidate(sbx_ctx* ctx) {
+    std::lock_guard<std::mutex> g(ctx->mi_lock);
+    for (auto& en : ctx->mi) {
+        const uint64_t g0 = en.gen.load(std::memory_order_relaxed);
+        en.gen.store(g0 + 1, std::memory_order_relaxed);
+        std::atomic_thread_fence(std::memory_order_release);
+        for (auto& w : en.key) w.store(0xffffffffu, std::memory_order_relaxed);
+        en.used = false;
+        en.gen.store(g0 + 2, std::memory_order_release);
+    }
+}
+
+int sbx_set_texture2d(sbx_ctx* ctx, int width, int height, int format, const void* texels, void* stream) {
+    if (!ctx) return SBX_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (!texels) {                                                 // back to hlsltoy's checkerboard (kept on the device since sbx_create)
+        ctx->tex2d_bound = false;
+        mi_invalidate(ctx);
+        return SBX_OK;
+    }
+    if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(ctx, SBX_ERR_ARG, "texture sizes run from 1 to 16384");
+    if (format != SBX_FORMAT_RGBA8 && format != SBX_FORMAT_RGBA32F) return fail(ctx, SBX_ERR_ARG, "texture format must be SBX_FORMAT_RGBA8 or SBX_FORMAT_RGBA32F");
+    if (((uintptr_t)texels & (format == SBX_FORMAT_RGBA8 ? 3u : 15u)) != 0) return fail(ctx, SBX_ERR_ARG, "misaligned texels");
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipSetDevice", e);
+    const size_t n = (size_t)width * (size_t)height;
+    if (n > ctx->tex2d_user_cap) {
+        // (a larger texture frees the old copy, which an in-flight render may read: hipFree synchronises the device first)
+        if (ctx->tex2d_user) (void)hipFree(ctx->tex2d_user);
+        ctx->tex2d_user = nullptr; ctx->tex2d_user_cap = 0; ctx->tex2d_bound = false;
+        if ((e = hipMalloc((void**)&ctx->tex2d_user, n * sizeof(float4))) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc (texture)", e);
+        ctx->tex2d_user_cap = n;
+    }
+    if (format == SBX_FORMAT_RGBA8) launch_unorm8_to_float4(static_cast<const unsigned*>(texels), ctx->tex2d_user, n, s);
+    else if ((e = hipMemcpyAsync(ctx->tex2d_user, texels, n * sizeof(float4), hipMemcpyDeviceToDevice, s)) != hipSuccess)
+        return fail(ctx, SBX_ERR_HIP, "texture copy", e);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "texture copy launch", e);
+    ctx->tex2d_w = width; ctx->tex2d_h = height; ctx->tex2d_bound = true;
+    mi_invalidate(ctx);
+    // the call returns when the copy is done (the caller's buffer is not referenced afterwards); inside a stream capture it cannot wait
+    if (!stream_is_capturing(s) && (e = hipStreamSynchronize(s)) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "texture copy", e);
+    return SBX_OK;
+}
+
 int sbx_set_noise_volumes(sbx_ctx* ctx, int shape_size, const float* shape_rgba, int detail_size, const float* detail_rgba,
                           void* stream) {
     if (!ctx) return SBX_ERR_ARG;
@@ -1589,17 +1708,7 @@ int sbx_set_noise_volumes(sbx_ctx* ctx, int shape_size, const float* shape_rgba,
         if ((e = hipMalloc((void**)&ctx->noise_tex2, n2 * sizeof(float))) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
         ctx->noise_tex2_size = detail_size;
     }
-    {   // cached sbx_main_image frames may have used the old volumes
-        std::lock_guard<std::mutex> g(ctx->mi_lock);
-        for (auto& en : ctx->mi) {
-            const uint64_t g0 = en.gen.load(std::memory_order_relaxed);
-            en.gen.store(g0 + 1, std::memory_order_relaxed);
-            std::atomic_thread_fence(std::memory_order_release);
-            for (auto& w : en.key) w.store(0xffffffffu, std::memory_order_relaxed);
-            en.used = false;
-            en.gen.store(g0 + 2, std::memory_order_release);
-        }
-    }
+    mi_invalidate(ctx);                                            // cached sbx_main_image frames may have used the old volumes
     launch_extract_r(shape_rgba, ctx->noise_tex, n1, (hipStream_t)stream);
     launch_extract_r(detail_rgba, ctx->noise_tex2, n2, (hipStream_t)stream);
     e = hipGetLastError();

@@ -134,6 +134,14 @@ __device__ __forceinline__ void store_rgba(const RowMap& M, float* out, size_t i
     }
 }
 
+// the four-channel form for apps whose alpha is not the constant 1 of main.h:52 (APP_2D: app_2d.h writes `color` itself, :108):
+// float4 pixels as computed, or R8G8B8A8_UNORM words with unorm8_(alpha) in the top byte (what sbx_pack_unorm8 does with c.w).
+// Three-channel outputs (RowMap.rgb 1 and 3) cannot hold such a pixel: their entry points refuse these apps on the host.
+__device__ __forceinline__ void store_rgba4(const RowMap& M, float* out, size_t idx, float4 c) {
+    if (M.rgb == 2) reinterpret_cast<unsigned*>(out)[idx] = unorm8_(c.x) | (unorm8_(c.y) << 8) | (unorm8_(c.z) << 16) | (unorm8_(c.w) << 24);
+    else reinterpret_cast<float4*>(out)[idx] = c;
+}
+
 // launchers (one per app), defined next to their kernels
 void launch_clouds(const FrameClouds& F, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
                    bool build_table);
@@ -184,6 +192,8 @@ dim3 sdf_ao_grid(const RowMap& M);
 dim3 vinyl_grid(const RowMap& M);
 dim3 clouds_best_grid(const RowMap& M);
 dim3 clouds_ue4_grid(const RowMap& M);
+bool launch_2d(const Frame2d& F, const RowMap& M, float* out, hipStream_t s, bool tex);   // false: a three-channel map (nothing launched)
+void launch_unorm8_to_float4(const unsigned* in, float4* out, size_t n, hipStream_t s);
 int launch_noise_eval(int fn, const float* xyz, const float* par, float* out, size_t n, hipStream_t s);
 void launch_worley_volume(int size, float* out, hipStream_t s);
 void launch_exp4k_eval(const float* a, float* out, size_t n, hipStream_t s);

@@ -244,4 +244,20 @@ struct FrameVinyl {
     int steps;                 // march steps: 60 (the C++ build) or 180 (the GLSL / HLSL builds, SBX_APP_VINYL_GPU)   :411-416
 };
 
+// ---- APP_2D / APP_2D_TEX (src/app_2d.h:70-111; not APP_* defines of the reference) -----------------
+// Everything mainImage decides from the uniforms alone: the phase of t = mod(u_time, 16) (:80-103; 4 = none of the four branches
+// runs, color stays (0, 0, 0, 0)), the time the phase hands perturb_tunnel / perturb_road and its mix weight.
+struct Frame2d {
+    double rres_x, rres_y;    // recip64(u_res): fragCoord / u_res as an exact multiply (sbx_math.h div_by)      :72
+    double rpi;               // recip64(PI): a / PI as an exact multiply                                         :60
+    float time;               // u_time (phases 0, 2) or 1 (phases 1, 3)                                         :83,88-89,95,99-100
+    float w, omw;             // mix weight (t - 4) / 4 or (t - 12) / 4, and 1 - w (GLSL mix)                      :90,101
+    int phase;                // 0: tunnel, 1: tunnel -> road, 2: road, 3: road -> tunnel, 4: none (t = 4, 8, 12 or NaN)
+    // APP_2D_TEX: the context's copy of t0 (sbx_set_texture2d), RGBA32F texels, row 0 at v = 0
+    const float4* tex;
+    int tw, th;
+    float ftw, fth;
+    double rtw, rth;          // recip64(tw), recip64(th): the wrap's quotient
+};
+
 }  // namespace sbx

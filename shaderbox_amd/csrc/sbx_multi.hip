@@ -482,6 +482,8 @@ static int render_spans(sbx_multi* m, int app, const sbx_uniforms* uni, const vo
 int sbx_multi_render(sbx_multi* m, int app, const sbx_uniforms* uni, const void* aux, float* frame, void* stream) {
     if (!m) return SBX_ERR_ARG;
     if (!uni || !frame) return mfail(m, SBX_ERR_ARG, "NULL uniforms or frame");
+    // APP_2D writes its own alpha (src/app_2d.h:108) and the exchanges move 3-channel slabs: multi-GPU frames of it are not offered
+    if (app == SBX_APP_2D || app == SBX_APP_2D_TEX) return mfail(m, SBX_ERR_UNSUPPORTED, "APP_2D / APP_2D_TEX: no multi-GPU frames");
     const int W = (int)uni->u_res[0], H = (int)uni->u_res[1];
     if (W <= 0 || H <= 0 || (float)W != uni->u_res[0] || (float)H != uni->u_res[1]) return mfail(m, SBX_ERR_ARG, "bad u_res");
     const int n = (int)m->ranks.size();

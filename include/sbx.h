@@ -35,8 +35,8 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d and sbx_checkerboard_texture: new enum values after the old ones and new entry points only, no value renumbered
- * and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
+ * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
 int sbx_abi_version(void);
@@ -94,7 +94,16 @@ typedef enum sbx_app {
     /* SBX_APP_2D built with USE_TEXTURE (src/app_2d.h:3-30): sample() is u_tex0.Sample(u_sampler0, uv), the t0 texture of
        sbx_set_texture2d (default: hlsltoy's 128x128 checkerboard, util/hlsltoy/src/hlsltoy.cpp:66-87, 217-223, bound with a
        LINEAR / WRAP sampler :242-249, 434-437) filtered by the sbx texture-filter spec reduced to two axes and four channels. */
-    SBX_APP_2D_TEX = 14
+    SBX_APP_2D_TEX = 14,
+    /* not an APP_* define of the reference: src/app_func.h, the function plotter with its own mainImage (:63-111), in the branch
+       it compiles (`#if 1 // 2D`, :79-85): t = (fragCoord + .5) / u_res (:72), n = worley_fbm((t, 0)) — the tiled Worley fBm of
+       :17-47, nine noise_w (src/noise_worley.h:20-51) over the periods 4, 8, 16, 24, 32, 64 — and fragColor = (n, n, n, 1) (:110),
+       no sRGB.  u_time and u_mouse do not enter.  Alpha is 1, so every output form holds it (rgb, span, split, SBX_FORMAT_RGBA8,
+       sbx_multi_render).  The reference does not compile as shipped (its ashima-noise submodule is absent); the port is what the
+       compiled branch computes under the math spec of DESIGN.md §3, which is also the shader's GLSL meaning.  hlsltoy's HLSL build
+       would flip t.y and hash cell -1 for L - 1 at the left and bottom edges (its fmod): parity with it is not pinned.
+       The `#else // 1D` plot branch (ashima's cnoise / snoise) is not ported. */
+    SBX_APP_FUNC = 15
 } sbx_app;
 
 typedef enum sbx_status {
@@ -373,7 +382,8 @@ int sbx_last_kernel_ms(sbx_ctx* ctx, float* ms);
  * per point: "noise_iq" (src/noise_iq.h:11-29, out[0]); "hash_w" (src/noise_worley.h:5-17);
  * "noise_w" (:20-51; params[0] = domain_repeat; out = sqrt F1, sqrt F2, |cell id|);
  * "fbm_worley_tile" (src/fbm.h:8 as instantiated at util/ddsvolgen/src/ddsvolgen.cpp:52;
- * params = lacunarity, init_gain, gain; out[0]).
+ * params = lacunarity, init_gain, gain; out[0]); "worley_fbm" (src/app_func.h:41-47 over :17-39: the nine noise_w of
+ * SBX_APP_FUNC at the point, out[0]; params unused).
  * (include/sbx_test.h documents three more names that exist for the parity tests of the recorded-domain forms.) */
 int sbx_noise_eval(sbx_ctx* ctx, const char* fn, const float* xyz, const float* params, float* out,
                    size_t n, void* stream);

@@ -17,7 +17,7 @@ from . import shard  # noqa: F401  (pure-python row-block arithmetic, no GPU nee
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsbx.so")
 
-APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX = range(15)
+APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC = range(16)
 APPS = {"APP_PLANET": APP_PLANET, "APP_CLOUDS": APP_CLOUDS, "APP_VINYL": APP_VINYL, "APP_EGG": APP_EGG,
         "APP_RAYTRACER": APP_RAYTRACER, "APP_ATMOSPHERE": APP_ATMOSPHERE, "APP_SDF_AO": APP_SDF_AO,
         "APP_CLOUDS_BEST": APP_CLOUDS_BEST,    # src/app_clouds_best.h (stand-alone shader, not an APP_* define)
@@ -27,7 +27,8 @@ APPS = {"APP_PLANET": APP_PLANET, "APP_CLOUDS": APP_CLOUDS, "APP_VINYL": APP_VIN
         "APP_VINYL_GPU": APP_VINYL_GPU,        # APP_VINYL with the 180 march steps of its GLSL / HLSL builds (src/app_vinyl.h:411-416)
         "APP_PLANET_ATMOSPHERE": APP_PLANET_ATMOSPHERE,   # config 5's composite: APP_PLANET with APP_ATMOSPHERE's sky as background (include/sbx.h)
         "APP_2D": APP_2D,                      # src/app_2d.h, the tunnel / road UV demo (own mainImage; alpha is not 1, include/sbx.h)
-        "APP_2D_TEX": APP_2D_TEX}              # APP_2D + USE_TEXTURE (src/app_2d.h:3-30): sample() reads t0 (Renderer.set_texture2d)
+        "APP_2D_TEX": APP_2D_TEX,              # APP_2D + USE_TEXTURE (src/app_2d.h:3-30): sample() reads t0 (Renderer.set_texture2d)
+        "APP_FUNC": APP_FUNC}                  # src/app_func.h's 2D branch, the tiled Worley fBm (own mainImage; alpha 1, include/sbx.h)
 
 SBX_OK, SBX_ERR_ARG, SBX_ERR_UNSUPPORTED, SBX_ERR_HIP, SBX_ERR_NO_DEVICE, SBX_ERR_FAULT = 0, -1, -2, -3, -4, -5
 SBX_FORMAT_RGBA32F, SBX_FORMAT_RGBA8 = 0, 1
@@ -659,7 +660,7 @@ class Renderer:
         return ms.value
 
     def noise(self, fn, xyz, params=(0.0, 0.0, 0.0)):
-        """Library noise functions (noise_iq / hash_w / noise_w / fbm_worley_tile) over points xyz[n,3] -> [n,3]."""
+        """Library noise functions (noise_iq / hash_w / noise_w / fbm_worley_tile / worley_fbm) over points xyz[n,3] -> [n,3]."""
         xyz = xyz.to(self.tdev, self.torch.float32).contiguous().view(-1, 3)
         par = (ctypes.c_float * 3)(*[float(v) for v in params])
         out = self.torch.empty_like(xyz)

@@ -75,6 +75,9 @@ struct sbx_ctx {
     size_t tex2d_user_cap = 0;             // texels
     int tex2d_w = 0, tex2d_h = 0;          // of tex2d_user
     bool tex2d_bound = false;              // false: renders read tex2d_def
+    // APP_FUNC: hash_w of every cell its six periods reach (kern_func.hip), built at sbx_create by one synchronous launch — so no
+    // host thread ever sees it half built and no stream has to be ordered after it
+    float4* func_tab = nullptr;
     // sbx_main_image: the frames of the last MI_FRAMES distinct (app, uniforms, aux) seen, each in pinned host memory behind a
     // sequence lock — host threads that hit read their pixel WITHOUT any lock or shared write (the reference's harness calls
     // mainImage from many threads, src/def.h:7-8); only a miss takes mi_lock and renders.  `gen` is even while an entry is stable
@@ -519,6 +522,14 @@ int sbx_create(int device, sbx_ctx** out) {
             return SBX_ERR_HIP;
         }
     }
+    if (hipMalloc((void**)&ctx->func_tab, func_table_bytes()) != hipSuccess ||
+        (launch_func_table(ctx->func_tab, nullptr), hipGetLastError()) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+        if (ctx->func_tab) (void)hipFree(ctx->func_tab);
+        (void)hipFree(ctx->tex2d_def);
+        (void)hipFree(ctx->ytab);
+        delete ctx;
+        return SBX_ERR_HIP;
+    }
     *out = ctx;
     return SBX_OK;
 }
@@ -545,6 +556,7 @@ void sbx_destroy(sbx_ctx* ctx) {
     if (ctx->tex_scan) (void)hipFree(ctx->tex_scan);
     if (ctx->tex2d_def) (void)hipFree(ctx->tex2d_def);
     if (ctx->tex2d_user) (void)hipFree(ctx->tex2d_user);
+    if (ctx->func_tab) (void)hipFree(ctx->func_tab);
     if (ctx->have_ytab_event) (void)hipEventDestroy(ctx->ytab_ready);
     for (auto& sl : ctx->slots) for (auto& u : sl.users) (void)hipEventDestroy(u.second);
     for (auto& e : ctx->event_pool) (void)hipEventDestroy(e);
@@ -691,7 +703,7 @@ static int render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const v
     if (M_in.nrows == 0) return SBX_OK;
     if (device_fault(ctx)) return fail(ctx, SBX_ERR_FAULT, fault_text(ctx));
     // argument checks come before anything is enqueued or recorded
-    if (app < SBX_APP_PLANET || app > SBX_APP_2D_TEX) return fail(ctx, SBX_ERR_UNSUPPORTED, "app is not on the accelerated path");
+    if (app < SBX_APP_PLANET || app > SBX_APP_FUNC) return fail(ctx, SBX_ERR_UNSUPPORTED, "app is not on the accelerated path");
     if (is_app_2d(app) && (M_in.rgb == 1 || M_in.rgb == 3))
         return fail(ctx, SBX_ERR_UNSUPPORTED, "APP_2D writes its own alpha: three-channel outputs cannot hold its pixels");
     sbx_aux_clouds AC;
@@ -788,6 +800,7 @@ static int render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const v
         (void)launch_2d(F, M, rgba, s, tex);                         // (three-channel maps were refused above)
         break;
     }
+    case SBX_APP_FUNC: launch_func(FrameFunc{uni->u_res[0], uni->u_res[1], ctx->func_tab}, M, rgba, s, ctx->variant); break;
     default: break;
     }
     if (tp) { (void)hipEventRecord(tp->ev1, s); tp->complete = true; }
@@ -1227,7 +1240,8 @@ extern "C" int sbx_span_table(int app, const sbx_uniforms* uni, const void* aux,
     const int W = (int)uni->u_res[0], H = (int)uni->u_res[1];
     if (W <= 0 || H <= 0 || (float)W != uni->u_res[0] || (float)H != uni->u_res[1] || W > 65536 || H > 65536) return SBX_ERR_ARG;
     if (!split_ok(H, block_rows, nranks, root_rounds, rounds)) return SBX_ERR_ARG;
-    if (app < SBX_APP_PLANET || app > SBX_APP_PLANET_ATMOSPHERE) return SBX_ERR_UNSUPPORTED;
+    // APP_FUNC: no cost model (span_probe), its cost is uniform over the frame — every block's span is the whole row
+    if (app < SBX_APP_PLANET || (app > SBX_APP_PLANET_ATMOSPHERE && app != SBX_APP_FUNC)) return SBX_ERR_UNSUPPORTED;
     const int nblocks = (H + block_rows - 1) / block_rows;
     const int ntiles = (W + SPAN_ALIGN - 1) / SPAN_ALIGN;
     const SpanProbe P = span_probe(app, *uni, aux);
@@ -1614,9 +1628,10 @@ int sbx_noise_eval(sbx_ctx* ctx, const char* fn, const float* xyz, const float* 
                    void* stream) {
     if (!ctx) return SBX_ERR_ARG;
     if (!fn || !xyz || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    static const char* names[] = {"noise_iq", "hash_w", "noise_w", "fbm_worley_tile", "normalize", "wit_normalize", "wit_record"};
+    static const char* names[] = {"noise_iq", "hash_w", "noise_w", "fbm_worley_tile", "normalize", "wit_normalize", "wit_record",
+                                  "worley_fbm"};
     int id = -1;
-    for (int i = 0; i < 7; ++i) if (std::strcmp(fn, names[i]) == 0) id = i;
+    for (int i = 0; i < 8; ++i) if (std::strcmp(fn, names[i]) == 0) id = i;
     if (id < 0) return fail(ctx, SBX_ERR_ARG, "unknown noise function");
     const float zero[3] = {0.f, 0.f, 0.f};
     if ((id == 2 || id == 3) && !params) return fail(ctx, SBX_ERR_ARG, "noise_w / fbm_worley_tile need params");

@@ -194,6 +194,9 @@ dim3 clouds_best_grid(const RowMap& M);
 dim3 clouds_ue4_grid(const RowMap& M);
 bool launch_2d(const Frame2d& F, const RowMap& M, float* out, hipStream_t s, bool tex);   // false: a three-channel map (nothing launched)
 void launch_unorm8_to_float4(const unsigned* in, float4* out, size_t n, hipStream_t s);
+void launch_func(const FrameFunc& F, const RowMap& M, float* out, hipStream_t s, int variant);
+void launch_func_table(float4* tab, hipStream_t s);   // APP_FUNC's hash table (kern_func.hip), func_table_bytes() of device memory
+size_t func_table_bytes();
 int launch_noise_eval(int fn, const float* xyz, const float* par, float* out, size_t n, hipStream_t s);
 void launch_worley_volume(int size, float* out, hipStream_t s);
 void launch_exp4k_eval(const float* a, float* out, size_t n, hipStream_t s);

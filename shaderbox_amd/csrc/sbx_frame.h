@@ -260,4 +260,12 @@ struct Frame2d {
     double rtw, rth;          // recip64(tw), recip64(th): the wrap's quotient
 };
 
+// ---- APP_FUNC (src/app_func.h:63-111, the `#if 1 // 2D` branch; not an APP_* define of the reference) ----------------------
+// The shader reads only u_res: t = (fragCoord + .5) / u_res (:72).  The hash table holds hash_w of every cell the six periods can
+// reach from pos.z = 0 (kern_func.hip, built once per context at sbx_create).
+struct FrameFunc {
+    float res_x, res_y;       // u_res, the divisors of :72 (IEEE quotients)
+    const float4* tab;        // FUNC_TABLE_CELLS hashes (kern_func.hip); unused by the plain kernel
+};
+
 }  // namespace sbx

@@ -119,7 +119,6 @@ struct sbx_ctx {
     SpanSlot span_slots[4];
     unsigned span_next = 0;
     TileOrderSet tile_orders;              // the dispatch order's tables (sbx_tile_order.h)
-    void* egg_side = nullptr;        // kern_egg.hip EggSide: queues, streams and events of APP_EGG's finisher launches
     std::string err;
 };
 
@@ -138,8 +137,7 @@ static int bind_fault_word(int device) {
     }
     unsigned* dev = nullptr;
     if (hipHostGetDevicePointer((void**)&dev, g_fault_word[device], 0) != hipSuccess) return SBX_ERR_HIP;
-    if (bind_fault_clouds(dev) != hipSuccess || bind_fault_clouds_ue4(dev) != hipSuccess || bind_fault_planet(dev) != hipSuccess ||
-        bind_fault_egg(dev) != hipSuccess)
+    if (bind_fault_clouds(dev) != hipSuccess || bind_fault_clouds_ue4(dev) != hipSuccess || bind_fault_planet(dev) != hipSuccess)
         return SBX_ERR_HIP;
     return SBX_OK;
 }
@@ -543,7 +541,6 @@ void sbx_destroy(sbx_ctx* ctx) {
     for (auto& en : ctx->mi) if (en.host.load()) (void)hipHostFree(en.host.load());
     for (float* h : ctx->mi_retired) (void)hipHostFree(h);
     if (ctx->pt_host) (void)hipHostFree(ctx->pt_host);
-    egg_side_destroy(ctx->egg_side);
     tile_order_destroy(ctx->tile_orders);
     if (ctx->hs_dev) (void)hipFree(ctx->hs_dev);
     if (ctx->hs_copy) (void)hipStreamDestroy(ctx->hs_copy);
@@ -678,11 +675,9 @@ static unsigned device_fault_code(const sbx_ctx* ctx) {
     return w ? *(volatile const unsigned*)w : 0u;
 }
 static bool device_fault(const sbx_ctx* ctx) { return device_fault_code(ctx) != 0u; }
-static const char* kFaultTextEgg = "a finisher of an APP_EGG launch on this device gave up waiting for the launch's own waves (kern_egg.hip "
-                                   "k_egg_finish): the frame is incomplete; re-render after sbx_clear_fault";
 static const char* fault_text(const sbx_ctx* ctx) {
     const unsigned c = device_fault_code(ctx);
-    return c == 2u ? kFaultTextWait : c == 3u ? kFaultTextEgg : kFaultText;
+    return c == 2u ? kFaultTextWait : kFaultText;
 }
 
 // Domain of the margin-based culls of EGG / SDF_AO / VINYL (bounding spheres and boxes around members placed by rotations) and
@@ -762,12 +757,7 @@ static int render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const v
                                                     // a captured launch is replayed later, possibly over volumes re-bound in place with
                                                     // other texel ranges: no bounds baked into a graph (the plain exp_ / IEEE divide)
                                                     (ctx->tex_bounds_valid && !capturing) ? ctx->tex_bounds : nullptr); break;
-    case SBX_APP_EGG:
-        // the finishers' queues and streams, on first use; a stream being captured gets the plain kernel (a graph would bake a queue
-        // and its sequence number in)
-        if (!ctx->egg_side && !capturing) ctx->egg_side = egg_side_create();
-        launch_egg(build_egg(*uni), M, rgba, s, sdf_variant, capturing ? nullptr : ctx->egg_side);
-        break;
+    case SBX_APP_EGG: launch_egg(build_egg(*uni), M, rgba, s, sdf_variant); break;
     case SBX_APP_RAYTRACER: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots); break;
     case SBX_APP_ATMOSPHERE: launch_atmosphere(build_atmosphere(*uni), M, rgba, s, ctx->precision); break;
     case SBX_APP_SDF_AO: {

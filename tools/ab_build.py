@@ -36,8 +36,8 @@ PLANET_VARIANTS = [("PL_ATM_FIN", 0), ("PL_PAIRS", 0), ("PL_SPEC", 0), ("PL_TB2"
 RT_VARIANTS = [("RT_AXIS_PLANES", 0), ("RT_WITNESS", 0), ("RT_LDS_FRAME", 0)]
 
 
-# kern_egg.hip.  EGG_COOP 1 = round 6's survivor queue + finisher kernel (bit-exact, measured, not faster: shipped off, kept buildable)
-EGG_VARIANTS = [("EGG_COOP", 1), ("EGG_HOT_FIRST", 0), ("EGG_WITNESS", 0), ("EGG_VCONST", 0)]
+# kern_egg.hip
+EGG_VARIANTS = [("EGG_HOT_FIRST", 0), ("EGG_WITNESS", 0), ("EGG_VCONST", 0)]
 
 
 def build_one(spec):

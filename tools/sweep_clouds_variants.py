@@ -67,7 +67,7 @@ def one_raytracer(path, N):
 
 def one_egg(path, N):
     """APP_EGG (libraries named libsbx_v_egg_*): the default kernel == the witness's test edge (2) == the un-culled IEEE kernel (1) on
-    random (time, mouse, size) frames — for EGG_COOP=1 that is the survivor queue and the finisher kernel against the plain union"""
+    random (time, mouse, size) frames"""
     import numpy as np
     import torch
     import shaderbox_amd

@@ -12,6 +12,7 @@
 //     app "2d" / "2d_tex": src/app_2d.h (its alpha is not 1: the .f32 frames carry it; single GPU only), the USE_TEXTURE build
 //              reading hlsltoy's default 128x128 checkerboard at t0
 //     app "func": src/app_func.h, the tiled Worley fBm of its compiled 2D branch (grey, alpha 1; u_time and --mouse do not enter)
+//     app "atmosphere_ground": src/app_atmosphere.h without FROM_SPACE, the camera one metre above the ground (--mouse does not enter)
 //     APP_CLOUDS with USE_NOISE_TEX (app "clouds_tex"; hlsltoy's argv[2], argv[3], hlsltoy.cpp:227-238):
 //              --noise-tex shape.dds,detail.dds   (DX10 RGBA32F volume .dds as util/ddsvolgen / sbx_ddsvolgen write)
 //              --noise-tex bake:128,64            (bake the two volumes here with sbx_worley_volume)
@@ -33,8 +34,8 @@
 
 static int app_from_name(const std::string& s) {
     const char* names[] = {"planet", "clouds", "vinyl", "egg", "raytracer", "atmosphere", "sdf_ao", "clouds_best", "clouds_tex", "clouds_ue4",
-                           "clouds_sky", "vinyl_gpu", "planet_atmosphere", "2d", "2d_tex", "func"};
-    const int n = 16;
+                           "clouds_sky", "vinyl_gpu", "planet_atmosphere", "2d", "2d_tex", "func", "atmosphere_ground"};
+    const int n = 17;
     std::string low;
     for (char c : s) low += (char)tolower(c);
     for (int i = 0; i < n; ++i)

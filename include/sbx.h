@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -49,7 +49,8 @@ typedef enum sbx_app {
     SBX_APP_VINYL = 2,      /* C++-build semantics: 60 march steps (src/app_vinyl.h:411-416) */
     SBX_APP_EGG = 3,
     SBX_APP_RAYTRACER = 4,
-    SBX_APP_ATMOSPHERE = 5,
+    SBX_APP_ATMOSPHERE = 5,  /* src/app_atmosphere.h as shipped, FROM_SPACE defined (:162): the sky dome (:190-209).  The build without
+                                the define is SBX_APP_ATMOSPHERE_GROUND */
     SBX_APP_SDF_AO = 6,
     /* not an APP_* define of the reference: the stand-alone shader src/app_clouds_best.h (own mainImage :669-696),
        numbered after the reference's apps */
@@ -103,7 +104,21 @@ typedef enum sbx_app {
        compiled branch computes under the math spec of DESIGN.md §3, which is also the shader's GLSL meaning.  hlsltoy's HLSL build
        would flip t.y and hash cell -1 for L - 1 at the left and bottom edges (its fmod): parity with it is not pinned.
        The `#else // 1D` plot branch (ashima's cnoise / snoise) is not ported. */
-    SBX_APP_FUNC = 15
+    SBX_APP_FUNC = 15,
+    /* APP_ATMOSPHERE compiled WITHOUT FROM_SPACE (src/app_atmosphere.h:162, 168-174, 210-225): mainImage of src/main.h:6-53 with
+       FOV 1 (:230), eye = (0, earth_radius + 1, 0), look_at = (0, earth_radius + 1.5, -1) (:172-173; both y values are exact in
+       binary32) — a perspective camera one metre above the ground, looking at the horizon.  setup_scene (:177-181) is unchanged: the
+       sun of SBX_APP_ATMOSPHERE for the same u_time.  render (:211-224): terrain = plane((0, -1, 0), earth_radius), hit = no_hit,
+       intersect_plane(eye, terrain, hit) (src/intersect.h:61-77, with its P0 = (d, d, d) and its `denom < 1e-6` and
+       `t < 0 || t > hit.t` tests as written); hit.t > max_dist -> get_incident_light (:78-160) along the PRIMARY RAY, else
+       (.33, .33, .33); then linear_to_srgb, alpha 1.  u_mouse does not enter.  The camera has no roll, so the row decides sky or
+       ground (the bottom 22 % of a 16:9 frame is ground); sky channels exceed 1 near the sun and are stored unclamped in float
+       frames.  A NaN DIRECTION IS A GROUND HIT (a non-finite fragCoord given to sbx_render_points): `denom < 1e-6` is false, t is
+       NaN, `t < 0 || t > hit.t` is false, the hit is recorded and the pixel is grey — not black as in the dome build.  Alpha is 1, so
+       every output form holds it (rgb, span, split, SBX_FORMAT_RGBA8, sbx_multi_render).  sbx_set_variant(1) selects the plain
+       kernel (no wave-level exits, none of the kernel-internal math forms); SBX_PRECISION_1E4 applies (below).  No reference-held
+       answers: parity unpinned — bit-identical to the model over the oracle's get_incident_light (tests/atmosphere_ground_model.py). */
+    SBX_APP_ATMOSPHERE_GROUND = 16
 } sbx_app;
 
 typedef enum sbx_status {
@@ -351,11 +366,14 @@ enum { SBX_FORMAT_RGBA32F = 0, SBX_FORMAT_RGBA8 = 1 };
 int sbx_set_output_format(sbx_ctx* ctx, int format);
 
 /* PRECISION TIER of the frame-granular and per-pixel entry points (default SBX_PRECISION_EXACT: every pixel bit-identical to the
- * CPU oracle of this repository).  SBX_PRECISION_1E4 is a labelled, opt-in tolerance tier for SBX_APP_ATMOSPHERE only (every other
- * app ignores it and stays exact): BASELINE.json's bar is 1e-4 per float channel against the C++ reference, not bit-equality, and
- * APP_ATMOSPHERE (src/app_atmosphere.h:50-160: 336 exp per in-dome pixel, no threshold that amplifies a rounding difference) meets
- * it with the hardware's binary32 exp2 in place of the math spec's binary64 table form — about half the frame time.  Max |diff|
- * against the oracle over every pixel of the 7680x4320 frame and over a sweep of sun positions is asserted in the tests.
+ * CPU oracle of this repository).  SBX_PRECISION_1E4 is a labelled, opt-in tolerance tier for SBX_APP_ATMOSPHERE and
+ * SBX_APP_ATMOSPHERE_GROUND only (every other app ignores it and stays exact): BASELINE.json's bar is 1e-4 per float channel against
+ * the C++ reference, not bit-equality, and get_incident_light (src/app_atmosphere.h:50-160: 336 exp per sky pixel, no threshold that
+ * amplifies a rounding difference) meets it with the hardware's binary32 exp2 in place of the math spec's binary64 table form — about
+ * half the frame time.  SBX_APP_ATMOSPHERE: max |diff| against the oracle over every pixel of the 7680x4320 frame and over a sweep of
+ * sun positions is asserted in the tests (measured 2.4e-7).  SBX_APP_ATMOSPHERE_GROUND: max |tier - exact| over every pixel of the
+ * 3840x2160 frame at u_time 0, .37, 2, 3.1 and 100.25 is asserted <= 1e-4; measured 4.8e-7 (at u_time 2 and 3.1, where channels
+ * reach 2.96 and 1.79 near the sun); ground pixels are exact, and sbx_set_variant(1) (sbx_test.h) renders the exact frame under it.
  * Not offered for APP_CLOUDS / APP_PLANET: their coverage and density edges turn a 1-ulp difference into 1e-3 pixels. */
 enum { SBX_PRECISION_EXACT = 0, SBX_PRECISION_1E4 = 1 };
 int sbx_set_precision(sbx_ctx* ctx, int precision);

@@ -36,6 +36,8 @@
 #define SBX_SELECTED_APP SBX_APP_2D
 #elif defined(APP_FUNC)     /* src/app_func.h's compiled 2D branch, the tiled Worley fBm (own mainImage :63-111): not an APP_* define of the reference */
 #define SBX_SELECTED_APP SBX_APP_FUNC
+#elif defined(APP_ATMOSPHERE_GROUND)   /* src/app_atmosphere.h built without FROM_SPACE (the ground camera, include/sbx.h); tested before APP_ATMOSPHERE */
+#define SBX_SELECTED_APP SBX_APP_ATMOSPHERE_GROUND
 #elif defined(APP_PLANET)
 #define SBX_SELECTED_APP SBX_APP_PLANET
 #elif defined(APP_CLOUDS)
@@ -53,7 +55,7 @@
 #elif defined(APP_CLOUDS_BEST)   /* src/app_clouds_best.h, the stand-alone shader (no APP_* define in the reference) */
 #define SBX_SELECTED_APP SBX_APP_CLOUDS_BEST
 #else
-#error "define one of APP_PLANET APP_CLOUDS APP_VINYL APP_EGG APP_RAYTRACER APP_ATMOSPHERE APP_SDF_AO (or APP_CLOUDS_BEST APP_PLANET_ATMOSPHERE APP_2D APP_2D_TEX APP_FUNC)"
+#error "define one of APP_PLANET APP_CLOUDS APP_VINYL APP_EGG APP_RAYTRACER APP_ATMOSPHERE APP_SDF_AO (or APP_CLOUDS_BEST APP_PLANET_ATMOSPHERE APP_2D APP_2D_TEX APP_FUNC APP_ATMOSPHERE_GROUND)"
 #endif
 
 namespace sbx_host {

@@ -21,6 +21,8 @@ extern "C" {
  * 2 / 3 = the default kernels, except APP_EGG / APP_SDF_AO / APP_VINYL(_GPU): 2 = their square-root witness with the recording
  * edge raised to 1.0, so that the re-run path (csrc/sbx_sdf.h, Wit) executes on ordinary frames; 3 = the culled kernels with the
  * IEEE roots only.  APP_FUNC: 1 = hash_w in place for every cell (no hash table; worley_fbm as src/app_func.h writes it).
+ * SBX_APP_ATMOSPHERE_GROUND: 1 = the plain statement of src/app_atmosphere.h:211-224 lane by lane (no wave-level exit, guarded exp,
+ * sqrt_n_, division by the exact reciprocal; exact, whatever sbx_set_precision says).  SBX_APP_ATMOSPHERE ignores the knob.
  * All variants are specified to produce identical bits (tests/test_gpu_parity.py sweeps them against each other). */
 int sbx_set_variant(sbx_ctx* ctx, int variant);
 

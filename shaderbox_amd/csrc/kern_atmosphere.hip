@@ -6,6 +6,10 @@
 // sun_dir (a _mutable global rotated by setup_scene, :177-181) is a frame constant built on the
 // host from (0,1,0), i.e. it restarts from its initialiser for every pixel (GLSL semantics).
 // Magnitudes are ~6.4e6 in binary32, so the evaluation order below is part of the result.
+//
+// k_atmosphere_ground (SBX_APP_ATMOSPHERE_GROUND) is the same file built WITHOUT FROM_SPACE (:171-174, :210-225): a perspective camera
+// one metre above the ground, intersect_plane (src/intersect.h:61-77) with the flat terrain, get_incident_light along the primary
+// ray where there is no hit and (.33, .33, .33) where there is.
 #include <cmath>
 #ifndef ATM_NO_FIN
 #define ATM_NO_FIN 0
@@ -54,6 +58,58 @@ __global__ void __launch_bounds__(64 * ATM_TX, ATM_MIN_WAVES) k_atmosphere(Frame
     store_rgba(M, out, px.idx, to_srgb(col));
 }
 
+// ---- the ground camera: app_atmosphere.h without FROM_SPACE ---------------------------------------------------------------------
+// render :211-224 around the shared atm_incident_light.  FIN = true adds the wave-level exit below and sbx_atmosphere.h's
+// shortcuts (its "THE GROUND CAMERA" paragraph shows each for these rays; the dead-ray exit is compiled out: DEAD = false);
+// FIN = false is the plain statement, lane by lane (sbx_set_variant 1, and non-finite uniforms).
+template <bool FIN, int PREC = 0>
+__global__ void __launch_bounds__(64 * ATM_TX, ATM_MIN_WAVES) k_atmosphere_ground(FrameAtmosphere F, RowMap M, float* out) {
+    const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();
+    constexpr bool T64 = FIN && ATM_EXP_REG && ATM_EXP64 && !ATM_EXP4K;
+    __shared__ double etab[32];
+    __shared__ double etab64[T64 ? 64 : 1];
+    if (threadIdx.x < 32) etab[threadIdx.x] = kExp2Tab[threadIdx.x];
+    if (T64 && threadIdx.x < 64) etab64[threadIdx.x] = kExp2Tab64[threadIdx.x];
+    if (ATM_TX > 1) __syncthreads(); else __builtin_amdgcn_wave_barrier();
+    const Pixel px = pixel_of_thread<8, ATM_TX>(M);
+    if (!px.valid) return;
+    const v2 pc = point_cam(F.cam, px.fx, px.fy);
+    const v3 rd = primary_dir(F.cam, pc);
+
+    // terrain = plane((0, -1, 0), earth_radius), hit = no_hit, intersect_plane(eye, terrain, hit)   :211-218, intersect.h:61-77
+    const v3 n = V3(0.f, -1.f, 0.f);
+    const float max_dist = 1e8f;                                    // def.h:77
+    float hit_t = max_dist + 1e1f;                                  // no_hit.t, def.h:78-83
+    const float denom = dot(n, rd);                                 // (the whole dot: 0 * NaN and 0 * inf make a NaN denom)
+    if (!(denom < 1e-6f)) {                                         // a NaN denom goes on, as in the reference
+        const v3 P0 = V3(ATM_EARTH_R, ATM_EARTH_R, ATM_EARTH_R);
+        const float t = dot(P0 - F.cam.eye, n) / denom;
+        if (!(t < 0.f || t > hit_t)) hit_t = t;                     // a NaN t is recorded: a NaN direction is a GROUND pixel
+    }
+    const bool sky = hit_t > max_dist;                              // :220
+    const v3 ground = V3(.33f, .33f, .33f);                         // :223
+
+    // The camera has no roll, so sky / ground is a matter of the row: whole waves lie under the horizon (22 % of the frame) and
+    // leave here, before any table read or march.  Wave-uniform; the waves of the horizon row's tiles are mixed and go on.
+    if (FIN && __builtin_amdgcn_ballot_w64(sky) == 0ull) {
+        tile_cost_store(M, tl_t0);
+        store_rgba(M, out, px.idx, to_srgb(ground));
+        return;
+    }
+    v3 col = ground;
+    if (FIN) {
+        // every lane of a mixed wave takes part in the march (its wave-wide tests count lanes): a ground lane marches straight up,
+        // a ray inside the domain sbx_atmosphere.h shows for the sky rays, and drops the result
+        const v3 rs = sky ? rd : V3(0.f, 1.f, 0.f);
+        const v3 light = atm_incident_light<FIN, PREC, false>(F.cam.eye, rs, F.sun_dir, etab, etab64);
+        col = sky ? light : ground;
+    } else if (sky) {
+        col = atm_incident_light<false, 0, false>(F.cam.eye, rd, F.sun_dir, etab, etab64);   // :221
+    }
+    tile_cost_store(M, tl_t0);
+    store_rgba(M, out, px.idx, to_srgb(col));
+}
+
 // exp_reg4k_ as a standalone function (sbx_math_eval "exp_reg4k"): the same table, read from global memory, the same instruction
 // sequence as inside k_atmosphere — for the exhaustive comparison with exp_
 __global__ void __launch_bounds__(256) k_exp4k_eval(const float* __restrict__ a, float* __restrict__ out, size_t n) {
@@ -78,6 +134,22 @@ void launch_atmosphere(const FrameAtmosphere& F, const RowMap& M, float* out, hi
     if (fin && precision == 1) hipLaunchKernelGGL((k_atmosphere<true, 1>), (grid_for<8, ATM_TX>(M)), dim3(64 * ATM_TX), 0, s, F, M, out);   // the tolerance tier
     else if (fin) hipLaunchKernelGGL(k_atmosphere<true>, (grid_for<8, ATM_TX>(M)), dim3(64 * ATM_TX), 0, s, F, M, out);
     else hipLaunchKernelGGL(k_atmosphere<false>, (grid_for<8, ATM_TX>(M)), dim3(64 * ATM_TX), 0, s, F, M, out);
+}
+
+void launch_atmosphere_ground(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision, int variant) {
+    // FIN as in launch_atmosphere, with the eye (a constant of the app) among the checked values; variant 1 is the plain form
+    const float chk[] = {F.cam.res_x, F.cam.res_y, F.cam.aspect_x, F.cam.fov, F.sun_dir.x, F.sun_dir.y, F.sun_dir.z,
+                         F.cam.fwd.x, F.cam.fwd.y, F.cam.fwd.z, F.cam.up.x, F.cam.up.y, F.cam.up.z, F.cam.right.x, F.cam.right.y, F.cam.right.z,
+                         F.cam.eye.x, F.cam.eye.y, F.cam.eye.z};
+    bool fin = std::isfinite(F.cam.rres_x) && std::isfinite(F.cam.rres_y) && variant != 1;
+    for (float v : chk) fin = fin && std::isfinite(v);
+#if ATM_NO_FIN
+    fin = false;
+#endif
+    const dim3 g = grid_for<8, ATM_TX>(M), b(64 * ATM_TX);
+    if (fin && precision == 1) hipLaunchKernelGGL((k_atmosphere_ground<true, 1>), g, b, 0, s, F, M, out);   // the tolerance tier
+    else if (fin) hipLaunchKernelGGL(k_atmosphere_ground<true>, g, b, 0, s, F, M, out);
+    else hipLaunchKernelGGL(k_atmosphere_ground<false>, g, b, 0, s, F, M, out);
 }
 
 }  // namespace sbx

@@ -58,6 +58,23 @@ __device__ __forceinline__ bool isect_atmosphere(v3 ro, v3 rd, float& t1) {
                            // UP (acos never returns pi exactly), and a light sample under the ground ends its march before it could reach the
                            // centre.  (isect_atmosphere keeps sqrt_n_: its argument can be exactly 0.)
 #define ATM_LEN(x) ((FIN && ATM_SQRT_RS) ? sqrt_rs_(x) : sqrt_n_(x))
+// THE GROUND CAMERA (k_atmosphere_ground, SBX_APP_ATMOSPHERE_GROUND: app_atmosphere.h without FROM_SPACE).  Its rays start at the same
+// origin (0, R + 1, 0), R = earth_radius, but their directions come from get_primary_ray, not from the dome mapping, so the arguments
+// above are restated for them.  A ray reaches atm_incident_light only when intersect_plane records no hit, i.e. when
+// denom = dot((0, -1, 0), rd) < 1e-6 is TRUE: that excludes every NaN component (0 * NaN and 0 * inf are NaN) and leaves
+// rd.y > -1e-6 with rd.x, rd.z finite.  With a finite camera (FIN) rd is normalize() of a vector whose length is >= 1 (the camera
+// basis is fixed: |fwd + up y + right x|^2 >= 1), hence a unit vector to a few ulp — or (0, 0, 0) when the squared length overflows
+// (fragCoords beyond 1e19: v / inf; -0 < 1e-6, a sky ray that stays at its origin).  For both:
+//   * |s|^2 = (R + 1)^2 + 2 (R + 1) rd.y t + t^2 >= (R + 1)^2 (1 - 1e-12) for every t >= 0: a view sample is never more than 3e-6 m
+//     below the camera's own height, so |s| >= 6.36e6 and height = |s| - R is within a rounding (ulp(6.36e6) = .5) of >= 1 m.
+//     ATM_SQRT_RS: |s|^2 ~ 4e13, never 0, never inf (t <= t1 <= 2 atmosphere_radius).  The light march starts from such a sample
+//     and is the dome's own: each of its samples is at most t1 / 8 <= 1.7e6 from one that is above the ground (or from the view
+//     sample), so it stays >= 4.6e6 from the centre.
+//   * ATM_DIV3: |s| >= 2^22, so |height| is 0 or a multiple of .5, at most 60e3 + a rounding: inside the dome's domain.
+//   * the density exp arguments -height / H lie in [-50.1, +.001] — a sub-range of the dome's [-80, 2^18] (no ray dives into the planet).
+//   * ATM_TAU4K tests its own precondition on the wave, whatever the rays are.
+//   * DEAD RAYS (atm_incident_light below): no optical depth can overflow (every density term is <= e^.001 * step), so the test is
+//     never true for these rays; k_atmosphere_ground compiles it OUT (DEAD = false) rather than carry a ballot per view sample.
 // PREC = 1: the TOLERANCE tier (include/sbx.h sbx_set_precision, SBX_PRECISION_1E4; opt-in, never the default, never in bench.py's
 // `value`).  north_star's bar is 1e-4 per channel, not bit-equality, and this kernel — 336 exp per in-dome pixel, each 15 instructions
 // of binary64 table arithmetic — has no threshold that turns a rounding difference into a different pixel: every exp becomes
@@ -128,7 +145,7 @@ __device__ __forceinline__ bool sun_light(v3 ro, v3 rd, float& odR, float& odM, 
 }
 
 // get_incident_light :78-160 for the ray (ro, rd): 16 view samples, each with an 8-sample march towards the sun
-template <bool FIN, int PREC = 0>
+template <bool FIN, int PREC = 0, bool DEAD = true>
 __device__ __forceinline__ v3 atm_incident_light(v3 ro, v3 rd, v3 sun_dir, const double (&etab)[32], const double* etab64) {
     v3 col = V3(0.f, 0.f, 0.f);
     float t1;
@@ -164,8 +181,8 @@ __device__ __forceinline__ v3 atm_incident_light(v3 ro, v3 rd, v3 sun_dir, const
 #define ATM_DEAD_EXIT 1
 #endif
             const float inf = u2f(0x7f800000u);
-            const bool dead = ATM_DEAD_EXIT && (odR == inf || odM == inf);
-            if (ATM_DEAD_EXIT && __builtin_amdgcn_ballot_w64(!dead) == 0ull) break;      // wave-uniform
+            const bool dead = DEAD && ATM_DEAD_EXIT && (odR == inf || odM == inf);
+            if (DEAD && ATM_DEAD_EXIT && __builtin_amdgcn_ballot_w64(!dead) == 0ull) break;      // wave-uniform
             float lR = 0.f, lM = 0.f;
             if (!dead && sun_light<FIN, PREC>(s, sun_dir, lR, lM, etab, etab64, K)) {
                 const v3 tau = betaR * (odR + lR) + betaM * 1.1f * (odM + lM);

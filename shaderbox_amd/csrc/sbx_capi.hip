@@ -312,6 +312,14 @@ static FrameAtmosphere build_atmosphere(const sbx_uniforms& U) {
     return F;
 }
 
+// app_atmosphere.h without FROM_SPACE: the camera of :172-173 (both y values exact in binary32), the same sun
+static FrameAtmosphere build_atmosphere_ground(const sbx_uniforms& U) {
+    FrameAtmosphere F = build_atmosphere(U);
+    const float earth_radius = 6360e3f;                                             // :37
+    F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(0, earth_radius + 1.f, 0), V3(0, earth_radius + 1.5f, -1));   // :172-173,230
+    return F;
+}
+
 static FrameSdfAo build_sdf_ao(const sbx_uniforms& U, const sbx_aux_sdf_ao& A) {
     FrameSdfAo F;
     const m3 rot = rotate_around_y(U.u_time * 50.f);                   // app_sdf_ao.h:45-50
@@ -698,7 +706,7 @@ static int render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const v
     if (M_in.nrows == 0) return SBX_OK;
     if (device_fault(ctx)) return fail(ctx, SBX_ERR_FAULT, fault_text(ctx));
     // argument checks come before anything is enqueued or recorded
-    if (app < SBX_APP_PLANET || app > SBX_APP_FUNC) return fail(ctx, SBX_ERR_UNSUPPORTED, "app is not on the accelerated path");
+    if (app < SBX_APP_PLANET || app > SBX_APP_ATMOSPHERE_GROUND) return fail(ctx, SBX_ERR_UNSUPPORTED, "app is not on the accelerated path");
     if (is_app_2d(app) && (M_in.rgb == 1 || M_in.rgb == 3))
         return fail(ctx, SBX_ERR_UNSUPPORTED, "APP_2D writes its own alpha: three-channel outputs cannot hold its pixels");
     sbx_aux_clouds AC;
@@ -760,6 +768,7 @@ static int render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const v
     case SBX_APP_EGG: launch_egg(build_egg(*uni), M, rgba, s, sdf_variant); break;
     case SBX_APP_RAYTRACER: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots); break;
     case SBX_APP_ATMOSPHERE: launch_atmosphere(build_atmosphere(*uni), M, rgba, s, ctx->precision); break;
+    case SBX_APP_ATMOSPHERE_GROUND: launch_atmosphere_ground(build_atmosphere_ground(*uni), M, rgba, s, ctx->precision, ctx->variant); break;
     case SBX_APP_SDF_AO: {
         sbx_aux_sdf_ao A;
         if (aux) A = *(const sbx_aux_sdf_ao*)aux; else sbx_aux_sdf_ao_defaults(&A);
@@ -1142,7 +1151,8 @@ int sbx_rank_rows_max(int height, int block_rows, int nranks) {
 // Spans: which part of a row-block is worth sending to another GPU (include/sbx.h "span exchange")
 // ---------------------------------------------------------------------------------------------
 // Several apps leave mainImage through an early exit for a large part of the frame: APP_CLOUDS below the horizon
-// (src/app_clouds.h:212), APP_ATMOSPHERE outside the dome (acos of an argument below -1 is a NaN direction, the atmosphere test
+// (src/app_clouds.h:212), the ground-camera build of APP_ATMOSPHERE where the primary ray hits the terrain plane
+// (src/app_atmosphere.h:211-224: a constant grey), APP_ATMOSPHERE outside the dome (acos of an argument below -1 is a NaN direction, the atmosphere test
 // fails, src/app_atmosphere.h:196-207,85-88), APP_PLANET where the view ray misses the atmosphere shell (src/app_planet.h:315-321).
 // Such pixels cost a few hundred instructions; shipping them costs 12 bytes each on the one xGMI link between their renderer
 // and the frame's owner, which at 7680x4320 is the slower of the two by far.  So the split deals out only the SPAN of each
@@ -1170,6 +1180,7 @@ static SpanProbe span_probe(int app, const sbx_uniforms& U, const void* aux) {
         break;
     }
     case SBX_APP_ATMOSPHERE: P.cam = build_atmosphere(U).cam; break;
+    case SBX_APP_ATMOSPHERE_GROUND: P.cam = build_atmosphere_ground(U).cam; break;
     case SBX_APP_PLANET: P.cam = build_planet(U).cam; break;
     default: P.model = false; P.cam = Camera{}; break;
     }
@@ -1210,6 +1221,15 @@ static bool span_heavy(const SpanProbe& P, float fx, float fy) {
         }
         return false;
     }
+    case SBX_APP_ATMOSPHERE_GROUND: {
+        // k_atmosphere_ground's own plane test (intersect.h:61-77 with dot(P0 - eye, n) = 1): no hit <=> sky <=> the 16 x 8 march.
+        // The camera has no roll, so a row-block is under the horizon as a whole or sky over its whole width.
+        const v3 dir = primary_dir(P.cam, pc);
+        const float denom = dot(V3(0.f, -1.f, 0.f), dir);
+        if (denom < 1e-6f) return true;
+        const float t = 1.f / denom;
+        return t < 0.f || t > 1e8f;
+    }
     case SBX_APP_PLANET: {                                         // intersect_sphere(eye, {0, 1 + max_height}), kern_planet.hip
         const v3 ro = P.cam.eye, rd = primary_dir(P.cam, pc);
         const float radius = 1.f + .4f;                            // planet.radius + max_height   app_planet.h:16-20,311-312
@@ -1231,7 +1251,7 @@ extern "C" int sbx_span_table(int app, const sbx_uniforms* uni, const void* aux,
     if (W <= 0 || H <= 0 || (float)W != uni->u_res[0] || (float)H != uni->u_res[1] || W > 65536 || H > 65536) return SBX_ERR_ARG;
     if (!split_ok(H, block_rows, nranks, root_rounds, rounds)) return SBX_ERR_ARG;
     // APP_FUNC: no cost model (span_probe), its cost is uniform over the frame — every block's span is the whole row
-    if (app < SBX_APP_PLANET || (app > SBX_APP_PLANET_ATMOSPHERE && app != SBX_APP_FUNC)) return SBX_ERR_UNSUPPORTED;
+    if (app < SBX_APP_PLANET || (app > SBX_APP_PLANET_ATMOSPHERE && app != SBX_APP_FUNC && app != SBX_APP_ATMOSPHERE_GROUND)) return SBX_ERR_UNSUPPORTED;
     const int nblocks = (H + block_rows - 1) / block_rows;
     const int ntiles = (W + SPAN_ALIGN - 1) / SPAN_ALIGN;
     const SpanProbe P = span_probe(app, *uni, aux);

@@ -1,4 +1,4 @@
-"""ctypes front end of the CPU oracle (oracle/libsbx_oracle.so).
+"""ctypes front end of the CPU oracle (oracle/libsbx_oracle.so) and of the reference builds (oracle/_ref/libsbx_ref_*.so).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, by __graft_entry__.smoke() and by the
 cpu_baseline leg of bench.py.  The product package (shaderbox_amd/) never imports it.
@@ -22,6 +22,109 @@ def build(variant="", subdir=""):
     name = os.path.join(subdir, "libsbx_oracle%s.so" % variant)
     subprocess.run(["make", "-s", "-C", _HERE, name], check=True)
     return os.path.join(_HERE, name)
+
+
+REF_DIR = os.path.join(_HERE, "_ref")
+# the reference builds oracle/Makefile knows (REF_NAMES): the oracle's app names where the oracle has the app, plus the three
+# the oracle does not implement ("2d", "2d_tex", "atmosphere_ground": tests/app2d_model.py, tests/atmosphere_ground_model.py)
+# and the noise library
+REF_APPS = ("planet", "clouds", "clouds_sky", "vinyl", "egg", "raytracer", "atmosphere", "atmosphere_ground", "sdf_ao",
+            "clouds_best", "2d", "2d_tex")
+REF_NAMES = REF_APPS + ("noise",)
+
+
+def reference_root():
+    """The directory oracle/Makefile takes the reference tree from (its REFERENCE variable, which the environment may set)."""
+    return subprocess.run(["make", "-s", "-C", _HERE, "print-reference"], check=True, capture_output=True, text=True).stdout.strip()
+
+
+def build_reference(reference=None):
+    """Make every oracle/_ref/libsbx_ref_*.so from the reference tree where it lies (`make ref`); does nothing where that tree
+    is absent.  Returns the names of the builds present afterwards."""
+    cmd = ["make", "-s", "-j8", "-C", _HERE, "ref"]
+    if reference is not None:
+        cmd.append("REFERENCE=%s" % reference)
+    subprocess.run(cmd, check=True)
+    return Reference.available()
+
+
+class Reference:
+    """The reference's own shader headers, compiled verbatim over oracle/glsl_env.h (oracle/README.md "How it is pinned").
+    Same render / render_rows / main_image signatures as Oracle; `app` is an oracle app id or a name of REF_APPS.  The
+    reference's aux uniforms are compile-time constants in its C++ form (src/uniform_buffer.h:13), so aux must be None."""
+
+    def __init__(self):
+        self._libs = {}
+        self._texture = None
+
+    @staticmethod
+    def available():
+        return tuple(n for n in REF_NAMES if os.path.exists(os.path.join(REF_DIR, "libsbx_ref_%s.so" % n)))
+
+    @staticmethod
+    def name_of(app):
+        if isinstance(app, str):
+            return app
+        for name, i in APP_IDS.items():
+            if i == int(app):
+                return name
+        raise ValueError("reference: unknown app %r" % (app,))
+
+    def _lib(self, app):
+        name = self.name_of(app)
+        if name not in self._libs:
+            path = os.path.join(REF_DIR, "libsbx_ref_%s.so" % name)
+            if name not in REF_NAMES or not os.path.exists(path):
+                raise ValueError("reference: no build of %r under oracle/_ref" % (app,))
+            lib = ctypes.CDLL(path)
+            fp = ctypes.POINTER(ctypes.c_float)
+            if name == "noise":
+                lib.sbxr_noise.argtypes = [ctypes.c_char_p, fp, fp, fp, ctypes.c_long]
+            else:
+                lib.sbxr_main_image.argtypes = [fp, ctypes.c_float, ctypes.c_float, fp]
+                lib.sbxr_render_rows.argtypes = [fp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, fp, ctypes.c_int]
+                lib.sbxr_set_texture2d.argtypes = [ctypes.c_int, ctypes.c_int, fp]
+            self._libs[name] = lib
+        return self._libs[name]
+
+    def main_image(self, app, width, height, time, fx, fy, mouse=(0.0, 0.0), aux=None):
+        assert aux is None, "the reference's aux uniforms are compile-time constants"
+        u = Oracle._uni(width, height, time, mouse)
+        out = np.zeros(4, dtype=np.float32)
+        self._lib(app).sbxr_main_image(Oracle._fp(u), float(fx), float(fy), Oracle._fp(out))
+        return out
+
+    def render_rows(self, app, width, height, time, rows, mouse=(0.0, 0.0), aux=None, threads=None):
+        """rows: iterable of global row indices (0 = bottom). Returns float32 [len(rows), W, 4]."""
+        assert aux is None, "the reference's aux uniforms are compile-time constants"
+        rows = np.ascontiguousarray(np.asarray(list(rows), dtype=np.int32))
+        u = Oracle._uni(width, height, time, mouse)
+        out = np.zeros((len(rows), int(width), 4), dtype=np.float32)
+        if threads is None:
+            threads = os.cpu_count() or 1
+        self._lib(app).sbxr_render_rows(Oracle._fp(u), rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(rows),
+                                        Oracle._fp(out), int(threads))
+        return out
+
+    def render(self, app, width, height, time, mouse=(0.0, 0.0), aux=None, threads=None):
+        """Whole frame, float32 [H, W, 4], row 0 = bottom."""
+        return self.render_rows(app, width, height, time, range(int(height)), mouse, aux, threads)
+
+    def set_texture2d(self, rgba):
+        """Bind the RGBA32F [h, w, 4] image (row 0 at v = 0) that the "2d_tex" build samples."""
+        t = np.ascontiguousarray(rgba, dtype=np.float32)
+        assert t.ndim == 3 and t.shape[2] == 4
+        self._texture = t                               # the library keeps the pointer
+        self._lib("2d_tex").sbxr_set_texture2d(t.shape[1], t.shape[0], Oracle._fp(t))
+
+    def noise(self, fn, xyz, par=(0.0, 0.0, 0.0)):
+        """the reference's noise functions over points xyz[n,3] -> float32 [n,3]; fn as Oracle.noise, plus "hash" (of x)"""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        par = np.ascontiguousarray(np.asarray(par, dtype=np.float32))
+        out = np.zeros_like(xyz)
+        if self._lib("noise").sbxr_noise(fn.encode(), Oracle._fp(xyz), Oracle._fp(par), Oracle._fp(out), len(xyz)) != 0:
+            raise ValueError("reference: unknown noise function %r" % fn)
+        return out
 
 
 class Oracle:

@@ -1,7 +1,8 @@
 """Vectorised numpy restatement of SBX_APP_2D / SBX_APP_2D_TEX (src/app_2d.h:70-111; include/sbx.h).
 
-The reference holds no answers for this shader, and the CPU oracle does not implement it: this module IS the definition the GPU
-tests compare against, pinned by review and by tests/test_app2d_cpu.py.  Every step is binary32 in the written order (explicit
+The CPU oracle does not implement this shader: the GPU tests compare against this module, and this module is compared bit for
+bit with src/app_2d.h itself, compiled verbatim in both of its forms (oracle/_ref/libsbx_ref_2d.so and _2d_tex.so;
+tests/test_oracle_vs_reference.py), besides tests/test_app2d_cpu.py.  Every step is binary32 in the written order (explicit
 np.float32 constants, so that nothing widens to float64); atan is the binary64 atan2 of the math spec, taken from the oracle
 (oracle.math("atan2"), which only reads oracle/).  Divisions are the plain IEEE binary32 quotients — the kernel's multiplies by a
 binary64 reciprocal (div_by, sbx_math.h) are proven equal to them, and the GPU tests check that they are.

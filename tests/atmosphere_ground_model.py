@@ -1,6 +1,8 @@
 """numpy restatement of SBX_APP_ATMOSPHERE_GROUND (src/app_atmosphere.h built without FROM_SPACE; include/sbx.h).
 
-The CPU oracle renders the FROM_SPACE build only, so this module IS the definition the GPU tests compare against.  What it adds to
+The CPU oracle renders the FROM_SPACE build only, so the GPU tests compare against this module, and this module is compared bit
+for bit with src/app_atmosphere.h compiled without its FROM_SPACE line (oracle/_ref/libsbx_ref_atmosphere_ground.so;
+tests/test_oracle_vs_reference.py).  What it adds to
 the oracle is little: mainImage's camera part (oracle/ref_apps.h:29-40), get_primary_ray and intersect_plane (oracle/ref_lib.h),
 restated in binary32 step by step in the oracle's operation order (oracle/ovec.h: dot = (x x + y y) + z z, normalize = divide by
 sqrtf, cross) with explicit np.float32 values so that nothing widens to float64 — tests/test_atmosphere_ground_cpu.py pins that

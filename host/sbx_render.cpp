@@ -9,6 +9,7 @@
 //              [--wind x,y,z] [--sun x,y,z] [--sun-color r,g,b] [--sun-power P] [--sky-radius R] [--sky-height Y]
 //              [--sigma S] [--coverage C] [--thick T] [--steps N] [--light-steps N]
 //     APP_SDF_AO aux block (:484-487):  [--fog-density D] [--fog-falloff F]
+//     app "sdf_ao_shadow" / "sdf_ao_normals": src/app_sdf_ao.h with its `#if 0` at :269 (soft shadows) / :217 (normals view) on; same fog flags
 //     app "2d" / "2d_tex": src/app_2d.h (its alpha is not 1: the .f32 frames carry it; single GPU only), the USE_TEXTURE build
 //              reading hlsltoy's default 128x128 checkerboard at t0
 //     app "func": src/app_func.h, the tiled Worley fBm of its compiled 2D branch (grey, alpha 1; u_time and --mouse do not enter)
@@ -34,8 +35,8 @@
 
 static int app_from_name(const std::string& s) {
     const char* names[] = {"planet", "clouds", "vinyl", "egg", "raytracer", "atmosphere", "sdf_ao", "clouds_best", "clouds_tex", "clouds_ue4",
-                           "clouds_sky", "vinyl_gpu", "planet_atmosphere", "2d", "2d_tex", "func", "atmosphere_ground"};
-    const int n = 17;
+                           "clouds_sky", "vinyl_gpu", "planet_atmosphere", "2d", "2d_tex", "func", "atmosphere_ground", "sdf_ao_shadow", "sdf_ao_normals"};
+    const int n = 19;
     std::string low;
     for (char c : s) low += (char)tolower(c);
     for (int i = 0; i < n; ++i)
@@ -140,7 +141,7 @@ int main(int argc, char** argv) {
         if (!pattern_ok(*p)) { fprintf(stderr, "bad file pattern %s: one %%d / %%0Nd conversion at most, a literal percent as %%%%\n", p->c_str()); return 2; }
     const void* aux = nullptr;
     if ((id == SBX_APP_CLOUDS || id == SBX_APP_CLOUDS_TEX || id == SBX_APP_CLOUDS_SKY) && have_ac) aux = &ac;
-    if (id == SBX_APP_SDF_AO && have_as) aux = &as;
+    if ((id == SBX_APP_SDF_AO || id == SBX_APP_SDF_AO_SHADOW || id == SBX_APP_SDF_AO_NORMALS) && have_as) aux = &as;
 
     sbx_ctx* ctx = nullptr;
     int rc = sbx_create(0, &ctx);

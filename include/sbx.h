@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -51,7 +51,8 @@ typedef enum sbx_app {
     SBX_APP_RAYTRACER = 4,
     SBX_APP_ATMOSPHERE = 5,  /* src/app_atmosphere.h as shipped, FROM_SPACE defined (:162): the sky dome (:190-209).  The build without
                                 the define is SBX_APP_ATMOSPHERE_GROUND */
-    SBX_APP_SDF_AO = 6,
+    SBX_APP_SDF_AO = 6,      /* src/app_sdf_ao.h as shipped: both `#if 0` blocks off (:217-219, :269-274).  The builds with one of them on are
+                                SBX_APP_SDF_AO_SHADOW and SBX_APP_SDF_AO_NORMALS */
     /* not an APP_* define of the reference: the stand-alone shader src/app_clouds_best.h (own mainImage :669-696),
        numbered after the reference's apps */
     SBX_APP_CLOUDS_BEST = 7,
@@ -118,7 +119,21 @@ typedef enum sbx_app {
        every output form holds it (rgb, span, split, SBX_FORMAT_RGBA8, sbx_multi_render).  sbx_set_variant(1) selects the plain
        kernel (no wave-level exits, none of the kernel-internal math forms); SBX_PRECISION_1E4 applies (below).  No reference-held
        answers: parity unpinned — bit-identical to the model over the oracle's get_incident_light (tests/atmosphere_ground_model.py). */
-    SBX_APP_ATMOSPHERE_GROUND = 16
+    SBX_APP_ATMOSPHERE_GROUND = 16,
+    /* APP_SDF_AO compiled with the `#if 0` at src/app_sdf_ao.h:269 turned on (:269-274): at a hit, sh = sdf_shadow({p + sun_dir * 0.05,
+       sun_dir}) — the 20-step soft-shadow march of :183-207 towards sun_dir = normalize(1, 2, 1) (:209): sdf(p) first, `t > 20` leaves
+       with the umbra so far, `d.x < .005` returns .05, then t += d.x and umbra = min(umbra, 32 * d.x / t) — and sh multiplies the key
+       light (:225).  Everything else as SBX_APP_SDF_AO: same camera, same sbx_aux_sdf_ao block (fog density and falloff; the defaults
+       when aux is NULL), same fog, abs (:310) and sRGB epilogue; pixels that miss the scene are unchanged.  sbx_set_variant(1) selects
+       the plain kernel as for SBX_APP_SDF_AO; SBX_PRECISION_1E4 is ignored.  Definition: tests/sdf_ao_builds_model.py, pinned against
+       frames of the edited reference header (tests/golden/sdf_ao_builds/). */
+    SBX_APP_SDF_AO_SHADOW = 17,
+    /* APP_SDF_AO compiled with the `#if 0` at src/app_sdf_ao.h:217 turned on (:217-219; the shadow block off as shipped): illuminate
+       returns hit.normal — sdf_normal's six-tap gradient, normalized (:152-163) — as the colour.  That value still goes through
+       render's fog mix and abs (:305-310) and main.h's linear_to_srgb, so a frame shows |mix(n, 1, fog)|^(1/2.2); a zero gradient's
+       normalize(0) = NaN is the pixel's data.  Pixels that miss the scene are unchanged (background under fog).  Aux block, variants
+       and precision as SBX_APP_SDF_AO_SHADOW. */
+    SBX_APP_SDF_AO_NORMALS = 18
 } sbx_app;
 
 typedef enum sbx_status {

@@ -23,6 +23,8 @@ extern "C" {
  * IEEE roots only.  APP_FUNC: 1 = hash_w in place for every cell (no hash table; worley_fbm as src/app_func.h writes it).
  * SBX_APP_ATMOSPHERE_GROUND: 1 = the plain statement of src/app_atmosphere.h:211-224 lane by lane (no wave-level exit, guarded exp,
  * sqrt_n_, division by the exact reciprocal; exact, whatever sbx_set_precision says).  SBX_APP_ATMOSPHERE ignores the knob.
+ * SBX_APP_SDF_AO_SHADOW / SBX_APP_SDF_AO_NORMALS: every value as for APP_SDF_AO, the shadow march included — 1 = no culling, the spec's
+ * compare-and-select min / max and the IEEE roots along the shadow ray too; 2 / 3 = the witness's test edge / the IEEE roots only.
  * All variants are specified to produce identical bits (tests/test_gpu_parity.py sweeps them against each other). */
 int sbx_set_variant(sbx_ctx* ctx, int variant);
 

@@ -17,7 +17,7 @@ from . import shard  # noqa: F401  (pure-python row-block arithmetic, no GPU nee
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsbx.so")
 
-APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND = range(17)
+APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS = range(19)
 APPS = {"APP_PLANET": APP_PLANET, "APP_CLOUDS": APP_CLOUDS, "APP_VINYL": APP_VINYL, "APP_EGG": APP_EGG,
         "APP_RAYTRACER": APP_RAYTRACER, "APP_ATMOSPHERE": APP_ATMOSPHERE, "APP_SDF_AO": APP_SDF_AO,
         "APP_CLOUDS_BEST": APP_CLOUDS_BEST,    # src/app_clouds_best.h (stand-alone shader, not an APP_* define)
@@ -29,7 +29,9 @@ APPS = {"APP_PLANET": APP_PLANET, "APP_CLOUDS": APP_CLOUDS, "APP_VINYL": APP_VIN
         "APP_2D": APP_2D,                      # src/app_2d.h, the tunnel / road UV demo (own mainImage; alpha is not 1, include/sbx.h)
         "APP_2D_TEX": APP_2D_TEX,              # APP_2D + USE_TEXTURE (src/app_2d.h:3-30): sample() reads t0 (Renderer.set_texture2d)
         "APP_FUNC": APP_FUNC,                  # src/app_func.h's 2D branch, the tiled Worley fBm (own mainImage; alpha 1, include/sbx.h)
-        "APP_ATMOSPHERE_GROUND": APP_ATMOSPHERE_GROUND}   # APP_ATMOSPHERE without FROM_SPACE: the camera 1 m above the ground (include/sbx.h)
+        "APP_ATMOSPHERE_GROUND": APP_ATMOSPHERE_GROUND,   # APP_ATMOSPHERE without FROM_SPACE: the camera 1 m above the ground (include/sbx.h)
+        "APP_SDF_AO_SHADOW": APP_SDF_AO_SHADOW,    # APP_SDF_AO with the soft-shadow march compiled in (src/app_sdf_ao.h:269-274, 183-207)
+        "APP_SDF_AO_NORMALS": APP_SDF_AO_NORMALS}  # APP_SDF_AO with the normals view compiled in (src/app_sdf_ao.h:217-219)
 
 SBX_OK, SBX_ERR_ARG, SBX_ERR_UNSUPPORTED, SBX_ERR_HIP, SBX_ERR_NO_DEVICE, SBX_ERR_FAULT = 0, -1, -2, -3, -4, -5
 SBX_FORMAT_RGBA32F, SBX_FORMAT_RGBA8 = 0, 1

@@ -1,9 +1,12 @@
 // shaderbox_amd/csrc/kern_sdf_ao.hip — APP_SDF_AO: skate-ramp SDF with distance-field AO and fog.
 //
 // Follows /root/reference/src/app_sdf_ao.h: sdf_pipe :54-113, sdf :115-150, sdf_normal :152-163,
-// sdf_ao :165-181, illuminate :211-243, render_impl :245-285 (shadow march compiled out, :269-274),
-// render (height fog) :287-311; SDF primitives from src/sdf.h.  The two constant-angle rotations
-// (rotate_around_x(-90), rotate_around_y(180)) and normalize(1,2,1) are frame constants.
+// sdf_ao :165-181, sdf_shadow :183-207, illuminate :211-243, render_impl :245-285, render (height fog) :287-311; SDF primitives
+// from src/sdf.h.  The header's two `#if 0` blocks are the template parameter BUILD of the pixel function and the kernel:
+//   AO_DEFAULT  as shipped (SBX_APP_SDF_AO): sh = 1, the shadow march compiled out (:269-274)
+//   AO_SHADOW   the block at :269-274 compiled in (SBX_APP_SDF_AO_SHADOW): sh = sdf_shadow({p + sun_dir * 0.05, sun_dir})
+//   AO_NORMALS  the block at :217-219 compiled in (SBX_APP_SDF_AO_NORMALS): illuminate returns hit.normal
+// The two constant-angle rotations (rotate_around_x(-90), rotate_around_y(180)) and normalize(1,2,1) are frame constants.
 #include "sbx_device.h"
 #include "sbx_sdf.h"
 
@@ -12,6 +15,8 @@
 #endif
 
 namespace sbx {
+
+enum { AO_DEFAULT = 0, AO_SHADOW = 1, AO_NORMALS = 2 };
 
 // HW (the CULL kernels, which run for tame frames only: finite u_time, u_res checked by the C API, hence finite points): the SDF's min /
 // max as v_min_f32 / v_max_f32 (sbx_sdf.h hmin_ / hmax_).  Besides the primitives' own, the unions below are safe: every operand is a
@@ -97,8 +102,32 @@ __device__ __forceinline__ D2 ao_sdf(const FrameSdfAo& F, v3 pos, W& w) {       
 #define AO_WITNESS 1       // witnessed five-instruction square roots (sbx_sdf.h Wit), as in k_egg: 0 = the IEEE roots only
 #endif
 
-// One pixel up to (rgb, t) — render_impl :245-285 — with the roots of witness `w`
+// sdf_shadow :183-207 for the ray (o, sun_dir), statement for statement: sdf before the `t > end` test, `d.x < .005` returns
+// `darkest`, then t += d.x, then umbra = min(umbra, 32 * d.x / t) — the spec's min, `(b < a) ? b : a`, under which a NaN quotient
+// leaves umbra as it is (fmin_; not the hardware's minimum), and an IEEE quotient.
+// Its points are finite wherever the hit point is (o = p + .05 sun_dir, t a sum of at most 20 finite distances), so ao_sdf's
+// preconditions hold as they do for the primary march: ao_pipe_far is pointwise; the HW min / max need finite points and see the
+// same primitives; the roots go through the SAME witness `w` — its recorded domain is every argument in [2^-102, +inf), which a
+// point 20 units further out does not leave, and an argument outside it (a point ON a cylinder's axis) is recorded and the wave
+// re-runs the pixel with the IEEE roots, exactly as for the primary march.
+// Lanes leave the loop one by one (the hit lanes of a wave that are lit walk all 20 steps, the ones in umbra stop at the occluder);
+// the loop ends for the wave when its last lane has left — the compiler's exec-mask loop is the wave-level exit.
 template <bool CULL, class W>
+__device__ __forceinline__ float ao_shadow(const FrameSdfAo& F, v3 o, W& w) {
+    float t = 0.f, umbra = 1.f;
+    for (int i = 0; i < 20; ++i) {
+        const v3 pi = o + F.sun_dir * t;
+        const float d = ao_sdf<CULL>(F, pi, w).d;
+        if (t > 20.f) break;
+        if (d < .005f) return .05f;
+        t += d;
+        umbra = fmin_(umbra, 32.f * d / t);
+    }
+    return umbra;
+}
+
+// One pixel up to (rgb, t) — render_impl :245-285 — with the roots of witness `w`
+template <bool CULL, int BUILD, class W>
 __device__ __forceinline__ void ao_pixel(const FrameSdfAo& F, v3 ro, v2 pc, W& w, v3& rgb, float& t, v3& rd) {
     rd = AO_WIT_DIR ? primary_dir(F.cam, pc, w) : primary_dir(F.cam, pc);
     rgb = V3(.1f, .1f, .7f);                                      // background :9-12
@@ -124,6 +153,7 @@ __device__ __forceinline__ void ao_pixel(const FrameSdfAo& F, v3 ro, v2 pc, W& w
                 ao_sdf<CULL>(F, p + V3(e, 0, 0), w).d - ao_sdf<CULL>(F, p - V3(e, 0, 0), w).d,
                 ao_sdf<CULL>(F, p + V3(0, e, 0), w).d - ao_sdf<CULL>(F, p - V3(0, e, 0), w).d,
                 ao_sdf<CULL>(F, p + V3(0, 0, e), w).d - ao_sdf<CULL>(F, p - V3(0, 0, e), w).d));
+            if (BUILD == AO_NORMALS) { rgb = n; return; }        // illuminate :217-219 compiled in (a NaN normal is the pixel's data)
             // sdf_ao :165-181
             float occlusion = 0.f, inv2k = 1.f;
             for (float k = 1.f; k <= 5.f; k += 1.f) {
@@ -135,7 +165,8 @@ __device__ __forceinline__ void ao_pixel(const FrameSdfAo& F, v3 ro, v2 pc, W& w
                 occlusion += inv2k * (.5f * k - dd);
             }
             const float ao = 1.f - clamp_(occlusion, 0.f, 1.f);
-            const float sh = 1.f;
+            float sh = 1.f;
+            if (BUILD == AO_SHADOW) sh = ao_shadow<CULL>(F, p + F.sun_dir * 0.05f, w);   // :269-274 compiled in
             // illuminate :211-243
             v3 accum = V3(0, 0, 0);
             const float sun_ray = fmax_(0.f, dot(F.sun_dir, n));
@@ -157,7 +188,7 @@ __device__ __forceinline__ void ao_pixel(const FrameSdfAo& F, v3 ro, v2 pc, W& w
     }
 }
 
-template <bool CULL, int WIT>      // WIT: 0 IEEE roots, 1 witnessed roots, 2 the witness's test edge (sbx_set_variant 2), as k_egg
+template <bool CULL, int WIT, int BUILD = AO_DEFAULT>   // WIT: 0 IEEE roots, 1 witnessed roots, 2 the witness's test edge (sbx_set_variant 2), as k_egg
 __global__ void __launch_bounds__(WG_THREADS, AO_MIN_WAVES) k_sdf_ao(FrameSdfAo F, RowMap M, float* __restrict__ out) {
     const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();      // (the dispatch order's cost table, RowMap.cost)
     const Pixel px = pixel_of_thread(M);
@@ -169,14 +200,14 @@ __global__ void __launch_bounds__(WG_THREADS, AO_MIN_WAVES) k_sdf_ao(FrameSdfAo 
     if (WIT != 0) {
         Wit<true> w;
         if (WIT == 2) w.lo = 0x3F800000u;
-        ao_pixel<CULL>(F, ro, pc, w, rgb, t, rd);
+        ao_pixel<CULL, BUILD>(F, ro, pc, w, rgb, t, rd);
         if (__builtin_amdgcn_ballot_w64(w.bad) != 0ull) {
             Wit<false> w0;
-            ao_pixel<CULL>(F, ro, pc, w0, rgb, t, rd);
+            ao_pixel<CULL, BUILD>(F, ro, pc, w0, rgb, t, rd);
         }
     } else {
         Wit<false> w0;
-        ao_pixel<CULL>(F, ro, pc, w0, rgb, t, rd);
+        ao_pixel<CULL, BUILD>(F, ro, pc, w0, rgb, t, rd);
     }
     // fog :287-311 (t is the march length at exit)
     const float fog_factor = F.fog_density * exp_(-ro.y * F.fog_falloff)
@@ -189,11 +220,19 @@ __global__ void __launch_bounds__(WG_THREADS, AO_MIN_WAVES) k_sdf_ao(FrameSdfAo 
 
 dim3 sdf_ao_grid(const RowMap& M) { return grid_for(M); }
 
-void launch_sdf_ao(const FrameSdfAo& F, const RowMap& M, float* out, hipStream_t s, int variant) {
-    if (variant == 1) hipLaunchKernelGGL((k_sdf_ao<false, 0>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else if (variant == 2) hipLaunchKernelGGL((k_sdf_ao<true, 2>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else if (variant == 3) hipLaunchKernelGGL((k_sdf_ao<true, 0>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else hipLaunchKernelGGL((k_sdf_ao<true, AO_WITNESS>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+template <int BUILD>
+static void launch_sdf_ao_build(const FrameSdfAo& F, const RowMap& M, float* out, hipStream_t s, int variant) {
+    if (variant == 1) hipLaunchKernelGGL((k_sdf_ao<false, 0, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    else if (variant == 2) hipLaunchKernelGGL((k_sdf_ao<true, 2, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    else if (variant == 3) hipLaunchKernelGGL((k_sdf_ao<true, 0, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    else hipLaunchKernelGGL((k_sdf_ao<true, AO_WITNESS, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+}
+
+// build: 0 SBX_APP_SDF_AO, 1 SBX_APP_SDF_AO_SHADOW, 2 SBX_APP_SDF_AO_NORMALS
+void launch_sdf_ao(const FrameSdfAo& F, const RowMap& M, float* out, hipStream_t s, int variant, int build) {
+    if (build == AO_SHADOW) launch_sdf_ao_build<AO_SHADOW>(F, M, out, s, variant);
+    else if (build == AO_NORMALS) launch_sdf_ao_build<AO_NORMALS>(F, M, out, s, variant);
+    else launch_sdf_ao_build<AO_DEFAULT>(F, M, out, s, variant);
 }
 
 }  // namespace sbx

@@ -706,7 +706,7 @@ static int render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const v
     if (M_in.nrows == 0) return SBX_OK;
     if (device_fault(ctx)) return fail(ctx, SBX_ERR_FAULT, fault_text(ctx));
     // argument checks come before anything is enqueued or recorded
-    if (app < SBX_APP_PLANET || app > SBX_APP_ATMOSPHERE_GROUND) return fail(ctx, SBX_ERR_UNSUPPORTED, "app is not on the accelerated path");
+    if (app < SBX_APP_PLANET || app > SBX_APP_SDF_AO_NORMALS) return fail(ctx, SBX_ERR_UNSUPPORTED, "app is not on the accelerated path");
     if (is_app_2d(app) && (M_in.rgb == 1 || M_in.rgb == 3))
         return fail(ctx, SBX_ERR_UNSUPPORTED, "APP_2D writes its own alpha: three-channel outputs cannot hold its pixels");
     sbx_aux_clouds AC;
@@ -769,10 +769,10 @@ static int render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const v
     case SBX_APP_RAYTRACER: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots); break;
     case SBX_APP_ATMOSPHERE: launch_atmosphere(build_atmosphere(*uni), M, rgba, s, ctx->precision); break;
     case SBX_APP_ATMOSPHERE_GROUND: launch_atmosphere_ground(build_atmosphere_ground(*uni), M, rgba, s, ctx->precision, ctx->variant); break;
-    case SBX_APP_SDF_AO: {
+    case SBX_APP_SDF_AO: case SBX_APP_SDF_AO_SHADOW: case SBX_APP_SDF_AO_NORMALS: {   // one scene, three builds of app_sdf_ao.h (include/sbx.h)
         sbx_aux_sdf_ao A;
         if (aux) A = *(const sbx_aux_sdf_ao*)aux; else sbx_aux_sdf_ao_defaults(&A);
-        launch_sdf_ao(build_sdf_ao(*uni, A), M, rgba, s, sdf_variant);
+        launch_sdf_ao(build_sdf_ao(*uni, A), M, rgba, s, sdf_variant, app == SBX_APP_SDF_AO_SHADOW ? 1 : app == SBX_APP_SDF_AO_NORMALS ? 2 : 0);
         break;
     }
     case SBX_APP_PLANET: launch_planet(build_planet(*uni), M, rgba, s, cull_variant); break;
@@ -985,7 +985,7 @@ int sbx_main_image_batch(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const v
 // ---- sbx_main_image: the per-pixel entry over cached frames ----------------------------------------------------------------
 static int mi_aux_bytes(int app, const void* aux) {
     return !aux ? 0 : ((app == SBX_APP_CLOUDS || app == SBX_APP_CLOUDS_TEX || app == SBX_APP_CLOUDS_SKY) ? (int)sizeof(sbx_aux_clouds)
-                       : (app == SBX_APP_SDF_AO ? (int)sizeof(sbx_aux_sdf_ao)
+                       : ((app == SBX_APP_SDF_AO || app == SBX_APP_SDF_AO_SHADOW || app == SBX_APP_SDF_AO_NORMALS) ? (int)sizeof(sbx_aux_sdf_ao)
                        : (app == SBX_APP_CLOUDS_UE4 ? (int)sizeof(sbx_aux_clouds_ue4) : 0)));
 }
 // the cache key of a frame as words: app, aux size, the uniforms, the aux block (zero padded)
@@ -1250,8 +1250,10 @@ extern "C" int sbx_span_table(int app, const sbx_uniforms* uni, const void* aux,
     const int W = (int)uni->u_res[0], H = (int)uni->u_res[1];
     if (W <= 0 || H <= 0 || (float)W != uni->u_res[0] || (float)H != uni->u_res[1] || W > 65536 || H > 65536) return SBX_ERR_ARG;
     if (!split_ok(H, block_rows, nranks, root_rounds, rounds)) return SBX_ERR_ARG;
-    // APP_FUNC: no cost model (span_probe), its cost is uniform over the frame — every block's span is the whole row
-    if (app < SBX_APP_PLANET || (app > SBX_APP_PLANET_ATMOSPHERE && app != SBX_APP_FUNC && app != SBX_APP_ATMOSPHERE_GROUND)) return SBX_ERR_UNSUPPORTED;
+    // APP_FUNC: no cost model (span_probe), its cost is uniform over the frame — every block's span is the whole row; the builds of
+    // APP_SDF_AO have none either, as APP_SDF_AO itself (the ramps fill the frame from every camera angle)
+    if (app < SBX_APP_PLANET || (app > SBX_APP_PLANET_ATMOSPHERE && app != SBX_APP_FUNC && app != SBX_APP_ATMOSPHERE_GROUND &&
+                                 app != SBX_APP_SDF_AO_SHADOW && app != SBX_APP_SDF_AO_NORMALS)) return SBX_ERR_UNSUPPORTED;
     const int nblocks = (H + block_rows - 1) / block_rows;
     const int ntiles = (W + SPAN_ALIGN - 1) / SPAN_ALIGN;
     const SpanProbe P = span_probe(app, *uni, aux);

@@ -6,7 +6,7 @@
 // mod / mix / floor / max are the GLSL forms of sbx_math.h, PI the binary32 value of 3.14159265359 (src/def.h:51).
 //
 // The phase of t = mod(u_time, 16) and its mix weight depend on the uniforms only: the host decides them once per frame
-// (build_2d, sbx_capi.hip) and launches the kernel of that phase, so the road phase carries no atan2 and the undefined phase
+// (build_2d, sbx_frames.hip) and launches the kernel of that phase, so the road phase carries no atan2 and the undefined phase
 // (t = 4, 8, 12 or NaN: no branch of :82-103 runs, `color` is uninitialised; the port writes (0, 0, 0, 0) times the tent) no
 // sample at all.  NaN and Inf flow through as data (the r = 0 pixel of an odd frame size, points far outside the frame).
 //

@@ -23,7 +23,7 @@
 namespace sbx {
 
 // Is everything but the ground plane farther away than the ground?  Every other member of the union is
-// >= .7 * (|p - oc| - orad) (FrameEgg, built in sbx_capi.hip), so with K = 1.43 (ground + 1e-3) + orad (1.43 > 1/.7),
+// >= .7 * (|p - oc| - orad) (FrameEgg, built in sbx_frames.hip), so with K = 1.43 (ground + 1e-3) + orad (1.43 > 1/.7),
 // |p - oc| > K puts all of them strictly above the ground's distance: sdf() is the ground plane, exactly.
 // The test runs on the WORLD point P against the centre carried to world space (FrameEgg.ocw): |P - ocw| is |p - oc| up to the 1e-6
 // by which a rounded rotation matrix changes a length, far inside the 0.1 % by which 1.43 exceeds 1 / .7 — so a point that is far

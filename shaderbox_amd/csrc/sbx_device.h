@@ -150,7 +150,7 @@ constexpr int CLOUDS_YTAB_ROWS = 4096;      // march steps covered by the per-fr
 constexpr int CLOUDS_YTAB_BYTES = CLOUDS_YTAB_ROWS * 48;
 constexpr int CLOUDS_YTAB_BIG_MAX = 1 << 20;   // longest march served by the context's one on-demand table (48 MB); beyond it: the table-less kernels
 constexpr int CLOUDS_YTAB_RING = 8;         // eager tables: one per REBUILD (key change), round robin; reuse of a slot waits
-                                            // for the launches that may still read it (sbx_capi.hip render_clouds)
+                                            // for the launches that may still read it (sbx_ytab.hip render_clouds)
 constexpr int CLOUDS_YTAB_CAPTURE = 8;      // tables used only by launches recorded into a stream capture
 void launch_clouds_tex(const FrameClouds& F, const RowMap& M, float* out, hipStream_t s, const float* shape_r, int shape_size,
                        const float* detail_r, int detail_size, const float* bounds);     // bounds: {lo1, hi1, lo2, hi2} of the texels, or NULL

@@ -1,0 +1,167 @@
+// shaderbox_amd/csrc/sbx_eval.hip — the hooks that evaluate one piece of the math spec or of a kernel on the device for the tests
+// (include/sbx_test.h), and the binding of what the textured apps sample: t0 of APP_2D_TEX, the noise volumes of APP_CLOUDS_TEX.
+#include "sbx_ctx.h"
+#include <cstring>
+
+using namespace sbx;
+
+extern "C" {
+
+int sbx_pack_unorm8(sbx_ctx* ctx, int width, int rows, const float* rgba, unsigned char* out, int flip_y, void* stream) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (width <= 0 || rows < 0 || (rows > 0 && (!rgba || !out))) return fail(ctx, SBX_ERR_ARG, "bad pack arguments");
+    if (rows == 0) return SBX_OK;
+    const int rc = use_device(ctx);
+    if (rc != SBX_OK) return rc;
+    launch_pack_unorm8(width, rows, flip_y != 0, rgba, out, (hipStream_t)stream);
+    return launched(ctx, "pack launch");
+}
+
+int sbx_math_eval(sbx_ctx* ctx, const char* fn, const float* a, const float* b, float* out, size_t n, void* stream) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!fn || !a || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    static const char* names[] = {"sin", "cos", "tan", "exp", "pow", "acos", "atan2", "hash", "div", "div_rd", "exp_h13", "pow_h", "sqrt_n", "sqrt_ieee", "exp_reg", "exp_reg_plain", "exp_reg64", "exp_reg64_plain", "exp_small", "exp_small_plain", "exp_reg4k", "sin_b40", "div3", "sqrt_rs", "divn", "srgb_pow", "pow_spec"};
+    int id = -1;
+    for (int i = 0; i < 27; ++i) if (std::strcmp(fn, names[i]) == 0) id = i;
+    if (id < 0) return fail(ctx, SBX_ERR_ARG, "unknown math function");
+    if ((id == 4 || id == 6 || id == 8 || id == 9 || id == 11 || id == 22 || id == 24 || id == 26) && !b) return fail(ctx, SBX_ERR_ARG, "binary function needs b");
+    if (n == 0) return SBX_OK;
+    const int rc = use_device(ctx);
+    if (rc != SBX_OK) return rc;
+    if (id >= 21) { if (launch_math_eval(id, a, b, out, n, (hipStream_t)stream) != 0) return fail(ctx, SBX_ERR_ARG, "math function not in the kernel"); }
+    else if (id == 20) launch_exp4k_eval(a, out, n, (hipStream_t)stream);                 // k_atmosphere's 4096-entry form
+    else if (id >= 14) launch_cl_exp_eval(a, out, n, (hipStream_t)stream, id - 14);   // exp_reg_ of sbx_math.h (|x| <= 80): k_clouds' / k_atmosphere's form
+    else if (launch_math_eval(id, a, b, out, n, (hipStream_t)stream) != 0) return fail(ctx, SBX_ERR_ARG, "math function not in the kernel");
+    return launched(ctx, "math_eval launch");
+}
+
+int sbx_noise_eval(sbx_ctx* ctx, const char* fn, const float* xyz, const float* params, float* out, size_t n,
+                   void* stream) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!fn || !xyz || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    static const char* names[] = {"noise_iq", "hash_w", "noise_w", "fbm_worley_tile", "normalize", "wit_normalize", "wit_record",
+                                  "worley_fbm"};
+    int id = -1;
+    for (int i = 0; i < 8; ++i) if (std::strcmp(fn, names[i]) == 0) id = i;
+    if (id < 0) return fail(ctx, SBX_ERR_ARG, "unknown noise function");
+    const float zero[3] = {0.f, 0.f, 0.f};
+    if ((id == 2 || id == 3) && !params) return fail(ctx, SBX_ERR_ARG, "noise_w / fbm_worley_tile need params");
+    if (n == 0) return SBX_OK;
+    const int rc = use_device(ctx);
+    if (rc != SBX_OK) return rc;
+    launch_noise_eval(id, xyz, params ? params : zero, out, n, (hipStream_t)stream);
+    return launched(ctx, "noise_eval launch");
+}
+
+int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!rgba || size <= 0 || size > 1024) return fail(ctx, SBX_ERR_ARG, "bad volume arguments");
+    const int rc = use_device(ctx);
+    if (rc != SBX_OK) return rc;
+    launch_worley_volume(size, rgba, (hipStream_t)stream);
+    return launched(ctx, "worley_volume launch");
+}
+
+int sbx_set_texture2d(sbx_ctx* ctx, int width, int height, int format, const void* texels, void* stream) {
+    if (!ctx) return SBX_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (!texels) {                                                 // back to hlsltoy's checkerboard (kept on the device since sbx_create)
+        ctx->tex2d.bound = false;
+        mi_invalidate(ctx);
+        return SBX_OK;
+    }
+    if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(ctx, SBX_ERR_ARG, "texture sizes run from 1 to 16384");
+    if (format != SBX_FORMAT_RGBA8 && format != SBX_FORMAT_RGBA32F) return fail(ctx, SBX_ERR_ARG, "texture format must be SBX_FORMAT_RGBA8 or SBX_FORMAT_RGBA32F");
+    if (((uintptr_t)texels & (format == SBX_FORMAT_RGBA8 ? 3u : 15u)) != 0) return fail(ctx, SBX_ERR_ARG, "misaligned texels");
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipSetDevice", e);
+    const size_t n = (size_t)width * (size_t)height;
+    if (n > ctx->tex2d.user_cap) {
+        // (a larger texture frees the old copy, which an in-flight render may read: hipFree synchronises the device first)
+        if (ctx->tex2d.user) (void)hipFree(ctx->tex2d.user);
+        ctx->tex2d.user = nullptr; ctx->tex2d.user_cap = 0; ctx->tex2d.bound = false;
+        if ((e = hipMalloc((void**)&ctx->tex2d.user, n * sizeof(float4))) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc (texture)", e);
+        ctx->tex2d.user_cap = n;
+    }
+    if (format == SBX_FORMAT_RGBA8) launch_unorm8_to_float4(static_cast<const unsigned*>(texels), ctx->tex2d.user, n, s);
+    else if ((e = hipMemcpyAsync(ctx->tex2d.user, texels, n * sizeof(float4), hipMemcpyDeviceToDevice, s)) != hipSuccess)
+        return fail(ctx, SBX_ERR_HIP, "texture copy", e);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "texture copy launch", e);
+    ctx->tex2d.w = width; ctx->tex2d.h = height; ctx->tex2d.bound = true;
+    mi_invalidate(ctx);
+    // the call returns when the copy is done (the caller's buffer is not referenced afterwards); inside a stream capture it cannot wait
+    if (!stream_is_capturing(s) && (e = hipStreamSynchronize(s)) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "texture copy", e);
+    return SBX_OK;
+}
+
+int sbx_set_noise_volumes(sbx_ctx* ctx, int shape_size, const float* shape_rgba, int detail_size, const float* detail_rgba,
+                          void* stream) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!shape_rgba || !detail_rgba || shape_size <= 0 || detail_size <= 0 || shape_size > 1024 || detail_size > 1024)
+        return fail(ctx, SBX_ERR_ARG, "bad noise volume arguments");
+    ctx->noise.bounds_valid = false;                                 // whatever happens below, the old volumes' bounds are gone
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipSetDevice", e);
+    const size_t n1 = (size_t)shape_size * shape_size * shape_size, n2 = (size_t)detail_size * detail_size * detail_size;
+    // (re)allocation frees buffers an in-flight render may read: hipFree synchronises the device first
+    if (shape_size != ctx->noise.shape_size || !ctx->noise.shape) {
+        if (ctx->noise.shape) (void)hipFree(ctx->noise.shape);
+        ctx->noise.shape = nullptr; ctx->noise.shape_size = 0;
+        if ((e = hipMalloc((void**)&ctx->noise.shape, n1 * sizeof(float))) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
+        ctx->noise.shape_size = shape_size;
+    }
+    if (detail_size != ctx->noise.detail_size || !ctx->noise.detail) {
+        if (ctx->noise.detail) (void)hipFree(ctx->noise.detail);
+        ctx->noise.detail = nullptr; ctx->noise.detail_size = 0;
+        if ((e = hipMalloc((void**)&ctx->noise.detail, n2 * sizeof(float))) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
+        ctx->noise.detail_size = detail_size;
+    }
+    mi_invalidate(ctx);                                            // cached sbx_main_image frames may have used the old volumes
+    launch_extract_r(shape_rgba, ctx->noise.shape, n1, (hipStream_t)stream);
+    launch_extract_r(detail_rgba, ctx->noise.detail, n2, (hipStream_t)stream);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "noise volume copy launch", e);
+    // The range of the texel values: k_clouds_tex derives a bound on the density from it and, inside that bound, uses the cheaper
+    // exp form that is equal to exp_ there (kern_clouds_tex.hip clouds_tex_density_bound).  The scan is read back here, so the call
+    // waits for its own copies; inside a stream capture nothing can be read back and the volumes stay without bounds (exp_ itself).
+    ctx->noise.bounds_valid = false;
+    if (!stream_is_capturing((hipStream_t)stream)) {
+        if (!ctx->noise.scan && (e = hipMalloc((void**)&ctx->noise.scan, 6 * sizeof(unsigned))) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
+        launch_minmax_r(ctx->noise.shape, n1, ctx->noise.scan, (hipStream_t)stream);
+        launch_minmax_r(ctx->noise.detail, n2, ctx->noise.scan + 3, (hipStream_t)stream);
+        unsigned h[6];
+        if ((e = hipMemcpyAsync(h, ctx->noise.scan, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream)) != hipSuccess ||
+            (e = hipStreamSynchronize((hipStream_t)stream)) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "noise volume scan", e);
+        if (!h[2] && !h[5] && h[0] <= h[1] && h[3] <= h[4]) {
+            ctx->noise.bounds[0] = minmax_key_to_float(h[0]); ctx->noise.bounds[1] = minmax_key_to_float(h[1]);
+            ctx->noise.bounds[2] = minmax_key_to_float(h[3]); ctx->noise.bounds[3] = minmax_key_to_float(h[4]);
+            ctx->noise.bounds_valid = true;
+        }
+    }
+    return SBX_OK;
+}
+
+int sbx_tex3d_eval(sbx_ctx* ctx, int size, const float* rgba, const float* xyz, float* out, size_t n, void* stream) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!rgba || !xyz || !out || size <= 0 || size > 1024) return fail(ctx, SBX_ERR_ARG, "bad tex3d arguments");
+    if (n == 0) return SBX_OK;
+    const int rc = use_device(ctx);
+    if (rc != SBX_OK) return rc;
+    launch_tex3d_eval(size, rgba, xyz, out, n, (hipStream_t)stream);
+    return launched(ctx, "tex3d_eval launch");
+}
+
+}  // extern "C"
+
+void sbx::release(NoiseVolumes& N) {
+    if (N.shape) (void)hipFree(N.shape);
+    if (N.detail) (void)hipFree(N.detail);
+    if (N.scan) (void)hipFree(N.scan);
+    N = NoiseVolumes();
+}
+void sbx::release(Texture2d& T) {
+    if (T.def) (void)hipFree(T.def);
+    if (T.user) (void)hipFree(T.user);
+    T = Texture2d();
+}

@@ -1,0 +1,337 @@
+// shaderbox_amd/csrc/sbx_frames.hip — the per-frame constant block of every app, and the defaults of the aux blocks.
+//
+// What the reference's hosts and the frame-constant prologue of each mainImage() compute from the uniforms alone, evaluated once per
+// frame on the host with the shared math spec (sbx_math.h) and handed to the kernels as arguments.  Pure host math over the spec: it
+// is compiled with the library's flags, -ffp-contract=off among them, because they are part of that spec.
+#include "sbx_ctx.h"
+#include <cstring>
+
+using namespace sbx;
+
+namespace sbx {
+
+FrameClouds build_clouds(const sbx_uniforms& U, const sbx_aux_clouds& A, bool sky_sphere) {
+    FrameClouds F;
+    // setup_camera app_clouds.h:23-30
+    const v3 eye = V3(0, -.5f, 0);
+    const float angle = U.u_mouse[0] * .5f;
+    const v3 look_at = mul(rotate_around_y(angle), V3(0, 0, -1));
+    F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, eye, look_at);   // FOV 1. :219
+    F.sun_dir = V3(A.sun_dir[0], A.sun_dir[1], A.sun_dir[2]);
+    F.sun_color = V3(A.sun_color[0], A.sun_color[1], A.sun_color[2]);
+    const v3 wind = V3(A.wind_dir[0], A.wind_dir[1], A.wind_dir[2]);
+    F.wind_off = wind * U.u_time * (1.f / .001f);                      // :167
+    F.sun_power = A.sun_power;
+    F.sigma = A.sigma_scattering;
+    F.steps = A.cld_march_steps;
+    F.lsteps = A.illum_march_steps;
+    F.dt = A.cld_thick / (float)A.cld_march_steps;                     // :98,180
+    F.cov = 1.f - A.cld_coverage;                                      // :83
+    F.cov_hi = F.cov + .0135f;                                         // :84
+    F.cov_rd = recip64(F.cov_hi - F.cov);
+    F.cov_d = F.cov_hi - F.cov;
+    F.cov_r = 1.0f / F.cov_d;
+    F.lip_ok = 0;                                                      // decided per launch (launch_clouds)
+    F.exp_small = 0;
+    F.thr1 = F.thr2 = 0.f;                                             // set per launch (launch_clouds)
+    // SKY_SPHERE (:8,14-19,154-162)
+    F.sky = sky_sphere ? 1 : 0;
+    F.atm_y = A.atm_ground_y;
+    F.atm_r = A.atm_radius;
+    F.nf = sky_sphere ? ((1.f / A.atm_radius) * 10.f) : .001f;        // cld_noise_factor :18 / :20
+    F.sky_rot = rotate_around_x(U.u_time);                            // :160
+    return F;
+}
+
+static BezierFrame bezier_frame(v3 a, v3 b, v3 c) {                    // sdf.h:147-153
+    BezierFrame B;
+    B.b = b;
+    B.w = normalize(cross(c - b, a - b));
+    B.u = normalize(c - b);
+    B.v = normalize(cross(B.w, B.u));
+    B.a2 = V2(dot(a - b, B.u), dot(a - b, B.v));
+    B.c2 = V2(dot(c - b, B.u), dot(c - b, B.v));
+    B.bc = (a + b + c) * (1.f / 3.f);              // any point works; the radius below is measured from it
+    B.br = fmax_(fmax_(length(a - B.bc), length(b - B.bc)), length(c - B.bc)) * 1.001f + 1e-4f;
+    return B;
+}
+static CylFrame cyl_frame(v3 P0, v3 P1) {                              // sdf.h:104,106-107
+    CylFrame C;
+    C.dir = normalize(P1 - P0);
+    C.len1 = length(P1);
+    C.len0 = length(P0);
+    return C;
+}
+static v3 ik_solver(v3 start, v3 goal_abs, float L1, float L2) {       // IK.h:5-52
+    const v3 goal = goal_abs - start;
+    const float G = length(goal);
+    const float cos_theta = (L1 * L1 + G * G - L2 * L2) / (2.f * L1 * G);
+    const float sin_theta = sqrt_(1.f - cos_theta * cos_theta);
+    const m3 rot = M3(cos_theta, -sin_theta, 0, sin_theta, cos_theta, 0, 0, 0, 1.f);
+    return start + mul(rot, normalize(goal) * L1);
+}
+FrameEgg build_egg(const sbx_uniforms& U) {
+    FrameEgg F;
+    F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(.0f, .25f, 5.25f), V3(.0f, .25f, .0f));   // app_egg.h:23-27,253
+    const float t = U.u_time;
+    F.rot_y = rotate_around_y(t * -100.0f);                            // :40
+    const v3 wheel_pos = V3(0, 1.2f, 0);
+    const float pedal_radius = 0.3f, pedal_speed = 400.f, pedal_off = 0.2f;
+    const m3 rot_z = rotate_around_z(-t * pedal_speed);                // :73,76
+    F.left_foot = wheel_pos + mul(rot_z, V3(0.f, pedal_radius, pedal_off));
+    F.right_foot = wheel_pos + mul(rot_z, V3(0.f, -pedal_radius, -pedal_off));
+    const v3 side = V3(0, 0, pedal_off);
+    const float femur = 0.8f, tibia = 0.75f;
+    const v3 zero = V3(0.f, 0.f, 0.f);
+    const v3 knee_l = ik_solver(zero + side, F.left_foot, femur, tibia);   // :84-85
+    const v3 knee_r = ik_solver(zero - side, F.right_foot, femur, tibia);  // :95-96
+    F.leg_l = bezier_frame(-(zero + side), -knee_l, -F.left_foot);         // :111-113
+    F.leg_r = bezier_frame(-(zero - side), -knee_r, -F.right_foot);        // :114-116
+    const v3 left_toe = normalize(V3(F.left_foot.y - knee_l.y, knee_l.x - F.left_foot.x, 0));     // :120
+    const v3 right_toe = normalize(V3(F.right_foot.y - knee_r.y, knee_r.x - F.right_foot.x, 0));  // :125
+    F.foot_l = cyl_frame(zero, left_toe / 8.f);
+    F.foot_r = cyl_frame(zero, right_toe / 8.f);
+    // Bounding sphere of the egg, legs, feet and wheel (everything but the ground), see kern_egg.hip egg_far: each
+    // member m has a centre c and a radius rho such that its sdf value is >= .7 * (|p - c| - rho) wherever that is
+    // positive: egg spheres r + .36 (two smooth-mins of k = .5 lower the union by <= .25), tubes br + .061 (the .85
+    // factor and the thickness), toe cylinders .161 around their midpoint (max(axis, slabs) >= |.|/sqrt2 - 1/16),
+    // wheel 1.03.
+    F.foot_ml = -F.left_foot + left_toe * (-1.f / 16.f);
+    F.foot_mr = -F.right_foot + right_toe * (-1.f / 16.f);
+    const float egg_y = 0.65f;
+    const v3 cs[8] = {V3(0, egg_y, 0), V3(0, egg_y - 0.45f, 0), V3(0, egg_y + 0.45f, 0), F.leg_l.bc, F.leg_r.bc,
+                      -F.left_foot + left_toe * (-1.f / 16.f), -F.right_foot + right_toe * (-1.f / 16.f), -wheel_pos};
+    const float rs[8] = {.475f + .36f, .25f + .36f, .25f + .36f, F.leg_l.br + .061f, F.leg_r.br + .061f, .161f, .161f, 1.03f};
+    v3 c = V3(0, 0, 0);
+    for (int i = 0; i < 8; ++i) c = c + cs[i] * .125f;
+    float R = 0.f;
+    for (int i = 0; i < 8; ++i) R = fmax_(R, length(cs[i] - c) + rs[i]);
+    F.oc = c;
+    F.orad = R * 1.001f + 1e-3f;
+    F.ocw = mul(transpose(F.rot_y), c + V3(0, 0.5f, 3.5f));        // p = rot_y P - (0, .5, 3.5)  <=>  P = rot_y^T (p + (0, .5, 3.5))
+    return F;
+}
+
+FrameRaytracer build_raytracer(const sbx_uniforms& U) {
+    FrameRaytracer F;
+    const float cb = 2.f;                                              // cb_plane_dist cornell_box.h:62
+    // setup_camera app_raytracer.h:38-44
+    v2 mouse = V2(0, 0);
+    if (!(U.u_mouse[0] < 1e-4f)) mouse = V2(2.f * (U.u_res[0] / U.u_mouse[0]) - 1.f, 2.f * (U.u_res[1] / U.u_mouse[1]) - 1.f);
+    const m3 rot_y = rotate_around_y(mouse.x * 30.f);
+    const v3 eye = mul(rot_y, V3(0, cb, 2.333f * cb));
+    F.cam = make_camera(U.u_res[0], U.u_res[1], tan_(radians_(30.f)), eye, V3(0, cb, 0));   // FOV :138
+    // materials: zero-initialised slots (App. B5), mat_debug :20-25, cornell box cornell_box.h:47-55
+    for (int i = 0; i < 8; ++i) F.mats[i] = RtMaterial{V3(0, 0, 0), 0.f, 0.f, 0.f, 0.f};
+    F.mats[0] = RtMaterial{V3(1.f, 1.f, 1.f), 0.f, 1.f, 0.f, 0.f};
+    F.mats[1] = RtMaterial{V3(0.7913f, 0.7913f, 0.7913f), .5f, 1.f, 0.f, 0.f};
+    F.mats[2] = RtMaterial{V3(0.6795f, 0.0612f, 0.0529f), .5f, 1.f, 0.f, 0.f};
+    F.mats[3] = RtMaterial{V3(0.1878f, 0.1274f, 0.4287f), .5f, 1.f, 0.f, 0.f};
+    F.mats[4] = RtMaterial{V3(0.95f, 0.64f, 0.54f), .1f, 1.f, 1.f, 0.f};
+    F.mats[5] = RtMaterial{V3(1.f, 0.77f, 0.345f), .05f, 1.333f, 1.f, 0.f};
+    for (int i = 0; i < 8; ++i) {                                      // util_optics.h:10-11 with n1 = 1, per material
+        const float Rn = (1.f - F.mats[i].ior) / (1.f + F.mats[i].ior);
+        F.mats[i].r0 = Rn * Rn;
+    }
+    // planes, in array-index order ground, behind, front, ceiling, left, right  cornell_box.h:57-69
+    F.planes[0] = RtPlane{V3(0, -1, 0), 0.f, 1};
+    F.planes[1] = RtPlane{V3(0, 0, -1), -cb, 1};
+    F.planes[2] = RtPlane{V3(0, 0, 1), cb, 1};
+    F.planes[3] = RtPlane{V3(0, 1, 0), 2.f * cb, 1};
+    F.planes[4] = RtPlane{V3(1, 0, 0), cb, 2};
+    F.planes[5] = RtPlane{V3(-1, 0, 0), -cb, 3};
+    // spheres cornell_box.h:71-82 + animation app_raytracer.h:29-34
+    const float s = sin_(U.u_time), c = cos_(U.u_time);
+    F.spheres[0] = RtSphere{V3(0, 2.5f * cb + 0.4f, 0), 1.5f, 0, recip64(1.5f)};
+    F.spheres[1] = RtSphere{V3(0.75f, 1, -0.75f) + V3(0, abs_(s), c + 1.f), 0.75f, 4, recip64(0.75f)};
+    F.spheres[2] = RtSphere{V3(-0.75f, 0.75f, 0.f), 0.75f, 5, recip64(0.75f)};
+    F.light = V3(0, 2.f * cb - 0.2f, 1.5f);
+    return F;
+}
+
+FrameAtmosphere build_atmosphere(const sbx_uniforms& U) {
+    FrameAtmosphere F;
+    F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(0, 0, 0), V3(0, 1, 0));   // app_atmosphere.h:164-175,230
+    const m3 rot = rotate_around_x(-abs_(sin_(U.u_time / 2.f)) * 90.f);             // :179
+    F.sun_dir = mul(V3(0, 1, 0), rot);                                              // :180 (v * M)
+    return F;
+}
+
+// app_atmosphere.h without FROM_SPACE: the camera of :172-173 (both y values exact in binary32), the same sun
+FrameAtmosphere build_atmosphere_ground(const sbx_uniforms& U) {
+    FrameAtmosphere F = build_atmosphere(U);
+    const float earth_radius = 6360e3f;                                             // :37
+    F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(0, earth_radius + 1.f, 0), V3(0, earth_radius + 1.5f, -1));   // :172-173,230
+    return F;
+}
+
+FrameSdfAo build_sdf_ao(const sbx_uniforms& U, const sbx_aux_sdf_ao& A) {
+    FrameSdfAo F;
+    const m3 rot = rotate_around_y(U.u_time * 50.f);                   // app_sdf_ao.h:45-50
+    F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, mul(rot, V3(0, 3, 5)), V3(0, 0, 0));
+    F.rx_m90 = rotate_around_x(-90.f);
+    F.ry_180 = rotate_around_y(180.f);
+    F.sun_dir = normalize(V3(1, 2, 1));
+    F.fog_density = A.fog_density;
+    F.fog_falloff = A.fog_falloff;
+    return F;
+}
+
+static Capsule capsule(v3 a, v3 b) {                                   // sdf.h:168-169
+    Capsule c;
+    c.a = a;
+    c.ab = b - a;
+    c.rd = recip64(dot(c.ab, c.ab));
+    return c;
+}
+FrameVinyl build_vinyl(const sbx_uniforms& U, int steps) {
+    FrameVinyl F;
+    F.steps = steps;                                                   // :411-416
+    const float t = U.u_time;
+    F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(0, 5.75f, 6.75f), V3(0, -2.5f, 0));   // app_vinyl.h:56-64,459
+    F.platter_rot = mul(rotate_around_y(t * 200.f), rotate_around_x(sin_(t) * .1f));          // :417,424-426
+    F.sun_dir = normalize(V3(-1, 4, -3));
+    F.ry30 = rotate_around_y(30.f);
+    F.rym30 = rotate_around_y(-30.f);
+    F.wobble = rotate_around_x(sin_(t * 3.6758f) * .1f);
+    const float R = .1f, H = .8f;
+    const v3 base_p = V3(-7, 0, -5);
+    const v3 a1 = V3(-6, H, -3), a11 = V3(-4.25f, H, 2), a2 = V3(-4.1f, H, 2.45f), a33 = V3(-3.5f, H, 3), a3 = V3(-2, H, 4);
+    F.arm1 = capsule(base_p + V3(-1, H, -2), a1);
+    F.arm2 = capsule(a1, a11);
+    F.arm3 = capsule(a33, a3);
+    F.armb = bezier_frame(a11, a2, a33);
+    F.a3 = a3;
+    const v3 arm_fwd = normalize(a3 - a33);
+    const v3 arm_up = V3(0, 1, 0);
+    const v3 arm_right = cross(arm_fwd, arm_up);
+    F.arm_xform = m3{arm_fwd, arm_up, arm_right};
+    const float clr_r = R * 1.5f;
+    F.collar = cyl_frame(V3(0, 0, 0), V3(0, 0, 0) + arm_fwd * .05f);
+    F.fl_rot = mul(F.arm_xform, rotate_around_x(45.f));
+    F.fl_sub1 = arm_right * clr_r;
+    F.fl_sub2 = arm_up * clr_r;
+    F.fl_rot2 = rotate_around_x(-45.f);
+    F.ctg_rot = rotate_around_z(44.f);
+    F.cut_rx10 = rotate_around_x(10.f);
+    F.cut_rym5 = rotate_around_y(-5.f);
+    F.cut2_rz10 = rotate_around_z(10.f);
+    (void)R;
+    return F;
+}
+
+FramePlanet build_planet(const sbx_uniforms& U, bool atm_sky) {
+    FramePlanet F;
+    F.atm_sky = atm_sky ? 1 : 0;
+    F.atm_sun = build_atmosphere(U).sun_dir;
+    F.cam = make_camera(U.u_res[0], U.u_res[1], tan_(radians_(30.f)), V3(0, 0, -2.5f), V3(0, 0, 2));   // app_planet.h:47-58,368
+    const m3 rot_y = rotate_around_y(27.f);                            // :307
+    F.rot = mul(rotate_around_x(U.u_time * -12.f), rot_y);             // :308
+    F.rot_cloud = mul(rotate_around_x(U.u_time * 8.f), rot_y);         // :309
+    F.rot_t = transpose(F.rot);                                        // :356
+    F.L = mul(F.rot, normalize(V3(1, 1, 0)));                          // :289
+    return F;
+}
+
+FrameCloudsBest build_clouds_best(const sbx_uniforms& U) {
+    FrameCloudsBest F;
+    F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(0, 1.f, 0), V3(0, 1.6f, -1));   // app_clouds_best.h:635-641,663
+    F.sun_dir = normalize(V3(0, 0, -1));                               // :415
+    F.wind_z = -U.u_time * .2f;                                        // :414
+    const float cld_thick = 90.f;                                      // :412
+    F.march_step = cld_thick / float(CB_STEPS);                        // :603
+    F.cov = .3125f;                                                    // :411
+    F.cov_rd = recip64((F.cov + .035f) - F.cov);                       // smoothstep(cov, cov + .035, dens) :583
+    // y of the march: projection.y = dir.y / dir.y = 1, so origin.y = eye.y + 1 * 100 and iter.y = 1 * march_step
+    const float origin_y = F.cam.eye.y + 1.0f * 100.f;                 // :611
+    const float iter_y = 1.0f * F.march_step;                          // :606
+    float pos_y = origin_y;
+    for (int i = 0; i < CB_STEPS; ++i) {
+        const float height = (pos_y - origin_y) / cld_thick;           // :619-620
+        F.row[i].illum = exp_(height) / 1.95f;                         // illuminate_volume :591-597
+        float q = (pos_y * .001f + 0.f) * 2.032f;                      // density_func :581-582 (wind.y = 0)
+        for (int k = 0; k < 5; ++k) { F.row[i].qy[k] = q; q = q * 2.6434f; }   // fbm: p *= lacunarity
+        pos_y = pos_y + iter_y;                                        // :628
+    }
+    return F;
+}
+
+FrameCloudsUe4 build_clouds_ue4(const sbx_uniforms& U, const sbx_aux_clouds_ue4& A) {
+    FrameCloudsUe4 F;
+    const v3 eye = V3(0, -.5f, 0);                                      // host mapping: src/app_clouds.h:23-30
+    const v3 look_at = mul(rotate_around_y(U.u_mouse[0] * .5f), V3(0, 0, -1));
+    F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, eye, look_at);
+    if (A.use_dirs) {
+        F.sun_dir = V3(A.sun_dir[0], A.sun_dir[1], A.sun_dir[2]);
+        F.wind_dir = V3(A.wind_dir[0], A.wind_dir[1], A.wind_dir[2]);
+    } else {
+        F.sun_dir = normalize(V3(0, abs_(sin_(U.u_time * .3f)), -1));    // SUN_DIR app_clouds.usf:14
+        F.wind_dir = V3(0, 0, -U.u_time * .2f);                          // WIND_DIR :13
+    }
+    F.march_step = A.thickness / float(UE4_STEPS);                      // :199
+    F.absorbtion = A.absorbtion;
+    F.cov = 1.f - A.coverage;                                           // :256
+    F.cov_rd = recip64((F.cov + A.fuzziness) - F.cov);                  // :175
+    F.cov_d = (F.cov + A.fuzziness) - F.cov;
+    F.cov_r = 1.0f / F.cov_d;
+    for (int i = 0; i < UE4_STEPS; ++i) F.eh[i] = exp_(float(i) / float(UE4_STEPS)) / 1.75f;   // :213,221
+    return F;
+}
+
+// APP_2D / APP_2D_TEX (src/app_2d.h:70-111): what mainImage decides from the uniforms alone
+Frame2d build_2d(const sbx_uniforms& U) {
+    Frame2d F{};
+    F.rres_x = recip64(U.u_res[0]); F.rres_y = recip64(U.u_res[1]);
+    F.rpi = recip64(3.14159265359f);                                   // PI, src/def.h:51
+    const float t = mod_(U.u_time, 16.f);                              // :80
+    F.w = 0.f; F.time = 1.f;
+    if (t < 4.f) { F.phase = 0; F.time = U.u_time; }                   // :82
+    else if (t > 4.f && t < 8.f) { F.phase = 1; F.w = (t - 4.f) / 4.f; }     // :88
+    else if (t > 8.f && t < 12.f) { F.phase = 2; F.time = U.u_time; }        // :94
+    else if (t > 12.f) { F.phase = 3; F.w = (t - 12.f) / 4.f; }              // :99
+    else F.phase = 4;                                                  // t = 4, 8, 12 or NaN: no branch runs
+    F.omw = 1.f - F.w;
+    return F;
+}
+
+}  // namespace sbx
+
+extern "C" {
+
+void sbx_checkerboard_texture(int size, int freq, uint32_t* out) {    // hlsltoy.cpp:66-87 (square: its buffer[y*h + x])
+    if (!out || size <= 0) return;
+    for (int y = 0; y < size; ++y)
+        for (int x = 0; x < size; ++x)
+            out[(size_t)y * size + x] = ((x & freq) == (y & freq)) ? 0xff000000u : 0xffffffffu;
+}
+
+void sbx_aux_clouds_ue4_defaults(sbx_aux_clouds_ue4* a) {              // app_clouds.usf:4-7
+    if (!a) return;
+    std::memset(a, 0, sizeof(*a));
+    a->coverage = .50f; a->thickness = 15.f; a->absorbtion = 1.030725f; a->fuzziness = 0.035f;
+    a->sun_dir[2] = -1.f; a->use_dirs = 0;
+}
+
+void sbx_aux_clouds_defaults(sbx_aux_clouds* a) {                      // uniform_buffer.h:39-55
+    if (!a) return;
+    std::memset(a, 0, sizeof(*a));
+    a->wind_dir[2] = .2f;
+    a->sun_dir[2] = -1.f;
+    a->sun_color[0] = 1.f; a->sun_color[1] = .7f; a->sun_color[2] = .55f;
+    a->sun_power = 8.f;
+    a->cld_march_steps = 100;
+    a->illum_march_steps = 6;
+    a->sigma_scattering = .15f;
+    a->cld_coverage = .535f;
+    a->cld_thick = 125.f;
+    a->atm_radius = 5000.f;
+    a->atm_ground_y = 4750.f;
+}
+void sbx_aux_sdf_ao_defaults(sbx_aux_sdf_ao* a) {                      // uniform_buffer.h:56-60
+    if (!a) return;
+    std::memset(a, 0, sizeof(*a));
+    a->fog_density = .1f;
+    a->fog_falloff = .5f;
+}
+
+}  // extern "C"

@@ -22,6 +22,7 @@
 // loaded.  RCCL itself is dlopen'ed on first use, so a single-GPU host of libsbx never needs it.
 #include "../../include/sbx.h"
 #include "../../include/sbx_test.h"
+#include "sbx_apps.h"
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <cstdio>
@@ -483,7 +484,7 @@ int sbx_multi_render(sbx_multi* m, int app, const sbx_uniforms* uni, const void*
     if (!m) return SBX_ERR_ARG;
     if (!uni || !frame) return mfail(m, SBX_ERR_ARG, "NULL uniforms or frame");
     // APP_2D writes its own alpha (src/app_2d.h:108) and the exchanges move 3-channel slabs: multi-GPU frames of it are not offered
-    if (app == SBX_APP_2D || app == SBX_APP_2D_TEX) return mfail(m, SBX_ERR_UNSUPPORTED, "APP_2D / APP_2D_TEX: no multi-GPU frames");
+    if (sbx::app_owns_alpha(app)) return mfail(m, SBX_ERR_UNSUPPORTED, "APP_2D / APP_2D_TEX: no multi-GPU frames");
     const int W = (int)uni->u_res[0], H = (int)uni->u_res[1];
     if (W <= 0 || H <= 0 || (float)W != uni->u_res[0] || (float)H != uni->u_res[1]) return mfail(m, SBX_ERR_ARG, "bad u_res");
     const int n = (int)m->ranks.size();

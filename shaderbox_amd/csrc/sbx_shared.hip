@@ -21,9 +21,7 @@
 // event, so that the render stream carries [wait][render] instead of [wait][render][set], was measured and is SLOWER — an event
 // record plus a cross-stream wait per frame cost more than a one-thread kernel in line (eighth-frames of an 8-rank CLOUDS split:
 // 0.304 -> 0.355 ms per frame, profiles/r05_log.md).
-#include "../../include/sbx.h"
-#include "../../include/sbx_test.h"
-#include "sbx_device.h"
+#include "sbx_ctx.h"
 #include <cstring>
 #include <unistd.h>
 
@@ -90,10 +88,6 @@ __global__ void __launch_bounds__(256) k_model_landing(const uint4* __restrict__
     }
     while (wall_clock64() < t0 + ticks) __builtin_amdgcn_s_sleep(8);
 }
-
-unsigned* fault_word_device(int device);         // sbx_capi.hip: the device's sticky fault word, as a device pointer
-int ctx_device(const sbx_ctx* ctx);
-int ctx_fail(sbx_ctx* ctx, int code, const char* what, hipError_t e);
 
 }  // namespace sbx
 

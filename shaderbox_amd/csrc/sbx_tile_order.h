@@ -1,5 +1,5 @@
 // sbx_tile_order.h — the host side of the DISPATCH ORDER (RowMap.order / .cost): which launches get a table, when one is built, adopted
-// and retired.  Included by sbx_capi.hip only; the sort itself is kern_util.hip (launch_order_build).  DESIGN.md 5.1,
+// and retired.  Host only (sbx_ctx.h); the sort itself is kern_util.hip (launch_order_build).  DESIGN.md 5.1,
 // profiles/r06_tile_order.txt.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,6 +7,7 @@
 #include <cstring>
 #include <utility>
 #include <vector>
+#include "sbx_apps.h"
 #include "sbx_device.h"
 #include "sbx_frame.h"
 
@@ -19,14 +20,7 @@ namespace sbx {
 // later and every TILE_ORDER_REFRESH launches after that.  A context keeps up to TILE_ORDER_KEYS shapes per app (least recently used
 // replaced): the ranks of an emulated multi-GPU frame driven through one context each keep their table, as separate processes would.
 constexpr int TILE_ORDER_RING = 4, TILE_ORDER_REFRESH = 64, TILE_ORDER_KEYS = 8;
-// What a MOVING scene means for an app's table (measured on animated frames, profiles/r06_tile_order.txt section 11):
-//   TILE_SCENE_FREE    the costs do not follow the scene (APP_VINYL: -7 % standing or moving): the plain refresh schedule
-//   TILE_SCENE_REFRESH they drift with it (APP_CLOUDS: a table 8-64 frames old keeps 0.6-3 % of the 6 % a fresh one gives): while the
-//                      scene moves the table is rebuilt behind EVERY launch (23 us of a 2.2-3.4 ms frame: -3.6 ... -4.5 %)
-//   TILE_SCENE_KEYED   they jump with it (APP_EGG: the silhouette's 16 x 4-pixel tiles are others a frame later; with tables even one
-//                      frame old an animated launch is 8-27 % SLOWER than in the kernel's own hot-first order): the scene is part of
-//                      the table's key — a scene that stands still gets its table, a moving one never does
-enum { TILE_SCENE_FREE = 0, TILE_SCENE_REFRESH = 1, TILE_SCENE_KEYED = 2 };
+// (what a MOVING scene means for an app's table — the TILE_SCENE_* policies — is a fact about the app: sbx_apps.h)
 struct TileOrder {
     unsigned* mem = nullptr;               // cost | classes | TILE_ORDER_RING tables, `cap` words each | the sort's histograms
     size_t cap = 0;
@@ -43,7 +37,7 @@ struct TileOrder {
 };
 // a context's tables: by app id (enum sbx_app), a few launch shapes each
 struct TileOrderSet {
-    TileOrder tab[16][TILE_ORDER_KEYS];
+    TileOrder tab[SBX_APP_COUNT][TILE_ORDER_KEYS];
     unsigned long long clock = 0;
     hipStream_t last_stream = nullptr;     // the stream of the last launch that could take an order, and how many in a row came on it
     int same_stream = 0;
@@ -74,7 +68,7 @@ static bool tile_order_slot_free(TileOrderSet& S, TileOrder& T, int slot) {
 }
 static TileOrder* tile_order_begin(TileOrderSet& S, int app, RowMap& M, dim3 grid, hipStream_t s, bool capturing, unsigned long long scene, int scene_policy) {
     static const int mode = [] { const char* v = getenv("SBX_TILE_ORDER"); return v ? atoi(v) : 1; }();   // 0 off; 2: costs and tables but no order (debugging)
-    if (mode == 0 || capturing || app < 0 || app >= 16 || M.frag || M.r0 != 0 || grid.x == 0 || grid.x > 0xffffu || grid.y > 0xffffu) return nullptr;
+    if (mode == 0 || capturing || !app_valid(app) || M.frag || M.r0 != 0 || grid.x == 0 || grid.x > 0xffffu || grid.y > 0xffffu) return nullptr;
     const size_t n = (size_t)grid.x * grid.y;
     if (n < 4096) return nullptr;                                 // (small launches: nothing to order)
     const bool keyed = scene_policy == TILE_SCENE_KEYED;

@@ -1,0 +1,116 @@
+// shaderbox_amd/csrc/sbx_ytab.hip — APP_CLOUDS' y tables (YTables, sbx_ctx.h): which table a launch of k_clouds reads, when one
+// is rebuilt, and who has to wait for whom.
+#include "sbx_ctx.h"
+#include <cstring>
+
+namespace sbx {
+
+// APP_CLOUDS launch with the y-table bookkeeping.  Three cases:
+//  (1) no table (per-lane variant, or a step count the table does not cover): nothing cached, nothing touched;
+//  (2) the stream is being captured: the build goes into the capture, into a slot of the capture ring, together with
+//      the render kernel; cache key, events and the eager ring are left alone (nothing has executed yet);
+//  (3) eager: rebuild into the next ring slot only when the key changed — after waiting for every launch that may
+//      still be reading that slot — and record, per stream, an event behind each consumer of the current slot.
+int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rgba, hipStream_t s, bool capturing) {
+    const bool uses_table = ctx->variant == 0 && F.steps > 0 && F.steps <= CLOUDS_YTAB_ROWS;
+    if (!uses_table && ctx->variant == 0 && F.steps > CLOUDS_YTAB_ROWS && F.steps <= CLOUDS_YTAB_BIG_MAX && !capturing) {
+        // (4) a march longer than the ring's tables: the context's one big table (round 3 fell back to the table-less kernels
+        //     here, ~2x slower per step)
+        const float key[3] = {F.cam.eye.y, F.wind_off.y, F.dt};
+        hipError_t e;
+        if (!ctx->ytab.have_big_ready) {
+            if ((e = hipEventCreateWithFlags(&ctx->ytab.big_ready, hipEventDisableTiming)) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipEventCreate", e);
+            ctx->ytab.have_big_ready = true;
+        }
+        const bool rebuild = !ctx->ytab.big_valid || ctx->ytab.big_steps != F.steps || std::memcmp(key, ctx->ytab.big_key, sizeof(key)) != 0;
+        if (rebuild) {
+            ctx->ytab.big_valid = false;
+            if ((e = hipDeviceSynchronize()) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipDeviceSynchronize", e);   // readers of the old table
+            if (F.steps > ctx->ytab.big_rows) {
+                if (ctx->ytab.big) (void)hipFree(ctx->ytab.big);
+                ctx->ytab.big = nullptr; ctx->ytab.big_rows = 0;
+                const int rows = (F.steps + 4095) / 4096 * 4096;
+                if ((e = hipMalloc((void**)&ctx->ytab.big, (size_t)rows * 48)) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
+                ctx->ytab.big_rows = rows;
+            }
+        } else {
+            (void)hipStreamWaitEvent(s, ctx->ytab.big_ready, 0);
+        }
+        launch_clouds(F, M, rgba, s, 0, ctx->ytab.big, ctx->ytab.big_rows, rebuild);
+        if (rebuild) {
+            (void)hipEventRecord(ctx->ytab.big_ready, s);
+            std::memcpy(ctx->ytab.big_key, key, sizeof(key));
+            ctx->ytab.big_steps = F.steps;
+            ctx->ytab.big_valid = true;
+        }
+        return SBX_OK;
+    }
+    if (!uses_table) {
+        launch_clouds(F, M, rgba, s, ctx->variant, nullptr, 0, false);
+        return SBX_OK;
+    }
+    if (capturing) {
+        char* tab = ctx->ytab.ring + (size_t)(CLOUDS_YTAB_RING + (ctx->ytab.cap_next++ % CLOUDS_YTAB_CAPTURE)) * CLOUDS_YTAB_BYTES;
+        launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, true);
+        return SBX_OK;
+    }
+    const float key[3] = {F.cam.eye.y, F.wind_off.y, F.dt};
+    const bool rebuild = !ctx->ytab.valid || F.steps != ctx->ytab.steps || std::memcmp(key, ctx->ytab.key, sizeof(key)) != 0;
+    if (!ctx->ytab.have_ready) {
+        if (hipEventCreateWithFlags(&ctx->ytab.ready, hipEventDisableTiming) != hipSuccess)
+            return fail(ctx, SBX_ERR_HIP, "hipEventCreate");
+        ctx->ytab.have_ready = true;
+    }
+    int slot = ctx->ytab.slot;
+    if (rebuild) {
+        slot = (int)(ctx->ytab.next++ % CLOUDS_YTAB_RING);
+        YTables::Slot& sl = ctx->ytab.slots[slot];
+        // Earlier readers of the slot we are about to overwrite: every stream that launched a reader of it.  The event is recorded
+        // NOW, on the reader's stream — behind everything that stream holds, its readers included — and this stream waits for it.
+        // (Until round 6 every launch re-recorded its stream's event right after the kernel: a barrier packet per frame, 26 us
+        // between two back-to-back 2.4 ms launches of one stream — profiles/r06_streams3_trace.txt — to protect a rebuild that an
+        // animation with the default wind never does.)
+        for (auto& u : sl.users) {
+            if (u.first != s) {
+                const bool ok = !stream_is_capturing(u.first) && hipEventRecord(u.second, u.first) == hipSuccess &&
+                                hipStreamWaitEvent(s, u.second, 0) == hipSuccess;
+                if (!ok) { (void)hipGetLastError(); (void)hipDeviceSynchronize(); (void)hipGetLastError(); }   // (a stream that is gone)
+            }
+            ctx->event_pool.push_back(u.second);
+        }
+        sl.users.clear();
+    } else if (s != ctx->ytab.stream) {
+        (void)hipStreamWaitEvent(s, ctx->ytab.ready, 0);           // table was built on another stream
+    }
+    char* tab = ctx->ytab.ring + (size_t)slot * CLOUDS_YTAB_BYTES;
+    launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, rebuild);
+    if (rebuild) {
+        (void)hipEventRecord(ctx->ytab.ready, s);                  // the build is enqueued: now the cache state is true
+        std::memcpy(ctx->ytab.key, key, sizeof(key));
+        ctx->ytab.steps = F.steps;
+        ctx->ytab.slot = slot;
+        ctx->ytab.stream = s;
+        ctx->ytab.valid = true;
+    }
+    YTables::Slot& sl = ctx->ytab.slots[slot];                               // this stream reads the slot: remembered, nothing recorded
+    bool found = false;
+    for (auto& u : sl.users) if (u.first == s) { found = true; break; }
+    if (!found) {
+        hipEvent_t ev{};
+        if (!ctx->event_pool.empty()) { ev = ctx->event_pool.back(); ctx->event_pool.pop_back(); }
+        else if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipEventCreate");
+        sl.users.emplace_back(s, ev);
+    }
+    return SBX_OK;
+}
+
+void release(YTables& Y) {
+    if (Y.ring) (void)hipFree(Y.ring);
+    if (Y.big) (void)hipFree(Y.big);
+    if (Y.have_big_ready) (void)hipEventDestroy(Y.big_ready);
+    if (Y.have_ready) (void)hipEventDestroy(Y.ready);
+    for (auto& sl : Y.slots) for (auto& u : sl.users) (void)hipEventDestroy(u.second);
+    Y = YTables();
+}
+
+}  // namespace sbx

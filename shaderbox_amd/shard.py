@@ -1,4 +1,4 @@
-"""Row-block arithmetic of the multi-GPU split (pure Python mirror of sbx_split_* in sbx_capi.hip).
+"""Row-block arithmetic of the multi-GPU split (pure Python mirror of sbx_split_* in sbx_split.hip).
 
 The frame shards as cyclic row-blocks: blocks of `block_rows` rows, rank r owns blocks r, r+N, ...
 Equal contiguous strips do not balance (the bottom ~25 % of an APP_CLOUDS frame never marches,

@@ -66,17 +66,66 @@ def test_render_points_random_against_oracle(renderer, oracle, app):
     assert compare(got_host, ref) == (0.0, 0)
 
 
+def bind_small_volumes(renderer):
+    """clouds_tex renders only once its noise volumes are bound: 16^3 Worley volumes, as the texture tests use"""
+    vol = renderer.worley_volume(16)
+    renderer.set_noise_volumes(vol, vol)
+
+
 def test_render_points_pixel_centres_equal_the_frame(renderer):
-    """the point list at every pixel centre of a frame, in a scrambled order, is that frame (both paths share the kernels)"""
+    """the point list at every pixel centre of a frame, in a scrambled order, is that frame (both paths share the kernels) — for
+    EVERY app of the enum (all four channels: the 2D apps write their own alpha), so each one goes through the range check, the
+    aux defaults and the launch switch by two entry points"""
+    import shaderbox_amd
     import torch
     w, h, t = 200, 120, 1.25
-    for app in ("clouds", "egg", "atmosphere", "planet", "raytracer", "sdf_ao"):
+    bind_small_volumes(renderer)
+    for app in shaderbox_amd.APPS:
         frame = renderer.render(app, w, h, t).cpu().numpy().reshape(-1, 4)
         ys, xs = np.divmod(np.arange(w * h), w)
         perm = np.random.default_rng(3).permutation(w * h)
         pts = np.stack([xs[perm] + .5, ys[perm] + .5], axis=1).astype(np.float32)
         got = renderer.render_points(app, w, h, t, torch.from_numpy(pts)).cpu().numpy()
         assert compare(got, frame[perm]) == (0.0, 0), app
+
+
+def aux_pair(renderer, app):
+    """two aux blocks of `app` that differ in ONE field its pixels depend on"""
+    import ctypes
+    import shaderbox_amd
+    if app.startswith("sdf_ao"):
+        A, B = shaderbox_amd.sdf_ao_defaults(), shaderbox_amd.sdf_ao_defaults()
+        A.fog_density, B.fog_density = .05, .3
+    elif app == "clouds_ue4":
+        A, B = shaderbox_amd.AuxCloudsUe4(), shaderbox_amd.AuxCloudsUe4()
+        renderer.lib.sbx_aux_clouds_ue4_defaults(ctypes.byref(A))
+        renderer.lib.sbx_aux_clouds_ue4_defaults(ctypes.byref(B))
+        A.coverage, B.coverage = .4, .6
+    else:
+        A, B = shaderbox_amd.clouds_defaults(), shaderbox_amd.clouds_defaults()
+        A.cld_coverage, B.cld_coverage = .4, .7
+    return A, B
+
+
+@pytest.mark.parametrize("app", ["sdf_ao", "sdf_ao_shadow", "sdf_ao_normals", "clouds", "clouds_sky", "clouds_tex", "clouds_ue4"])
+def test_main_image_cache_keys_the_aux_block_of_every_app_that_has_one(renderer, app):
+    """sbx_main_image at ONE pixel centre, with aux block A and then with B (one live field apart): each answer is that pixel of
+    sbx_render_rows with the same block, bit for bit, and the two differ.  An app whose block were left out of the cache key
+    would answer B's call with A's frame, rc 0."""
+    w, h, t = 64, 32, 1.25
+    if app == "clouds_tex":
+        bind_small_volumes(renderer)
+    A, B = aux_pair(renderer, app)
+    fa = renderer.render(app, w, h, t, aux=A).cpu().numpy().reshape(h, w, 4)
+    fb = renderer.render(app, w, h, t, aux=B).cpu().numpy().reshape(h, w, 4)
+    differ = np.argwhere((fa.view(np.uint32) != fb.view(np.uint32)).any(axis=-1))
+    assert len(differ) > 0, "the two aux blocks must give different frames"
+    y, x = (int(v) for v in differ[len(differ) // 2])
+    ga = np.array(renderer.main_image(app, w, h, t, (x + .5, y + .5), aux=A), dtype=np.float32)
+    gb = np.array(renderer.main_image(app, w, h, t, (x + .5, y + .5), aux=B), dtype=np.float32)
+    assert compare(ga[None], fa[y, x][None]) == (0.0, 0)
+    assert compare(gb[None], fb[y, x][None]) == (0.0, 0)
+    assert (ga.view(np.uint32) != gb.view(np.uint32)).any()
 
 
 def test_points_with_fractional_resolution_and_bad_arguments(renderer, oracle):
@@ -298,7 +347,7 @@ def test_bench_relief_calibration_for_the_span_exchange(renderer):
 
 
 def test_clouds_marches_longer_than_the_ring_tables(renderer, oracle):
-    """cld_march_steps beyond the 4096 rows of the y-table ring: the context's on-demand table (sbx_capi.hip render_clouds case 4)
+    """cld_march_steps beyond the 4096 rows of the y-table ring: the context's on-demand table (sbx_ytab.hip render_clouds case 4)
     instead of round 3's table-less fallback; same bits as the per-lane kernel and the oracle, across key changes and streams"""
     import torch
     import shaderbox_amd

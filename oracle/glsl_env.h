@@ -19,6 +19,51 @@
 #ifndef SBX_GLSL_ENV_H
 #define SBX_GLSL_ENV_H
 
+/* The aux uniforms (cbuffer b1).  In the reference's C++ form they are compile-time constants, `const type name = default`
+ * (src/uniform_buffer.h:13); the copy of that header the make rule generates writes `= SBX_REF_AUX_<name>(default)` instead.  Each
+ * of these is the default unless the build's command line says otherwise, -D'SBX_REF_AUX_cld_coverage(d)=(0.600000024)': the
+ * aux-set builds of oracle/aux_sets.py.  The value stays a constant initialiser (app_clouds.h:15-17 initialises a const
+ * thread_local from two of them, once per thread). */
+#ifndef SBX_REF_AUX_wind_dir
+#define SBX_REF_AUX_wind_dir(d) d
+#endif
+#ifndef SBX_REF_AUX_sun_dir
+#define SBX_REF_AUX_sun_dir(d) d
+#endif
+#ifndef SBX_REF_AUX_sun_color
+#define SBX_REF_AUX_sun_color(d) d
+#endif
+#ifndef SBX_REF_AUX_sun_power
+#define SBX_REF_AUX_sun_power(d) d
+#endif
+#ifndef SBX_REF_AUX_cld_march_steps
+#define SBX_REF_AUX_cld_march_steps(d) d
+#endif
+#ifndef SBX_REF_AUX_illum_march_steps
+#define SBX_REF_AUX_illum_march_steps(d) d
+#endif
+#ifndef SBX_REF_AUX_sigma_scattering
+#define SBX_REF_AUX_sigma_scattering(d) d
+#endif
+#ifndef SBX_REF_AUX_cld_coverage
+#define SBX_REF_AUX_cld_coverage(d) d
+#endif
+#ifndef SBX_REF_AUX_cld_thick
+#define SBX_REF_AUX_cld_thick(d) d
+#endif
+#ifndef SBX_REF_AUX_atm_radius
+#define SBX_REF_AUX_atm_radius(d) d
+#endif
+#ifndef SBX_REF_AUX_atm_ground_y
+#define SBX_REF_AUX_atm_ground_y(d) d
+#endif
+#ifndef SBX_REF_AUX_fog_density
+#define SBX_REF_AUX_fog_density(d) d
+#endif
+#ifndef SBX_REF_AUX_fog_falloff
+#define SBX_REF_AUX_fog_falloff(d) d
+#endif
+
 extern "C" {
 float sbxm_sin(float), sbxm_cos(float), sbxm_tan(float), sbxm_acos(float), sbxm_exp(float), sbxm_sqrt(float), sbxm_abs(float),
     sbxm_floor(float), sbxm_fract(float), sbxm_radians(float);

@@ -6,8 +6,11 @@ cpu_baseline leg of bench.py.  The product package (shaderbox_amd/) never import
 import ctypes
 import os
 import subprocess
+import sys
 
 import numpy as np
+
+from . import aux_sets
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -39,9 +42,10 @@ def reference_root():
 
 
 def build_reference(reference=None):
-    """Make every oracle/_ref/libsbx_ref_*.so from the reference tree where it lies (`make ref`); does nothing where that tree
-    is absent.  Returns the names of the builds present afterwards."""
-    cmd = ["make", "-s", "-j8", "-C", _HERE, "ref"]
+    """Make every oracle/_ref/libsbx_ref_*.so from the reference tree where it lies (`make ref`: the default builds and the
+    aux-set builds of oracle/aux_sets.py); does nothing where that tree is absent.  Returns the names of the default builds
+    present afterwards (Reference.available_aux() lists the others)."""
+    cmd = ["make", "-s", "-j8", "-C", _HERE, "ref", "PYTHON=%s" % sys.executable]
     if reference is not None:
         cmd.append("REFERENCE=%s" % reference)
     subprocess.run(cmd, check=True)
@@ -50,16 +54,47 @@ def build_reference(reference=None):
 
 class Reference:
     """The reference's own shader headers, compiled verbatim over oracle/glsl_env.h (oracle/README.md "How it is pinned").
-    Same render / render_rows / main_image signatures as Oracle; `app` is an oracle app id or a name of REF_APPS.  The
-    reference's aux uniforms are compile-time constants in its C++ form (src/uniform_buffer.h:13), so aux must be None."""
+    Same render / render_rows / main_image signatures as Oracle; `app` is an oracle app id or a name of REF_APPS.
+
+    aux: in the reference's C++ form the aux uniforms are compile-time constants (src/uniform_buffer.h:13), so one build holds
+    one aux block.  tests/golden/reference_aux_sets.json names the blocks that have a build (a set = the fields that differ from
+    the defaults); `make ref` compiles `<build>@<set>` for each with the set's values in place of the defaults, as literals of
+    the same binary32 values (oracle/aux_sets.py).  `aux=` takes the block the oracle and the kernels take (a ctypes structure of
+    shaderbox_amd, its bytes, or aux_sets.block()) and is answered by the build whose set equals it field for field, the default
+    build for a block of defaults; a block no build was compiled for is a ValueError, never the defaults."""
 
     def __init__(self):
         self._libs = {}
+        self._builds = {}                               # (app, aux bytes) -> build name
         self._texture = None
 
     @staticmethod
     def available():
         return tuple(n for n in REF_NAMES if os.path.exists(os.path.join(REF_DIR, "libsbx_ref_%s.so" % n)))
+
+    @staticmethod
+    def available_aux():
+        """the aux-set builds (`<build>@<set>`) of the fixture that oracle/_ref holds"""
+        return tuple(n for n in aux_sets.build_names() if os.path.exists(os.path.join(REF_DIR, "libsbx_ref_%s.so" % n)))
+
+    @classmethod
+    def build_for(cls, app, aux=None):
+        """the name of the build that renders `app` with the aux block `aux`: the app's own for None or a block of defaults,
+        `<app>@<set>` for a block that equals a set of the fixture field for field; ValueError for any other block"""
+        name = cls.name_of(app)
+        if aux is None:
+            return name
+        kind = aux_sets.KIND_OF.get(name)
+        if kind is None:
+            raise ValueError("reference: the %s build reads no aux block" % name)
+        got = aux_sets.from_bytes(kind, aux)
+        if aux_sets.same_block(kind, got, aux_sets.block(kind)):
+            return name
+        for set_name, over in aux_sets.load()[kind].items():
+            if aux_sets.same_block(kind, got, aux_sets.block(kind, over)):
+                return name + "@" + set_name
+        raise ValueError("reference: no build of %s has this aux block compiled in (tests/golden/reference_aux_sets.json lists "
+                         "the sets that have one): %s" % (name, {n: got[n].tolist() for n in aux_sets.fields(kind)}))
 
     @staticmethod
     def name_of(app):
@@ -70,12 +105,15 @@ class Reference:
                 return name
         raise ValueError("reference: unknown app %r" % (app,))
 
-    def _lib(self, app):
-        name = self.name_of(app)
+    def _lib(self, app, aux=None):
+        key = (app, None if aux is None else (aux.tobytes() if isinstance(aux, np.ndarray) else bytes(aux)))
+        if key not in self._builds:
+            self._builds[key] = self.build_for(app, aux)
+        name = self._builds[key]
         if name not in self._libs:
             path = os.path.join(REF_DIR, "libsbx_ref_%s.so" % name)
-            if name not in REF_NAMES or not os.path.exists(path):
-                raise ValueError("reference: no build of %r under oracle/_ref" % (app,))
+            if name.split("@")[0] not in REF_NAMES or not os.path.exists(path):
+                raise ValueError("reference: no build of %r under oracle/_ref" % (name,))
             lib = ctypes.CDLL(path)
             fp = ctypes.POINTER(ctypes.c_float)
             if name == "noise":
@@ -88,22 +126,20 @@ class Reference:
         return self._libs[name]
 
     def main_image(self, app, width, height, time, fx, fy, mouse=(0.0, 0.0), aux=None):
-        assert aux is None, "the reference's aux uniforms are compile-time constants"
         u = Oracle._uni(width, height, time, mouse)
         out = np.zeros(4, dtype=np.float32)
-        self._lib(app).sbxr_main_image(Oracle._fp(u), float(fx), float(fy), Oracle._fp(out))
+        self._lib(app, aux).sbxr_main_image(Oracle._fp(u), float(fx), float(fy), Oracle._fp(out))
         return out
 
     def render_rows(self, app, width, height, time, rows, mouse=(0.0, 0.0), aux=None, threads=None):
         """rows: iterable of global row indices (0 = bottom). Returns float32 [len(rows), W, 4]."""
-        assert aux is None, "the reference's aux uniforms are compile-time constants"
         rows = np.ascontiguousarray(np.asarray(list(rows), dtype=np.int32))
         u = Oracle._uni(width, height, time, mouse)
         out = np.zeros((len(rows), int(width), 4), dtype=np.float32)
         if threads is None:
             threads = os.cpu_count() or 1
-        self._lib(app).sbxr_render_rows(Oracle._fp(u), rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(rows),
-                                        Oracle._fp(out), int(threads))
+        self._lib(app, aux).sbxr_render_rows(Oracle._fp(u), rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(rows),
+                                             Oracle._fp(out), int(threads))
         return out
 
     def render(self, app, width, height, time, mouse=(0.0, 0.0), aux=None, threads=None):
@@ -157,7 +193,7 @@ class Oracle:
     def _aux(aux):
         if aux is None:
             return None, None
-        buf = np.frombuffer(bytes(aux), dtype=np.uint8).copy()
+        buf = np.frombuffer(aux.tobytes() if isinstance(aux, np.ndarray) else bytes(aux), dtype=np.uint8).copy()
         return buf, buf.ctypes.data_as(ctypes.c_void_p)
 
     def main_image(self, app, width, height, time, fx, fy, mouse=(0.0, 0.0), aux=None):

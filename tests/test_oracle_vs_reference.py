@@ -5,8 +5,9 @@ restatement: a wrong term in it is copied faithfully and seen by nobody.  oracle
 headers, compiled verbatim over oracle/glsl_env.h (oracle/Makefile `ref`, oracle/README.md "How it is pinned"); this file compares
 the two: whole frames at three sizes, several times and mouse positions, off-centre and out-of-frame fragCoords, the noise
 library, the committed golden frames, and the two Python models that stand in for the oracle (tests/app2d_model.py,
-tests/atmosphere_ground_model.py).  Every comparison is over the bits of all four channels, NaN equal to NaN: no tolerance, no
-excluded pixel.
+tests/atmosphere_ground_model.py); and, for the aux uniform block (cbuffer b1), every set of tests/golden/reference_aux_sets.json
+against the build that has the set compiled in ("the aux sets" below).  Every comparison is over the bits of all four channels,
+NaN equal to NaN: no tolerance, no excluded pixel.
 
 Where the reference tree is on the machine the builds are (re)made first, and all of them must then exist; elsewhere the tests
 use what oracle/_ref holds (it travels with the tree to the GPU machine) and skip only when it holds no library.
@@ -17,6 +18,7 @@ import os
 import numpy as np
 import pytest
 
+from oracle import aux_sets
 from oracle.oracle import APP_IDS, REF_NAMES, Reference, build_reference, reference_root
 from tests import app2d_model as M2
 from tests import atmosphere_ground_model as MG
@@ -243,6 +245,217 @@ def test_atmosphere_ground_model_points(ref):
     for t in (0.37, 9.25):
         b = np.stack([ref.main_image("atmosphere_ground", w, h, t, x, y) for x, y in pts])
         assert_same(MG.main_image(w, h, t, pts[:, 0], pts[:, 1]), b, ("atmosphere_ground points", t))
+
+
+# ---- the aux sets ------------------------------------------------------------------------------------------------------
+# In the reference's C++ form an aux uniform is a compile-time constant (src/uniform_buffer.h:13), so the builds above hold the
+# defaults and only the defaults.  tests/golden/reference_aux_sets.json names aux blocks that move the kernels onto their other
+# paths (light marches, y table, exp forms, stage cut-offs, the SKY_SPHERE sphere); `make ref` compiles one build per (header,
+# set) with the set's binary32 values in place of the defaults (oracle/aux_sets.py), and Reference answers `aux=` with the build
+# whose set equals the block field for field.
+
+AUX_SETS = aux_sets.load()
+AUX_CASES = [(b, name) for kind, by_name in AUX_SETS.items() for b, _, _ in aux_sets.BUILDS[kind] for name in by_name]
+AUX_SIZES = [(96, 54), (97, 61)]
+AUX_TIMES = [0.37, 9.25, -3.1]
+
+
+def aux_block(build, name=None):
+    kind = aux_sets.KIND_OF[build]
+    return aux_sets.block(kind, AUX_SETS[kind][name] if name else None)
+
+
+def need_aux(ref, build, name):
+    if "%s@%s" % (build, name) not in ref.available_aux():
+        pytest.skip("no reference build %s@%s under oracle/_ref" % (build, name))
+
+
+def test_every_aux_set_has_its_builds(ref):
+    """wherever the reference tree is, `make ref` (the `ref` fixture ran it) made <build>@<set> for every set of the fixture"""
+    if not os.path.isdir(os.path.join(reference_root(), "src")):
+        pytest.skip("the reference tree is not on this machine")
+    want = aux_sets.build_names()
+    assert len(want) == len(set(want)) == len(AUX_CASES) and len(want) >= 28
+    assert list(ref.available_aux()) == want
+    # the sets the project's paths need, under the names the other tests use
+    assert {"steer", "yz", "exp_on", "exp_off", "long", "cov_hi", "cov_lo", "wind_y", "zero", "degenerate", "outside",
+            "small_sphere"} <= set(AUX_SETS["clouds"])
+    fog = {(v["fog_density"], v["fog_falloff"]) for v in AUX_SETS["sdf_ao"].values() if len(v) == 2}
+    assert {(.25, .3), (0, .5), (2.5, 0), (-.1, 4)} <= fog
+
+
+def test_aux_literals_and_blocks_hold_the_same_binary32():
+    """what the build compiles and what the oracle and the kernels are handed: one binary32 per field.  The literal is %.9g of it
+    (read back as binary32 under -fsingle-precision-constant), with a decimal point or an exponent; integers are integers; and a
+    block of defaults is the block the library's own defaults call fills"""
+    import shaderbox_amd
+    from shaderbox_amd import build
+    build.build(verbose=False)
+    assert aux_block("clouds").tobytes() == bytes(shaderbox_amd.clouds_defaults())
+    assert aux_block("sdf_ao").tobytes() == bytes(shaderbox_amd.sdf_ao_defaults())
+    for kind, by_name in AUX_SETS.items():
+        for name, over in by_name.items():
+            b = aux_sets.block(kind, over)
+            for field in over:
+                text = aux_sets.literal(b[field])
+                if b.dtype[field].kind == "i":
+                    assert text == "(%d)" % over[field]
+                    continue
+                nums = text[text.index("(") + 1:-1].split(",")
+                assert len(nums) == (3 if b.dtype[field].shape else 1) and text.startswith("vec3(" if b.dtype[field].shape else "(")
+                assert all("." in n or "e" in n for n in nums), (name, field, text)
+                # decimal -> binary32 in one rounding, as the compiler reads a float literal
+                got = np.array([np.float32(n) for n in nums], dtype=np.float32)
+                assert got.tobytes() == np.asarray(b[field], dtype=np.float32).tobytes(), (name, field, text)
+                assert got.tobytes() == np.asarray(over[field], dtype=np.float32).tobytes()
+
+
+def test_exp_sets_lie_on_either_side_of_the_exp_small_bound():
+    """launch_clouds (kern_clouds.hip) takes the exp_small_ kernels when sigma, dt >= 0 and .94 sigma dt <= .2049 in binary64, with
+    dt = cld_thick / cld_march_steps in binary32 (build_clouds, sbx_frames.hip).  With the default dt = 1.25 the edge is
+    sigma = .17438...; .1744 and .1746 both lie beyond it (.204920, .205155), so the pair is .1743 (.204803) and .1745 (.205038)."""
+    def product(name):
+        b = aux_block("clouds", name)
+        dt = np.float32(b["cld_thick"]) / np.float32(b["cld_march_steps"])
+        return .94 * float(b["sigma_scattering"]) * float(dt)
+    assert set(AUX_SETS["clouds"]["exp_on"]) == set(AUX_SETS["clouds"]["exp_off"]) == {"sigma_scattering"}
+    assert 0 < product("exp_on") <= .2049 < product("exp_off")
+    assert abs(product("exp_on") - .2049) < 2e-4 and abs(product("exp_off") - .2049) < 2e-4      # both next to the edge
+
+
+@pytest.mark.parametrize("build,name", AUX_CASES)
+def test_aux_frames_equal_the_aux_set_build(oracle, ref, build, name):
+    need_aux(ref, build, name)
+    aux = aux_block(build, name)
+    for w, h in AUX_SIZES:
+        for t in AUX_TIMES:
+            for mouse in [(0.0, 0.0)] + ([MOUSE] if build in MOUSE_APPS else []):
+                assert_same(oracle.render(APP_IDS[build], w, h, t, mouse=mouse, aux=aux),
+                            ref.render(build, w, h, t, mouse=mouse, aux=aux), (build, name, w, h, t, mouse))
+
+
+@pytest.mark.parametrize("build", ["clouds", "clouds_sky", "sdf_ao"])
+def test_aux_defaults_block_is_the_default_build(oracle, ref, build):
+    """a block of defaults is answered by the default build, and is what aux=None means on the oracle's side"""
+    need(ref, build)
+    aux = aux_block(build)
+    assert Reference.build_for(build, aux) == build
+    w, h, t = 97, 61, 9.25
+    want = ref.render(build, w, h, t)
+    assert_same(ref.render(build, w, h, t, aux=aux), want, (build, "defaults block, reference"))
+    assert_same(oracle.render(APP_IDS[build], w, h, t, aux=aux), want, (build, "defaults block"))
+    assert_same(oracle.render(APP_IDS[build], w, h, t), want, (build, "no block"))
+
+
+@pytest.mark.parametrize("build", ["clouds", "clouds_sky"])
+@pytest.mark.parametrize("name", ["steer", "yz"])
+def test_aux_main_image_off_centre_and_out_of_frame(oracle, ref, build, name):
+    need_aux(ref, build, name)
+    aux = aux_block(build, name)
+    w, h = 1920, 1080
+    pts = points(w, h)
+    for t, mouse in [(9.25, (0.0, 0.0)), (0.37, MOUSE)]:
+        a = np.stack([oracle.main_image(APP_IDS[build], w, h, t, x, y, mouse=mouse, aux=aux) for x, y in pts])
+        b = np.stack([ref.main_image(build, w, h, t, x, y, mouse=mouse, aux=aux) for x, y in pts])
+        assert_same(a, b, (build, name, "main_image", t, mouse))
+    assert_same(ref.main_image(build, 96, 54, 0.37, 10.5, 20.5, aux=aux), ref.render(build, 96, 54, 0.37, aux=aux)[20, 10],
+                (build, name, "centre"))
+
+
+# field -> (a set that changes this field and no other, the builds whose text reads the field, the builds whose text does not).
+# wind_dir: app_clouds.h:167 is compiled out under SKY_SPHERE; atm_radius and atm_ground_y: read only under SKY_SPHERE (:14-19).
+BOTH = ("clouds", "clouds_sky")
+AUX_FIELD_WITNESS = {
+    "wind_dir": ("wind_y", ("clouds",), ("clouds_sky",)),
+    "sun_dir": ("yz", BOTH, ()),
+    "sun_color": ("one_sun_color", BOTH, ()),
+    "sun_power": ("one_sun_power", BOTH, ()),
+    "cld_march_steps": ("zero", BOTH, ()),
+    "illum_march_steps": ("one_illum_steps", BOTH, ()),
+    "sigma_scattering": ("exp_off", BOTH, ()),
+    "cld_coverage": ("cov_lo", BOTH, ()),
+    "cld_thick": ("one_thick", BOTH, ()),
+    "atm_radius": ("outside", ("clouds_sky",), ("clouds",)),
+    "atm_ground_y": ("one_ground_y", ("clouds_sky",), ("clouds",)),
+    "fog_density": ("fog_none", ("sdf_ao",), ()),
+    "fog_falloff": ("one_falloff", ("sdf_ao",), ()),
+}
+
+
+def test_every_aux_field_has_a_witness():
+    assert set(AUX_FIELD_WITNESS) == set(aux_sets.fields("clouds")) | set(aux_sets.fields("sdf_ao")) and len(AUX_FIELD_WITNESS) == 13
+    for field, (name, reads, ignores) in AUX_FIELD_WITNESS.items():
+        kind = aux_sets.KIND_OF[reads[0]]
+        b, d = aux_block(reads[0], name), aux_block(reads[0])
+        assert {f for f in aux_sets.fields(kind) if np.asarray(b[f]).tobytes() != np.asarray(d[f]).tobytes()} == {field}, (field, name)
+        assert set(reads) | set(ignores) == {b for b, _, _ in aux_sets.BUILDS[kind]}
+
+
+@pytest.mark.parametrize("field", sorted(AUX_FIELD_WITNESS))
+def test_every_aux_field_is_read_where_the_text_reads_it(ref, field):
+    """reference build against reference build: a set that changes ONE field changes the frame of every header that reads the
+    field (more than a thousand of 5 184 pixels), and no bit of a header that does not"""
+    name, reads, ignores = AUX_FIELD_WITNESS[field]
+    w, h, t = 96, 54, 0.37
+    for build in reads + ignores:
+        need(ref, build)
+        need_aux(ref, build, name)
+        a, d = ref.render(build, w, h, t, aux=aux_block(build, name)), ref.render(build, w, h, t)
+        changed = int((~same_bits(a, d)).any(axis=-1).sum())
+        if build in reads:
+            assert changed > 1000, (field, build, name, changed)
+        else:
+            assert changed == 0, (field, build, name, changed)
+
+
+def test_sets_the_text_does_not_read_equal_the_default_build(ref):
+    """wind_y under SKY_SPHERE, outside and small_sphere without it: every bit of the default build's frame, at every size, time and
+    mouse position of the frame test"""
+    for build, name in [("clouds_sky", "wind_y"), ("clouds", "outside"), ("clouds", "small_sphere")]:
+        need(ref, build)
+        need_aux(ref, build, name)
+        for w, h in AUX_SIZES:
+            for t in AUX_TIMES:
+                for mouse in [(0.0, 0.0), MOUSE]:
+                    assert_same(ref.render(build, w, h, t, mouse=mouse, aux=aux_block(build, name)),
+                                ref.render(build, w, h, t, mouse=mouse), (build, name, "is not read", w, h, t, mouse))
+
+
+def test_outside_set_pins_the_nan_sky(oracle, ref):
+    """atm_radius 100 around a centre 4750 below the eye: the eye is outside the sphere, and every sky pixel of the SKY_SPHERE
+    build is NaN in the reference build; the oracle has NaN in the same pixels (the frame test compares them all)"""
+    need_aux(ref, "clouds_sky", "outside")
+    aux = aux_block("clouds_sky", "outside")
+    a = ref.render("clouds_sky", 96, 54, 0.37, aux=aux)
+    nan = np.isnan(a).any(axis=-1)
+    assert nan.sum() > 1000 and not nan.all()
+    assert not np.isnan(ref.render("clouds_sky", 96, 54, 0.37)).any()
+    assert (np.isnan(oracle.render(APP_IDS["clouds_sky"], 96, 54, 0.37, aux=aux)).any(axis=-1) == nan).all()
+
+
+def test_a_block_without_a_build_is_an_error(ref):
+    """never the defaults: a block that equals no set, a block of another layout, an aux block for an app that has none"""
+    need(ref, "clouds")
+    odd = aux_block("clouds")
+    odd["cld_coverage"] = np.nextafter(np.float32(AUX_SETS["clouds"]["steer"]["cld_coverage"]), np.float32(1))
+    for call in (lambda: ref.render("clouds", 16, 9, 0.37, aux=odd),
+                 lambda: ref.render_rows("clouds_sky", 16, 9, 0.37, [0], aux=odd),
+                 lambda: ref.main_image("clouds", 16, 9, 0.37, .5, .5, aux=odd),
+                 lambda: ref.render("sdf_ao", 16, 9, 0.37, aux=aux_block("clouds", "yz")),     # a clouds block is no fog block
+                 lambda: ref.render("clouds", 16, 9, 0.37, aux=aux_block("sdf_ao", "fog_mid")),
+                 lambda: ref.render("egg", 16, 9, 0.37, aux=aux_block("sdf_ao"))):
+        with pytest.raises(ValueError):
+            call()
+    # one field of a set alone is not the set
+    part = aux_block("clouds")
+    part["sun_dir"] = AUX_SETS["clouds"]["steer"]["sun_dir"]
+    with pytest.raises(ValueError):
+        ref.render("clouds", 16, 9, 0.37, aux=part)
+    # -0 is not 0: the literal would differ
+    neg = aux_block("sdf_ao", "fog_none")
+    neg["fog_density"] = -0.0
+    with pytest.raises(ValueError):
+        ref.render("sdf_ao", 16, 9, 0.37, aux=neg)
 
 
 # ---- the kernels -------------------------------------------------------------------------------------------------------

@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -47,7 +47,8 @@ typedef enum sbx_app {
     SBX_APP_PLANET = 0,
     SBX_APP_CLOUDS = 1,
     SBX_APP_VINYL = 2,      /* C++-build semantics: 60 march steps (src/app_vinyl.h:411-416) */
-    SBX_APP_EGG = 3,
+    SBX_APP_EGG = 3,         /* src/app_egg.h as shipped: BEZIER defined (:37) and the `#if 1` egg (:46-52).  The builds with one of the two
+                                switches the other way are SBX_APP_EGG_STRAIGHT and SBX_APP_EGG_OVAL */
     SBX_APP_RAYTRACER = 4,
     SBX_APP_ATMOSPHERE = 5,  /* src/app_atmosphere.h as shipped, FROM_SPACE defined (:162): the sky dome (:190-209).  The build without
                                 the define is SBX_APP_ATMOSPHERE_GROUND */
@@ -133,7 +134,31 @@ typedef enum sbx_app {
        render's fog mix and abs (:305-310) and main.h's linear_to_srgb, so a frame shows |mix(n, 1, fog)|^(1/2.2); a zero gradient's
        normalize(0) = NaN is the pixel's data.  Pixels that miss the scene are unchanged (background under fog).  Aux block, variants
        and precision as SBX_APP_SDF_AO_SHADOW. */
-    SBX_APP_SDF_AO_NORMALS = 18
+    SBX_APP_SDF_AO_NORMALS = 18,
+    /* APP_EGG compiled without the `#define BEZIER` of src/app_egg.h:37: the legs are four sd_cylinder segments (src/sdf.h:95-109)
+       instead of the two sd_bezier tubes of :111-116 — left_leg_a = sd_cylinder(p + pelvis, 0, knee_l - side, thick) and left_leg_b =
+       sd_cylinder(p + knee_l, 0, left_foot_pos - knee_l, thick) (:86-93), right_leg_a = sd_cylinder(p + pelvis, 0, knee_r + side, thick)
+       with pelvis = -side and right_leg_b = sd_cylinder(p + knee_r, 0, right_foot_pos - knee_r, thick) (:97-104); thick = .05, the knees
+       are the IK solver's (:85, :96).  THE TWO LEGS ARE NOT JOINED ALIKE (:106-109): legs = op_add(vec2(op_blend(left_leg_a.x,
+       left_leg_b.x, .01), material), op_add(right_leg_a, right_leg_b)) — the left knee is a smooth minimum with k = .01 (src/sdf.h:38-47),
+       the right knee a plain union.  Everything else as SBX_APP_EGG: the `#if 1` egg of three blended spheres, feet, wheel, ground and
+       the order of their unions (:140-143), camera (:23-27, FOV 1), the 80-step trace and the 20-step shadowmarch of ground hits
+       (:161-231), the flat colours, `depth` fresh per invocation (:188), the bars (:239-248), abs, linear_to_srgb, alpha 1, no aux
+       block.  u_mouse does not enter.  Alpha is 1, so every output form holds it (rgb, span, split, SBX_FORMAT_RGBA8,
+       sbx_multi_render).  sbx_set_variant 0-3 mean what they mean for SBX_APP_EGG (1 = every member evaluated everywhere, 2 / 3 = the
+       recorded-domain roots with the re-run forced / the IEEE roots only); SBX_PRECISION_1E4 is ignored.  Definition:
+       tests/egg_builds_model.py, pinned against frames and points of the edited reference header (tests/golden/egg_builds/). */
+    SBX_APP_EGG_STRAIGHT = 19,
+    /* APP_EGG compiled with the `#if 1` at src/app_egg.h:46 turned to `#if 0` (BEZIER defined as shipped): the egg is the `#else` of
+       :53-66 — ONE sphere, sd_sphere(iscale * (scale * (p - vec3(0, egg_y, 0))), 0.475) with egg_y = .65, s = 1.55, scale =
+       diag(s, 1, 1) and iscale = diag(1. / s, 1. / s, 1.) — instead of the three spheres and two op_blend of :47-52.  OPERATION ORDER:
+       the inner product first, scale * q, then iscale * (that); each mat3 * vec3 is (col0 * v.x + col1 * v.y) + col2 * v.z, zero
+       terms included (0 * inf is a NaN and (-0) + 0 is +0, as in the reference's C++ build), and 1. / s is the binary32 quotient.
+       So x is scaled up by s and down again (two roundings, not the identity), y is divided by s, z is unchanged: a spheroid
+       stretched to .475 * 1.55 along y — its top stands above the blended egg's — whose field is not a distance (it under-estimates
+       along y by the factor 1.55).  Everything else, the variants and the precision tier as SBX_APP_EGG_STRAIGHT says; the legs are
+       the Bezier tubes. */
+    SBX_APP_EGG_OVAL = 20
 } sbx_app;
 
 typedef enum sbx_status {

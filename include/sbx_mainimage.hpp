@@ -42,6 +42,10 @@
 #define SBX_SELECTED_APP SBX_APP_SDF_AO_SHADOW
 #elif defined(APP_SDF_AO_NORMALS)   /* src/app_sdf_ao.h with the `#if 0` at :217 on (the normals view, include/sbx.h); tested before APP_SDF_AO */
 #define SBX_SELECTED_APP SBX_APP_SDF_AO_NORMALS
+#elif defined(APP_EGG_STRAIGHT)     /* src/app_egg.h without its `#define BEZIER` (:37; the cylinder legs, include/sbx.h); tested before APP_EGG */
+#define SBX_SELECTED_APP SBX_APP_EGG_STRAIGHT
+#elif defined(APP_EGG_OVAL)         /* src/app_egg.h with the `#if 1` at :46 off (the one scaled sphere, include/sbx.h); tested before APP_EGG */
+#define SBX_SELECTED_APP SBX_APP_EGG_OVAL
 #elif defined(APP_PLANET)
 #define SBX_SELECTED_APP SBX_APP_PLANET
 #elif defined(APP_CLOUDS)
@@ -59,7 +63,7 @@
 #elif defined(APP_CLOUDS_BEST)   /* src/app_clouds_best.h, the stand-alone shader (no APP_* define in the reference) */
 #define SBX_SELECTED_APP SBX_APP_CLOUDS_BEST
 #else
-#error "define one of APP_PLANET APP_CLOUDS APP_VINYL APP_EGG APP_RAYTRACER APP_ATMOSPHERE APP_SDF_AO (or APP_CLOUDS_BEST APP_PLANET_ATMOSPHERE APP_2D APP_2D_TEX APP_FUNC APP_ATMOSPHERE_GROUND APP_SDF_AO_SHADOW APP_SDF_AO_NORMALS)"
+#error "define one of APP_PLANET APP_CLOUDS APP_VINYL APP_EGG APP_RAYTRACER APP_ATMOSPHERE APP_SDF_AO (or APP_CLOUDS_BEST APP_PLANET_ATMOSPHERE APP_2D APP_2D_TEX APP_FUNC APP_ATMOSPHERE_GROUND APP_SDF_AO_SHADOW APP_SDF_AO_NORMALS APP_EGG_STRAIGHT APP_EGG_OVAL)"
 #endif
 
 namespace sbx_host {

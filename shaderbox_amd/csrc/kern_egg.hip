@@ -7,6 +7,14 @@
 // axes) is a frame constant evaluated once on the host (FrameEgg); only the point-dependent part
 // runs per march step.  `depth` (a _mutable global, :188) is a per-thread register that starts
 // at -max_dist for every pixel = GLSL per-invocation semantics.
+//
+// BUILD (sbx_frame.h EGG_*; include/sbx.h) is the header's build, the two one-line switches of its sdf():
+//   EGG_DEFAULT    as shipped (SBX_APP_EGG)
+//   EGG_STRAIGHT   without `#define BEZIER` (:37; SBX_APP_EGG_STRAIGHT): the legs are the four sd_cylinder segments of :86-93, :97-104,
+//                  the left pair joined by op_blend(.., .01), the right pair by op_add (:106-109)
+//   EGG_OVAL       the `#if 1` at :46 turned to `#if 0` (SBX_APP_EGG_OVAL): the egg is the one sphere of :53-66, evaluated at
+//                  iscale * (scale * (p - (0, egg_y, 0))) with s = 1.55
+// A template parameter: every `BUILD ==` below is decided at compile time, and k_egg<., ., EGG_DEFAULT> is the kernel it was.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -29,20 +37,23 @@ namespace sbx {
 // by which a rounded rotation matrix changes a length, far inside the 0.1 % by which 1.43 exceeds 1 / .7 — so a point that is far
 // never pays for the turntable rotation (round 4: the culled call is ~28 instead of ~45 instructions; sky and ground waves are
 // mostly such calls).  Any valid cull returns the same bits: it only ever claims what the full union would have returned.
+// EGG_OVAL: its egg only gives >= (|q| - .74) / 1.55 (below), a slope under .7, so its constant is 1.56 > 1.55 (1 + 1e-3) — with the
+// same 0.1 % for the rotation — and .7 > 1 / 1.56 keeps every other member's bound.
+template <int BUILD>
 __device__ __forceinline__ bool egg_far(const FrameEgg& F, v3 P, float ground_d) {
     const v3 q = P - F.ocw;
-    const float K = (ground_d + 1e-3f) * 1.43f + F.orad;
+    const float K = (ground_d + 1e-3f) * (BUILD == EGG_OVAL ? 1.56f : 1.43f) + F.orad;
     return ground_d >= 0.f && dot(q, q) > K * K;
 }
 
 // CULL = false (sbx_set_variant 1) evaluates every member everywhere: the reference form, kept for the parity sweeps
 // W: the square roots' witness (sbx_sdf.h): Wit<true> takes the five-instruction roots and records arguments outside their domain
-template <bool CULL, class W>
+template <bool CULL, int BUILD, class W>
 __device__ __forceinline__ D2 egg_sdf(const FrameEgg& F, v3 P, W& w) {
     const float mat_egg = 1.f, mat_bike = 2.f, mat_ground = 3.f;              // :17-20
     {
         const D2 ground = {dot(V3(0.f, 1.f, 0.f), P) + (1.2f + 0.5f), mat_ground};       // sd_plane :136-138
-        if (CULL && egg_far(F, P, ground.d)) return ground;
+        if (CULL && egg_far<BUILD>(F, P, ground.d)) return ground;
     }
     const v3 p = mul(F.rot_y, P) - V3(0, 0.5f, 3.5f);                         // :40-41
     // Members are evaluated cheapest first with a running minimum `dmin`; a member whose lower bound exceeds it
@@ -52,6 +63,17 @@ __device__ __forceinline__ D2 egg_sdf(const FrameEgg& F, v3 P, W& w) {
     //   foot   : max(axis, |u + 1/16| - 1/16) - .05            >= |P - M| / sqrt2 - 1/16 - .05   (M = midpoint)
     //   egg    : two smooth-mins (k = .5) of three spheres     >= |p - (0, .65, 0)| - .7 - .25
     //   leg    : bezier_far (sbx_sdf.h)
+    // EGG_OVAL's egg: w = iscale (scale q) with q = p - (0, .65, 0) is (q.x up to two roundings, q.y / 1.55, q.z): every component
+    //   is at least the 1 / 1.55 (1 - 2^-22) of q's in magnitude, so the sphere gives |w| - .475 >= |q| / 1.5501 - .475, and
+    //   |q| > 1.552 (dmin + .475 + 2e-3) puts it above dmin + 1e-3
+    // EGG_STRAIGHT's legs: sd_cylinder0 is max(dist, -plane_1, -plane_2) - R.  With u = dot(dir, P) the axial coordinate and r = dist
+    //   the radial one, the planes are -u - len and u, whose maximum is |u + len / 2| - len / 2: the field is
+    //   max(r, |a| - h) - R for a = u + h the axial coordinate from the MIDPOINT M and h = len / 2, and max(r, |a| - h) >=
+    //   max(r, |a|) - h >= |P - M| / sqrt2 - h (along a diagonal the maximum grows only at 1 / sqrt2 of the distance; the feet's
+    //   bound).  So a leg is > dmin + 1e-3 where |p - M| > 1.4143 (dmin + h + R + 1e-3).  op_blend(a, b, k) = mix(b, a, h) - k h (1 - h)
+    //   lies between min(a, b) - k / 4 and min(a, b), so the left pair (k = .01) is above dmin + 1e-3 where BOTH members are above
+    //   dmin + .0025 + 1e-3: FrameEgg.leg_k = h + R + .0025 + 1e-3 for all four, and the left pair is skipped or evaluated as one
+    //   (op_blend of a +inf is NaN, not the other member).  1e-3 more outside the product covers the rounding of M and of dot.
     const float inf = u2f(0x7f800000u);
     const D2 ground = {dot(V3(0.f, 1.f, 0.f), P) + (1.2f + 0.5f), mat_ground};           // sd_plane :136-138
     float dmin = ground.d;
@@ -82,8 +104,17 @@ __device__ __forceinline__ D2 egg_sdf(const FrameEgg& F, v3 P, W& w) {
     D2 egg = {inf, mat_egg};
     {
         const v3 qe = p - V3(0, egg_y, 0);
-        const float K = dmin * 1.001f + (.95f + 3e-3f);
-        if (!(pos_d && dot(qe, qe) > K * K)) {
+        const float K = BUILD == EGG_OVAL ? (dmin + (.475f + 2e-3f)) * 1.552f : dmin * 1.001f + (.95f + 3e-3f);
+        if (BUILD == EGG_OVAL) {                                                         // :53-66
+            if (!(pos_d && dot(qe, qe) > K * K)) {
+                // mat3 * vec3 is (c0 v.x + c1 v.y) + c2 v.z, scale first, then iscale, zero terms included: 0 * inf is a NaN, and
+                // (-0) + 0 is +0.  1. / s is the binary32 quotient (the reference's -fsingle-precision-constant).
+                const float s = 1.55f;
+                const m3 scale = M3(s, 0, 0, 0, 1, 0, 0, 0, 1);
+                const m3 iscale = M3(1.f / s, 0, 0, 0, 1.f / s, 0, 0, 0, 1.f);
+                egg.d = w.length(mul(iscale, mul(scale, qe))) - 0.475f;
+            }
+        } else if (!(pos_d && dot(qe, qe) > K * K)) {
             const float egg_m = w.length(p - V3(0, egg_y, 0)) - 0.475f;                  // :47-49
             const float egg_b = w.length(p - V3(0, egg_y - 0.45f, 0)) - 0.25f;
             const float egg_t = w.length(p - V3(0, egg_y + 0.45f, 0)) - 0.25f;
@@ -95,19 +126,39 @@ __device__ __forceinline__ D2 egg_sdf(const FrameEgg& F, v3 P, W& w) {
 
     const D2 _1 = op_add2(feet, bike);
     const D2 _2 = op_add2(egg, _1);
-    const float leg_l = (CULL && bezier_far(F.leg_l, p, thick, dmin)) ? inf : sd_bezier_x(F.leg_l, p, thick, w);     // :102-118
-    const float leg_r = (CULL && bezier_far(F.leg_r, p, thick, dmin)) ? inf : sd_bezier_x(F.leg_r, p, thick, w);
-    const D2 legs = op_add2(D2{leg_l, mat_egg}, D2{leg_r, mat_egg});
+    D2 legs;
+    if constexpr (BUILD == EGG_STRAIGHT) {                                               // :86-93, :97-109
+        const FrameEggStraight& L = static_cast<const FrameEggStraight&>(F);             // (what k_egg<., ., EGG_STRAIGHT> is given)
+        auto far = [&](int i) {
+            const v3 q = p - L.leg_m[i];
+            const float K = (dmin + L.leg_k[i]) * 1.4143f + 1e-3f;
+            return pos_d && dot(q, q) > K * K;
+        };
+        auto leg = [&](int i) { return sd_cylinder0<false>(L.leg[i], p + L.leg_o[i], thick, w); };
+        // the right pair first: a plain union, each member on its own; then the left pair, as one
+        D2 right_a = {inf, mat_egg}, right_b = {inf, mat_egg};
+        if (!far(2)) right_a.d = leg(2);
+        dmin = fmin_(dmin, right_a.d);
+        if (!far(3)) right_b.d = leg(3);
+        dmin = fmin_(dmin, right_b.d);
+        D2 left = {inf, mat_egg};
+        if (!(far(0) && far(1))) left.d = op_blend(leg(0), leg(1), .01f);
+        legs = op_add2(left, op_add2(right_a, right_b));
+    } else {
+        const float leg_l = (CULL && bezier_far(F.leg_l, p, thick, dmin)) ? inf : sd_bezier_x(F.leg_l, p, thick, w);     // :102-118
+        const float leg_r = (CULL && bezier_far(F.leg_r, p, thick, dmin)) ? inf : sd_bezier_x(F.leg_r, p, thick, w);
+        legs = op_add2(D2{leg_l, mat_egg}, D2{leg_r, mat_egg});
+    }
     const D2 _3 = op_add2(legs, _2);
     return op_add2(ground, _3);
 }
 
-template <bool CULL, class W>
+template <bool CULL, int BUILD, class W>
 __device__ __forceinline__ float egg_shadowmarch(const FrameEgg& F, v3 ro, v3 rd, W& w) {   // :161-186
     float t = 0.f, umbra = 1.f;
     for (int i = 0; i < 20; ++i) {
         const v3 p = ro + rd * t;
-        const D2 d = egg_sdf<CULL>(F, p, w);
+        const D2 d = egg_sdf<CULL, BUILD>(F, p, w);
         if (t > 10.f) break;
         if (d.d < 0.001f) return 0.1f;
         t += d.d;
@@ -159,11 +210,11 @@ __device__ __forceinline__ void hot_first_tile(const HotRect& R, int gx, int& bx
 struct EggRay { float t; bool done, hit; int mat; v3 hp; int steps; };
 
 // the trace's 80 steps, up to the hit or the far plane
-template <bool CULL, class W>
+template <bool CULL, int BUILD, class W>
 __device__ __forceinline__ void egg_trace_steps(const FrameEgg& F, v3 ro, v3 rd, EggRay& r, W& w) {
     for (int i = 0; i < 80; ++i) {                          // render_scene :190-231
         const v3 p = ro + rd * r.t;
-        const D2 d = egg_sdf<CULL>(F, p, w);
+        const D2 d = egg_sdf<CULL, BUILD>(F, p, w);
         if (r.t > 15.f) { r.done = true; break; }
         if (d.d < 0.001f) { r.hit = true; r.mat = (int)d.m; r.hp = p; r.done = true; break; }
         r.t += d.d;
@@ -178,14 +229,14 @@ __device__ __forceinline__ void egg_trace_steps(const FrameEgg& F, v3 ro, v3 rd,
 #endif
 
 // One pixel up to (colour, depth) — render_scene :190-231 — with the roots of witness `w`
-template <bool CULL, class W>
+template <bool CULL, int BUILD, class W>
 __device__ __forceinline__ void egg_pixel(const FrameEgg& F, v2 pc, W& w, v3& color, float& depth, int& st_trace, int& st_shadow) {
     const v3 ro = F.cam.eye, rd = primary_dir(F.cam, pc, w);
     depth = -1e8f;                                          // :188, fresh per pixel
     color = V3(.1f, .1f, .7f);                              // background :9-12
     EggRay r;
     r.t = 0.f; r.done = false; r.hit = false; r.mat = 0; r.hp = V3(0, 0, 0); r.steps = 0;
-    egg_trace_steps<CULL>(F, ro, rd, r, w);
+    egg_trace_steps<CULL, BUILD>(F, ro, rd, r, w);
 #ifdef SBX_EGG_STATS
     st_trace = r.steps;
     st_shadow = (r.hit && r.mat == 3) ? 1 : 0;
@@ -195,7 +246,7 @@ __device__ __forceinline__ void egg_pixel(const FrameEgg& F, v2 pc, W& w, v3& co
         float s = 1.f;
         if (r.mat == 3) {
             const v3 sh_dir = V3(0, 1, 1);
-            s = egg_shadowmarch<CULL>(F, r.hp + sh_dir * 0.05f, sh_dir, w);
+            s = egg_shadowmarch<CULL, BUILD>(F, r.hp + sh_dir * 0.05f, sh_dir, w);
         }
         v3 base = V3(1, 1, 1);                              // illuminate :29-35
         if (r.mat == 3) base = V3(13.f / 255.f, 104.f / 255.f, 0.f / 255.f);
@@ -214,8 +265,10 @@ __device__ __forceinline__ v3 egg_bars(v3 color, float pcx, float depth) {
 
 // WIT: 0 = IEEE roots; 1 = witnessed roots (the shipped form); 2 = the same with the witness's lower edge at 1.0, so that waves
 // near any primitive's axis DO record and re-run (sbx_set_variant 2: the test of the re-run path — same frame required)
-template <bool CULL, int WIT>
-__global__ void __launch_bounds__(64 * EGG_TX) k_egg(FrameEgg F, RowMap M, float* __restrict__ out, HotRect hot) {
+template <int BUILD> struct EggFrame { using type = FrameEgg; };
+template <> struct EggFrame<EGG_STRAIGHT> { using type = FrameEggStraight; };      // FrameEgg and the four cylinders (sbx_frame.h)
+template <bool CULL, int WIT, int BUILD = EGG_DEFAULT>
+__global__ void __launch_bounds__(64 * EGG_TX) k_egg(typename EggFrame<BUILD>::type F, RowMap M, float* __restrict__ out, HotRect hot) {
 #ifdef SBX_EGG_STATS
     const unsigned long long st_t0 = __builtin_amdgcn_s_memrealtime();      // census build (tools/egg_census.py): 100 MHz counter
 #endif
@@ -242,14 +295,14 @@ __global__ void __launch_bounds__(64 * EGG_TX) k_egg(FrameEgg F, RowMap M, float
     if (WIT != 0) {
         Wit<true> w;
         if (WIT == 2) w.lo = 0x3F800000u;
-        egg_pixel<CULL>(F, pc, w, color, depth, st_trace, st_shadow);
+        egg_pixel<CULL, BUILD>(F, pc, w, color, depth, st_trace, st_shadow);
         if (__builtin_amdgcn_ballot_w64(w.bad) != 0ull) {      // some lane took a root outside the proved interval: the IEEE forms
             Wit<false> w0;
-            egg_pixel<CULL>(F, pc, w0, color, depth, st_trace, st_shadow);
+            egg_pixel<CULL, BUILD>(F, pc, w0, color, depth, st_trace, st_shadow);
         }
     } else {
         Wit<false> w0;
-        egg_pixel<CULL>(F, pc, w0, color, depth, st_trace, st_shadow);
+        egg_pixel<CULL, BUILD>(F, pc, w0, color, depth, st_trace, st_shadow);
     }
     tile_cost_store_at(M, tl_t0, bx, by);                  // (bx, by: after the hot-first mapping)
     color = egg_bars(color, pc.x, depth);
@@ -316,21 +369,28 @@ static HotRect egg_hot_rect(const FrameEgg& F, const RowMap& M, dim3 grid) {
     if (x1 <= x0 || y1 <= y0) return none;
     return HotRect{x0, y0, x1 - x0, y1 - y0};
 }
-template <bool CULL, int WIT>
-static void launch_egg_t(const FrameEgg& F, const RowMap& M, float* out, hipStream_t s, dim3 grid, HotRect hot, size_t pad) {
-    hipLaunchKernelGGL((k_egg<CULL, WIT>), grid, dim3(64 * EGG_TX), pad, s, F, M, out, hot);
+template <bool CULL, int WIT, int BUILD>
+static void launch_egg_t(const FrameEggStraight& F, const RowMap& M, float* out, hipStream_t s, dim3 grid, HotRect hot, size_t pad) {
+    const typename EggFrame<BUILD>::type& Fb = F;            // the build's part of the frame
+    hipLaunchKernelGGL((k_egg<CULL, WIT, BUILD>), grid, dim3(64 * EGG_TX), pad, s, Fb, M, out, hot);
+}
+template <int BUILD>
+static void launch_egg_b(const FrameEggStraight& F, const RowMap& M, float* out, hipStream_t s, int variant, dim3 grid, HotRect hot, size_t pad) {
+    if (variant == 1) launch_egg_t<false, 0, BUILD>(F, M, out, s, grid, hot, pad);
+    else if (variant == 2) launch_egg_t<true, 2, BUILD>(F, M, out, s, grid, hot, pad);
+    else if (variant == 3) launch_egg_t<true, 0, BUILD>(F, M, out, s, grid, hot, pad);
+    else launch_egg_t<true, EGG_WITNESS, BUILD>(F, M, out, s, grid, hot, pad);
 }
 
 dim3 egg_grid(const RowMap& M) { return grid_for<EGG_TW, EGG_TX>(M); }
 
-void launch_egg(const FrameEgg& F, const RowMap& M, float* out, hipStream_t s, int variant) {
+void launch_egg(const FrameEggStraight& F, const RowMap& M, float* out, hipStream_t s, int variant, int build) {
     const dim3 grid = grid_for<EGG_TW, EGG_TX>(M);
     const HotRect hot = egg_hot_rect(F, M, grid);
     static const int pad = []() { const char* e = std::getenv("SBX_DEBUG_LDS_PAD"); return e ? std::atoi(e) : EGG_LDS_PAD; }();
-    if (variant == 1) launch_egg_t<false, 0>(F, M, out, s, grid, hot, (size_t)pad);
-    else if (variant == 2) launch_egg_t<true, 2>(F, M, out, s, grid, hot, (size_t)pad);
-    else if (variant == 3) launch_egg_t<true, 0>(F, M, out, s, grid, hot, (size_t)pad);
-    else launch_egg_t<true, EGG_WITNESS>(F, M, out, s, grid, hot, (size_t)pad);
+    if (build == EGG_STRAIGHT) launch_egg_b<EGG_STRAIGHT>(F, M, out, s, variant, grid, hot, (size_t)pad);
+    else if (build == EGG_OVAL) launch_egg_b<EGG_OVAL>(F, M, out, s, variant, grid, hot, (size_t)pad);
+    else launch_egg_b<EGG_DEFAULT>(F, M, out, s, variant, grid, hot, (size_t)pad);
 }
 
 }  // namespace sbx

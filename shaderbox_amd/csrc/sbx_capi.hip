@@ -239,7 +239,11 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
                                                     // a captured launch is replayed later, possibly over volumes re-bound in place with
                                                     // other texel ranges: no bounds baked into a graph (the plain exp_ / IEEE divide)
                                                     (ctx->noise.bounds_valid && !capturing) ? ctx->noise.bounds : nullptr); break;
-    case SBX_APP_EGG: launch_egg(build_egg(*uni), M, rgba, s, sdf_variant); break;
+    // one scene, three builds of app_egg.h (include/sbx.h).  The app is part of the key of a dispatch-order table (tile_order_begin) and
+    // of a frame cached by sbx_main_image (mi_make_key): neither is ever served to another build
+    case SBX_APP_EGG: launch_egg(build_egg(*uni, EGG_DEFAULT), M, rgba, s, sdf_variant, EGG_DEFAULT); break;
+    case SBX_APP_EGG_STRAIGHT: launch_egg(build_egg(*uni, EGG_STRAIGHT), M, rgba, s, sdf_variant, EGG_STRAIGHT); break;
+    case SBX_APP_EGG_OVAL: launch_egg(build_egg(*uni, EGG_OVAL), M, rgba, s, sdf_variant, EGG_OVAL); break;
     case SBX_APP_RAYTRACER: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots); break;
     case SBX_APP_ATMOSPHERE: launch_atmosphere(build_atmosphere(*uni), M, rgba, s, ctx->precision); break;
     case SBX_APP_ATMOSPHERE_GROUND: launch_atmosphere_ground(build_atmosphere_ground(*uni), M, rgba, s, ctx->precision, ctx->variant); break;

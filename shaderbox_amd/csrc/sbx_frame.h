@@ -160,6 +160,16 @@ struct FrameEgg {
     v3 oc; float orad;          // sphere around everything but the ground plane, in sdf()'s p space (kern_egg.hip egg_far)
     v3 ocw;                     // the same centre in WORLD space, rot_y^T (oc + (0, .5, 3.5)): the cull test needs no rotation
 };
+// The build without `#define BEZIER` (app_egg.h:37; SBX_APP_EGG_STRAIGHT): FrameEgg and the four sd_cylinder legs of :86-93, :97-104,
+// in the order left a (pelvis -> knee), left b (knee -> foot), right a, right b.  A type of its own, so that the kernels of the
+// other builds take the arguments they always took (k_egg's shipped build compiles to the same instructions as before it had builds).
+struct FrameEggStraight : FrameEgg {
+    CylFrame leg[4];            // axes knee_l - side, left_foot - knee_l, knee_r + side, right_foot - knee_r (all with P0 = 0)
+    v3 leg_o[4];                // what sdf() adds to p before the call: side, knee_l, -side, knee_r
+    v3 leg_m[4];                // midpoints of the cylinders in p space: -leg_o - dir * len1 / 2 (kern_egg.hip)
+    float leg_k[4];             // len1 / 2 + thick + .0025 + 1e-3: half length, radius, what op_blend(.., .01) can take off, slack
+};
+enum { EGG_DEFAULT = 0, EGG_STRAIGHT = 1, EGG_OVAL = 2 };   // the builds of app_egg.h (include/sbx.h): SBX_APP_EGG, _EGG_STRAIGHT, _EGG_OVAL
 
 // ---- APP_RAYTRACER (src/app_raytracer.h, cornell_box.h) -------------------------------------
 struct RtPlane { v3 n; float d; int mat; };

@@ -70,8 +70,9 @@ static v3 ik_solver(v3 start, v3 goal_abs, float L1, float L2) {       // IK.h:5
     const m3 rot = M3(cos_theta, -sin_theta, 0, sin_theta, cos_theta, 0, 0, 0, 1.f);
     return start + mul(rot, normalize(goal) * L1);
 }
-FrameEgg build_egg(const sbx_uniforms& U) {
-    FrameEgg F;
+// build: EGG_DEFAULT (app_egg.h as shipped), EGG_STRAIGHT (without `#define BEZIER`, :37) or EGG_OVAL (`#if 1` at :46 -> `#if 0`)
+FrameEggStraight build_egg(const sbx_uniforms& U, int build) {
+    FrameEggStraight F;
     F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(.0f, .25f, 5.25f), V3(.0f, .25f, .0f));   // app_egg.h:23-27,253
     const float t = U.u_time;
     F.rot_y = rotate_around_y(t * -100.0f);                            // :40
@@ -81,12 +82,21 @@ FrameEgg build_egg(const sbx_uniforms& U) {
     F.left_foot = wheel_pos + mul(rot_z, V3(0.f, pedal_radius, pedal_off));
     F.right_foot = wheel_pos + mul(rot_z, V3(0.f, -pedal_radius, -pedal_off));
     const v3 side = V3(0, 0, pedal_off);
-    const float femur = 0.8f, tibia = 0.75f;
+    const float femur = 0.8f, tibia = 0.75f, thick = .05f;
     const v3 zero = V3(0.f, 0.f, 0.f);
     const v3 knee_l = ik_solver(zero + side, F.left_foot, femur, tibia);   // :84-85
     const v3 knee_r = ik_solver(zero - side, F.right_foot, femur, tibia);  // :95-96
     F.leg_l = bezier_frame(-(zero + side), -knee_l, -F.left_foot);         // :111-113
     F.leg_r = bezier_frame(-(zero - side), -knee_r, -F.right_foot);        // :114-116
+    // the straight legs (:86-93, :97-104): sd_cylinder(p + o, 0, axis, thick) fills, in p space, the segment from -o to -o - axis
+    const v3 leg_o[4] = {zero + side, knee_l, zero - side, knee_r};
+    const v3 leg_axis[4] = {knee_l - side, F.left_foot - knee_l, knee_r + side, F.right_foot - knee_r};
+    for (int i = 0; i < 4; ++i) {
+        F.leg[i] = cyl_frame(zero, leg_axis[i]);
+        F.leg_o[i] = leg_o[i];
+        F.leg_m[i] = -leg_o[i] + F.leg[i].dir * (F.leg[i].len1 * -.5f);
+        F.leg_k[i] = F.leg[i].len1 * .5f + (thick + .0025f + 1e-3f);
+    }
     const v3 left_toe = normalize(V3(F.left_foot.y - knee_l.y, knee_l.x - F.left_foot.x, 0));     // :120
     const v3 right_toe = normalize(V3(F.right_foot.y - knee_r.y, knee_r.x - F.right_foot.x, 0));  // :125
     F.foot_l = cyl_frame(zero, left_toe / 8.f);
@@ -96,19 +106,42 @@ FrameEgg build_egg(const sbx_uniforms& U) {
     // positive: egg spheres r + .36 (two smooth-mins of k = .5 lower the union by <= .25), tubes br + .061 (the .85
     // factor and the thickness), toe cylinders .161 around their midpoint (max(axis, slabs) >= |.|/sqrt2 - 1/16),
     // wheel 1.03.
+    // The other builds have other members, so the sphere is the build's own (it also drives k_egg's hot rectangle):
+    //   straight legs: max(line, plane, plane) - R >= |p - M| / sqrt2 - len / 2 - R around the midpoint M, and op_blend(a, b, .01)
+    //                  lies at most .01 / 4 below min(a, b): rho = sqrt2 (len / 2 + R + .0025), which is 1.4143 leg_k
+    //   oval egg:      |iscale scale q| >= |q| / 1.55, so the value is >= (|q| - 1.55 * .475) / 1.55: rho = .74, at the slope
+    //                  1 / 1.55 < .7 that egg_far<EGG_OVAL> allows for (every other member's .7 holds a fortiori)
     F.foot_ml = -F.left_foot + left_toe * (-1.f / 16.f);
     F.foot_mr = -F.right_foot + right_toe * (-1.f / 16.f);
     const float egg_y = 0.65f;
-    const v3 cs[8] = {V3(0, egg_y, 0), V3(0, egg_y - 0.45f, 0), V3(0, egg_y + 0.45f, 0), F.leg_l.bc, F.leg_r.bc,
-                      -F.left_foot + left_toe * (-1.f / 16.f), -F.right_foot + right_toe * (-1.f / 16.f), -wheel_pos};
-    const float rs[8] = {.475f + .36f, .25f + .36f, .25f + .36f, F.leg_l.br + .061f, F.leg_r.br + .061f, .161f, .161f, 1.03f};
-    v3 c = V3(0, 0, 0);
-    for (int i = 0; i < 8; ++i) c = c + cs[i] * .125f;
-    float R = 0.f;
-    for (int i = 0; i < 8; ++i) R = fmax_(R, length(cs[i] - c) + rs[i]);
-    F.oc = c;
-    F.orad = R * 1.001f + 1e-3f;
-    F.ocw = mul(transpose(F.rot_y), c + V3(0, 0.5f, 3.5f));        // p = rot_y P - (0, .5, 3.5)  <=>  P = rot_y^T (p + (0, .5, 3.5))
+    if (build == EGG_DEFAULT) {
+        const v3 cs[8] = {V3(0, egg_y, 0), V3(0, egg_y - 0.45f, 0), V3(0, egg_y + 0.45f, 0), F.leg_l.bc, F.leg_r.bc,
+                          -F.left_foot + left_toe * (-1.f / 16.f), -F.right_foot + right_toe * (-1.f / 16.f), -wheel_pos};
+        const float rs[8] = {.475f + .36f, .25f + .36f, .25f + .36f, F.leg_l.br + .061f, F.leg_r.br + .061f, .161f, .161f, 1.03f};
+        v3 c = V3(0, 0, 0);
+        for (int i = 0; i < 8; ++i) c = c + cs[i] * .125f;
+        float R = 0.f;
+        for (int i = 0; i < 8; ++i) R = fmax_(R, length(cs[i] - c) + rs[i]);
+        F.oc = c;
+        F.orad = R * 1.001f + 1e-3f;
+    } else {
+        v3 cs[10];
+        float rs[10];
+        int n = 0;
+        auto member = [&](v3 c, float rho) { cs[n] = c; rs[n] = rho; ++n; };
+        if (build == EGG_OVAL) member(V3(0, egg_y, 0), .74f);
+        else { member(V3(0, egg_y, 0), .475f + .36f); member(V3(0, egg_y - 0.45f, 0), .25f + .36f); member(V3(0, egg_y + 0.45f, 0), .25f + .36f); }
+        if (build == EGG_STRAIGHT) for (int i = 0; i < 4; ++i) member(F.leg_m[i], F.leg_k[i] * 1.4143f);
+        else { member(F.leg_l.bc, F.leg_l.br + .061f); member(F.leg_r.bc, F.leg_r.br + .061f); }
+        member(F.foot_ml, .161f); member(F.foot_mr, .161f); member(-wheel_pos, 1.03f);
+        v3 c = V3(0, 0, 0);
+        for (int i = 0; i < n; ++i) c = c + cs[i] * (1.f / (float)n);
+        float R = 0.f;
+        for (int i = 0; i < n; ++i) R = fmax_(R, length(cs[i] - c) + rs[i]);
+        F.oc = c;
+        F.orad = R * 1.001f + 1e-3f;
+    }
+    F.ocw = mul(transpose(F.rot_y), F.oc + V3(0, 0.5f, 3.5f));     // p = rot_y P - (0, .5, 3.5)  <=>  P = rot_y^T (p + (0, .5, 3.5))
     return F;
 }
 

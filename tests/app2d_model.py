@@ -9,29 +9,16 @@ binary64 reciprocal (div_by, sbx_math.h) are proven equal to them, and the GPU t
 """
 import numpy as np
 
-F = np.float32
-PI = F(3.14159265359)                       # src/def.h:51
-ZERO, HALF, ONE, TWO, FOUR, TWELVE, SIXTEEN = F(0), F(.5), F(1), F(2), F(4), F(12), F(16)
+from tests.model_common import F, ONE, TWO, ZERO, fmax, mod, oracle, same_bits
 
-_ORACLE = None
+PI = F(3.14159265359)                       # src/def.h:51
+HALF, FOUR, TWELVE, SIXTEEN = F(.5), F(4), F(12), F(16)
 
 
 def _atan2(y, x):
-    global _ORACLE
-    if _ORACLE is None:
-        from oracle.oracle import Oracle
-        _ORACLE = Oracle()
     y = np.ascontiguousarray(y, dtype=F)
     x = np.ascontiguousarray(np.broadcast_to(x, y.shape), dtype=F)
-    return _ORACLE.math("atan2", y.ravel(), x.ravel()).reshape(y.shape)
-
-
-def mod(x, y):                              # GLSL mod: x - y * floor(x / y)
-    return x - y * np.floor(x / y)
-
-
-def fmax(a, b):                             # the fmax_ rule of sbx_math.h: (a < b) ? b : a
-    return np.where(a < b, b, a).astype(F)
+    return oracle().math("atan2", y.ravel(), x.ravel()).reshape(y.shape)
 
 
 def phase(u_time):
@@ -153,9 +140,3 @@ def frame(width, height, u_time, tex=None, rows=None):
     fy = (ys.astype(F) + HALF)[:, None]
     fx, fy = np.broadcast_arrays(fx, fy)
     return main_image(width, height, u_time, fx, fy, tex)
-
-
-def same_bits(a, b):
-    """per-element bit equality with NaN == NaN (any NaN)"""
-    a, b = np.asarray(a, dtype=F), np.asarray(b, dtype=F)
-    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))

@@ -11,19 +11,10 @@ import os
 
 import numpy as np
 
-F = np.float32
-HALF, ONE, W_OFF = F(.5), F(1), F(.015)
+from tests.model_common import F, ONE, mod, oracle, same_bits
+
+HALF, W_OFF = F(.5), F(.015)
 PERIODS = (4, 8, 16, 24, 32, 64)             # the distinct domain repeats of worley_tex_left / _middle / _right (:17-39)
-
-_ORACLE = None
-
-
-def oracle():
-    global _ORACLE
-    if _ORACLE is None:
-        from oracle.oracle import Oracle
-        _ORACLE = Oracle()
-    return _ORACLE
 
 
 def oracle_noise_w(xyz, L, chunk=1 << 16):
@@ -100,10 +91,6 @@ def _fract(x):
     return x - np.floor(x)
 
 
-def mod(x, y):                               # GLSL mod: x - y * floor(x / y)
-    return x - y * np.floor(x / y)
-
-
 def hash_w(x):
     """hash_w over points float32 [..., 3] -> float32 [..., 3]"""
     x = np.asarray(x, dtype=F)
@@ -146,9 +133,3 @@ def table_cells():
             y, x = np.meshgrid(np.arange(L, dtype=F), np.arange(L, dtype=F), indexing="ij")
             cells.append(np.stack([x.ravel(), y.ravel(), np.full(L * L, z, dtype=F)], axis=-1))
     return np.concatenate(cells).astype(F)
-
-
-def same_bits(a, b):
-    """per-element bit equality with NaN == NaN (any NaN)"""
-    a, b = np.asarray(a, dtype=F), np.asarray(b, dtype=F)
-    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))

@@ -11,8 +11,9 @@ algebra against the oracle's compiled `primary_ray` hook.  The sky itself is the
 """
 import numpy as np
 
-F = np.float32
-ZERO, ONE, TWO = F(0), F(1), F(2)
+from tests import model_common as C
+from tests.model_common import F, ZERO, _f, dot, get_primary_ray, oracle, same_bits
+
 EARTH_RADIUS = F(6360e3)                            # src/app_atmosphere.h:37
 EYE = (F(0), EARTH_RADIUS + F(1.0), F(0))           # :172
 LOOK_AT = (F(0), EARTH_RADIUS + F(1.5), F(-1))      # :173
@@ -21,52 +22,9 @@ MAX_DIST = F(1e8)                                   # src/def.h:77
 NO_HIT_T = MAX_DIST + F(1e1)                        # src/def.h:78-83
 GROUND = F(.33)                                     # :223
 
-_ORACLE = None
 
-
-def oracle():
-    global _ORACLE
-    if _ORACLE is None:
-        from oracle.oracle import Oracle
-        _ORACLE = Oracle()
-    return _ORACLE
-
-
-def dot(a, b):                                      # oracle/ovec.h:67
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
-
-
-def normalize(v):                                   # oracle/ovec.h:69-70
-    n = np.sqrt(dot(v, v))
-    return (v[0] / n, v[1] / n, v[2] / n)
-
-
-def cross(a, b):                                    # oracle/ovec.h:71-73
-    return (a[1] * b[2] - b[1] * a[2], a[2] * b[0] - b[2] * a[0], a[0] * b[1] - b[0] * a[1])
-
-
-def _f(x):
-    return np.asarray(x, dtype=F)
-
-
-def point_cam(width, height, fx, fy, fov=FOV):      # oracle/ref_apps.h:31,35-36 (main.h:33,40,44-46); point_cam.z = -1
-    fx, fy = _f(fx), _f(fy)
-    w, h = F(width), F(height)
-    with np.errstate(all="ignore"):
-        aspect = w / h
-        return ((TWO * (fx / w) - ONE) * aspect) * fov, ((TWO * (fy / h) - ONE) * ONE) * fov
-
-
-def get_primary_ray(pcx, pcy, eye, look_at):        # oracle/ref_lib.h:56-65 (util.h:5-20); the point's z is not read
-    eye, look_at = tuple(map(F, eye)), tuple(map(F, look_at))
-    pcx, pcy = _f(pcx), _f(pcy)
-    with np.errstate(all="ignore"):
-        fwd = normalize((look_at[0] - eye[0], look_at[1] - eye[1], look_at[2] - eye[2]))
-        up = (ZERO, ONE, ZERO)
-        right = cross(up, fwd)
-        up = cross(fwd, right)
-        v = tuple((fwd[k] + up[k] * pcy) + right[k] * pcx for k in range(3))
-        return normalize(v)
+def point_cam(width, height, fx, fy, fov=FOV):      # main.h:44-46 with this header's FOV
+    return C.point_cam(width, height, fx, fy, fov)
 
 
 def intersect_plane_t(rd, origin=EYE, direction=(ZERO, F(-1), ZERO), distance=EARTH_RADIUS):
@@ -119,9 +77,3 @@ def horizon_row(width, height):
     pcx, pcy = point_cam(width, height, np.full(height, F(.5)), np.arange(height, dtype=F) + F(.5))
     sky = intersect_plane_t(get_primary_ray(pcx, pcy, EYE, LOOK_AT)) > MAX_DIST
     return int(np.argmax(sky)) if sky.any() else height
-
-
-def same_bits(a, b):
-    """per-element bit equality with NaN == NaN (any NaN)"""
-    a, b = np.asarray(a, dtype=F), np.asarray(b, dtype=F)
-    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))

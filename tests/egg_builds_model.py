@@ -13,35 +13,24 @@ operation order (oracle/ovec.h: dot = (x x + y y) + z z, normalize = three divis
 with its zero terms; oracle/sbx_math_ref.h: min / max as compare-and-select, mix = x (1 - a) + y a), every value an explicit
 np.float32 so that nothing widens to float64.  sin, cos and pow are the oracle's (Oracle.math).  What sdf() computes from u_time
 alone (src/app_egg.h:40, 68-96, 120, 125) is evaluated once per frame (`scene`), in the same operations; sdf is pinned against the
-oracle's hook `egg.sdf`.  Camera algebra is shared with tests/sdf_ao_builds_model.py.
+oracle's hook `egg.sdf`.  The vector algebra and the camera are tests/model_common.py's.
 """
 import concurrent.futures
 
 import numpy as np
 
-from tests.atmosphere_ground_model import cross
-from tests.sdf_ao_builds_model import dot, fmax, fmin, get_primary_ray, normalize, oracle, point_cam, same_bits  # noqa: F401
+from tests.model_common import (F, ONE, TWO, ZERO, _const, _f, _sincos, cross, dot, fmax, fmin, get_primary_ray, normalize, op_add2,
+                                 oracle, point_cam, same_bits)
 
-F = np.float32
-ZERO, ONE, TWO, HALF = F(0), F(1), F(2), F(.5)
+HALF = F(.5)
 BUILDS = ("default", "straight", "oval")
 APP_OF = {"default": "egg", "straight": "egg_straight", "oval": "egg_oval"}
-RADIANS = F(0.017453292519943295)                   # oracle/sbx_math_ref.h m_radians
 EYE, LOOK_AT = (F(.0), F(.25), F(5.25)), (F(.0), F(.25), F(.0))      # :23-27
 MAT_EGG, MAT_BIKE, MAT_GROUND = 1, 2, 3             # :17-20
 COLORS = {MAT_GROUND: (F(13.) / F(255.), F(104.) / F(255.), F(0.) / F(255.)), MAT_EGG: (F(0.9), F(0.95), F(0.95)),
           MAT_BIKE: (F(.2), F(.2), F(.2))}          # illuminate :29-35
 THICK = F(.05)
-
-
-def _f(x):
-    return np.asarray(x, dtype=F)
-
-
-def _sincos(deg):
-    a = _f(F(deg) * RADIANS).reshape(1)
-    o = oracle()
-    return o.math("sin", a)[0], o.math("cos", a)[0]
+FOV = F(1.)                                         # :253
 
 
 def mat_vec(m, v):
@@ -86,11 +75,6 @@ def mix(x, y, a):                                   # m_mix
 def op_blend(a, b, k):                              # sdf.h:38-47
     h = clamp(HALF + HALF * (b - a) / k, ZERO, ONE)
     return mix(b, a, h) - k * h * (ONE - h)
-
-
-def op_add2(a, b):                                  # sdf.h:5-11: d1.x < d2.x ? d1 : d2
-    k = a[0] < b[0]
-    return np.where(k, a[0], b[0]), np.where(k, a[1], b[1])
 
 
 def ik_solver(start, goal_abs, l1, l2):             # IK.h:5-52
@@ -179,10 +163,6 @@ def scene(u_time):
             _SCENES.clear()
         _SCENES[key] = S
     return _SCENES[key]
-
-
-def _const(v, like):
-    return np.full(like.shape, v, dtype=F)
 
 
 def sdf(build, u_time, px, py, pz, members=None):
@@ -311,7 +291,7 @@ def main_image(build, width, height, u_time, fx, fy, parts=None):
     assert build in BUILDS, build
     fx, fy = np.broadcast_arrays(_f(fx), _f(fy))
     shape = fx.shape
-    pcx, pcy = point_cam(width, height, fx.ravel(), fy.ravel())
+    pcx, pcy = point_cam(width, height, fx.ravel(), fy.ravel(), FOV)
     rd = get_primary_ray(pcx, pcy, EYE, LOOK_AT)
     rgb, depth = render_scene(build, u_time, EYE, rd, parts)
     with np.errstate(all="ignore"):                 # render :233-251

@@ -12,40 +12,21 @@ mainImage -> render -> render_impl -> sdf_shadow / illuminate, vectorised over p
 operation order (oracle/ovec.h: dot = (x x + y y) + z z, normalize = three divisions by sqrtf; oracle/sbx_math_ref.h: min / max as
 compare-and-select, mix = x (1 - a) + y a), every value an explicit np.float32 so that nothing widens to float64.  sin, cos, exp
 and pow are the oracle's (Oracle.math).  sdf is restated here (a known-answer hook per point would take minutes per frame) and
-pinned against the hook `sdf_ao.sdf`; camera algebra is shared with tests/atmosphere_ground_model.py.
+pinned against the hook `sdf_ao.sdf`; the vector algebra and the camera are tests/model_common.py's.
 """
 import concurrent.futures
 import struct
 
 import numpy as np
 
-from tests.atmosphere_ground_model import dot, get_primary_ray, normalize, oracle, point_cam, same_bits  # noqa: F401
+from tests.model_common import (F, ONE, TWO, ZERO, _const, _f, _sincos, dot, fmax, fmin, get_primary_ray, normalize, op_add2, oracle,
+                                 point_cam, same_bits)
 
-F = np.float32
-ZERO, ONE, TWO = F(0), F(1), F(2)
 BUILDS = ("default", "shadow", "normals")
 FOG_DENSITY, FOG_FALLOFF = F(.1), F(.5)             # src/uniform_buffer.h:56-60 (oracle/ref_lib.h sdf_ao_aux_t)
 SIZE = (F(1.3), F(1.), F(1.25))                     # :52
 MATERIALS = np.array([[1, 1, 1], [0, .2, 0], [.1, .1, .1], [.1, .1, .1], [.1, .1, .1], [.4, .4, .4]], dtype=F)   # :35-43
-RADIANS = F(0.017453292519943295)                   # oracle/sbx_math_ref.h m_radians
-
-
-def _f(x):
-    return np.asarray(x, dtype=F)
-
-
-def _sincos(deg):
-    a = _f(F(deg) * RADIANS).reshape(1)
-    o = oracle()
-    return o.math("sin", a)[0], o.math("cos", a)[0]
-
-
-def fmax(a, b):                                     # m_max: (a < b) ? b : a
-    return np.where(a < b, b, a)
-
-
-def fmin(a, b):                                     # m_min: (b < a) ? b : a
-    return np.where(b < a, b, a)
+FOV = F(1.)                                         # :313
 
 
 def aux_bytes(aux):
@@ -74,21 +55,12 @@ def sd_y_cylinder(p, r, h):                         # sdf.h:85-93
     return fmax(np.sqrt(p[0] * p[0] + p[2] * p[2]) - r, np.abs(p[1]) - h / TWO)
 
 
-def op_add2(a, b):                                  # sdf.h:5-11: d1.x < d2.x ? d1 : d2
-    k = a[0] < b[0]
-    return np.where(k, a[0], b[0]), np.where(k, a[1], b[1])
-
-
 def _mul_rx(p, s, c):                               # mul(p, rotate_around_x): columns (1,0,0), (0,c,-s), (0,s,c)
     return ((p[0] * ONE + p[1] * ZERO) + p[2] * ZERO, (p[0] * ZERO + p[1] * c) + p[2] * (-s), (p[0] * ZERO + p[1] * s) + p[2] * c)
 
 
 def _mul_ry(p, s, c):                               # mul(p, rotate_around_y): columns (c,0,s), (0,1,0), (-s,0,c)
     return ((p[0] * c + p[1] * ZERO) + p[2] * s, (p[0] * ZERO + p[1] * ONE) + p[2] * ZERO, (p[0] * (-s) + p[1] * ZERO) + p[2] * c)
-
-
-def _const(v, like):
-    return np.full(like.shape, v, dtype=F)
 
 
 def sdf_pipe(pos):                                  # :54-113
@@ -293,7 +265,7 @@ def main_image(build, width, height, u_time, fx, fy, aux=None, parts=None):
     density, falloff = (FOG_DENSITY, FOG_FALLOFF) if aux is None else (F(aux[0]), F(aux[1]))
     fx, fy = np.broadcast_arrays(_f(fx), _f(fy))
     shape = fx.shape
-    pcx, pcy = point_cam(width, height, fx.ravel(), fy.ravel())
+    pcx, pcy = point_cam(width, height, fx.ravel(), fy.ravel(), FOV)
     eye, look_at = camera(u_time)
     rd = get_primary_ray(pcx, pcy, eye, look_at)
     rgb, t = render_impl(build, eye, rd, parts)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from tests import egg_builds_model as M
+from tests.app_checks import assert_same
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "egg_builds")
@@ -30,16 +31,6 @@ def golden(build):
     assert z["points_out"].shape == z["points_shipped"].shape == (4096, 4)
     assert tuple(z["points_uniforms"][:4]) == (1920, 1080, 0, 0)
     return [(float(u[4]), z[k]) for k, u in zip(keys, z["uniforms"])], z["points"], z["points_uniforms"], z["points_out"], z["points_shipped"]
-
-
-def assert_same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    ok = M.same_bits(got, want)
-    if not ok.all():
-        i = np.argwhere(~ok)[:3]
-        raise AssertionError("%s: %d differing channels, first %s: got %s want %s"
-                             % (what, int((~ok).sum()), i.tolist(), [got[tuple(j)] for j in i], [want[tuple(j)] for j in i]))
 
 
 # ---- what the three builds share: the shipped build against the oracle --------------------------------------------------------

@@ -1,36 +1,17 @@
 """GPU tests of SBX_APP_2D / SBX_APP_2D_TEX (src/app_2d.h; include/sbx.h): every layer bit for bit, NaN == NaN, all four channels,
 against the numpy restatement of tests/app2d_model.py."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import app2d_model as M
+from tests.app_checks import assert_same, build_dropin, run_dropin
+from tests.app_checks import renderer  # noqa: F401 (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TIMES = [0.37, 2.0, 5.5, 9.25, 13.0, 4.0, 8.0, 12.0, 16.37, -3.1, 1000.9]
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import shaderbox_amd
-    r = shaderbox_amd.Renderer(0)
-    yield r
-    r.close()
-
-
-def assert_same(got, want, what):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else np.asarray(got)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    ok = M.same_bits(got, want)
-    if not ok.all():
-        i = np.argwhere(~ok)[:3]
-        raise AssertionError("%s: %d differing channels, first %s: got %s want %s"
-                             % (what, int((~ok).sum()), i.tolist(), [got[tuple(j)] for j in i], [want[tuple(j)] for j in i]))
 
 
 @pytest.mark.parametrize("w,h", [(1920, 1080), (3840, 2160)])
@@ -209,44 +190,8 @@ def test_bad_texture_arguments(renderer):
     assert_same(renderer.render("2d_tex", 96, 54, 0.37), M.frame(96, 54, 0.37, M.decode_unorm8(M.checkerboard_texture())), "after refusals")
 
 
-DROPIN = r'''
-#include "sbx_mainimage.hpp"
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-struct vec2 { float x, y; float operator[](int i) const { return i ? y : x; } };
-struct vec4 { float v[4]; float& operator[](int i) { return v[i]; } };
-int main(int argc, char** argv) {
-    const int W = atoi(argv[1]), H = atoi(argv[2]);
-    iResolution[0] = (float)W; iResolution[1] = (float)H;
-    iGlobalTime = (float)atof(argv[3]);
-    std::vector<float> px((size_t)W * H * 4);
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            vec4 c;
-            mainImage(c, vec2{x + .5f, y + .5f});
-            for (int k = 0; k < 4; ++k) px[((size_t)y * W + x) * 4 + k] = c[k];
-        }
-    FILE* f = fopen(argv[4], "wb");
-    fwrite(px.data(), sizeof(float), px.size(), f);
-    fclose(f);
-    return 0;
-}
-'''
-
-
 def test_cpp_dropin(tmp_path):
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    src = tmp_path / "dropin.cpp"
-    src.write_text(DROPIN)
-    lib = os.path.join(ROOT, "shaderbox_amd", "lib")
     for define, tex in [("APP_2D", None), ("APP_2D_TEX", M.decode_unorm8(M.checkerboard_texture()))]:
-        exe = str(tmp_path / define)
-        subprocess.run(["g++", "-std=c++17", "-O2", "-D__HIP_PLATFORM_AMD__", "-D" + define, "-I" + os.path.join(ROOT, "include"),
-                        "-I" + os.path.join(rocm, "include"), "-o", exe, str(src), "-L" + lib, "-lsbx", "-L" + os.path.join(rocm, "lib"),
-                        "-lamdhip64", "-Wl,-rpath," + lib, "-Wl,-rpath," + os.path.join(rocm, "lib")], check=True)
+        exe = build_dropin(tmp_path, [define], define)
         for w, h, t in [(320, 180, 0.37), (97, 61, 9.25), (64, 48, 13.0)]:
-            out = str(tmp_path / "px.f32")
-            subprocess.run([exe, str(w), str(h), repr(t), out], check=True, timeout=120)
-            got = np.fromfile(out, dtype=np.float32).reshape(h, w, 4)
-            assert_same(got, M.frame(w, h, t, tex), (define, w, h, t))
+            assert_same(run_dropin(exe, w, h, t, tmp_path), M.frame(w, h, t, tex), (define, w, h, t))

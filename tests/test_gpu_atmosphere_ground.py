@@ -8,6 +8,9 @@ import numpy as np
 import pytest
 
 from tests import atmosphere_ground_model as M
+from tests.app_checks import (assert_same, build_dropin, check_loopback_exchanges, check_rgba8, check_rows_host_rows_ranks_and_splits,
+                              frame_cache, run_dropin, run_sbx_render, same_tensor)
+from tests.app_checks import renderer  # noqa: F401 (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -17,37 +20,7 @@ TIMES = (0.0, .37, 2.0, 3.1, 100.25)
 F = np.float32
 
 
-@pytest.fixture(scope="module")
-def renderer():
-    import shaderbox_amd
-    r = shaderbox_amd.Renderer(0)
-    yield r
-    r.close()
-
-
-_FRAMES = {}
-
-
-def model_frame(w, h, t):
-    if (w, h, t) not in _FRAMES:
-        _FRAMES[(w, h, t)] = M.frame(w, h, t)
-    return _FRAMES[(w, h, t)]
-
-
-def assert_same(got, want, what):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else np.asarray(got)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    ok = M.same_bits(got, want)
-    if not ok.all():
-        i = np.argwhere(~ok)[:3]
-        raise AssertionError("%s: %d differing channels, first %s: got %s want %s"
-                             % (what, int((~ok).sum()), i.tolist(), [got[tuple(j)] for j in i], [want[tuple(j)] for j in i]))
-
-
-def same_tensor(a, b, what):
-    import torch
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    assert torch.equal(a.view(torch.int32), b.view(torch.int32)), what
+model_frame = frame_cache(M.frame)
 
 
 @pytest.mark.parametrize("w,h", [(1, 1), (7, 3), (33, 9), (257, 2), (96, 54), (320, 180)])
@@ -189,57 +162,16 @@ def test_non_finite_uniforms(renderer):
 
 
 def test_rows_host_rows_ranks_and_splits(renderer):
-    import torch
-    from shaderbox_amd import shard
     w, h, br, t = 320, 180, 8, 2.0
-    whole = renderer.render(APP, w, h, t)
-    assert_same(whole, model_frame(w, h, t), "whole")
-    parts = [renderer.render(APP, w, h, t, rows=(a, b)) for a, b in [(0, 13), (13, 39), (39, 40), (40, 41), (41, h)]]
-    same_tensor(torch.cat(parts), whole, "rows")
-    host = np.zeros((h, w, 4), dtype=F)
-    renderer.render_to_host(APP, w, h, t, host)
-    assert np.array_equal(host.view(np.uint32), whole.cpu().numpy().view(np.uint32)), "host rows"
-    for n in (2, 3):
-        for rr, rounds in [(1, 1), (1, 2)]:
-            rows_max = shard.rank_rows_max(h, br, n, rr, rounds)
-            gathered = torch.empty((n * rows_max, w, 4), dtype=torch.float32, device=renderer.tdev)
-            for r in range(n):
-                renderer.render_rank(APP, w, h, t, br, r, n, out=gathered[r * rows_max:(r + 1) * rows_max], root_rounds=rr, rounds=rounds)
-            frame = renderer.assemble(gathered, w, h, br, n, root_rounds=rr, rounds=rounds)
-            same_tensor(frame, whole, (n, rr, rounds, "rank + assemble"))
-            for ch in (4, 3):
-                inplace = torch.full((h, w, 4), float("nan"), device=renderer.tdev)
-                if ch == 3:
-                    inplace[..., 3] = 1.0
-                for r in range(n):
-                    renderer.render_rank_in_place(APP, w, h, t, br, r, n, inplace, root_rounds=rr, rounds=rounds, channels=ch)
-                same_tensor(inplace, whole, (n, rr, rounds, ch, "in place"))
-            for ch in (4, 3):                                            # slab pieces, four channels and sbx_render_split_rgb
-                slabs = torch.empty((n, rows_max, w, ch), dtype=torch.float32, device=renderer.tdev)
-                for r in range(n):
-                    renderer.render_rank_rows(APP, w, h, t, br, r, n, 0, 5, slabs[r], root_rounds=rr, rounds=rounds)
-                    renderer.render_rank_rows(APP, w, h, t, br, r, n, 5, rows_max, slabs[r], root_rounds=rr, rounds=rounds)
-                root = torch.full((h, w, 4), float("nan"), device=renderer.tdev)
-                renderer.render_rank_in_place(APP, w, h, t, br, 0, n, root, root_rounds=rr, rounds=rounds)
-                renderer.assemble_peers(slabs[1:].contiguous(), w, h, br, n, root, root_rounds=rr, rounds=rounds)
-                same_tensor(root, whole, (n, rr, rounds, ch, "peers"))
+    check_rows_host_rows_ranks_and_splits(renderer, APP, w, h, t, model_frame(w, h, t), cuts=[13, 39, 40, 41], block_rows=br)
 
 
 @pytest.mark.parametrize("n", [2, 3])
 def test_exchanges_through_loopback_ranks(renderer, n):
     """the span exchange (peer + root + assemble; only sky blocks carry spans) and the direct exchange's rgb slabs, every rank's
     schedule on this GPU"""
-    import torch
-    from shaderbox_amd.distributed import LoopbackWorld
     w, h, t = 1000, 333, 2.0
-    full = renderer.render(APP, w, h, t)
-    for exchange, groups, relief in [("spans", 1, (1, 1)), ("spans", 2, (1, 2)), ("direct", 1, (1, 1))]:
-        world = LoopbackWorld(n)
-        plans = world.plans(renderer, w, h, block_rows=8, groups=groups, root_rounds=relief[0], rounds=relief[1], exchange=exchange)
-        plans[0].frame.fill_(-7.0)
-        got = LoopbackWorld.render(plans, APP, t)
-        torch.cuda.synchronize()
-        same_tensor(got, full, (n, exchange, groups, relief))
+    check_loopback_exchanges(renderer, APP, n, w, h, t)
 
 
 @pytest.mark.parametrize("nranks", [2, 4])
@@ -262,17 +194,8 @@ def test_multi_renderer_on_one_device(renderer, nranks):
 
 def test_rgba8_frames(renderer):
     w, h, t = 800, 450, 2.0
-    try:
-        renderer.set_output_format("rgba32f")
-        f = renderer.render(APP, w, h, t)
-        assert float(f[..., :3].max()) > 1.0                            # channels above 1 clamp to 255
-        packed = renderer.pack_unorm8(f, flip_y=False)
-        renderer.set_output_format("rgba8")
-        got = renderer.render(APP, w, h, t)
-        assert np.array_equal(got.cpu().numpy(), packed.cpu().numpy())
-        assert (got.cpu().numpy()[..., 3] == 255).all()
-    finally:
-        renderer.set_output_format("rgba32f")
+    f = check_rgba8(renderer, APP, w, h, t)
+    assert float(f[..., :3].max()) > 1.0                                # channels above 1 clamp to 255
 
 
 def test_dome_build_untouched_on_the_same_context(renderer, oracle):
@@ -289,46 +212,10 @@ def test_dome_build_untouched_on_the_same_context(renderer, oracle):
     assert_same(renderer.render("planet_atmosphere", 160, 90, t), oracle.render(12, 160, 90, t), "planet composite vs oracle")
 
 
-DROPIN = r'''
-#include "sbx_mainimage.hpp"
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-struct vec2 { float x, y; float operator[](int i) const { return i ? y : x; } };
-struct vec4 { float v[4]; float& operator[](int i) { return v[i]; } };
-int main(int argc, char** argv) {
-    const int W = atoi(argv[1]), H = atoi(argv[2]);
-    iResolution[0] = (float)W; iResolution[1] = (float)H;
-    iGlobalTime = (float)atof(argv[3]);
-    std::vector<float> px((size_t)W * H * 4);
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            vec4 c;
-            mainImage(c, vec2{x + .5f, y + .5f});
-            for (int k = 0; k < 4; ++k) px[((size_t)y * W + x) * 4 + k] = c[k];
-        }
-    FILE* f = fopen(argv[4], "wb");
-    fwrite(px.data(), sizeof(float), px.size(), f);
-    fclose(f);
-    return 0;
-}
-'''
-
-
 def test_cpp_dropin(tmp_path):
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    src = tmp_path / "dropin.cpp"
-    src.write_text(DROPIN)
-    lib = os.path.join(ROOT, "shaderbox_amd", "lib")
-    exe = str(tmp_path / "APP_ATMOSPHERE_GROUND")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-D__HIP_PLATFORM_AMD__", "-DAPP_ATMOSPHERE_GROUND", "-I" + os.path.join(ROOT, "include"),
-                    "-I" + os.path.join(rocm, "include"), "-o", exe, str(src), "-L" + lib, "-lsbx", "-L" + os.path.join(rocm, "lib"),
-                    "-lamdhip64", "-Wl,-rpath," + lib, "-Wl,-rpath," + os.path.join(rocm, "lib")], check=True)
+    exe = build_dropin(tmp_path, ["APP_ATMOSPHERE_GROUND"], "APP_ATMOSPHERE_GROUND")
     for w, h, t in [(96, 54, 0.37), (33, 9, 2.0)]:
-        out = str(tmp_path / "px.f32")
-        subprocess.run([exe, str(w), str(h), repr(t), out], check=True, timeout=120)
-        got = np.fromfile(out, dtype=F).reshape(h, w, 4)
-        assert_same(got, model_frame(w, h, t), ("dropin", w, h, t))
+        assert_same(run_dropin(exe, w, h, t, tmp_path), model_frame(w, h, t), ("dropin", w, h, t))
 
 
 def test_mainimage_demo_through_the_host_makefile(tmp_path):
@@ -348,12 +235,5 @@ def test_mainimage_demo_through_the_host_makefile(tmp_path):
 
 
 def test_sbx_render_host(tmp_path):
-    exe = os.path.join(ROOT, "host", "sbx_render")
-    assert os.path.exists(exe), "host/sbx_render is built by build()"
     w, h, t = 257, 130, 2.0
-    out = str(tmp_path / "ground.f32")
-    subprocess.run([exe, "--app", APP, "--res", "%dx%d" % (w, h), "--time", repr(t), "--f32", out], check=True, timeout=120)
-    raw = np.fromfile(out, dtype=F)
-    assert raw.size >= w * h * 4
-    got = raw[-w * h * 4:].reshape(h, w, 4)
-    assert_same(got, model_frame(w, h, t), "sbx_render --app atmosphere_ground")
+    assert_same(run_sbx_render(tmp_path, APP, w, h, t), model_frame(w, h, t), "sbx_render --app atmosphere_ground")

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from tests import sdf_ao_builds_model as M
+from tests.app_checks import assert_same
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "sdf_ao_builds")
@@ -24,15 +25,6 @@ def golden(build):
         assert (u[0], u[1], u[2], u[3]) == (64, 36, 0, 0) and k == "t%g" % u[4]
         assert z[k].shape == (36, 64, 4) and z[k].dtype == np.float32
     return [(float(u[4]), z[k]) for k, u in zip(keys, z["uniforms"])]
-
-
-def assert_same(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    ok = M.same_bits(got, want)
-    if not ok.all():
-        i = np.argwhere(~ok)[:3]
-        raise AssertionError("%s: %d differing channels, first %s: got %s want %s"
-                             % (what, int((~ok).sum()), i.tolist(), [got[tuple(j)] for j in i], [want[tuple(j)] for j in i]))
 
 
 def hits(build, w, h, t):

@@ -11,6 +11,8 @@
 //     APP_SDF_AO aux block (:484-487):  [--fog-density D] [--fog-falloff F]
 //     app "sdf_ao_shadow" / "sdf_ao_normals": src/app_sdf_ao.h with its `#if 0` at :269 (soft shadows) / :217 (normals view) on; same fog flags
 //     app "egg_straight" / "egg_oval": src/app_egg.h without its `#define BEZIER` (:37, cylinder legs) / with its `#if 1` at :46 off (one scaled sphere)
+//     app "clouds_height" / "clouds_luminance": src/app_clouds.h with the `#if 0` of illuminate_volume at :97 (lit by height, no light march) /
+//              at :118 (the light march's transmittance itself) on; every APP_CLOUDS aux flag applies
 //     app "2d" / "2d_tex": src/app_2d.h (its alpha is not 1: the .f32 frames carry it; single GPU only), the USE_TEXTURE build
 //              reading hlsltoy's default 128x128 checkerboard at t0
 //     app "func": src/app_func.h, the tiled Worley fBm of its compiled 2D branch (grey, alpha 1; u_time and --mouse do not enter)
@@ -37,8 +39,8 @@
 static int app_from_name(const std::string& s) {
     const char* names[] = {"planet", "clouds", "vinyl", "egg", "raytracer", "atmosphere", "sdf_ao", "clouds_best", "clouds_tex", "clouds_ue4",
                            "clouds_sky", "vinyl_gpu", "planet_atmosphere", "2d", "2d_tex", "func", "atmosphere_ground", "sdf_ao_shadow", "sdf_ao_normals",
-                           "egg_straight", "egg_oval"};
-    const int n = 21;
+                           "egg_straight", "egg_oval", "clouds_height", "clouds_luminance"};
+    const int n = 23;
     std::string low;
     for (char c : s) low += (char)tolower(c);
     for (int i = 0; i < n; ++i)
@@ -142,7 +144,7 @@ int main(int argc, char** argv) {
     for (const std::string* p : {&ppm, &f32})
         if (!pattern_ok(*p)) { fprintf(stderr, "bad file pattern %s: one %%d / %%0Nd conversion at most, a literal percent as %%%%\n", p->c_str()); return 2; }
     const void* aux = nullptr;
-    if ((id == SBX_APP_CLOUDS || id == SBX_APP_CLOUDS_TEX || id == SBX_APP_CLOUDS_SKY) && have_ac) aux = &ac;
+    if ((id == SBX_APP_CLOUDS || id == SBX_APP_CLOUDS_TEX || id == SBX_APP_CLOUDS_SKY || id == SBX_APP_CLOUDS_HEIGHT || id == SBX_APP_CLOUDS_LUMINANCE) && have_ac) aux = &ac;
     if ((id == SBX_APP_SDF_AO || id == SBX_APP_SDF_AO_SHADOW || id == SBX_APP_SDF_AO_NORMALS) && have_as) aux = &as;
 
     sbx_ctx* ctx = nullptr;

@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -45,7 +45,8 @@ int sbx_abi_version(void);
  * APP_SDF_AO (src/uniform_buffer.h:56, util/hlsltoy/src/hlsltoy.cpp:488). */
 typedef enum sbx_app {
     SBX_APP_PLANET = 0,
-    SBX_APP_CLOUDS = 1,
+    SBX_APP_CLOUDS = 1,      /* src/app_clouds.h as shipped: both `#if 0` of illuminate_volume (:97, :118) off.  The builds with one of them
+                                on are SBX_APP_CLOUDS_HEIGHT and SBX_APP_CLOUDS_LUMINANCE */
     SBX_APP_VINYL = 2,      /* C++-build semantics: 60 march steps (src/app_vinyl.h:411-416) */
     SBX_APP_EGG = 3,         /* src/app_egg.h as shipped: BEZIER defined (:37) and the `#if 1` egg (:46-52).  The builds with one of the two
                                 switches the other way are SBX_APP_EGG_STRAIGHT and SBX_APP_EGG_OVAL */
@@ -158,7 +159,26 @@ typedef enum sbx_app {
        stretched to .475 * 1.55 along y — its top stands above the blended egg's — whose field is not a distance (it under-estimates
        along y by the factor 1.55).  Everything else, the variants and the precision tier as SBX_APP_EGG_STRAIGHT says; the legs are
        the Bezier tubes. */
-    SBX_APP_EGG_OVAL = 20
+    SBX_APP_EGG_OVAL = 20,
+    /* APP_CLOUDS compiled with the `#if 0` of src/app_clouds.h:97 turned to `#if 1` (:118 as shipped): the height-lit build.
+       illuminate_volume's light march (:100-115) is gone; `float luminance = exp(height) / 2.;` stands in its place, with height the
+       main march's cloud.height = float(i) / float(cld_march_steps) of the step (:183).  So per lit main step i (density >= .005,
+       :132) illuminate_volume returns (luminance * sun_power) * henyey_greenstein_phase_func(clamp(dot(sun_dir, eye.direction), 0, 1))
+       with luminance = exp(float(i) / float(cld_march_steps)) / 2., exp the math spec's binary32 exp, the division by 2 exact.
+       illum_march_steps is not read; sun_dir enters only the sky colour and the phase.  Everything else as SBX_APP_CLOUDS: camera,
+       render_sky_color, the `< 0.05` horizon exit (:212: the same span table), density_func, integrate_volume, the alpha > .999
+       exit, the cutoff smoothstep, abs, linear_to_srgb, alpha 1.  Aux block: sbx_aux_clouds (NULL = its defaults).  The procedural
+       build only: the combinations with SKY_SPHERE / USE_NOISE_TEX and the build with BOTH switches on are not offered.  Alpha is 1,
+       so every output form holds it (rows, points, sbx_main_image*, ranks, splits, rgb, span, the store exchange, SBX_FORMAT_RGBA8,
+       sbx_multi_render).  sbx_set_variant(ctx, 1) = the plain per-lane kernel, as for SBX_APP_CLOUDS.  Definition:
+       tests/clouds_builds_model.py, pinned against frames and points of the edited reference header (tests/golden/clouds_builds/). */
+    SBX_APP_CLOUDS_HEIGHT = 21,
+    /* APP_CLOUDS compiled with the `#if 0` of src/app_clouds.h:118 turned to `#if 1` (:97 as shipped): the raw-luminance build.  The
+       light march of :100-115 runs exactly as in SBX_APP_CLOUDS and illuminate_volume returns its vol.transmittance unscaled
+       (`return luminance;`): sun_power is not read and the phase function is not evaluated (sun_dir still enters the sky colour and
+       the light march's direction).  Everything else, the aux block, the output forms, the variant and what is not offered as
+       SBX_APP_CLOUDS_HEIGHT says. */
+    SBX_APP_CLOUDS_LUMINANCE = 22
 } sbx_app;
 
 typedef enum sbx_status {

@@ -46,6 +46,10 @@
 #define SBX_SELECTED_APP SBX_APP_EGG_STRAIGHT
 #elif defined(APP_EGG_OVAL)         /* src/app_egg.h with the `#if 1` at :46 off (the one scaled sphere, include/sbx.h); tested before APP_EGG */
 #define SBX_SELECTED_APP SBX_APP_EGG_OVAL
+#elif defined(APP_CLOUDS_HEIGHT)    /* src/app_clouds.h with the `#if 0` at :97 on (lit by height, no light march; include/sbx.h); tested before APP_CLOUDS */
+#define SBX_SELECTED_APP SBX_APP_CLOUDS_HEIGHT
+#elif defined(APP_CLOUDS_LUMINANCE) /* src/app_clouds.h with the `#if 0` at :118 on (the light march's transmittance itself); tested before APP_CLOUDS */
+#define SBX_SELECTED_APP SBX_APP_CLOUDS_LUMINANCE
 #elif defined(APP_PLANET)
 #define SBX_SELECTED_APP SBX_APP_PLANET
 #elif defined(APP_CLOUDS)
@@ -63,7 +67,7 @@
 #elif defined(APP_CLOUDS_BEST)   /* src/app_clouds_best.h, the stand-alone shader (no APP_* define in the reference) */
 #define SBX_SELECTED_APP SBX_APP_CLOUDS_BEST
 #else
-#error "define one of APP_PLANET APP_CLOUDS APP_VINYL APP_EGG APP_RAYTRACER APP_ATMOSPHERE APP_SDF_AO (or APP_CLOUDS_BEST APP_PLANET_ATMOSPHERE APP_2D APP_2D_TEX APP_FUNC APP_ATMOSPHERE_GROUND APP_SDF_AO_SHADOW APP_SDF_AO_NORMALS APP_EGG_STRAIGHT APP_EGG_OVAL)"
+#error "define one of APP_PLANET APP_CLOUDS APP_VINYL APP_EGG APP_RAYTRACER APP_ATMOSPHERE APP_SDF_AO (or APP_CLOUDS_BEST APP_PLANET_ATMOSPHERE APP_2D APP_2D_TEX APP_FUNC APP_ATMOSPHERE_GROUND APP_SDF_AO_SHADOW APP_SDF_AO_NORMALS APP_EGG_STRAIGHT APP_EGG_OVAL APP_CLOUDS_HEIGHT APP_CLOUDS_LUMINANCE)"
 #endif
 
 namespace sbx_host {

@@ -26,6 +26,7 @@ extern "C" {
  * SBX_APP_SDF_AO_SHADOW / SBX_APP_SDF_AO_NORMALS: every value as for APP_SDF_AO, the shadow march included — 1 = no culling, the spec's
  * compare-and-select min / max and the IEEE roots along the shadow ray too; 2 / 3 = the witness's test edge / the IEEE roots only.
  * SBX_APP_EGG_STRAIGHT / SBX_APP_EGG_OVAL: every value as for APP_EGG, over the build's own members and bounds.
+ * SBX_APP_CLOUDS_HEIGHT / SBX_APP_CLOUDS_LUMINANCE: as for APP_CLOUDS, 1 = the per-lane kernel of the build.
  * All variants are specified to produce identical bits (tests/test_gpu_parity.py sweeps them against each other). */
 int sbx_set_variant(sbx_ctx* ctx, int variant);
 

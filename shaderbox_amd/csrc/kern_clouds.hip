@@ -73,6 +73,14 @@
                            // 7 waves = 72 VGPRs spill 6 and lose 4 %)
 #endif
 
+#ifndef CL_MIN_WAVES_HEIGHT
+#define CL_MIN_WAVES_HEIGHT 8   // the HEIGHT build's y-table instantiations (no light march): 55-60 VGPRs of the 64, no scratch
+#endif
+#ifndef CL_MIN_WAVES_HEIGHT_NOTAB
+#define CL_MIN_WAVES_HEIGHT_NOTAB 5   // its table-less instantiations (every lane's own y terms, exp_ in place): 64-112 B of scratch at 8 waves,
+                                      // 16-48 B at 6, none at 5 (86-92 VGPRs) — where the other table-less kernels are held too
+#endif
+
 namespace sbx {
 
 // The REG kernels' exp (|sigma * dt| <= 80 shown on the host per launch) is one of the guard-less forms of sbx_math.h that are equal
@@ -124,6 +132,8 @@ __device__ __forceinline__ float hg_phase(float mu, float g) {  // volumetric.h:
 
 // illuminate_volume :91-123.  `phase` = henyey_greenstein(clamp(dot(L,V),0,1)) depends only on
 // the pixel's ray, so the caller evaluates it once per pixel (same inputs, same bits).
+// BUILD (CLOUDS_* of sbx_frame.h): CLOUDS_LUMINANCE returns the march's transmittance itself (the `#if 0` of :118 on).
+template <int BUILD>
 __device__ __forceinline__ float clouds_illuminate(const FrameClouds& F, v3 origin, float phase) {
     const v3 step = F.sun_dir * F.dt;
     v3 pos = origin + step;
@@ -133,13 +143,20 @@ __device__ __forceinline__ float clouds_illuminate(const FrameClouds& F, v3 orig
         transmittance *= exp_(-density * F.sigma * F.dt);
         pos = pos + step;
     }
+    if (BUILD == CLOUDS_LUMINANCE) return transmittance;
     return transmittance * F.sun_power * phase;
 }
+
+// The height-lit build's luminance of main step i (the `#if 0` of :97 on): exp(height) / 2. with height = float(i) / float(cld_march_steps)
+// (:183), the math spec's exp_.  A frame constant per step: k_clouds_lumtab tabulates it, the per-lane kernel and the table-less
+// kernels evaluate it in place — the same operations on the same inputs.
+__device__ __forceinline__ float clouds_height_lum(int i, int steps) { return exp_((float)i / (float)steps) / 2.f; }
 
 // ---------------------------------------------------------------------------------------------
 // variant 1 ("per-lane"): every lane evaluates all 8 lattice hashes of every noise cell itself.
 // Kept as the in-library cross-check of the cooperative kernel below (sbx_set_variant(ctx, 1)).
 // ---------------------------------------------------------------------------------------------
+template <int BUILD>
 __global__ void __launch_bounds__(WG_THREADS) k_clouds_perlane(FrameClouds F, RowMap M, float* __restrict__ out) {
     const Pixel px = pixel_of_thread<32>(M);
     if (!px.valid) return;
@@ -172,7 +189,8 @@ __global__ void __launch_bounds__(WG_THREADS) k_clouds_perlane(FrameClouds F, Ro
             projection = dir;
             origin = mul(F.sky_rot, impact - ac);
         }
-        const float phase = hg_phase(clamp_(dot(F.sun_dir, dir), 0.f, 1.f), .2f);
+        float phase = 0.f;                                     // (the raw-luminance build never evaluates it)
+        if (BUILD != CLOUDS_LUMINANCE) phase = hg_phase(clamp_(dot(F.sun_dir, dir), 0.f, 1.f), .2f);
         float transmittance = 1.f, radiance = 0.f, alpha = 0.f, t = 0.f;
         for (int i = 0; i < F.steps; ++i) {
             const v3 pos = origin + t * projection;
@@ -181,7 +199,9 @@ __global__ void __launch_bounds__(WG_THREADS) k_clouds_perlane(FrameClouds F, Ro
             if (!(density < .005f)) {                          // integrate_volume :132
                 const float T_i = exp_(-density * F.sigma * F.dt);
                 transmittance *= T_i;
-                radiance += (density * F.sigma) * clouds_illuminate(F, pos, phase) * transmittance * F.dt;
+                const float illum = BUILD == CLOUDS_HEIGHT ? (clouds_height_lum(i, F.steps) * F.sun_power) * phase
+                                                           : clouds_illuminate<BUILD>(F, pos, phase);
+                radiance += (density * F.sigma) * illum * transmittance * F.dt;
                 alpha += (1.f - T_i) * (1.f - alpha);
             }
             if (alpha > .999f) break;
@@ -256,6 +276,15 @@ __global__ void __launch_bounds__(64) k_clouds_ytab(FrameClouds F, YRow* __restr
     tab[i].gy = make_float4(gy[0] * hk_(0), gy[1] * hk_(1), gy[2] * hk_(2), gy[3] * hk_(3));
     tab[i].py157 = make_float4(p157[0], p157[1], p157[2], p157[3]);
 }
+
+// The height-lit build's luminance per main step (clouds_height_lum), once per frame like the y terms: one thread per step.  It lies
+// behind the frame's y rows, in the same table (lum_of): a table built for the HEIGHT build serves SBX_APP_CLOUDS as well.
+__global__ void __launch_bounds__(64) k_clouds_lumtab(int steps, float* __restrict__ lum) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= steps) return;
+    lum[i] = clouds_height_lum(i, steps);
+}
+__host__ __device__ __forceinline__ const float* lum_of(const YRow* tab, int steps) { return reinterpret_cast<const float*>(tab + steps); }
 
 // NFL: the noise factor is the literal .001 (the y-table kernels, which never run SKY_SPHERE frames); else F.nf
 template <bool NFL, bool B40 = false>          // B40: lattice indices shown below 2^40 on the host (sbx_noise.h hash1_b)
@@ -778,16 +807,26 @@ __device__ __forceinline__ v3 clouds_sky(const FrameClouds& F, v3 dir) {
 struct ClArgs { FrameClouds F; RowMap M; float* out; const YRow* ytab; };
 // LM, the light march (decided on the host from L * dt): 1 = no x and no y component (light_march_z), 2 = no x component
 // (light_march_yz; YTAB kernels only), 0 = general (coop_density per light sample)
-template <bool YTAB, bool REG, int LM, bool SM = false>   // SM: exp_small_ (launch_clouds: the frame's exp arguments lie in its domain)
-__global__ void __launch_bounds__(64 * CL_TX, (LM == 1 && (YTAB || !CL_NOTAB_GEN)) ? CL_MIN_WAVES : (LM == 2 ? CL_MIN_WAVES_YZ : CL_MIN_WAVES_GEN)) k_clouds(FrameClouds F, RowMap M, float* __restrict__ out_arg,
+// BUILD (CLOUDS_* of sbx_frame.h): CLOUDS_DEFAULT is app_clouds.h as shipped.  CLOUDS_LUMINANCE (`#if 0` of :118 on) runs the same light
+// marches and takes illuminate_volume's transmittance as it is: no phase function, its park slot is never written.  CLOUDS_HEIGHT
+// (`#if 0` of :97 on) has NO light march (LM is not read): a lit step computes T_i, reads the step's luminance exp(i / steps) / 2 —
+// k_clouds_lumtab's table behind the y rows, by the wave-uniform step index (a scalar load); the table-less kernels evaluate
+// clouds_height_lum in place — and integrates.  Nothing is parked, so its park area is the five slots that hold the integrator state,
+// the phase and the skip bound (1.25 KB instead of 3 KB), and its register budget is its own (CL_MIN_WAVES_HEIGHT).
+template <bool YTAB, bool REG, int LM, bool SM = false, int BUILD = CLOUDS_DEFAULT>   // SM: exp_small_ (launch_clouds: the frame's exp arguments lie in its domain)
+__global__ void __launch_bounds__(64 * CL_TX, BUILD == CLOUDS_HEIGHT ? (YTAB ? CL_MIN_WAVES_HEIGHT : CL_MIN_WAVES_HEIGHT_NOTAB) : (LM == 1 && (YTAB || !CL_NOTAB_GEN)) ? CL_MIN_WAVES : (LM == 2 ? CL_MIN_WAVES_YZ : CL_MIN_WAVES_GEN)) k_clouds(FrameClouds F, RowMap M, float* __restrict__ out_arg,
                                                           const YRow* __restrict__ ytab) {
     const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();        // (for the dispatch order's cost table, RowMap.cost)
     __shared__ WaveCache cache[CL_TX];
 #if CL_PARK
     // the march state a lit step does not need while its light march runs, parked in LDS for that time (a manual spill to
     // the fast memory: what the register allocator would otherwise send to scratch when the kernel is held to 96 VGPRs)
-    __shared__ float park[CL_TX][CL_PARK_N][64];
+    constexpr int PARK_0 = BUILD == CLOUDS_HEIGHT ? 5 : 0;          // the first slot the build uses: HEIGHT has slots 5-9 only
+    __shared__ float park[CL_TX][BUILD == CLOUDS_HEIGHT ? 5 : CL_PARK_N][64];
+#else
+    constexpr int PARK_0 = 0;
 #endif
+    (void)PARK_0;
     // exp's table: per-lane reads come from LDS, not from the vector L1.  REG kernels: the 64 entries of exp_reg64_ (512 B: 5.8 KB per
     // wave with the hash tables and the parked state — the 128-entry form's 6.3 KB is one allocation granule more and costs the
     // sixth wave: 2.62 -> 2.71 ms); the others: exp_'s 32.
@@ -807,8 +846,8 @@ __global__ void __launch_bounds__(64 * CL_TX, (LM == 1 && (YTAB || !CL_NOTAB_GEN
 #if CL_PARK
     // The integrator state of the pixel (transmittance, radiance, alpha) and its phase value change only in LIT steps (a fifth
     // of the main steps): they live in LDS slots 5-8 of the wave's park area for the whole march, not in registers.
-    float* const pk = &park[threadIdx.x >> 6][0][lane];
-    pk[5 * 64] = 1.f; pk[6 * 64] = 0.f; pk[7 * 64] = 0.f;
+    float* const pk = &park[threadIdx.x >> 6][0][lane];                   // slot n is pk[(n - PARK_0) * 64]
+    pk[(5 - PARK_0) * 64] = 1.f; pk[(6 - PARK_0) * 64] = 0.f; pk[(7 - PARK_0) * 64] = 0.f;
 #else
     float transmittance = 1.f, radiance = 0.f, alpha = 0.f;
 #endif
@@ -843,9 +882,10 @@ __global__ void __launch_bounds__(64 * CL_TX, (LM == 1 && (YTAB || !CL_NOTAB_GEN
                 origin = mul(F.sky_rot, impact - ac);
             }
 #if CL_PARK
-            pk[8 * 64] = hg_phase(clamp_(dot(F.sun_dir, dir), 0.f, 1.f), .2f);
+            if (BUILD != CLOUDS_LUMINANCE) pk[(8 - PARK_0) * 64] = hg_phase(clamp_(dot(F.sun_dir, dir), 0.f, 1.f), .2f);
 #else
-            float phase = hg_phase(clamp_(dot(F.sun_dir, dir), 0.f, 1.f), .2f);
+            float phase = 0.f;
+            if (BUILD != CLOUDS_LUMINANCE) phase = hg_phase(clamp_(dot(F.sun_dir, dir), 0.f, 1.f), .2f);
 #endif
             const v3 lstep = F.sun_dir * F.dt;
             // frame constants the light march multiplies / subtracts with, held in VGPRs: an fp32 VALU instruction with an
@@ -854,9 +894,9 @@ __global__ void __launch_bounds__(64 * CL_TX, (LM == 1 && (YTAB || !CL_NOTAB_GEN
             // 1 / c of coop_density_row's skip bound; c = 1.01 * 1.74 * D, D = dt * .001 * 2.03 * (|proj.x| + 1 + |proj.z|)
             const float lip_inv = 1.0f / ((1.01f * 1.74f) * ((F.dt * (.001f * 2.03f)) * ((abs_(projection.x) + 1.0f) + abs_(projection.z))));
 #if CL_PARK
-            if (LIP) pk[9 * 64] = F.lip_ok ? lip_inv : 0.f;   // lives in LDS: it is needed only where a first stage fails
+            if (LIP) pk[(9 - PARK_0) * 64] = F.lip_ok ? lip_inv : 0.f;   // lives in LDS: it is needed only where a first stage fails
                                                               // (0: r = gap * 0 is 0 or NaN, never >= 1: no sample is skipped)
-            const float* lip_slot = &pk[9 * 64];
+            const float* lip_slot = &pk[(9 - PARK_0) * 64];
 #else
             const float lip_inv_ok = F.lip_ok ? lip_inv : 0.f;
             const float* lip_slot = &lip_inv_ok;
@@ -902,12 +942,15 @@ __global__ void __launch_bounds__(64 * CL_TX, (LM == 1 && (YTAB || !CL_NOTAB_GEN
                     v3 lp = pos + lstep;                           // illuminate_volume :91-123
                     float ltrans = 1.f;
                     constexpr bool ZL = LM == 1 || (LM == 2 && YTAB);   // the marches that run with the march state parked
-                    if (ZL) {                                      // lstep.x == 0 (&& lstep.y == 0) (launch_clouds)
+                    if constexpr (BUILD == CLOUDS_HEIGHT) {
+                        // no light march: the step's luminance, the same for every pixel of the frame (uniform index: a scalar load)
+                        ltrans = YTAB ? lum_of(ytab, F.steps)[i] : clouds_height_lum(i, F.steps);
+                    } else if (ZL) {                                      // lstep.x == 0 (&& lstep.y == 0) (launch_clouds)
 #if CL_PARK
                         // what the march does not need while a light march runs: parked for that time (slots 0-4, 9-11)
-                        pk[0 * 64] = origin.x; pk[1 * 64] = origin.z; pk[2 * 64] = projection.x; pk[3 * 64] = projection.z;
-                        pk[4 * 64] = t;
-                        pk[10 * 64] = density; pk[11 * 64] = T_i;
+                        pk[(0 - PARK_0) * 64] = origin.x; pk[(1 - PARK_0) * 64] = origin.z; pk[(2 - PARK_0) * 64] = projection.x; pk[(3 - PARK_0) * 64] = projection.z;
+                        pk[(4 - PARK_0) * 64] = t;
+                        pk[(10 - PARK_0) * 64] = density; pk[(11 - PARK_0) * 64] = T_i;
                         asm volatile("" ::: "memory");     // the reloads below cannot be forwarded from these stores: the values
                                                            // are dead across the light march
 #endif
@@ -915,9 +958,9 @@ __global__ void __launch_bounds__(64 * CL_TX, (LM == 1 && (YTAB || !CL_NOTAB_GEN
                         else ltrans = light_march_yz<REG, SM>(F, lp, lstep, lit, lit_mask, S, lane, mfx, etab, vsigma, vdt, vcov, vcd, vcr);
 #if CL_PARK
                         asm volatile("" ::: "memory");
-                        origin.x = pk[0 * 64]; origin.z = pk[1 * 64]; projection.x = pk[2 * 64]; projection.z = pk[3 * 64];
-                        t = pk[4 * 64];
-                        density = pk[10 * 64]; T_i = pk[11 * 64];
+                        origin.x = pk[(0 - PARK_0) * 64]; origin.z = pk[(1 - PARK_0) * 64]; projection.x = pk[(2 - PARK_0) * 64]; projection.z = pk[(3 - PARK_0) * 64];
+                        t = pk[(4 - PARK_0) * 64];
+                        density = pk[(10 - PARK_0) * 64]; T_i = pk[(11 - PARK_0) * 64];
 #endif
                     } else {
                         for (int j = 0; j < F.lsteps; ++j) {
@@ -927,22 +970,22 @@ __global__ void __launch_bounds__(64 * CL_TX, (LM == 1 && (YTAB || !CL_NOTAB_GEN
                         }
                     }
 #if CL_PARK
-                    const float illum = ltrans * F.sun_power * pk[8 * 64];
+                    const float illum = BUILD == CLOUDS_LUMINANCE ? ltrans : ltrans * F.sun_power * pk[(8 - PARK_0) * 64];
                     bool full = false;
                     if (lit) {
-                        const float transmittance = pk[5 * 64] * T_i;
-                        pk[5 * 64] = transmittance;
-                        pk[6 * 64] = pk[6 * 64] + (density * F.sigma) * illum * transmittance * F.dt;
-                        float alpha = pk[7 * 64];
+                        const float transmittance = pk[(5 - PARK_0) * 64] * T_i;
+                        pk[(5 - PARK_0) * 64] = transmittance;
+                        pk[(6 - PARK_0) * 64] = pk[(6 - PARK_0) * 64] + (density * F.sigma) * illum * transmittance * F.dt;
+                        float alpha = pk[(7 - PARK_0) * 64];
                         alpha += (1.f - T_i) * (1.f - alpha);
-                        pk[7 * 64] = alpha;
+                        pk[(7 - PARK_0) * 64] = alpha;
                         full = alpha > .999f;                     // :197 — alpha changes in lit steps only, so the exit test lives here
                     }
                     if (full) alive = false;
                     alive_mask &= ~wave_mask(full);
                 }
 #else
-                    const float illum = ltrans * F.sun_power * phase;
+                    const float illum = BUILD == CLOUDS_LUMINANCE ? ltrans : ltrans * F.sun_power * phase;
                     if (lit) {
                         transmittance *= T_i;
                         radiance += (density * F.sigma) * illum * transmittance * F.dt;
@@ -984,7 +1027,7 @@ __global__ void __launch_bounds__(64 * CL_TX, (LM == 1 && (YTAB || !CL_NOTAB_GEN
     v3 col = sky;
     if (marches) {
 #if CL_PARK
-        const float radiance = pk[6 * 64], alpha = pk[7 * 64];
+        const float radiance = pk[(6 - PARK_0) * 64], alpha = pk[(7 - PARK_0) * 64];
 #endif
         const float a = alpha * smoothstep_(.0f, .2f, dot(dir, V3(0, 1, 0)));
         col = abs3(mix3(sky, V3s(radiance), a));               // :215-217
@@ -1054,8 +1097,13 @@ static bool clouds_index_domain(const FrameClouds& F) {
 
 dim3 clouds_grid(const RowMap& M) { return grid_for<CL_TW, CL_TX>(M); }
 
-void launch_clouds(const FrameClouds& F_in, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
-                   bool build_table) {
+// One build's launch: the kernel selection is the same for every build (REG / SM / y table / light-march form), over the build's own
+// instantiations.  The HEIGHT build has no light march, so the form of L * dt selects nothing there (its instantiations carry LM = 1
+// for the one thing LM decides outside the light march: the SM kernels' div3_ smoothstep in the main sample).
+template <int BUILD>
+static void launch_clouds_build(const FrameClouds& F_in, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
+                                bool build_table) {
+    constexpr bool HT = BUILD == CLOUDS_HEIGHT;
     FrameClouds F = F_in;
     F.lip_ok = clouds_lip_domain(F) ? 1 : 0;
     // exp_small_'s domain: x = -density * sigma * dt with 0 <= density <= .9375 (1 + 1e-6) (a blend of hashes in [0, 1] with weights
@@ -1073,36 +1121,49 @@ void launch_clouds(const FrameClouds& F_in, const RowMap& M, float* out, hipStre
     const unsigned pad = 0;
 #endif
     const v3 lstep = F.sun_dir * F.dt;                          // the kernel's own expression
-    const bool zl = lstep.x == 0.f && lstep.y == 0.f;
+    const bool zl = HT || (lstep.x == 0.f && lstep.y == 0.f);
     const bool yz = !zl && lstep.x == 0.f && CL_YZ_MARCH;        // NaN compares false: the general march
     // (SKY_SPHERE frames: the march does not run along dir / dir.y, so no y table — the table-less kernels, F.nf, F.sky)
     if (variant == 1) {
-        hipLaunchKernelGGL(k_clouds_perlane, grid_for<32>(M), dim3(WG_THREADS), 0, s, F, M, out);
+        hipLaunchKernelGGL(k_clouds_perlane<BUILD>, grid_for<32>(M), dim3(WG_THREADS), 0, s, F, M, out);
     } else if (!F.sky && ytab && F.steps <= ytab_rows && F.steps > 0) {
         YRow* tab = reinterpret_cast<YRow*>(ytab);
         if (build_table) hipLaunchKernelGGL(k_clouds_ytab, dim3((F.steps + 63) / 64), dim3(64), 0, s, F, tab);
+        // (the caller rebuilds a table that has no luminances before the HEIGHT build reads it: sbx_ytab.hip)
+        if (build_table && HT) hipLaunchKernelGGL(k_clouds_lumtab, dim3((F.steps + 63) / 64), dim3(64), 0, s, F.steps, const_cast<float*>(lum_of(tab, F.steps)));
         const YRow* ct = tab;
         // SM kernels: exp_small_'s domain AND lattice indices below 2^40 for sin_b40_
         const bool sm = F.exp_small && clouds_index_domain(F) && (!CL_DIV3 || clouds_div3_domain(F)) && CL_EXP_SMALL && CL_EXP_ASM && CL_EXP64;
-        if (reg && zl && sm) hipLaunchKernelGGL((k_clouds<true, true, 1, true>), grid, block, pad, s, F, M, out, ct);
-        else if (reg && zl) hipLaunchKernelGGL((k_clouds<true, true, 1>), grid, block, pad, s, F, M, out, ct);
-        else if (reg && yz && sm && CL_YZ_SM) hipLaunchKernelGGL((k_clouds<true, true, 2, true>), grid, block, 0, s, F, M, out, ct);
-        else if (reg && yz) hipLaunchKernelGGL((k_clouds<true, true, 2>), grid, block, 0, s, F, M, out, ct);
-        else if (reg && sm) hipLaunchKernelGGL((k_clouds<true, true, 0, true>), grid, block, 0, s, F, M, out, ct);
-        else if (reg) hipLaunchKernelGGL((k_clouds<true, true, 0>), grid, block, 0, s, F, M, out, ct);
-        else if (zl) hipLaunchKernelGGL((k_clouds<true, false, 1>), grid, block, 0, s, F, M, out, ct);
-        else if (yz) hipLaunchKernelGGL((k_clouds<true, false, 2>), grid, block, 0, s, F, M, out, ct);
-        else hipLaunchKernelGGL((k_clouds<true, false, 0>), grid, block, 0, s, F, M, out, ct);
+        if (reg && zl && sm) hipLaunchKernelGGL((k_clouds<true, true, 1, true, BUILD>), grid, block, pad, s, F, M, out, ct);
+        else if (reg && zl) hipLaunchKernelGGL((k_clouds<true, true, 1, false, BUILD>), grid, block, pad, s, F, M, out, ct);
+        else if (zl) hipLaunchKernelGGL((k_clouds<true, false, 1, false, BUILD>), grid, block, 0, s, F, M, out, ct);
+        else if constexpr (!HT) {
+            if (reg && yz && sm && CL_YZ_SM) hipLaunchKernelGGL((k_clouds<true, true, 2, true, BUILD>), grid, block, 0, s, F, M, out, ct);
+            else if (reg && yz) hipLaunchKernelGGL((k_clouds<true, true, 2, false, BUILD>), grid, block, 0, s, F, M, out, ct);
+            else if (reg && sm) hipLaunchKernelGGL((k_clouds<true, true, 0, true, BUILD>), grid, block, 0, s, F, M, out, ct);
+            else if (reg) hipLaunchKernelGGL((k_clouds<true, true, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct);
+            else if (yz) hipLaunchKernelGGL((k_clouds<true, false, 2, false, BUILD>), grid, block, 0, s, F, M, out, ct);
+            else hipLaunchKernelGGL((k_clouds<true, false, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct);
+        }
     } else {
         const YRow* ct = nullptr;
         const bool sm = F.exp_small && clouds_index_domain(F) && (!CL_DIV3 || clouds_div3_domain(F)) && CL_EXP_SMALL && CL_EXP_ASM && CL_EXP64;
-        if (reg && zl && sm) hipLaunchKernelGGL((k_clouds<false, true, 1, true>), grid, block, 0, s, F, M, out, ct);
-        else if (reg && sm) hipLaunchKernelGGL((k_clouds<false, true, 0, true>), grid, block, 0, s, F, M, out, ct);
-        else if (reg && zl) hipLaunchKernelGGL((k_clouds<false, true, 1>), grid, block, 0, s, F, M, out, ct);
-        else if (reg) hipLaunchKernelGGL((k_clouds<false, true, 0>), grid, block, 0, s, F, M, out, ct);
-        else if (zl) hipLaunchKernelGGL((k_clouds<false, false, 1>), grid, block, 0, s, F, M, out, ct);
-        else hipLaunchKernelGGL((k_clouds<false, false, 0>), grid, block, 0, s, F, M, out, ct);
+        if (reg && zl && sm) hipLaunchKernelGGL((k_clouds<false, true, 1, true, BUILD>), grid, block, 0, s, F, M, out, ct);
+        else if (reg && zl) hipLaunchKernelGGL((k_clouds<false, true, 1, false, BUILD>), grid, block, 0, s, F, M, out, ct);
+        else if (zl && !reg) hipLaunchKernelGGL((k_clouds<false, false, 1, false, BUILD>), grid, block, 0, s, F, M, out, ct);
+        else if constexpr (!HT) {
+            if (reg && sm) hipLaunchKernelGGL((k_clouds<false, true, 0, true, BUILD>), grid, block, 0, s, F, M, out, ct);
+            else if (reg) hipLaunchKernelGGL((k_clouds<false, true, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct);
+            else hipLaunchKernelGGL((k_clouds<false, false, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct);
+        }
     }
+}
+
+void launch_clouds(const FrameClouds& F, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
+                   bool build_table, int build) {
+    if (build == CLOUDS_HEIGHT) launch_clouds_build<CLOUDS_HEIGHT>(F, M, out, s, variant, ytab, ytab_rows, build_table);
+    else if (build == CLOUDS_LUMINANCE) launch_clouds_build<CLOUDS_LUMINANCE>(F, M, out, s, variant, ytab, ytab_rows, build_table);
+    else launch_clouds_build<CLOUDS_DEFAULT>(F, M, out, s, variant, ytab, ytab_rows, build_table);
 }
 
 hipError_t bind_fault_clouds(unsigned* word) { return hc_bind_fault_word(word); }

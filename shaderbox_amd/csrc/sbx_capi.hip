@@ -234,6 +234,9 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     TileOrder* const ordered = tile_order_begin(ctx->tile_orders, app, M, og, s, capturing, scene, T.scene_policy);
     switch (app) {
     case SBX_APP_CLOUDS: rc = render_clouds(ctx, build_clouds(*uni, AC), M, rgba, s, capturing); break;
+    // the builds of illuminate_volume's two switches (include/sbx.h): the same frame constants and the same y tables
+    case SBX_APP_CLOUDS_HEIGHT: rc = render_clouds(ctx, build_clouds(*uni, AC), M, rgba, s, capturing, CLOUDS_HEIGHT); break;
+    case SBX_APP_CLOUDS_LUMINANCE: rc = render_clouds(ctx, build_clouds(*uni, AC), M, rgba, s, capturing, CLOUDS_LUMINANCE); break;
     case SBX_APP_CLOUDS_SKY: launch_clouds(build_clouds(*uni, AC, true), M, rgba, s, ctx->variant, nullptr, 0, false); break;
     case SBX_APP_CLOUDS_TEX: launch_clouds_tex(build_clouds(*uni, AC), M, rgba, s, ctx->noise.shape, ctx->noise.shape_size, ctx->noise.detail, ctx->noise.detail_size,
                                                     // a captured launch is replayed later, possibly over volumes re-bound in place with

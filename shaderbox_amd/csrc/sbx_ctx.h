@@ -40,18 +40,20 @@ struct YTables {
     bool valid = false;
     float key[3] = {0, 0, 0};
     int steps = 0;
+    bool lum = false;                      // the current table also holds the HEIGHT build's luminances (they depend on steps alone)
     int slot = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ready{};
     bool have_ready = false;
     Slot slots[sbx::CLOUDS_YTAB_RING];
-    // march lengths beyond the ring's rows (CLOUDS_YTAB_ROWS): ONE table grown on demand (48 B per step), rebuilt when its key
+    // march lengths beyond the ring's rows (CLOUDS_YTAB_ROWS): ONE table grown on demand (52 B per step), rebuilt when its key
     // changes after waiting for the device — such frames take tens of milliseconds, the wait is noise
     char* big = nullptr;
     int big_rows = 0;
     bool big_valid = false;
     float big_key[3] = {0, 0, 0};
     int big_steps = 0;
+    bool big_lum = false;
     hipEvent_t big_ready{};
     bool have_big_ready = false;
 };
@@ -196,7 +198,7 @@ FrameCloudsUe4 build_clouds_ue4(const sbx_uniforms& U, const sbx_aux_clouds_ue4&
 Frame2d build_2d(const sbx_uniforms& U);
 
 // ---- sbx_ytab.hip
-int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rgba, hipStream_t s, bool capturing);
+int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rgba, hipStream_t s, bool capturing, int build = CLOUDS_DEFAULT);
 void release(YTables& Y);
 
 // ---- sbx_main_image.hip

@@ -144,11 +144,13 @@ __device__ __forceinline__ void store_rgba4(const RowMap& M, float* out, size_t 
 
 // launchers (one per app), defined next to their kernels
 void launch_clouds(const FrameClouds& F, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
-                   bool build_table);
-constexpr int CLOUDS_YTAB_ROWS = 4096;      // march steps covered by the per-frame y table (192 KB per table; beyond it the
-                                            // table-less kernels run: 1100 steps at 4K took 48 ms without a table)
-constexpr int CLOUDS_YTAB_BYTES = CLOUDS_YTAB_ROWS * 48;
-constexpr int CLOUDS_YTAB_BIG_MAX = 1 << 20;   // longest march served by the context's one on-demand table (48 MB); beyond it: the table-less kernels
+                   bool build_table, int build = CLOUDS_DEFAULT);   // build: CLOUDS_* (sbx_frame.h); build_table with CLOUDS_HEIGHT also
+                                                                    // writes the steps' luminances behind the y rows
+constexpr int CLOUDS_YTAB_ROWS = 4096;      // march steps covered by a y table of the ring (208 KB per table; beyond it the one big
+                                            // table below, or in a capture the table-less kernels: 1100 steps at 4K took 48 ms without a table)
+constexpr int CLOUDS_YTAB_STEP_BYTES = 48 + 4;   // per march step: its YRow and, behind the frame's rows, the HEIGHT build's luminance
+constexpr int CLOUDS_YTAB_BYTES = CLOUDS_YTAB_ROWS * CLOUDS_YTAB_STEP_BYTES;
+constexpr int CLOUDS_YTAB_BIG_MAX = 1 << 20;   // longest march served by the context's one on-demand table (52 MB); beyond it: the table-less kernels
 constexpr int CLOUDS_YTAB_RING = 8;         // eager tables: one per REBUILD (key change), round robin; reuse of a slot waits
                                             // for the launches that may still read it (sbx_ytab.hip render_clouds)
 constexpr int CLOUDS_YTAB_CAPTURE = 8;      // tables used only by launches recorded into a stream capture

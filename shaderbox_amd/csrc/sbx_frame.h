@@ -139,6 +139,11 @@ struct FrameClouds {
     float atm_y, atm_r;   // atmosphere = sphere((0, atm_ground_y, 0), atm_radius)                     app_clouds.h:15-17
     m3 sky_rot;           // rotate_around_x(u_time)                                                   app_clouds.h:160
 };
+// The builds of illuminate_volume's two `#if 0` switches (app_clouds.h:97, :118; include/sbx.h): SBX_APP_CLOUDS, _CLOUDS_HEIGHT,
+// _CLOUDS_LUMINANCE.  The frame constants are the same in all three, so the build is no field of FrameClouds — the shipped kernels
+// take the arguments they always took — but an argument of launch_clouds; the HEIGHT build's per-step luminances lie behind the
+// frame's y rows in the y table (kern_clouds.hip lum_of), so they need no pointer of their own either.
+enum { CLOUDS_DEFAULT = 0, CLOUDS_HEIGHT = 1, CLOUDS_LUMINANCE = 2 };
 
 // ---- APP_EGG (src/app_egg.h) ----------------------------------------------------------------
 struct BezierFrame {      // the P-independent part of sd_bezier (src/sdf.h:147-153)

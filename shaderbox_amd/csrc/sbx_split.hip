@@ -79,7 +79,7 @@ static SpanProbe span_probe(int app, const sbx_uniforms& U, const void* aux) {
     P.app = app;
     P.model = true;
     switch (app) {
-    case SBX_APP_CLOUDS: case SBX_APP_CLOUDS_TEX: case SBX_APP_CLOUDS_SKY: P.cam = build_clouds(U, aux_clouds(aux)).cam; break;
+    case SBX_APP_CLOUDS: case SBX_APP_CLOUDS_TEX: case SBX_APP_CLOUDS_SKY: case SBX_APP_CLOUDS_HEIGHT: case SBX_APP_CLOUDS_LUMINANCE: P.cam = build_clouds(U, aux_clouds(aux)).cam; break;
     case SBX_APP_ATMOSPHERE: P.cam = build_atmosphere(U).cam; break;
     case SBX_APP_ATMOSPHERE_GROUND: P.cam = build_atmosphere_ground(U).cam; break;
     case SBX_APP_PLANET: P.cam = build_planet(U).cam; break;
@@ -91,7 +91,7 @@ static SpanProbe span_probe(int app, const sbx_uniforms& U, const void* aux) {
 static bool span_heavy(const SpanProbe& P, float fx, float fy) {
     const v2 pc = point_cam(P.cam, fx, fy);
     switch (P.app) {
-    case SBX_APP_CLOUDS: case SBX_APP_CLOUDS_TEX: case SBX_APP_CLOUDS_SKY: {
+    case SBX_APP_CLOUDS: case SBX_APP_CLOUDS_TEX: case SBX_APP_CLOUDS_SKY: case SBX_APP_CLOUDS_HEIGHT: case SBX_APP_CLOUDS_LUMINANCE: {
         const v3 dir = primary_dir(P.cam, pc);
         return !(dir.y < 0.05f);                                   // app_clouds.h:212
     }

@@ -11,18 +11,24 @@ namespace sbx {
 //      the render kernel; cache key, events and the eager ring are left alone (nothing has executed yet);
 //  (3) eager: rebuild into the next ring slot only when the key changed — after waiting for every launch that may
 //      still be reading that slot — and record, per stream, an event behind each consumer of the current slot.
-int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rgba, hipStream_t s, bool capturing) {
+// build (CLOUDS_*): the three builds share the tables.  The HEIGHT build also reads the steps' luminances, which lie behind the y rows
+// and are written only by a rebuild made for it: a table without them counts as stale for that build (`lum`, `big_lum`), a table
+// with them serves the other builds unchanged.
+int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rgba, hipStream_t s, bool capturing, int build) {
+    const bool need_lum = build == CLOUDS_HEIGHT;
     const bool uses_table = ctx->variant == 0 && F.steps > 0 && F.steps <= CLOUDS_YTAB_ROWS;
     if (!uses_table && ctx->variant == 0 && F.steps > CLOUDS_YTAB_ROWS && F.steps <= CLOUDS_YTAB_BIG_MAX && !capturing) {
-        // (4) a march longer than the ring's tables: the context's one big table (round 3 fell back to the table-less kernels
-        //     here, ~2x slower per step)
+        // (4) a march longer than the ring's tables, e.g. the `long` aux set's 4200 steps: the context's one big table, allocated on
+        //     demand and so never inside a capture (the table-less kernels, ~2x slower per step, are left with a capture of such
+        //     a march and with marches beyond CLOUDS_YTAB_BIG_MAX)
         const float key[3] = {F.cam.eye.y, F.wind_off.y, F.dt};
         hipError_t e;
         if (!ctx->ytab.have_big_ready) {
             if ((e = hipEventCreateWithFlags(&ctx->ytab.big_ready, hipEventDisableTiming)) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipEventCreate", e);
             ctx->ytab.have_big_ready = true;
         }
-        const bool rebuild = !ctx->ytab.big_valid || ctx->ytab.big_steps != F.steps || std::memcmp(key, ctx->ytab.big_key, sizeof(key)) != 0;
+        const bool rebuild = !ctx->ytab.big_valid || ctx->ytab.big_steps != F.steps || std::memcmp(key, ctx->ytab.big_key, sizeof(key)) != 0 ||
+                             (need_lum && !ctx->ytab.big_lum);
         if (rebuild) {
             ctx->ytab.big_valid = false;
             if ((e = hipDeviceSynchronize()) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipDeviceSynchronize", e);   // readers of the old table
@@ -30,32 +36,34 @@ int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rg
                 if (ctx->ytab.big) (void)hipFree(ctx->ytab.big);
                 ctx->ytab.big = nullptr; ctx->ytab.big_rows = 0;
                 const int rows = (F.steps + 4095) / 4096 * 4096;
-                if ((e = hipMalloc((void**)&ctx->ytab.big, (size_t)rows * 48)) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
+                if ((e = hipMalloc((void**)&ctx->ytab.big, (size_t)rows * CLOUDS_YTAB_STEP_BYTES)) != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
                 ctx->ytab.big_rows = rows;
             }
         } else {
             (void)hipStreamWaitEvent(s, ctx->ytab.big_ready, 0);
         }
-        launch_clouds(F, M, rgba, s, 0, ctx->ytab.big, ctx->ytab.big_rows, rebuild);
+        launch_clouds(F, M, rgba, s, 0, ctx->ytab.big, ctx->ytab.big_rows, rebuild, build);
         if (rebuild) {
             (void)hipEventRecord(ctx->ytab.big_ready, s);
             std::memcpy(ctx->ytab.big_key, key, sizeof(key));
             ctx->ytab.big_steps = F.steps;
+            ctx->ytab.big_lum = need_lum;
             ctx->ytab.big_valid = true;
         }
         return SBX_OK;
     }
     if (!uses_table) {
-        launch_clouds(F, M, rgba, s, ctx->variant, nullptr, 0, false);
+        launch_clouds(F, M, rgba, s, ctx->variant, nullptr, 0, false, build);
         return SBX_OK;
     }
     if (capturing) {
         char* tab = ctx->ytab.ring + (size_t)(CLOUDS_YTAB_RING + (ctx->ytab.cap_next++ % CLOUDS_YTAB_CAPTURE)) * CLOUDS_YTAB_BYTES;
-        launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, true);
+        launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, true, build);
         return SBX_OK;
     }
     const float key[3] = {F.cam.eye.y, F.wind_off.y, F.dt};
-    const bool rebuild = !ctx->ytab.valid || F.steps != ctx->ytab.steps || std::memcmp(key, ctx->ytab.key, sizeof(key)) != 0;
+    const bool rebuild = !ctx->ytab.valid || F.steps != ctx->ytab.steps || std::memcmp(key, ctx->ytab.key, sizeof(key)) != 0 ||
+                         (need_lum && !ctx->ytab.lum);
     if (!ctx->ytab.have_ready) {
         if (hipEventCreateWithFlags(&ctx->ytab.ready, hipEventDisableTiming) != hipSuccess)
             return fail(ctx, SBX_ERR_HIP, "hipEventCreate");
@@ -83,11 +91,12 @@ int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rg
         (void)hipStreamWaitEvent(s, ctx->ytab.ready, 0);           // table was built on another stream
     }
     char* tab = ctx->ytab.ring + (size_t)slot * CLOUDS_YTAB_BYTES;
-    launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, rebuild);
+    launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, rebuild, build);
     if (rebuild) {
         (void)hipEventRecord(ctx->ytab.ready, s);                  // the build is enqueued: now the cache state is true
         std::memcpy(ctx->ytab.key, key, sizeof(key));
         ctx->ytab.steps = F.steps;
+        ctx->ytab.lum = need_lum;
         ctx->ytab.slot = slot;
         ctx->ytab.stream = s;
         ctx->ytab.valid = true;

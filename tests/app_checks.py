@@ -1,7 +1,12 @@
-"""The checks every app's GPU test file makes of the layers above its kernel, written once: rows, host rows, ranks and splits, the
-loopback exchanges, the 8-bit format, sbx_multi_render, the sbx_mainimage.hpp drop-in and host/sbx_render.  A test file states its
-app's name, sizes, times, aux block and expected frame and calls in here; what belongs to one app stays in its file.  A plain
-module (pytest does not collect it): the `renderer` fixture is imported by the test modules that use it."""
+"""What the GPU test files share, written once: the fixtures (`renderer`, `renderer8`, `volumes`, `variant_restored`), the comparisons
+(`compare`, `assert_same`, `same_tensor`, `bits_differ`), the app lists, and the checks every app's file makes of the layers above
+its kernel: rows, host rows, ranks and splits, the loopback exchanges, the 8-bit format, sbx_multi_render, the sbx_mainimage.hpp
+drop-in and host/sbx_render.  A test file states its app's name, sizes, times, aux block and expected frame and calls in here;
+what belongs to one app stays in its file.  A plain module (pytest does not collect it): a test module imports the fixtures it
+names.
+
+`compare`, `assert_same` and model_common.same_bits count NaN == NaN as equal; `same_tensor`, `bits_differ` and torch.equal on
+int32 views do not."""
 import os
 import subprocess
 
@@ -12,6 +17,11 @@ from tests.model_common import same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXCHANGES = [("spans", 1, (1, 1)), ("spans", 2, (1, 2)), ("direct", 1, (1, 1))]      # (exchange, groups, (root_rounds, rounds))
+# the apps whose kernels write alpha = 1 and render without bound resources, as the slab tests sweep them; and the same with the
+# compile-time builds of CLOUDS, VINYL and PLANET, as the point-list and 8-bit tests sweep them
+UNIT_ALPHA_APPS = ["clouds", "egg", "raytracer", "atmosphere", "planet", "sdf_ao", "vinyl", "clouds_best", "clouds_ue4"]
+POINT_APPS = ["planet", "clouds", "vinyl", "egg", "raytracer", "atmosphere", "sdf_ao", "clouds_best", "clouds_ue4", "clouds_sky",
+              "vinyl_gpu", "planet_atmosphere"]
 
 
 @pytest.fixture(scope="module")
@@ -20,6 +30,38 @@ def renderer():
     r = shaderbox_amd.Renderer(0)
     yield r
     r.close()
+
+
+@pytest.fixture(scope="module")
+def renderer8():
+    """a context of its own that writes SBX_FORMAT_RGBA8 (include/sbx.h sbx_set_output_format): the module's `renderer` stays float"""
+    import shaderbox_amd
+    r = shaderbox_amd.Renderer(0)
+    r.set_output_format("rgba8")
+    yield r
+    r.close()
+
+
+@pytest.fixture(scope="module")
+def volumes(renderer):
+    """two different baked volumes (ddsvolgen's tiled-Worley fBm at two sizes), device + host copies; a test binds them itself"""
+    v1 = renderer.worley_volume(32)
+    v2 = renderer.worley_volume(16)
+    return v1, v2, v1.cpu().numpy(), v2.cpu().numpy()
+
+
+@pytest.fixture
+def variant_restored(renderer):
+    """named by a test that switches kernels (sbx_set_variant) between its renders: the module's renderer is back on the default
+    kernels however the test ends"""
+    yield
+    renderer.set_variant(0)
+
+
+def bind_small_volumes(renderer):
+    """clouds_tex renders only once its noise volumes are bound: 16^3 Worley volumes, as the texture tests use"""
+    vol = renderer.worley_volume(16)
+    renderer.set_noise_volumes(vol, vol)
 
 
 def frame_cache(fn):
@@ -31,6 +73,39 @@ def frame_cache(fn):
             frames[key] = fn(*key)
         return frames[key]
     return cached
+
+
+def compare(gpu, ref):
+    """returns (max_abs_diff over non-NaN-matching channels, #pixels with any bit difference)"""
+    both_nan = np.isnan(gpu) & np.isnan(ref)
+    d = np.where(both_nan, 0.0, np.abs(gpu.astype(np.float64) - ref.astype(np.float64)))
+    d = np.nan_to_num(d, nan=np.inf)
+    bits = (gpu.view(np.uint32) != ref.view(np.uint32)) & ~both_nan
+    return float(d.max()), int(bits.any(axis=-1).sum())
+
+
+def bits_differ(a, b):
+    """#pixels of two tensors with any bit difference (a NaN differs from a NaN of other bits)"""
+    import torch
+    return int((a.view(torch.int32) != b.view(torch.int32)).any(dim=-1).sum().item())
+
+
+def both_variants(r, app, w, h, t, **kw):
+    """the frame of the default kernels and of the plain ones (sbx_set_variant 1), as numpy arrays"""
+    try:
+        r.set_variant(0)
+        a = r.render(app, w, h, t, **kw).cpu().numpy()
+        r.set_variant(1)
+        b = r.render(app, w, h, t, **kw).cpu().numpy()
+    finally:
+        r.set_variant(0)
+    return a, b
+
+
+def oracle_points(oracle, app, w, h, t, pts, mouse=(0.0, 0.0)):
+    """the oracle's mainImage at the fragCoords `pts` -> float32 [n, 4]"""
+    from oracle.oracle import APP_IDS
+    return np.stack([oracle.main_image(APP_IDS[app], w, h, t, float(x), float(y), mouse=mouse) for x, y in pts])
 
 
 def assert_same(got, want, what):
@@ -103,17 +178,25 @@ def check_rows_host_rows_ranks_and_splits(renderer, app, w, h, t, want, cuts, bl
                 same_tensor(root, whole, (n, rr, rounds, ch, "peers"))
 
 
-def check_loopback_exchanges(renderer, app, n, w, h, t):
-    """every rank's schedule of an n-rank world on this GPU, each of EXCHANGES: the one-launch frame"""
+def loop_frame(renderer, app, w, h, t, n, exchange, groups=1, relief=(1, 1), br=8, frames=1):
+    """every rank's FramePlan of an n-rank world on this GPU, `frames` frames into the same buffers -> (the last frame, the world)"""
     import torch
     from shaderbox_amd.distributed import LoopbackWorld
+    world = LoopbackWorld(n)
+    plans = world.plans(renderer, w, h, block_rows=br, groups=groups, root_rounds=relief[0], rounds=relief[1], exchange=exchange)
+    out = None
+    for _ in range(frames):
+        plans[0].frame.fill_(-7.0)                    # every pixel must be written again
+        out = LoopbackWorld.render(plans, app, t)
+    torch.cuda.synchronize()
+    return out, world
+
+
+def check_loopback_exchanges(renderer, app, n, w, h, t):
+    """every rank's schedule of an n-rank world on this GPU, each of EXCHANGES: the one-launch frame"""
     full = renderer.render(app, w, h, t)
     for exchange, groups, relief in EXCHANGES:
-        world = LoopbackWorld(n)
-        plans = world.plans(renderer, w, h, block_rows=8, groups=groups, root_rounds=relief[0], rounds=relief[1], exchange=exchange)
-        plans[0].frame.fill_(-7.0)
-        got = LoopbackWorld.render(plans, app, t)
-        torch.cuda.synchronize()
+        got, _ = loop_frame(renderer, app, w, h, t, n, exchange, groups, relief)
         same_tensor(got, full, (n, exchange, groups, relief))
 
 

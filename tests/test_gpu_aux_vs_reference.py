@@ -16,6 +16,7 @@ import pytest
 
 from oracle import aux_sets
 from oracle.oracle import Reference
+from tests.app_checks import renderer  # noqa: F401 (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -65,14 +66,6 @@ def ref():
     if not Reference.available_aux():
         pytest.skip("oracle/_ref holds no aux-set build")
     return Reference()
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import shaderbox_amd
-    r = shaderbox_amd.Renderer(0)
-    yield r
-    r.close()
 
 
 _frames = {}

@@ -8,6 +8,9 @@ require zero differing pixels, so any drift is caught long before it reaches 1e-
 import numpy as np
 import pytest
 
+from tests.app_checks import compare
+from tests.app_checks import renderer, variant_restored  # noqa: F401 (fixtures)
+
 pytestmark = pytest.mark.gpu
 
 CASES = [
@@ -21,21 +24,6 @@ CASES = [
     ("clouds_best", 256, 144), ("clouds_best", 160, 160),
 ]
 TIMES = [0.0, 0.37, 2.5]
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import shaderbox_amd
-    return shaderbox_amd.Renderer(0)
-
-
-def compare(gpu, ref):
-    """returns (max_abs_diff over non-NaN-matching channels, #pixels with any bit difference)"""
-    both_nan = np.isnan(gpu) & np.isnan(ref)
-    d = np.where(both_nan, 0.0, np.abs(gpu.astype(np.float64) - ref.astype(np.float64)))
-    d = np.nan_to_num(d, nan=np.inf)
-    bits = (gpu.view(np.uint32) != ref.view(np.uint32)) & ~both_nan
-    return float(d.max()), int(bits.any(axis=-1).sum())
 
 
 @pytest.mark.parametrize("app,w,h", CASES)
@@ -133,7 +121,7 @@ def test_error_codes(renderer):
     assert renderer.render("egg", 64, 64, 0.0, rows=(5, 5)).shape[0] == 0
 
 
-def test_clouds_cooperative_equals_perlane_full_size(renderer):
+def test_clouds_cooperative_equals_perlane_full_size(renderer, variant_restored):
     """BASELINE size (3840x2160): the wave-cooperative CLOUDS kernel is bit-identical to the per-lane
     cross-check kernel, which the small-frame tests above tie to the oracle."""
     import torch

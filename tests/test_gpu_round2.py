@@ -3,21 +3,10 @@ APP_CLOUDS, per-stream timing, and wider full-size oracle
 import numpy as np
 import pytest
 
+from tests.app_checks import UNIT_ALPHA_APPS, compare
+from tests.app_checks import renderer, volumes  # noqa: F401 (fixtures)
+
 pytestmark = pytest.mark.gpu
-
-
-def compare(gpu, ref):
-    both_nan = np.isnan(gpu) & np.isnan(ref)
-    d = np.where(both_nan, 0.0, np.abs(gpu.astype(np.float64) - ref.astype(np.float64)))
-    d = np.nan_to_num(d, nan=np.inf)
-    bits = (gpu.view(np.uint32) != ref.view(np.uint32)) & ~both_nan
-    return float(d.max()), int(bits.any(axis=-1).sum())
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import shaderbox_amd
-    return shaderbox_amd.Renderer(0)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -132,14 +121,6 @@ def test_timing_is_per_stream(renderer):
 # ---------------------------------------------------------------------------------------------------------
 # USE_NOISE_TEX build of APP_CLOUDS
 # ---------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def volumes(renderer):
-    """two different baked volumes (ddsvolgen's tiled-Worley fBm at two sizes), device + host copies"""
-    v1 = renderer.worley_volume(32)
-    v2 = renderer.worley_volume(16)
-    return v1, v2, v1.cpu().numpy(), v2.cpu().numpy()
-
-
 def test_texture_filter_matches_oracle(renderer, oracle, volumes):
     import torch
     v1, v2, h1, h2 = volumes
@@ -359,10 +340,7 @@ def test_clouds_ue4_material_parameters(renderer, oracle):
 # ---------------------------------------------------------------------------------------------------------
 # the direct exchange of the one-process-per-GPU path: root in place, peers' slabs without alpha, peer-only assembly
 # ---------------------------------------------------------------------------------------------------------
-ALL_APPS = ["clouds", "egg", "raytracer", "atmosphere", "planet", "sdf_ao", "vinyl", "clouds_best", "clouds_ue4"]
-
-
-@pytest.mark.parametrize("app", ALL_APPS)
+@pytest.mark.parametrize("app", UNIT_ALPHA_APPS)
 def test_rgb_slab_is_the_rgba_slab_without_alpha(renderer, app):
     """sbx_render_split_rgb writes the same three floats per pixel as sbx_render_split, densely (12 bytes per pixel), also for
     sub-ranges of the slab rows; and every kernel's alpha is the constant 1 the RGB form drops."""

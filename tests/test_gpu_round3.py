@@ -3,32 +3,10 @@ light march, the two-pass APP_PLANET, the tiled USE_NOISE_TEX kernel and the mul
 import numpy as np
 import pytest
 
+from tests.app_checks import both_variants, compare
+from tests.app_checks import renderer  # noqa: F401 (fixtures)
+
 pytestmark = pytest.mark.gpu
-
-
-def compare(gpu, ref):
-    both_nan = np.isnan(gpu) & np.isnan(ref)
-    d = np.where(both_nan, 0.0, np.abs(gpu.astype(np.float64) - ref.astype(np.float64)))
-    d = np.nan_to_num(d, nan=np.inf)
-    bits = (gpu.view(np.uint32) != ref.view(np.uint32)) & ~both_nan
-    return float(d.max()), int(bits.any(axis=-1).sum())
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import shaderbox_amd
-    r = shaderbox_amd.Renderer(0)
-    yield r
-    r.close()
-
-
-def both_variants(r, app, w, h, t, **kw):
-    r.set_variant(0)
-    a = r.render(app, w, h, t, **kw).cpu().numpy()
-    r.set_variant(1)
-    b = r.render(app, w, h, t, **kw).cpu().numpy()
-    r.set_variant(0)
-    return a, b
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -3,37 +3,15 @@
 import numpy as np
 import pytest
 
+from tests.app_checks import POINT_APPS, bind_small_volumes, compare, loop_frame, oracle_points
+from tests.app_checks import renderer, renderer8, variant_restored  # noqa: F401 (fixtures)
+
 pytestmark = pytest.mark.gpu
-
-ALL_APPS = ["planet", "clouds", "vinyl", "egg", "raytracer", "atmosphere", "sdf_ao", "clouds_best", "clouds_ue4", "clouds_sky",
-            "vinyl_gpu", "planet_atmosphere"]
-
-
-def compare(gpu, ref):
-    both_nan = np.isnan(gpu) & np.isnan(ref)
-    d = np.where(both_nan, 0.0, np.abs(gpu.astype(np.float64) - ref.astype(np.float64)))
-    d = np.nan_to_num(d, nan=np.inf)
-    bits = (gpu.view(np.uint32) != ref.view(np.uint32)) & ~both_nan
-    return float(d.max()), int(bits.any(axis=-1).sum())
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import shaderbox_amd
-    r = shaderbox_amd.Renderer(0)
-    yield r
-    r.close()
-
-
-def oracle_points(oracle, app, w, h, t, pts, mouse=(0.0, 0.0)):
-    from oracle.oracle import APP_IDS
-    return np.stack([oracle.main_image(APP_IDS[app], w, h, t, float(x), float(y), mouse=mouse) for x, y in pts])
-
 
 # ---------------------------------------------------------------------------------------------------------
 # mainImage(fragColor, fragCoord) at arbitrary coordinates (src/main.h:6-53: fragCoord is divided by u_res, never snapped)
 # ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("app", ALL_APPS)
+@pytest.mark.parametrize("app", POINT_APPS)
 def test_main_image_off_centre_and_outside_the_frame(renderer, oracle, app):
     """sbx_main_image must evaluate the coordinate it is given: off-centre samples (a supersampling host), coordinates outside
     the frame and on its edges.  Round 3 returned floor(fragCoord)'s pixel, clamped to the frame, with rc 0."""
@@ -49,7 +27,7 @@ def test_main_image_off_centre_and_outside_the_frame(renderer, oracle, app):
     assert compare(got[8], frame[53, 95]) == (0.0, 0) and compare(got[9], frame[0, 0]) == (0.0, 0)
 
 
-@pytest.mark.parametrize("app", ALL_APPS)
+@pytest.mark.parametrize("app", POINT_APPS)
 def test_render_points_random_against_oracle(renderer, oracle, app):
     """sbx_render_points / sbx_main_image_batch: n arbitrary fragCoords in one launch, bit-identical to the oracle's mainImage at
     those coordinates; the lanes of a wave are then NOT neighbouring pixels (hash cache, wave-wide exits and culls must not care)"""
@@ -64,12 +42,6 @@ def test_render_points_random_against_oracle(renderer, oracle, app):
     ref = oracle_points(oracle, app, w, h, t, pts)
     assert compare(got_dev, ref) == (0.0, 0)
     assert compare(got_host, ref) == (0.0, 0)
-
-
-def bind_small_volumes(renderer):
-    """clouds_tex renders only once its noise volumes are bound: 16^3 Worley volumes, as the texture tests use"""
-    vol = renderer.worley_volume(16)
-    renderer.set_noise_volumes(vol, vol)
 
 
 def test_render_points_pixel_centres_equal_the_frame(renderer):
@@ -170,19 +142,6 @@ def test_main_image_from_several_threads(renderer, oracle):
 # ---------------------------------------------------------------------------------------------------------
 # the 8-GPU form of the BASELINE configs on one GPU: every rank's real schedule (FramePlan) through a loopback world
 # ---------------------------------------------------------------------------------------------------------
-def loop_frame(renderer, app, w, h, t, n, exchange, groups=1, relief=(1, 1), br=8, frames=1):
-    import torch
-    from shaderbox_amd.distributed import LoopbackWorld
-    world = LoopbackWorld(n)
-    plans = world.plans(renderer, w, h, block_rows=br, groups=groups, root_rounds=relief[0], rounds=relief[1], exchange=exchange)
-    out = None
-    for _ in range(frames):
-        plans[0].frame.fill_(-7.0)                    # every pixel must be written again
-        out = LoopbackWorld.render(plans, app, t)
-    torch.cuda.synchronize()
-    return out, world
-
-
 @pytest.mark.parametrize("app", ["atmosphere", "planet"])
 def test_config5_eight_ranks_at_7680x4320_equal_one_launch(renderer, app):
     """BASELINE config 5 as it runs on 8 GPUs — cyclic 8-row blocks, root in place, ONE exchange — with all 8 ranks' FramePlans on
@@ -234,23 +193,29 @@ def test_hash_cache_fault_is_sticky_and_loud(renderer):
     every later render on that device fails with SBX_ERR_FAULT, sbx_last_error says why, sbx_clear_fault re-arms."""
     import torch
     import shaderbox_amd
-    assert renderer.fault_status() == 0
-    ref = renderer.render("clouds", 96, 54, .37)
-    assert renderer.lib.sbx_debug_raise_fault(renderer.ctx, None) == 0      # one wave through the path a failed miss loop takes
-    torch.cuda.synchronize()
-    assert renderer.fault_status() == shaderbox_amd.SBX_ERR_FAULT
-    with pytest.raises(shaderbox_amd.SbxError) as e:
-        renderer.render("clouds", 96, 54, .37)
-    assert e.value.code == shaderbox_amd.SBX_ERR_FAULT and "hash cache" in str(e.value)
-    other = shaderbox_amd.Renderer(0)                                     # the word belongs to the device, not to a context
-    with pytest.raises(shaderbox_amd.SbxError):
-        other.render("egg", 32, 32, .37)
-    assert b"hash cache" in other.lib.sbx_last_error(other.ctx)
-    other.clear_fault()
-    other.close()
-    assert renderer.fault_status() == 0
-    again = renderer.render("clouds", 96, 54, .37)
-    assert torch.equal(again.view(torch.int32), ref.view(torch.int32))
+    other = None
+    try:
+        assert renderer.fault_status() == 0
+        ref = renderer.render("clouds", 96, 54, .37)
+        assert renderer.lib.sbx_debug_raise_fault(renderer.ctx, None) == 0      # one wave through the path a failed miss loop takes
+        torch.cuda.synchronize()
+        assert renderer.fault_status() == shaderbox_amd.SBX_ERR_FAULT
+        with pytest.raises(shaderbox_amd.SbxError) as e:
+            renderer.render("clouds", 96, 54, .37)
+        assert e.value.code == shaderbox_amd.SBX_ERR_FAULT and "hash cache" in str(e.value)
+        other = shaderbox_amd.Renderer(0)                                     # the word belongs to the device, not to a context
+        with pytest.raises(shaderbox_amd.SbxError):
+            other.render("egg", 32, 32, .37)
+        assert b"hash cache" in other.lib.sbx_last_error(other.ctx)
+        other.clear_fault()
+        other.close()
+        assert renderer.fault_status() == 0
+        again = renderer.render("clouds", 96, 54, .37)
+        assert torch.equal(again.view(torch.int32), ref.view(torch.int32))
+    finally:                                       # a failed assert leaves neither the device's fault word nor a context behind
+        if other is not None:
+            other.close()
+        renderer.clear_fault()
 
 
 def test_multi_create_device_lists(renderer):
@@ -280,7 +245,7 @@ def test_multi_create_device_lists(renderer):
 # ADVICE r3
 # ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("app", ["vinyl", "vinyl_gpu", "sdf_ao", "egg"])
-def test_hardware_min_max_kernels_equal_plain_over_a_time_sweep(renderer, app):
+def test_hardware_min_max_kernels_equal_plain_over_a_time_sweep(renderer, variant_restored, app):
     """the SDF kernels' v_min_f32 / v_max_f32 (pinned with inline asm, sbx_sdf.h hmin_ / hmax_) against the compare-and-select
     spec form (variant 1: plain kernels) over a random u_time sweep, bit for bit — the zero-sign and NaN argument of the proof is
     about operand ORDER, so it is checked where it could break: many poses"""
@@ -346,7 +311,7 @@ def test_bench_relief_calibration_for_the_span_exchange(renderer):
     assert bench.auto_groups("auto", 9.2e6) == 1 and bench.auto_groups("auto", 29.7e6) == 3 and bench.auto_groups("2", 1e9) == 2
 
 
-def test_clouds_marches_longer_than_the_ring_tables(renderer, oracle):
+def test_clouds_marches_longer_than_the_ring_tables(renderer, variant_restored, oracle):
     """cld_march_steps beyond the 4096 rows of the y-table ring: the context's on-demand table (sbx_ytab.hip render_clouds case 4)
     instead of round 3's table-less fallback; same bits as the per-lane kernel and the oracle, across key changes and streams"""
     import torch
@@ -377,7 +342,7 @@ def test_clouds_marches_longer_than_the_ring_tables(renderer, oracle):
 # BASELINE config 5 read literally: APP_PLANET with APP_ATMOSPHERE's sky as its background (labelled extension, parity unpinned)
 # ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("w,h,t", [(256, 144, .37), (333, 187, 0.0), (640, 360, 2.5), (96, 54, 40.0)])
-def test_planet_atmosphere_composite_matches_oracle(renderer, oracle, w, h, t):
+def test_planet_atmosphere_composite_matches_oracle(renderer, variant_restored, oracle, w, h, t):
     """SBX_APP_PLANET_ATMOSPHERE (include/sbx.h): default and plain kernels == the oracle's restatement of the same definition,
     NaN == NaN; where APP_PLANET shows terrain the two apps agree, elsewhere the sky is APP_ATMOSPHERE's"""
     from oracle.oracle import APP_IDS
@@ -594,16 +559,7 @@ def test_witnessed_square_roots_of_the_sdf_kernels(renderer, oracle, app):
 # ---------------------------------------------------------------------------------------------------------
 # SBX_FORMAT_RGBA8: the kernels write the display format themselves (include/sbx.h sbx_set_output_format)
 # ---------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def renderer8():
-    import shaderbox_amd
-    r = shaderbox_amd.Renderer(0)
-    r.set_output_format("rgba8")
-    yield r
-    r.close()
-
-
-@pytest.mark.parametrize("app", ALL_APPS)
+@pytest.mark.parametrize("app", POINT_APPS)
 def test_rgba8_frames_equal_the_packed_float_frames(renderer, renderer8, app):
     """a frame, a strip and a rank's slab written as R8G8B8A8_UNORM words by the render kernel == sbx_pack_unorm8 of the float
     pixels, for every app (NaN pixels pack to 0 on both sides), odd sizes included"""

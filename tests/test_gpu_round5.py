@@ -10,23 +10,10 @@ import sys
 import numpy as np
 import pytest
 
+from tests.app_checks import ROOT, bits_differ
+from tests.app_checks import renderer, variant_restored  # noqa: F401 (fixtures)
+
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import shaderbox_amd
-    r = shaderbox_amd.Renderer(0)
-    yield r
-    r.close()
-
-
-def bits_differ(a, b):
-    import torch
-    return int((a.view(torch.int32) != b.view(torch.int32)).any(dim=-1).sum().item())
-
 
 # ---------------------------------------------------------------------------------------------------------
 # the store exchange (include/sbx.h sbx_shared_*, distributed.FramePlan exchange="stores")
@@ -118,44 +105,51 @@ def test_store_exchange_wait_times_out_into_the_fault_word(renderer):
     return SBX_ERR_FAULT until it is cleared"""
     import torch
     import shaderbox_amd
-    owner = renderer.shared_create(64 * 36 * 16, 2)
-    peer = renderer.shared_open(owner.export())
-    peer.set_timeout_ms(30)
-    peer.begin(1)                                  # no owner.begin before it
-    torch.cuda.synchronize()
-    assert renderer.fault_status() == shaderbox_amd.SBX_ERR_FAULT
-    with pytest.raises(shaderbox_amd.SbxError) as ei:
-        renderer.render("egg", 32, 32, 0.37)
-    assert ei.value.code == shaderbox_amd.SBX_ERR_FAULT and "store exchange" in str(ei.value)
-    renderer.clear_fault()
-    assert renderer.fault_status() == 0
-    # round 6 (ADVICE r5): the side whose wait gave up does NOT report that frame as in place — its signal kernel sees the abort
-    # word and stays silent, so the owner's wait for it gives up too instead of reading a frame overwritten under it
-    peer.end(1)
-    owner.set_timeout_ms(30)
-    owner.begin(0)                                 # (frame 1 of the owner's count: released now, too late for the peer's frame 1)
-    owner.end(0)                                   # waits for done[1] >= 1: never signalled
-    torch.cuda.synchronize()
-    assert renderer.fault_status() == shaderbox_amd.SBX_ERR_FAULT
-    renderer.clear_fault()
-    assert peer.nbytes == owner.nbytes == 64 * 36 * 16            # sbx_shared_bytes on the opened side (no blob layout in the binding)
-    peer.close()
-    owner.close()
-    # and the protocol in order works afterwards (a fresh pair: the timed-out one has lost a frame of its count):
-    # owner go, peer render + signal, owner wait
-    owner = renderer.shared_create(64 * 36 * 16, 2)
-    peer = renderer.shared_open(owner.export())
-    owner.begin(0)
-    peer.begin(1)
-    renderer.render_rank_in_place("egg", 64, 36, 0.37, 8, 1, 2, peer)
-    peer.end(1)
-    renderer.render_rank_in_place("egg", 64, 36, 0.37, 8, 0, 2, owner.tensor((36, 64, 4)))
-    owner.end(0)
-    ref = renderer.render("egg", 64, 36, 0.37)
-    torch.cuda.synchronize()
-    assert bits_differ(owner.tensor((36, 64, 4)), ref) == 0 and renderer.fault_status() == 0
-    peer.close()
-    owner.close()
+    owner = peer = None
+    try:
+        owner = renderer.shared_create(64 * 36 * 16, 2)
+        peer = renderer.shared_open(owner.export())
+        peer.set_timeout_ms(30)
+        peer.begin(1)                                  # no owner.begin before it
+        torch.cuda.synchronize()
+        assert renderer.fault_status() == shaderbox_amd.SBX_ERR_FAULT
+        with pytest.raises(shaderbox_amd.SbxError) as ei:
+            renderer.render("egg", 32, 32, 0.37)
+        assert ei.value.code == shaderbox_amd.SBX_ERR_FAULT and "store exchange" in str(ei.value)
+        renderer.clear_fault()
+        assert renderer.fault_status() == 0
+        # round 6 (ADVICE r5): the side whose wait gave up does NOT report that frame as in place — its signal kernel sees the abort
+        # word and stays silent, so the owner's wait for it gives up too instead of reading a frame overwritten under it
+        peer.end(1)
+        owner.set_timeout_ms(30)
+        owner.begin(0)                                 # (frame 1 of the owner's count: released now, too late for the peer's frame 1)
+        owner.end(0)                                   # waits for done[1] >= 1: never signalled
+        torch.cuda.synchronize()
+        assert renderer.fault_status() == shaderbox_amd.SBX_ERR_FAULT
+        renderer.clear_fault()
+        assert peer.nbytes == owner.nbytes == 64 * 36 * 16            # sbx_shared_bytes on the opened side (no blob layout in the binding)
+        peer.close()
+        owner.close()
+        # and the protocol in order works afterwards (a fresh pair: the timed-out one has lost a frame of its count):
+        # owner go, peer render + signal, owner wait
+        owner = renderer.shared_create(64 * 36 * 16, 2)
+        peer = renderer.shared_open(owner.export())
+        owner.begin(0)
+        peer.begin(1)
+        renderer.render_rank_in_place("egg", 64, 36, 0.37, 8, 1, 2, peer)
+        peer.end(1)
+        renderer.render_rank_in_place("egg", 64, 36, 0.37, 8, 0, 2, owner.tensor((36, 64, 4)))
+        owner.end(0)
+        ref = renderer.render("egg", 64, 36, 0.37)
+        torch.cuda.synchronize()
+        assert bits_differ(owner.tensor((36, 64, 4)), ref) == 0 and renderer.fault_status() == 0
+        peer.close()
+        owner.close()
+    finally:                                       # a failed assert leaves neither the device's fault word nor a shared frame behind
+        for sh in (peer, owner):
+            if sh is not None:
+                sh.close()
+        renderer.clear_fault()
 
 
 def _free_port():
@@ -470,7 +464,7 @@ def test_render_rows_into_host_memory_rgba8_and_errors(renderer):
 
 
 # ---- round 6: the dispatch order (csrc/sbx_tile_order.h) -------------------------------------------------------------------
-def test_dispatch_order_is_a_permutation_and_changes_no_pixel(renderer):
+def test_dispatch_order_is_a_permutation_and_changes_no_pixel(renderer, variant_restored):
     """From the fourth launch of a shape on, APP_CLOUDS (and CLOUDS_SKY, VINYL, EGG) dispatch their tiles by the cost earlier frames
     measured, longest first.  The table is a permutation of the launch's tiles — whatever the cost words hold —, frames rendered
     through it equal the per-lane kernel's (which never uses one) bit for bit, on one stream and on three (where the library

@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -50,7 +50,9 @@ typedef enum sbx_app {
     SBX_APP_VINYL = 2,      /* C++-build semantics: 60 march steps (src/app_vinyl.h:411-416) */
     SBX_APP_EGG = 3,         /* src/app_egg.h as shipped: BEZIER defined (:37) and the `#if 1` egg (:46-52).  The builds with one of the two
                                 switches the other way are SBX_APP_EGG_STRAIGHT and SBX_APP_EGG_OVAL */
-    SBX_APP_RAYTRACER = 4,
+    SBX_APP_RAYTRACER = 4,   /* src/app_raytracer.h as shipped: the `#if 1` of setup_scene (:29) and of the shadow ray (:107) on, the `#if 0` of
+                                illuminate (:61) off.  The builds with one of the three the other way are SBX_APP_RAYTRACER_PHONG,
+                                SBX_APP_RAYTRACER_NOSHADOW and SBX_APP_RAYTRACER_STATIC */
     SBX_APP_ATMOSPHERE = 5,  /* src/app_atmosphere.h as shipped, FROM_SPACE defined (:162): the sky dome (:190-209).  The build without
                                 the define is SBX_APP_ATMOSPHERE_GROUND */
     SBX_APP_SDF_AO = 6,      /* src/app_sdf_ao.h as shipped: both `#if 0` blocks off (:217-219, :269-274).  The builds with one of them on are
@@ -178,7 +180,31 @@ typedef enum sbx_app {
        (`return luminance;`): sun_power is not read and the phase function is not evaluated (sun_dir still enters the sky colour and
        the light march's direction).  Everything else, the aux block, the output forms, the variant and what is not offered as
        SBX_APP_CLOUDS_HEIGHT says. */
-    SBX_APP_CLOUDS_LUMINANCE = 22
+    SBX_APP_CLOUDS_LUMINANCE = 22,
+    /* APP_RAYTRACER compiled with the `#if 0` of src/app_raytracer.h:61 turned to `#if 1` (:29 and :107 as shipped): the Phong build.
+       illuminate calls illum_blinn_phong (src/light.h:44-62) instead of illum_cook_torrance; that function is compiled in the `#else`
+       branch of its own `#if 0 // Blinn specular` (:53), the Phong specular, so per lit hit
+           diffuse = max(0., dot(L, N)) * base_color;  R = reflect(-L, N);  specular = pow(max(0., dot(R, V)), 50.) * vec3(1, 1, 1)
+       with reflect(I, N) = I - 2. * dot(N, I) * N (src/util_optics.h:17-22), pow the math spec's binary32 pow, and
+       ambient + diffuse + specular returned.  The material's roughness and ior are not read; the mat_debug early return of :51-53
+       stands before it.  (The Blinn branch of :53 does not compile in the C++ form and is not offered.)  Everything else as
+       SBX_APP_RAYTRACER: camera (u_mouse turns it), the animated scene, the shadow ray, the reflection bounce, alpha 1.  No aux
+       block.  Every output form holds it (rows, host rows, points, sbx_main_image*, ranks, splits, rgb, the exchanges with whole
+       rows, SBX_FORMAT_RGBA8, sbx_multi_render).  sbx_set_variant as for SBX_APP_RAYTRACER (include/sbx_test.h).  Two switches at
+       once are not offered.  Definition: tests/raytracer_builds_model.py, pinned against frames and points of the edited reference
+       header (tests/golden/raytracer_builds/). */
+    SBX_APP_RAYTRACER_PHONG = 23,
+    /* APP_RAYTRACER compiled with the `#if 1 // shadow ray` of src/app_raytracer.h:107 turned to `#if 0` (:29 and :61 as shipped):
+       the unshadowed build.  :108-121 are gone: no second raytrace_iteration from the first hit towards the light and no
+       `color *= 0.1`.  Everything else, the output forms, the variants and what is not offered as SBX_APP_RAYTRACER_PHONG says; the
+       lighting is Cook-Torrance as shipped. */
+    SBX_APP_RAYTRACER_NOSHADOW = 24,
+    /* APP_RAYTRACER compiled with the `#if 1` of src/app_raytracer.h:29 turned to `#if 0` (:61 and :107 as shipped): the Cornell box
+       at rest.  setup_scene ends after setup_cornell_box: the left sphere stays at (0.75, 1, -0.75), the right one at
+       (-0.75, 0.75, 0.75) (src/cornell_box.h:77-82) and the light at (0, 3.8, 0) (:85; z is 0, not 1.5).  u_time is not read: every
+       value of it, inf and NaN included, gives the same frame; u_mouse turns the camera as shipped.  The shipped kernels over
+       another frame block.  Everything else as SBX_APP_RAYTRACER_PHONG says; the lighting is Cook-Torrance as shipped. */
+    SBX_APP_RAYTRACER_STATIC = 25
 } sbx_app;
 
 typedef enum sbx_status {

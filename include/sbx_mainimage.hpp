@@ -50,6 +50,12 @@
 #define SBX_SELECTED_APP SBX_APP_CLOUDS_HEIGHT
 #elif defined(APP_CLOUDS_LUMINANCE) /* src/app_clouds.h with the `#if 0` at :118 on (the light march's transmittance itself); tested before APP_CLOUDS */
 #define SBX_SELECTED_APP SBX_APP_CLOUDS_LUMINANCE
+#elif defined(APP_RAYTRACER_PHONG)    /* src/app_raytracer.h with the `#if 0` at :61 on (illum_blinn_phong's Phong specular; include/sbx.h); tested before APP_RAYTRACER */
+#define SBX_SELECTED_APP SBX_APP_RAYTRACER_PHONG
+#elif defined(APP_RAYTRACER_NOSHADOW) /* src/app_raytracer.h with the `#if 1` at :107 off (no shadow ray); tested before APP_RAYTRACER */
+#define SBX_SELECTED_APP SBX_APP_RAYTRACER_NOSHADOW
+#elif defined(APP_RAYTRACER_STATIC)   /* src/app_raytracer.h with the `#if 1` at :29 off (the Cornell box at rest); tested before APP_RAYTRACER */
+#define SBX_SELECTED_APP SBX_APP_RAYTRACER_STATIC
 #elif defined(APP_PLANET)
 #define SBX_SELECTED_APP SBX_APP_PLANET
 #elif defined(APP_CLOUDS)
@@ -67,7 +73,7 @@
 #elif defined(APP_CLOUDS_BEST)   /* src/app_clouds_best.h, the stand-alone shader (no APP_* define in the reference) */
 #define SBX_SELECTED_APP SBX_APP_CLOUDS_BEST
 #else
-#error "define one of APP_PLANET APP_CLOUDS APP_VINYL APP_EGG APP_RAYTRACER APP_ATMOSPHERE APP_SDF_AO (or APP_CLOUDS_BEST APP_PLANET_ATMOSPHERE APP_2D APP_2D_TEX APP_FUNC APP_ATMOSPHERE_GROUND APP_SDF_AO_SHADOW APP_SDF_AO_NORMALS APP_EGG_STRAIGHT APP_EGG_OVAL APP_CLOUDS_HEIGHT APP_CLOUDS_LUMINANCE)"
+#error "define one of APP_PLANET APP_CLOUDS APP_VINYL APP_EGG APP_RAYTRACER APP_ATMOSPHERE APP_SDF_AO (or APP_CLOUDS_BEST APP_PLANET_ATMOSPHERE APP_2D APP_2D_TEX APP_FUNC APP_ATMOSPHERE_GROUND APP_SDF_AO_SHADOW APP_SDF_AO_NORMALS APP_EGG_STRAIGHT APP_EGG_OVAL APP_CLOUDS_HEIGHT APP_CLOUDS_LUMINANCE APP_RAYTRACER_PHONG APP_RAYTRACER_NOSHADOW APP_RAYTRACER_STATIC)"
 #endif
 
 namespace sbx_host {

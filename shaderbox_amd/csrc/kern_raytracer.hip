@@ -6,6 +6,13 @@
 // :17-22), src/material.h, src/cornell_box.h.  The whole scene (6 planes, 3 spheres, 8 material
 // slots, the light) is frame-constant: it is built on the host (setup_scene :18-36 +
 // setup_cornell_box cornell_box.h:39-87) and arrives as kernel arguments in SGPRs.
+//
+// BUILD (sbx_frame.h RT_*): the file's compile-time switches, each one the other way (include/sbx.h).
+//   RT_PHONG     the `#if 0` of illuminate at :61 turned to `#if 1` (SBX_APP_RAYTRACER_PHONG): illum_blinn_phong (light.h:44-62, its
+//                compiled `#else` branch, the Phong specular) stands in for illum_cook_torrance
+//   RT_NOSHADOW  the `#if 1 // shadow ray` of render at :107 turned to `#if 0` (SBX_APP_RAYTRACER_NOSHADOW): :108-121 are gone
+// The third switch, setup_scene's `#if 1` at :29 (SBX_APP_RAYTRACER_STATIC), changes the frame block alone (sbx_frames.hip
+// build_raytracer): it runs the RT_DEFAULT kernels.
 #include <cmath>
 #include "sbx_device.h"
 #include "sbx_ldsframe.h"
@@ -25,6 +32,7 @@ __device__ __forceinline__ RtMaterial rt_ld(const RtMaterial& r) {
 }
 __device__ __forceinline__ v3 rt_ld(const v3& r) { return lds_ld(r); }
 __device__ __forceinline__ int rt_ld(const int& r) { return lds_ld(r); }
+__device__ __forceinline__ float rt_ld(const float& r) { return lds_ld(r); }
 #else
 template <class T> __device__ __forceinline__ const T& rt_ld(const T& r) { return r; }
 #endif
@@ -137,11 +145,16 @@ __device__ __forceinline__ Hit trace(const FrameRaytracer& F, v3 ro, v3 rd, int 
     return hit;
 }
 // get_material: linear scan; an id outside 0..7 yields the zero-initialised material (App. B5)
+template <int BUILD>
 __device__ __forceinline__ RtMaterial material_of(const FrameRaytracer& F, int id) {
     RtMaterial m;
     m.base_color = V3(0, 0, 0); m.roughness = 0.f; m.ior = 0.f; m.reflectivity = 0.f;
     m.r0 = 1.f;                                                  // ior 0: ((1 - 0) / (1 + 0))^2
 #if RT_LDS_FRAME
+    if (BUILD == RT_PHONG) {                                     // illum_blinn_phong reads base_color alone, render the reflectivity
+        if (id >= 0 && id < 8) { m.base_color = rt_ld(F.mats[id].base_color); m.reflectivity = rt_ld(F.mats[id].reflectivity); }
+        return m;
+    }
     if (id >= 0 && id < 8) m = rt_ld(F.mats[id]);               // one LDS read per member at the lane's own address
 #else
 #pragma unroll
@@ -166,14 +179,25 @@ __device__ __forceinline__ v3 cook_torrance(v3 V, v3 L, const Hit& hit, const Rt
     const float specular = (geo_term * rough_term * fresnel_term) / (3.14159265359f * NdotV * NdotL);
     return fmax_(0.f, NdotL) * (specular + mat.base_color);
 }
+// illum_blinn_phong, light.h:44-62 with the `#else` of :53 (the Phong specular; the Blinn branch does not compile in the C++ form).
+// reflect(incident, normal) = incident - 2 * dot(normal, incident) * normal (util_optics.h:17-22) with incident = -L: the unary minus
+// makes negative zeros, which stay.  `pow(..) * vec3(1, 1, 1)` is the float times each 1: the float itself.  No root.
+__device__ __forceinline__ v3 phong(v3 V, v3 L, const Hit& hit, const RtMaterial& mat) {
+    const v3 diffuse = fmax_(0.f, dot(L, hit.n)) * mat.base_color;          // :50
+    const v3 I = -L;
+    const v3 R = I - 2.f * dot(hit.n, I) * hit.n;                           // :57
+    const float specular = pow_(fmax_(0.f, dot(R, V)), 50.f);               // :52, :58
+    return diffuse + V3(specular, specular, specular);                      // :61
+}
 // (mat = material_of(hit.mat) and L = normalize(light - hit.o), light.h:18-27, come from the caller, which needs both again:
 // the scene block's reads are volatile, so the compiler would not share them)
-template <class W>
+template <int BUILD, class W>
 __device__ __forceinline__ v3 rt_illuminate(const FrameRaytracer& F, v3 eye, const Hit& hit, const RtMaterial& mat, v3 L, W& w) {   // :46-68
     if (hit.mat == 0) return rt_ld(F.mats[0].base_color);        // mat_debug: flat
     v3 accum = V3(.01f, .01f, .01f);                              // ambient_light light.h:16
     const v3 V = w.normalize(eye - hit.o);
-    accum = accum + cook_torrance(V, L, hit, mat, w);
+    if (BUILD == RT_PHONG) accum = accum + phong(V, L, hit, mat);       // :61-62
+    else accum = accum + cook_torrance(V, L, hit, mat, w);
     return accum;
 }
 
@@ -182,7 +206,7 @@ __device__ __forceinline__ v3 rt_illuminate(const FrameRaytracer& F, v3 eye, con
 #endif
 
 // One pixel's colour — render :88-136 — with the roots / normalisations of witness `w`.  Fs: the scene block (LDS copy or F).
-template <bool WALLS, class W>
+template <bool WALLS, int BUILD, class W>
 __device__ __forceinline__ v3 rt_pixel(const FrameRaytracer& F, const FrameRaytracer& Fs, v2 pc, W& w) {
     const v3 eye = F.cam.eye;
     v3 ro = eye, rd = primary_dir(F.cam, pc, w);
@@ -195,11 +219,11 @@ __device__ __forceinline__ v3 rt_pixel(const FrameRaytracer& F, const FrameRaytr
             break;
         }
         const float f = fresnel_factor(1.f, 1.f, dot(hit.n, -rd));
-        const RtMaterial mat = material_of(Fs, hit.mat);
+        const RtMaterial mat = material_of<BUILD>(Fs, hit.mat);
         const v3 shadow_line = rt_ld(Fs.light) - hit.o;           // = illuminate's light vector (point light, light.h:18-27)
         const v3 shadow_dir = w.normalize(shadow_line);
-        color = color + (1.f - f) * accum * rt_illuminate(Fs, eye, hit, mat, shadow_dir, w);   // primary origin on every bounce (:105)
-        if (i == 0) {                                             // shadow ray :108-121
+        color = color + (1.f - f) * accum * rt_illuminate<BUILD>(Fs, eye, hit, mat, shadow_dir, w);   // primary origin on every bounce (:105)
+        if (BUILD != RT_NOSHADOW && i == 0) {                     // shadow ray :108-121
             const Hit sh = trace<WALLS>(Fs, hit.o + shadow_dir * 1e-4f, shadow_dir, 0, w);
             if (sh.t < w.length(shadow_line)) color = color * 0.1f;
         }
@@ -216,7 +240,7 @@ __device__ __forceinline__ v3 rt_pixel(const FrameRaytracer& F, const FrameRaytr
     return color;
 }
 
-template <int WIT, bool WALLS = false>   // WIT: 0 IEEE forms, 1 witnessed fast forms, 2 the witness's test edge (sbx_set_variant 2); WALLS: hit_walls
+template <int WIT, bool WALLS = false, int BUILD = RT_DEFAULT>   // WIT: 0 IEEE forms, 1 witnessed fast forms, 2 the witness's test edge (sbx_set_variant 2); WALLS: hit_walls; BUILD: RT_*
 __global__ void __launch_bounds__(WG_THREADS) k_raytracer(FrameRaytracer F, RowMap M, float* __restrict__ out) {
     const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();      // (the dispatch order's cost table, RowMap.cost)
 #if RT_LDS_FRAME
@@ -233,14 +257,14 @@ __global__ void __launch_bounds__(WG_THREADS) k_raytracer(FrameRaytracer F, RowM
     if (WIT != 0) {
         Wit<true> w;
         if (WIT == 2) w.lo = 0x3F800000u;
-        color = rt_pixel<WALLS>(F, RT_F, pc, w);
+        color = rt_pixel<WALLS, BUILD>(F, RT_F, pc, w);
         if (__builtin_amdgcn_ballot_w64(w.bad) != 0ull) {      // some lane left the fast forms' proved domain: the IEEE forms
             Wit<false> w0;
-            color = rt_pixel<false>(F, RT_F, pc, w0);
+            color = rt_pixel<false, BUILD>(F, RT_F, pc, w0);
         }
     } else {
         Wit<false> w0;
-        color = rt_pixel<false>(F, RT_F, pc, w0);
+        color = rt_pixel<false, BUILD>(F, RT_F, pc, w0);
     }
     tile_cost_store(M, tl_t0);
     store_rgba(M, out, px.idx, to_srgb(color));
@@ -248,17 +272,26 @@ __global__ void __launch_bounds__(WG_THREADS) k_raytracer(FrameRaytracer F, RowM
 
 dim3 raytracer_grid(const RowMap& M) { return grid_for(M); }
 
-void launch_raytracer(const FrameRaytracer& F, const RowMap& M, float* out, hipStream_t s, int variant) {
+template <int BUILD>
+static void launch_build(const FrameRaytracer& F, const RowMap& M, float* out, hipStream_t s, int variant, bool walls) {
+    if (variant == 2 && walls) hipLaunchKernelGGL((k_raytracer<2, true, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);     // (the witness's test build
+    else if (variant == 2) hipLaunchKernelGGL((k_raytracer<2, false, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);         //  keeps hit_walls' domain too)
+    else if (variant == 1 || variant == 3) hipLaunchKernelGGL((k_raytracer<0, false, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    else if (!walls) hipLaunchKernelGGL((k_raytracer<RT_WITNESS, false, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    else hipLaunchKernelGGL((k_raytracer<RT_WITNESS, true, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+}
+
+void launch_raytracer(const FrameRaytracer& F, const RowMap& M, float* out, hipStream_t s, int variant, int build) {
     // hit_walls' conditions on the frame: the six planes are cornell_box.h's and every number of the frame is finite
     bool walls = RT_AXIS_PLANES && rt_walls_are_cornell(F);
     for (int i = 0; i < 3; ++i) walls = walls && std::isfinite(F.spheres[i].o.x) && std::isfinite(F.spheres[i].o.y) && std::isfinite(F.spheres[i].o.z) && std::isfinite(F.spheres[i].r);
     const float chk[] = {F.cam.eye.x, F.cam.eye.y, F.cam.eye.z, F.light.x, F.light.y, F.light.z};
     for (float v : chk) walls = walls && std::isfinite(v);
-    if (variant == 2 && walls) hipLaunchKernelGGL((k_raytracer<2, true>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);     // (the witness's test build
-    else if (variant == 2) hipLaunchKernelGGL((k_raytracer<2, false>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);         //  keeps hit_walls' domain too)
-    else if (variant == 1 || variant == 3) hipLaunchKernelGGL(k_raytracer<0>, grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else if (!walls) hipLaunchKernelGGL((k_raytracer<RT_WITNESS, false>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else hipLaunchKernelGGL((k_raytracer<RT_WITNESS, true>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    switch (build) {
+    case RT_PHONG: launch_build<RT_PHONG>(F, M, out, s, variant, walls); break;
+    case RT_NOSHADOW: launch_build<RT_NOSHADOW>(F, M, out, s, variant, walls); break;
+    default: launch_build<RT_DEFAULT>(F, M, out, s, variant, walls); break;     // RT_STATIC: the shipped kernels over its frame block
+    }
 }
 
 }  // namespace sbx

@@ -248,6 +248,10 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     case SBX_APP_EGG_STRAIGHT: launch_egg(build_egg(*uni, EGG_STRAIGHT), M, rgba, s, sdf_variant, EGG_STRAIGHT); break;
     case SBX_APP_EGG_OVAL: launch_egg(build_egg(*uni, EGG_OVAL), M, rgba, s, sdf_variant, EGG_OVAL); break;
     case SBX_APP_RAYTRACER: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots); break;
+    // the builds of app_raytracer.h's three switches (include/sbx.h): two kernel builds over the shipped frame, one frame of its own
+    case SBX_APP_RAYTRACER_PHONG: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots, RT_PHONG); break;
+    case SBX_APP_RAYTRACER_NOSHADOW: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots, RT_NOSHADOW); break;
+    case SBX_APP_RAYTRACER_STATIC: launch_raytracer(build_raytracer(*uni, RT_STATIC), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots, RT_STATIC); break;
     case SBX_APP_ATMOSPHERE: launch_atmosphere(build_atmosphere(*uni), M, rgba, s, ctx->precision); break;
     case SBX_APP_ATMOSPHERE_GROUND: launch_atmosphere_ground(build_atmosphere_ground(*uni), M, rgba, s, ctx->precision, ctx->variant); break;
     // one scene, three builds of app_sdf_ao.h (include/sbx.h)

@@ -187,7 +187,7 @@ int render_rows(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const void* aux,
 // ---- sbx_frames.hip: the frame-constant part of setup_camera()/setup_scene()/sdf() per app
 FrameClouds build_clouds(const sbx_uniforms& U, const sbx_aux_clouds& A, bool sky_sphere = false);
 FrameEggStraight build_egg(const sbx_uniforms& U, int build = EGG_DEFAULT);   // (the other builds read its FrameEgg part)
-FrameRaytracer build_raytracer(const sbx_uniforms& U);
+FrameRaytracer build_raytracer(const sbx_uniforms& U, int build = RT_DEFAULT);   // build: RT_* (sbx_frame.h); RT_STATIC is the scene at rest
 FrameAtmosphere build_atmosphere(const sbx_uniforms& U);
 FrameAtmosphere build_atmosphere_ground(const sbx_uniforms& U);
 FrameSdfAo build_sdf_ao(const sbx_uniforms& U, const sbx_aux_sdf_ao& A);

@@ -188,6 +188,11 @@ struct FrameRaytracer {
     RtMaterial mats[8];
     v3 light;             // lights[0].L
 };
+// The builds of app_raytracer.h's three compile-time switches (include/sbx.h): SBX_APP_RAYTRACER, _RAYTRACER_PHONG (illuminate's
+// `#if 0` at :61 on), _RAYTRACER_NOSHADOW (render's `#if 1` at :107 off), _RAYTRACER_STATIC (setup_scene's `#if 1` at :29 off).
+// The first two are kernel template parameters (kern_raytracer.hip); the third is another frame block for the shipped kernels
+// (build_raytracer).  FrameRaytracer is the same type in all four.
+enum { RT_DEFAULT = 0, RT_PHONG = 1, RT_NOSHADOW = 2, RT_STATIC = 3 };
 
 // ---- APP_ATMOSPHERE (src/app_atmosphere.h) --------------------------------------------------
 struct FrameAtmosphere {

@@ -145,7 +145,7 @@ FrameEggStraight build_egg(const sbx_uniforms& U, int build) {
     return F;
 }
 
-FrameRaytracer build_raytracer(const sbx_uniforms& U) {
+FrameRaytracer build_raytracer(const sbx_uniforms& U, int build) {
     FrameRaytracer F;
     const float cb = 2.f;                                              // cb_plane_dist cornell_box.h:62
     // setup_camera app_raytracer.h:38-44
@@ -173,12 +173,18 @@ FrameRaytracer build_raytracer(const sbx_uniforms& U) {
     F.planes[3] = RtPlane{V3(0, 1, 0), 2.f * cb, 1};
     F.planes[4] = RtPlane{V3(1, 0, 0), cb, 2};
     F.planes[5] = RtPlane{V3(-1, 0, 0), -cb, 3};
-    // spheres cornell_box.h:71-82 + animation app_raytracer.h:29-34
-    const float s = sin_(U.u_time), c = cos_(U.u_time);
+    // spheres and light as cornell_box.h:71-85 puts them: the whole scene of RT_STATIC (the `#if 1` at app_raytracer.h:29 off), which
+    // reads no u_time
     F.spheres[0] = RtSphere{V3(0, 2.5f * cb + 0.4f, 0), 1.5f, 0, recip64(1.5f)};
-    F.spheres[1] = RtSphere{V3(0.75f, 1, -0.75f) + V3(0, abs_(s), c + 1.f), 0.75f, 4, recip64(0.75f)};
-    F.spheres[2] = RtSphere{V3(-0.75f, 0.75f, 0.f), 0.75f, 5, recip64(0.75f)};
-    F.light = V3(0, 2.f * cb - 0.2f, 1.5f);
+    F.spheres[1] = RtSphere{V3(0.75f, 1, -0.75f), 0.75f, 4, recip64(0.75f)};
+    F.spheres[2] = RtSphere{V3(-0.75f, 0.75f, 0.75f), 0.75f, 5, recip64(0.75f)};
+    F.light = V3(0, 2.f * cb - 0.2f, 0);
+    if (build != RT_STATIC) {                                          // the animation app_raytracer.h:29-35
+        const float s = sin_(U.u_time), c = cos_(U.u_time);
+        F.spheres[1].o = F.spheres[1].o + V3(0, abs_(s), c + 1.f);
+        F.spheres[2].o.z = 0.f;
+        F.light.z = 1.5f;
+    }
     return F;
 }
 

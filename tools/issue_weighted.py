@@ -15,7 +15,7 @@ from sbxbench.pmc import CLASS_COUNTERS, ISSUE_CYCLES, issue_weighted  # noqa: E
 
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r06"
 KERNELS = [("clouds", "k_clouds<", "kern_clouds.hip", "_ZN3sbx8k_cloudsILb1ELb1ELi1ELb1ELi0E"), ("egg", "k_egg<", "kern_egg.hip", "_ZN3sbx5k_eggILb1ELi1"),
-           ("raytracer", "k_raytracer<", "kern_raytracer.hip", "_ZN3sbx11k_raytracerILi1ELb1"),
+           ("raytracer", "k_raytracer<", "kern_raytracer.hip", "_ZN3sbx11k_raytracerILi1ELb1ELi0E"),
            ("atmosphere", "k_atmosphere<", "kern_atmosphere.hip", "_ZN3sbx12k_atmosphereILb1ELi0"),
            ("planet", "k_planet<true, false>", "kern_planet.hip", "_ZN3sbx8k_planetILb1ELb0")]
 WANT = ["SQ_INSTS_VALU", "GRBM_GUI_ACTIVE"] + CLASS_COUNTERS

@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -47,7 +47,10 @@ typedef enum sbx_app {
     SBX_APP_PLANET = 0,
     SBX_APP_CLOUDS = 1,      /* src/app_clouds.h as shipped: both `#if 0` of illuminate_volume (:97, :118) off.  The builds with one of them
                                 on are SBX_APP_CLOUDS_HEIGHT and SBX_APP_CLOUDS_LUMINANCE */
-    SBX_APP_VINYL = 2,      /* C++-build semantics: 60 march steps (src/app_vinyl.h:411-416) */
+    SBX_APP_VINYL = 2,      /* C++-build semantics: 60 march steps (src/app_vinyl.h:411-416).  src/app_vinyl.h as shipped: the `#if 1` of
+                                setup_camera (:60) and of the shadow ray (:445) on, the `#if 0` of illuminate's ridge (:357) off.  The builds
+                                with one of the three the other way are SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES and
+                                SBX_APP_VINYL_NOSHADOW */
     SBX_APP_EGG = 3,         /* src/app_egg.h as shipped: BEZIER defined (:37) and the `#if 1` egg (:46-52).  The builds with one of the two
                                 switches the other way are SBX_APP_EGG_STRAIGHT and SBX_APP_EGG_OVAL */
     SBX_APP_RAYTRACER = 4,   /* src/app_raytracer.h as shipped: the `#if 1` of setup_scene (:29) and of the shadow ray (:107) on, the `#if 0` of
@@ -204,7 +207,28 @@ typedef enum sbx_app {
        (-0.75, 0.75, 0.75) (src/cornell_box.h:77-82) and the light at (0, 3.8, 0) (:85; z is 0, not 1.5).  u_time is not read: every
        value of it, inf and NaN included, gives the same frame; u_mouse turns the camera as shipped.  The shipped kernels over
        another frame block.  Everything else as SBX_APP_RAYTRACER_PHONG says; the lighting is Cook-Torrance as shipped. */
-    SBX_APP_RAYTRACER_STATIC = 25
+    SBX_APP_RAYTRACER_STATIC = 25 /* (the separating comma stands behind this comment) */,
+    /* APP_VINYL compiled with the `#if 1` of setup_camera at src/app_vinyl.h:60 turned to `#if 0` (:357 and :445 as shipped): the
+       close-up camera of :64-65, eye (-2, 1.5, 5.5) looking at (-1.5, 0, 0), over the label, the spindle and the headshell.  Scene,
+       march (the C++ build's 60 steps), shadow, shading and epilogue are SBX_APP_VINYL's: the shipped kernels over another frame block.
+       No aux block, u_mouse unused, alpha 1.  Every output form holds it (rows, host rows, points, sbx_main_image*, ranks, splits,
+       rgb, the exchanges with whole rows, SBX_FORMAT_RGBA8, sbx_multi_render).  sbx_set_variant 0-3 as for SBX_APP_VINYL
+       (include/sbx_test.h).  NaN pixels are data: sqrt of a negative dotLN * dot(V, N) in the groove shading (:339) gives some in
+       every build, more from this camera.  Not offered: the 180-step forms of the three builds, two switches at once, the SHADERTOY
+       branches, and the `#if 0` at :291 (hit.normal is still render's (0, 1, 0) there: the frame would be (0, sh, 0), a shadow mask).
+       Definition: tests/vinyl_builds_model.py, pinned against frames and points of the edited reference header
+       (tests/golden/vinyl_builds/). */
+    SBX_APP_VINYL_CLOSEUP = 26,
+    /* APP_VINYL compiled with the `#if 0` of illuminate at src/app_vinyl.h:357 turned to `#if 1` (:60 and :445 as shipped): the ridged
+       label.  After sdf_normal, hits of mat_label and mat_logo get :359-362 on the unrotated hit.origin:
+           r = length(hit.origin);  B = hit.origin / r;  s = saw(r * .9);  hit.normal = normalize(hit.normal + B * float(s > .975))
+       with saw(x) = x - floor(x).  Everything else, the output forms, the variants and what is not offered as SBX_APP_VINYL_CLOSEUP
+       says; the camera is the shipped one. */
+    SBX_APP_VINYL_RIDGES = 27,
+    /* APP_VINYL compiled with the `#if 1` of render at src/app_vinyl.h:445 turned to `#if 0` (:60 and :357 as shipped): the unshadowed
+       build.  :446-449 are gone: no 20-step sdf_shadow march from the hit, sh stays 1. and the colour is illuminate's.  Everything
+       else, the output forms, the variants and what is not offered as SBX_APP_VINYL_CLOSEUP says; the camera is the shipped one. */
+    SBX_APP_VINYL_NOSHADOW = 28
 } sbx_app;
 
 typedef enum sbx_status {

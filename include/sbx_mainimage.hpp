@@ -56,6 +56,12 @@
 #define SBX_SELECTED_APP SBX_APP_RAYTRACER_NOSHADOW
 #elif defined(APP_RAYTRACER_STATIC)   /* src/app_raytracer.h with the `#if 1` at :29 off (the Cornell box at rest); tested before APP_RAYTRACER */
 #define SBX_SELECTED_APP SBX_APP_RAYTRACER_STATIC
+#elif defined(APP_VINYL_CLOSEUP)  /* src/app_vinyl.h with the `#if 1` of setup_camera at :60 off (the close-up camera of :64-65; include/sbx.h); tested before APP_VINYL */
+#define SBX_SELECTED_APP SBX_APP_VINYL_CLOSEUP
+#elif defined(APP_VINYL_RIDGES)   /* src/app_vinyl.h with the `#if 0` of illuminate at :357 on (the ridge of label and logo); tested before APP_VINYL */
+#define SBX_SELECTED_APP SBX_APP_VINYL_RIDGES
+#elif defined(APP_VINYL_NOSHADOW) /* src/app_vinyl.h with the `#if 1` of render at :445 off (no sdf_shadow march); tested before APP_VINYL */
+#define SBX_SELECTED_APP SBX_APP_VINYL_NOSHADOW
 #elif defined(APP_PLANET)
 #define SBX_SELECTED_APP SBX_APP_PLANET
 #elif defined(APP_CLOUDS)
@@ -73,7 +79,7 @@
 #elif defined(APP_CLOUDS_BEST)   /* src/app_clouds_best.h, the stand-alone shader (no APP_* define in the reference) */
 #define SBX_SELECTED_APP SBX_APP_CLOUDS_BEST
 #else
-#error "define one of APP_PLANET APP_CLOUDS APP_VINYL APP_EGG APP_RAYTRACER APP_ATMOSPHERE APP_SDF_AO (or APP_CLOUDS_BEST APP_PLANET_ATMOSPHERE APP_2D APP_2D_TEX APP_FUNC APP_ATMOSPHERE_GROUND APP_SDF_AO_SHADOW APP_SDF_AO_NORMALS APP_EGG_STRAIGHT APP_EGG_OVAL APP_CLOUDS_HEIGHT APP_CLOUDS_LUMINANCE APP_RAYTRACER_PHONG APP_RAYTRACER_NOSHADOW APP_RAYTRACER_STATIC)"
+#error "define one of APP_PLANET APP_CLOUDS APP_VINYL APP_EGG APP_RAYTRACER APP_ATMOSPHERE APP_SDF_AO (or APP_CLOUDS_BEST APP_PLANET_ATMOSPHERE APP_2D APP_2D_TEX APP_FUNC APP_ATMOSPHERE_GROUND APP_SDF_AO_SHADOW APP_SDF_AO_NORMALS APP_EGG_STRAIGHT APP_EGG_OVAL APP_CLOUDS_HEIGHT APP_CLOUDS_LUMINANCE APP_RAYTRACER_PHONG APP_RAYTRACER_NOSHADOW APP_RAYTRACER_STATIC APP_VINYL_CLOSEUP APP_VINYL_RIDGES APP_VINYL_NOSHADOW)"
 #endif
 
 namespace sbx_host {

@@ -29,6 +29,7 @@ extern "C" {
  * SBX_APP_CLOUDS_HEIGHT / SBX_APP_CLOUDS_LUMINANCE: as for APP_CLOUDS, 1 = the per-lane kernel of the build.
  * APP_RAYTRACER and SBX_APP_RAYTRACER_PHONG / _NOSHADOW / _STATIC alike: 1 = the IEEE roots and normalisations with the six-plane loop of
  * raytrace_iteration; 2 = the witness's test edge; 3 = the IEEE roots and normalisations; each over the build's own code and frame.
+ * SBX_APP_VINYL_CLOSEUP / _RIDGES / _NOSHADOW: every value as for APP_VINYL, over the build's own code and frame.
  * All variants are specified to produce identical bits (tests/test_gpu_parity.py sweeps them against each other). */
 int sbx_set_variant(sbx_ctx* ctx, int variant);
 

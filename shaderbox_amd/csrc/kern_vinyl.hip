@@ -173,7 +173,10 @@ __device__ __forceinline__ v3 vinyl_base_color(int mat) {                       
 
 // One pixel up to its colour — render :406-457 — with the sdf's roots of witness `w`.  F: the kernel argument (camera, sun, steps:
 // SGPRs); Fs: the block sdf() reads (the LDS copy, or F itself).
-template <bool CULL, class W>
+// BUILD (sbx_frame.h VINYL_*): the header as shipped, or with one of two switches of its hit block the other way — VINYL_RIDGES, the
+// `#if 0` of illuminate's 6-tap branch on (the ridge of the label and the logo); VINYL_NOSHADOW, the `#if 1` around render's
+// sdf_shadow call off (sh stays 1.).  The close-up camera of setup_camera's `#else` is VINYL_DEFAULT over another frame block.
+template <bool CULL, int BUILD, class W>
 __device__ __forceinline__ void vinyl_pixel(const FrameVinyl& F, const FrameVinyl& Fs, v2 pc, W& w, v3& color) {
     const v3 ro = F.cam.eye, rd = primary_dir(F.cam, pc, w);
     color = V3(1, 1, 1);                                        // background :15-18
@@ -195,7 +198,7 @@ __device__ __forceinline__ void vinyl_pixel(const FrameVinyl& F, const FrameViny
         if (hit) {
             // sdf_shadow :379-404
             float sh = 1.f;
-            {
+            if constexpr (BUILD != VINYL_NOSHADOW) {
                 const v3 so = p + F.sun_dir * 0.05f;
                 float ts = 0.f;
                 for (int k = 0; k < 20; ++k) {
@@ -244,22 +247,36 @@ __device__ __forceinline__ void vinyl_pixel(const FrameVinyl& F, const FrameViny
                 lit = diffuse + specular;
             } else {
                 const float e = 0.001f;                              // sdf_normal :267-278
-                const v3 n = normalize(V3(      // (the IEEE form: flat surfaces give exact zero components, which the witness records)
+                v3 n = normalize(V3(      // (the IEEE form: flat surfaces give exact zero components, which the witness records)
                     vinyl_sdf<CULL>(Fs, p + V3(e, 0, 0), w).d - vinyl_sdf<CULL>(Fs, p - V3(e, 0, 0), w).d,
                     vinyl_sdf<CULL>(Fs, p + V3(0, e, 0), w).d - vinyl_sdf<CULL>(Fs, p - V3(0, e, 0), w).d,
                     vinyl_sdf<CULL>(Fs, p + V3(0, 0, e), w).d - vinyl_sdf<CULL>(Fs, p - V3(0, 0, e), w).d));
+                if constexpr (BUILD == VINYL_RIDGES) {               // the `#if 0` block after sdf_normal, on: the unrotated hit.origin
+                    if (mat == 3 || mat == 4) {                      // mat_label, mat_logo
+                        const float r = length(p);
+                        const v3 B = p / r;
+                        const float s = saw(r * .9f);
+                        n = normalize(n + B * ((s > .975f) ? 1.f : 0.f));
+                    }
+                }
                 const v3 diffuse = base * fmax_(0.f, dot(L, n));
                 const v3 H = w.normalize(V + L);
                 const v3 specular = pow_(fmax_(0.f, dot(H, n)), 50.f) * V3(1, 1, 1);
                 lit = diffuse + specular;
             }
-            color = lit * sh;
+            if constexpr (BUILD != VINYL_NOSHADOW) color = lit * sh;
+            else color = lit;                                        // lit * 1.f, bit for bit
         }
     }
 }
 
-template <bool CULL, int WIT>      // WIT: 0 IEEE roots, 1 witnessed roots, 2 the witness's test edge (sbx_set_variant 2), as k_egg
-__global__ void __launch_bounds__(WG_THREADS, VI_MIN_WAVES) k_vinyl(FrameVinyl F, RowMap M, float* __restrict__ out) {
+// The wave bound of an instantiation.  The shipped build keeps VI_MIN_WAVES for every form, its plain form (no culling: every member
+// live at once) with the 312 bytes of scratch that bound costs it; the plain forms of the other builds take 2 waves (173 VGPRs) and
+// spill nothing.
+constexpr int vinyl_min_waves(bool cull, int build) { return (!cull && build != VINYL_DEFAULT) ? 2 : VI_MIN_WAVES; }
+
+template <bool CULL, int WIT, int BUILD>      // WIT: 0 IEEE roots, 1 witnessed roots, 2 the witness's test edge (sbx_set_variant 2), as k_egg
+__global__ void __launch_bounds__(WG_THREADS, vinyl_min_waves(CULL, BUILD)) k_vinyl(FrameVinyl F, RowMap M, float* __restrict__ out) {
     const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();      // (the dispatch order's cost table, RowMap.cost)
 #if VI_LDS_FRAME
     // the frame block (~220 floats of rotations and primitive frames) in LDS: sbx_ldsframe.h
@@ -276,14 +293,14 @@ __global__ void __launch_bounds__(WG_THREADS, VI_MIN_WAVES) k_vinyl(FrameVinyl F
     if (WIT != 0) {
         Wit<true> w;
         if (WIT == 2) w.lo = 0x3F800000u;
-        vinyl_pixel<CULL>(F, VI_FS, pc, w, color);
+        vinyl_pixel<CULL, BUILD>(F, VI_FS, pc, w, color);
         if (__builtin_amdgcn_ballot_w64(w.bad) != 0ull) {
             Wit<false> w0;
-            vinyl_pixel<CULL>(F, VI_FS, pc, w0, color);
+            vinyl_pixel<CULL, BUILD>(F, VI_FS, pc, w0, color);
         }
     } else {
         Wit<false> w0;
-        vinyl_pixel<CULL>(F, VI_FS, pc, w0, color);
+        vinyl_pixel<CULL, BUILD>(F, VI_FS, pc, w0, color);
     }
     tile_cost_store(M, tl_t0);
     store_rgba(M, out, px.idx, to_srgb(color));
@@ -291,11 +308,20 @@ __global__ void __launch_bounds__(WG_THREADS, VI_MIN_WAVES) k_vinyl(FrameVinyl F
 
 dim3 vinyl_grid(const RowMap& M) { return grid_for(M); }
 
-void launch_vinyl(const FrameVinyl& F, const RowMap& M, float* out, hipStream_t s, int variant) {
-    if (variant == 1) hipLaunchKernelGGL((k_vinyl<false, 0>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else if (variant == 2) hipLaunchKernelGGL((k_vinyl<true, 2>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else if (variant == 3) hipLaunchKernelGGL((k_vinyl<true, 0>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else hipLaunchKernelGGL((k_vinyl<true, VI_WITNESS>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+template <int BUILD>
+static void launch_vinyl_build(const FrameVinyl& F, const RowMap& M, float* out, hipStream_t s, int variant) {
+    if (variant == 1) hipLaunchKernelGGL((k_vinyl<false, 0, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    else if (variant == 2) hipLaunchKernelGGL((k_vinyl<true, 2, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    else if (variant == 3) hipLaunchKernelGGL((k_vinyl<true, 0, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    else hipLaunchKernelGGL((k_vinyl<true, VI_WITNESS, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+}
+// build: VINYL_* (sbx_frame.h).  VINYL_CLOSEUP is a frame block (build_vinyl), not a kernel: the shipped instantiations run over it.
+void launch_vinyl(const FrameVinyl& F, const RowMap& M, float* out, hipStream_t s, int variant, int build) {
+    switch (build) {
+    case VINYL_RIDGES: launch_vinyl_build<VINYL_RIDGES>(F, M, out, s, variant); break;
+    case VINYL_NOSHADOW: launch_vinyl_build<VINYL_NOSHADOW>(F, M, out, s, variant); break;
+    default: launch_vinyl_build<VINYL_DEFAULT>(F, M, out, s, variant); break;
+    }
 }
 
 }  // namespace sbx

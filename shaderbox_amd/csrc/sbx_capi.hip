@@ -262,6 +262,11 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     case SBX_APP_PLANET_ATMOSPHERE: launch_planet(build_planet(*uni, true), M, rgba, s, cull_variant); break;
     case SBX_APP_VINYL: launch_vinyl(build_vinyl(*uni, 60), M, rgba, s, sdf_variant); break;
     case SBX_APP_VINYL_GPU: launch_vinyl(build_vinyl(*uni, 180), M, rgba, s, sdf_variant); break;
+    // the builds of app_vinyl.h's three switches (include/sbx.h), 60 steps each: one frame of its own for the shipped kernels, two kernel
+    // builds over the shipped frame.  The app is part of the key of a dispatch-order table and of sbx_main_image's cached frame
+    case SBX_APP_VINYL_CLOSEUP: launch_vinyl(build_vinyl(*uni, 60, VINYL_CLOSEUP), M, rgba, s, sdf_variant, VINYL_CLOSEUP); break;
+    case SBX_APP_VINYL_RIDGES: launch_vinyl(build_vinyl(*uni, 60), M, rgba, s, sdf_variant, VINYL_RIDGES); break;
+    case SBX_APP_VINYL_NOSHADOW: launch_vinyl(build_vinyl(*uni, 60), M, rgba, s, sdf_variant, VINYL_NOSHADOW); break;
     case SBX_APP_CLOUDS_BEST: launch_clouds_best(build_clouds_best(*uni), M, rgba, s); break;
     case SBX_APP_CLOUDS_UE4: launch_clouds_ue4(build_clouds_ue4(*uni, aux_clouds_ue4(aux)), M, rgba, s); break;
     case SBX_APP_2D: (void)launch_2d(build_2d(*uni), M, rgba, s, false); break;   // (three-channel maps were refused above)

@@ -191,7 +191,7 @@ FrameRaytracer build_raytracer(const sbx_uniforms& U, int build = RT_DEFAULT);  
 FrameAtmosphere build_atmosphere(const sbx_uniforms& U);
 FrameAtmosphere build_atmosphere_ground(const sbx_uniforms& U);
 FrameSdfAo build_sdf_ao(const sbx_uniforms& U, const sbx_aux_sdf_ao& A);
-FrameVinyl build_vinyl(const sbx_uniforms& U, int steps);
+FrameVinyl build_vinyl(const sbx_uniforms& U, int steps, int build = VINYL_DEFAULT);   // build: VINYL_* (sbx_frame.h); VINYL_CLOSEUP is the other camera
 FramePlanet build_planet(const sbx_uniforms& U, bool atm_sky = false);
 FrameCloudsBest build_clouds_best(const sbx_uniforms& U);
 FrameCloudsUe4 build_clouds_ue4(const sbx_uniforms& U, const sbx_aux_clouds_ue4& A);

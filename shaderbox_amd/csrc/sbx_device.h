@@ -165,7 +165,7 @@ void launch_raytracer(const FrameRaytracer& F, const RowMap& M, float* out, hipS
 void launch_atmosphere(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision = 0);
 void launch_atmosphere_ground(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision, int variant);   // kern_atmosphere.hip
 void launch_sdf_ao(const FrameSdfAo& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = 0);   // build: 1 / 2 = the shadow / normals builds (kern_sdf_ao.hip)
-void launch_vinyl(const FrameVinyl& F, const RowMap& M, float* out, hipStream_t s, int variant);
+void launch_vinyl(const FrameVinyl& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = VINYL_DEFAULT);   // build: VINYL_* (sbx_frame.h)
 void launch_clouds_best(const FrameCloudsBest& F, const RowMap& M, float* out, hipStream_t s);
 void launch_clouds_ue4(const FrameCloudsUe4& F, const RowMap& M, float* out, hipStream_t s);
 void launch_planet(const FramePlanet& F, const RowMap& M, float* out, hipStream_t s, int variant);

@@ -263,6 +263,11 @@ struct FrameVinyl {
     CylFrame collar;           // sd_cylinder(., 0, arm_fwd * .05, .)                         :173-176
     int steps;                 // march steps: 60 (the C++ build) or 180 (the GLSL / HLSL builds, SBX_APP_VINYL_GPU)   :411-416
 };
+// The builds of app_vinyl.h's compile-time switches (include/sbx.h): SBX_APP_VINYL, _VINYL_RIDGES (illuminate's `#if 0` at :357 on),
+// _VINYL_NOSHADOW (render's `#if 1` at :445 off), _VINYL_CLOSEUP (setup_camera's `#if 1` at :60 off).  RIDGES and NOSHADOW are kernel
+// template parameters (kern_vinyl.hip); CLOSEUP is another camera in the frame block for the shipped kernels (build_vinyl).
+// FrameVinyl is the same type in all four.
+enum { VINYL_DEFAULT = 0, VINYL_RIDGES = 1, VINYL_NOSHADOW = 2, VINYL_CLOSEUP = 3 };
 
 // ---- APP_2D / APP_2D_TEX (src/app_2d.h:70-111; not APP_* defines of the reference) -----------------
 // Everything mainImage decides from the uniforms alone: the phase of t = mod(u_time, 16) (:80-103; 4 = none of the four branches

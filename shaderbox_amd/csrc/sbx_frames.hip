@@ -223,11 +223,12 @@ static Capsule capsule(v3 a, v3 b) {                                   // sdf.h:
     c.rd = recip64(dot(c.ab, c.ab));
     return c;
 }
-FrameVinyl build_vinyl(const sbx_uniforms& U, int steps) {
+FrameVinyl build_vinyl(const sbx_uniforms& U, int steps, int build) {
     FrameVinyl F;
     F.steps = steps;                                                   // :411-416
     const float t = U.u_time;
-    F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(0, 5.75f, 6.75f), V3(0, -2.5f, 0));   // app_vinyl.h:56-64,459
+    if (build == VINYL_CLOSEUP) F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(-2, 1.5f, 5.5f), V3(-1.5f, 0, 0));   // setup_camera's `#else` :64-65
+    else F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(0, 5.75f, 6.75f), V3(0, -2.5f, 0));   // app_vinyl.h:56-64,459
     F.platter_rot = mul(rotate_around_y(t * 200.f), rotate_around_x(sin_(t) * .1f));          // :417,424-426
     F.sun_dir = normalize(V3(-1, 4, -3));
     F.ry30 = rotate_around_y(30.f);

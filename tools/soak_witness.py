@@ -15,7 +15,7 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 rng = np.random.default_rng(2024)
 R = shaderbox_amd.Renderer(0)
 total_bad = 0
-for app in (sys.argv[2].split(",") if len(sys.argv) > 2 else ("egg", "raytracer", "raytracer_phong", "raytracer_noshadow", "raytracer_static", "sdf_ao", "vinyl", "vinyl_gpu")):
+for app in (sys.argv[2].split(",") if len(sys.argv) > 2 else ("egg", "raytracer", "raytracer_phong", "raytracer_noshadow", "raytracer_static", "sdf_ao", "vinyl", "vinyl_gpu", "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow")):
     bad = 0
     pixels = 0
     for i in range(n):

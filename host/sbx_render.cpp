@@ -17,6 +17,8 @@
 //              its `#if 1` at :107 off (no shadow ray) / its `#if 1` at :29 off (the scene at rest: --time does not enter)
 //     app "vinyl_closeup" / "vinyl_ridges" / "vinyl_noshadow": src/app_vinyl.h with its `#if 1` at :60 off (the close-up camera) /
 //              its `#if 0` at :357 on (the ridge of label and logo) / its `#if 1` at :445 off (no shadow march); 60 march steps each
+//     app "planet_closeup" / "planet_cloudless" / "planet_unlit": src/app_planet.h with its `#if 0` at :51 on (the camera of :52-53) /
+//              without its `#define CLOUDS` at :63 (no cloud march, no cloud shadow) / without its `#define LIGHT` at :249 (unlit terrain)
 //     app "2d" / "2d_tex": src/app_2d.h (its alpha is not 1: the .f32 frames carry it; single GPU only), the USE_TEXTURE build
 //              reading hlsltoy's default 128x128 checkerboard at t0
 //     app "func": src/app_func.h, the tiled Worley fBm of its compiled 2D branch (grey, alpha 1; u_time and --mouse do not enter)
@@ -44,8 +46,8 @@ static int app_from_name(const std::string& s) {
     const char* names[] = {"planet", "clouds", "vinyl", "egg", "raytracer", "atmosphere", "sdf_ao", "clouds_best", "clouds_tex", "clouds_ue4",
                            "clouds_sky", "vinyl_gpu", "planet_atmosphere", "2d", "2d_tex", "func", "atmosphere_ground", "sdf_ao_shadow", "sdf_ao_normals",
                            "egg_straight", "egg_oval", "clouds_height", "clouds_luminance", "raytracer_phong", "raytracer_noshadow", "raytracer_static",
-                           "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow"};
-    const int n = 29;
+                           "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow", "planet_closeup", "planet_cloudless", "planet_unlit"};
+    const int n = 32;
     std::string low;
     for (char c : s) low += (char)tolower(c);
     for (int i = 0; i < n; ++i)

@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -44,7 +44,9 @@ int sbx_abi_version(void);
 /* App selector = the reference's APP_* project defines, in README.md:15-22 order, plus
  * APP_SDF_AO (src/uniform_buffer.h:56, util/hlsltoy/src/hlsltoy.cpp:488). */
 typedef enum sbx_app {
-    SBX_APP_PLANET = 0,
+    SBX_APP_PLANET = 0,      /* src/app_planet.h as shipped: CLOUDS (:63) and LIGHT (:249) defined, the `#if 0` of setup_camera (:51) off.  The
+                                 builds with one of the three the other way are SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS and
+                                 SBX_APP_PLANET_UNLIT */
     SBX_APP_CLOUDS = 1,      /* src/app_clouds.h as shipped: both `#if 0` of illuminate_volume (:97, :118) off.  The builds with one of them
                                 on are SBX_APP_CLOUDS_HEIGHT and SBX_APP_CLOUDS_LUMINANCE */
     SBX_APP_VINYL = 2,      /* C++-build semantics: 60 march steps (src/app_vinyl.h:411-416).  src/app_vinyl.h as shipped: the `#if 1` of
@@ -228,7 +230,29 @@ typedef enum sbx_app {
     /* APP_VINYL compiled with the `#if 1` of render at src/app_vinyl.h:445 turned to `#if 0` (:60 and :357 as shipped): the unshadowed
        build.  :446-449 are gone: no 20-step sdf_shadow march from the hit, sh stays 1. and the colour is illuminate's.  Everything
        else, the output forms, the variants and what is not offered as SBX_APP_VINYL_CLOSEUP says; the camera is the shipped one. */
-    SBX_APP_VINYL_NOSHADOW = 28
+    SBX_APP_VINYL_NOSHADOW = 28 /* (the separating comma stands behind this comment) */,
+    /* APP_PLANET compiled with the `#if 0` of setup_camera at src/app_planet.h:51 turned to `#if 1` (:63 and :249 as shipped): the
+       camera of :52-53, eye (0, 0, -1.93) looking at (-.1, .9, 2) — the limb seen from close by.  Terrain, clouds, lighting, shadow
+       and epilogue are SBX_APP_PLANET's.  No aux block, u_mouse unused, alpha 1.  Every output form holds it (rows, host rows,
+       points, sbx_main_image*, ranks, splits, rgb, spans with the atmosphere-shell test from this camera, the exchanges,
+       SBX_FORMAT_RGBA8, sbx_multi_render).  sbx_set_variant as for SBX_APP_PLANET: 1 = the plain kernel without its exact skips
+       (include/sbx_test.h).  NaN pixels are data: smoothstep(1 - .3 s, 1 - .2 s, N) with s = 0 is 0 / 0 where N == 1 (:270-273);
+       some tens per 64x36 frame in this build and the shipped one.  Not offered: two of the three switches at once, the flat
+       background() of :26, any of the three builds combined with SBX_APP_PLANET_ATMOSPHERE, the HLSL branch.
+       Definition: tests/planet_builds_model.py, pinned against frames and points of the edited reference header
+       (tests/golden/planet_builds/). */
+    SBX_APP_PLANET_CLOSEUP = 29,
+    /* APP_PLANET compiled without the `#define CLOUDS` of src/app_planet.h:63 (:51 and :249 as shipped): :344-347 and :355-361 are
+       gone — no 75-step clouds_march, no 5-step clouds_shadow_march.  `cloud` is the static object that nothing writes: cloud.radiance
+       and cloud.alpha are its zeros, shadow stays 1., and the two mix of :363 / :365 run on those zeros.  Everything else, the output
+       forms, the variant and what is not offered as SBX_APP_PLANET_CLOSEUP says; the camera is the shipped one. */
+    SBX_APP_PLANET_CLOUDLESS = 30,
+    /* APP_PLANET compiled without the `#define LIGHT` of src/app_planet.h:249 (:51 and :63 as shipped): N = w_normal.y (:254) and
+       ocean = water (:292); shoreline is not lit, sdf_terrain_normal with its six 7+7-octave detail maps and setup_lights are never
+       evaluated.  Clouds and their ground shadow as shipped.  No NaN pixel in any recorded frame (N == 1 needs a hit on the planet's
+       y axis).  Everything else, the output forms, the variant and what is not offered as SBX_APP_PLANET_CLOSEUP says; the camera is
+       the shipped one. */
+    SBX_APP_PLANET_UNLIT = 31
 } sbx_app;
 
 typedef enum sbx_status {

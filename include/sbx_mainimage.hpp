@@ -62,7 +62,13 @@
 #define SBX_SELECTED_APP SBX_APP_VINYL_RIDGES
 #elif defined(APP_VINYL_NOSHADOW) /* src/app_vinyl.h with the `#if 1` of render at :445 off (no sdf_shadow march); tested before APP_VINYL */
 #define SBX_SELECTED_APP SBX_APP_VINYL_NOSHADOW
-#elif defined(APP_PLANET)
+#elif defined(APP_PLANET_CLOSEUP)   /* src/app_planet.h with the `#if 0` of setup_camera at :51 on (the camera of :52-53; include/sbx.h); tested before APP_PLANET */
+#define SBX_SELECTED_APP SBX_APP_PLANET_CLOSEUP
+#elif defined(APP_PLANET_CLOUDLESS) /* src/app_planet.h without the `#define CLOUDS` of :63 (no cloud march, no cloud shadow); tested before APP_PLANET */
+#define SBX_SELECTED_APP SBX_APP_PLANET_CLOUDLESS
+#elif defined(APP_PLANET_UNLIT)     /* src/app_planet.h without the `#define LIGHT` of :249 (N = w_normal.y, ocean = water); tested before APP_PLANET */
+#define SBX_SELECTED_APP SBX_APP_PLANET_UNLIT
+#elif defined(APP_PLANET)           /* (APP_PLANET_ATMOSPHERE was tested first, above: it is not combined with the three builds) */
 #define SBX_SELECTED_APP SBX_APP_PLANET
 #elif defined(APP_CLOUDS)
 #define SBX_SELECTED_APP SBX_APP_CLOUDS
@@ -79,7 +85,7 @@
 #elif defined(APP_CLOUDS_BEST)   /* src/app_clouds_best.h, the stand-alone shader (no APP_* define in the reference) */
 #define SBX_SELECTED_APP SBX_APP_CLOUDS_BEST
 #else
-#error "define one of APP_PLANET APP_CLOUDS APP_VINYL APP_EGG APP_RAYTRACER APP_ATMOSPHERE APP_SDF_AO (or APP_CLOUDS_BEST APP_PLANET_ATMOSPHERE APP_2D APP_2D_TEX APP_FUNC APP_ATMOSPHERE_GROUND APP_SDF_AO_SHADOW APP_SDF_AO_NORMALS APP_EGG_STRAIGHT APP_EGG_OVAL APP_CLOUDS_HEIGHT APP_CLOUDS_LUMINANCE APP_RAYTRACER_PHONG APP_RAYTRACER_NOSHADOW APP_RAYTRACER_STATIC APP_VINYL_CLOSEUP APP_VINYL_RIDGES APP_VINYL_NOSHADOW)"
+#error "define one of APP_PLANET APP_CLOUDS APP_VINYL APP_EGG APP_RAYTRACER APP_ATMOSPHERE APP_SDF_AO (or APP_CLOUDS_BEST APP_PLANET_ATMOSPHERE APP_2D APP_2D_TEX APP_FUNC APP_ATMOSPHERE_GROUND APP_SDF_AO_SHADOW APP_SDF_AO_NORMALS APP_EGG_STRAIGHT APP_EGG_OVAL APP_CLOUDS_HEIGHT APP_CLOUDS_LUMINANCE APP_RAYTRACER_PHONG APP_RAYTRACER_NOSHADOW APP_RAYTRACER_STATIC APP_VINYL_CLOSEUP APP_VINYL_RIDGES APP_VINYL_NOSHADOW APP_PLANET_CLOSEUP APP_PLANET_CLOUDLESS APP_PLANET_UNLIT)"
 #endif
 
 namespace sbx_host {

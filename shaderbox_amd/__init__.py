@@ -17,7 +17,7 @@ from . import shard  # noqa: F401  (pure-python row-block arithmetic, no GPU nee
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsbx.so")
 
-APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW = range(29)
+APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW, APP_PLANET_CLOSEUP, APP_PLANET_CLOUDLESS, APP_PLANET_UNLIT = range(32)
 APPS = {"APP_PLANET": APP_PLANET, "APP_CLOUDS": APP_CLOUDS, "APP_VINYL": APP_VINYL, "APP_EGG": APP_EGG,
         "APP_RAYTRACER": APP_RAYTRACER, "APP_ATMOSPHERE": APP_ATMOSPHERE, "APP_SDF_AO": APP_SDF_AO,
         "APP_CLOUDS_BEST": APP_CLOUDS_BEST,    # src/app_clouds_best.h (stand-alone shader, not an APP_* define)
@@ -43,7 +43,10 @@ MORE_APPS = {"APP_EGG_STRAIGHT": APP_EGG_STRAIGHT,  # APP_EGG without `#define B
              "APP_RAYTRACER_STATIC": APP_RAYTRACER_STATIC,      # APP_RAYTRACER with the `#if 1` at src/app_raytracer.h:29 off: the Cornell box at rest
              "APP_VINYL_CLOSEUP": APP_VINYL_CLOSEUP,    # APP_VINYL with the `#if 1` at src/app_vinyl.h:60 off: the close-up camera of :64-65
              "APP_VINYL_RIDGES": APP_VINYL_RIDGES,      # APP_VINYL with the `#if 0` at src/app_vinyl.h:357 on: the ridge of label and logo
-             "APP_VINYL_NOSHADOW": APP_VINYL_NOSHADOW}  # APP_VINYL with the `#if 1` at src/app_vinyl.h:445 off: no sdf_shadow march
+             "APP_VINYL_NOSHADOW": APP_VINYL_NOSHADOW,  # APP_VINYL with the `#if 1` at src/app_vinyl.h:445 off: no sdf_shadow march
+             "APP_PLANET_CLOSEUP": APP_PLANET_CLOSEUP,      # APP_PLANET with the `#if 0` at src/app_planet.h:51 on: the camera of :52-53
+             "APP_PLANET_CLOUDLESS": APP_PLANET_CLOUDLESS,  # APP_PLANET without the `#define CLOUDS` of src/app_planet.h:63: no cloud march, no cloud shadow
+             "APP_PLANET_UNLIT": APP_PLANET_UNLIT}          # APP_PLANET without the `#define LIGHT` of src/app_planet.h:249: N = w_normal.y, ocean = water
 ALL_APPS = {**APPS, **MORE_APPS}
 
 SBX_OK, SBX_ERR_ARG, SBX_ERR_UNSUPPORTED, SBX_ERR_HIP, SBX_ERR_NO_DEVICE, SBX_ERR_FAULT = 0, -1, -2, -3, -4, -5

@@ -46,7 +46,10 @@ __device__ __forceinline__ Vol make_vol(v3 o) { return Vol{o, o, 0.f, 1.f, 0.f, 
 #define PL_DIVK(a, dlit) ((SKIP && PL_DIV3) ? div3_((a), (dlit), 1.0f / (dlit)) : div_by((a), 1.0 / (double)(dlit)))
 #ifndef PL_MED3
 #define PL_MED3 1           // the clamp of those smoothsteps as one v_med3_f32: their arguments (fBm sums of hashes, heights of finite positions)
-#endif                      // are never NaN on the tame frames of the SKIP kernels (finite u_time, u_res checked by the C API, fixed camera)
+#endif                      // are never NaN on the tame frames of the SKIP kernels (finite u_time, u_res checked by the C API, and a camera
+                            // whose eye and look_at are finite constants — the shipped one and PLANET_CLOSEUP's alike: fwd, up and right are
+                            // orthogonal with |fwd| = 1, so fwd + up y + right x is finite and no shorter than 1, rd and every march position
+                            // are finite, and so are their heights, with either form of pl_length)
 #define SMOOTHSTEP_K(e0, e1, x) ((SKIP && PL_DIV3 && PL_MED3) ? smoothstep_d3_med3((e0), (e1) - (e0), 1.0f / ((e1) - (e0)), (x)) \
                                  : (SKIP && PL_DIV3) ? smoothstep_d3((e0), (e1) - (e0), 1.0f / ((e1) - (e0)), (x)) \
                                                    : smoothstep_rd((e0), 1.0 / (double)((e1) - (e0)), (x)))
@@ -164,17 +167,24 @@ __device__ __forceinline__ float coop_fbm(WaveCache& S, v3 q, float lacunarity, 
 // o == 0 exactly (hit_o = 0, t = 0), every other lane has rd.x, rd.y either exactly 0 (the centre ray, which stops on the terrain
 // at |o| >= 1) or >= 1e-6 in magnitude (pixel centres), and o.x = (t0 + t) * rd.x has no cancellation: |o|^2 >= 1e-12 >> 2^-96 = 1.3e-29.
 // The SKIP kernels run only for tame frames (finite, bounded u_time); a NaN resolution gives NaN, which sqrt_n_ passes through.
+// This rests on the SHIPPED camera: the rays of PLANET_CLOSEUP's (eye (0, 0, -1.93), look_at (-.1, .9, 2)) are not aligned with the
+// planet's axis, so "rd.x, rd.y are 0 or >= 1e-6" does not hold for them.  A camera-free bound exists for most samples — a terrain
+// sample has |o| - 1 >= df.x and the march advances by .4567 df.x, so |o| > 1 at every sample and between any two of them, and a
+// cloud sample lies on the same ray no deeper than max_cld — but not for all: a march that uses up its 120 steps without a hit and
+// without passing max_ray_dist leaves max_cld at 1.6, and the cloud samples beyond its last step are bounded by nothing but the
+// ray's closest approach to the centre.  No frame is known to hold such a ray; no argument here excludes one.  So the CLOSEUP
+// instantiation takes the IEEE root for every length (RS = false) and keeps every other short form, none of which names the eye.
 #ifndef PL_SQRT_RS
 #define PL_SQRT_RS 1
 #endif
 #ifndef PL_SQRT_N
 #define PL_SQRT_N 1
 #endif
-template <bool SKIP>
+template <bool RS>
 __device__ __forceinline__ float pl_length(v3 v) {
     // (PL_SQRT_RS: sqrt_rs_, five instructions, exact for finite x >= 2^-102 — the lanes whose |o|^2 is exactly 0 are the ones that
     //  missed the atmosphere: they never commit a result, and what they compute here, a NaN, decides nothing)
-    return (SKIP && PL_SQRT_RS) ? sqrt_rs_(dot(v, v)) : (SKIP && PL_SQRT_N) ? sqrt_n_(dot(v, v)) : length(v);
+    return (RS && PL_SQRT_RS) ? sqrt_rs_(dot(v, v)) : (RS && PL_SQRT_N) ? sqrt_n_(dot(v, v)) : length(v);
 }
 #define PL_EXP(x) ((SKIP && PL_EXP4K) ? exp_reg4k_((x), kExp2Tab4096) : exp_(x))
 // clouds_map :102-119 + integrate_volume :79-100; `on` = lanes that commit
@@ -224,7 +234,7 @@ __device__ __forceinline__ void clouds_map(WaveCache& S, Vol& c, float t_step, b
 }
 
 // sdf_terrain_map / sdf_terrain_map_detail :175-199
-template <int OCT, bool SKIP>
+template <int OCT, bool SKIP, bool RS = SKIP>
 __device__ __forceinline__ v2 terrain_map(WaveCache& S, v3 pos, bool on, int lane) {
     const float h0 = coop_fbm<OCT, 0, SKIP>(S, pos * 2.0987f, 2.0244f, .454f, .454f, on, lane);
     const float n0 = SMOOTHSTEP_K(.35f, 1.f, h0);
@@ -242,7 +252,7 @@ __device__ __forceinline__ v2 terrain_map(WaveCache& S, v3 pos, bool on, int lan
         n1 = SMOOTHSTEP_K(.6f, 1.f, h1);
     }
     const float n = n0 + n1;
-    return V2(pl_length<SKIP>(pos) - 1.f - n * PL_MAX_HEIGHT, PL_DIVK(n, PL_MAX_HEIGHT));
+    return V2(pl_length<RS>(pos) - 1.f - n * PL_MAX_HEIGHT, PL_DIVK(n, PL_MAX_HEIGHT));
 }
 
 
@@ -328,7 +338,7 @@ __device__ __forceinline__ void pl_fbm_pair(WaveCache& S, v3& qa, float& qb_ax, 
     }
 }
 // sdf_terrain_map_detail(pos + d).x - sdf_terrain_map_detail(pos - d).x with d = e along axis AX   (:188-199, :201-212)
-template <int AX, bool SKIP>
+template <int AX, bool SKIP, bool RS = SKIP>
 __device__ __forceinline__ float terrain_detail_difference(WaveCache& S, v3 pos, float e, bool on, int lane) {
     // the two points: pos.c + e and pos.c - e on axis AX; pos.c + 0 = pos.c - 0 = pos.c on the others (no zero coordinates here)
     const float ca = (AX == 0 ? pos.x : AX == 1 ? pos.y : pos.z) + e, cb = (AX == 0 ? pos.x : AX == 1 ? pos.y : pos.z) - e;
@@ -353,8 +363,8 @@ __device__ __forceinline__ float terrain_detail_difference(WaveCache& S, v3 pos,
         n1a = SMOOTHSTEP_K(.6f, 1.f, h1a);
         n1b = SMOOTHSTEP_K(.6f, 1.f, h1b);
     }
-    const float va = pl_length<SKIP>(pa) - 1.f - (n0a + n1a) * PL_MAX_HEIGHT;
-    const float vb = pl_length<SKIP>(pb) - 1.f - (n0b + n1b) * PL_MAX_HEIGHT;
+    const float va = pl_length<RS>(pa) - 1.f - (n0a + n1a) * PL_MAX_HEIGHT;
+    const float vb = pl_length<RS>(pb) - 1.f - (n0b + n1b) * PL_MAX_HEIGHT;
     return va - vb;
 }
 
@@ -416,8 +426,26 @@ __device__ __forceinline__ v3 planet_background(v3 dir) {                       
 #ifndef PL_ATM_FIN
 #define PL_ATM_FIN 1
 #endif
-template <bool SKIP, bool ATM = false>
-__global__ void __launch_bounds__(WG_THREADS, PL_MIN_WAVES) k_planet(FramePlanet F, RowMap M, float* __restrict__ out) {
+// BUILD (sbx_frame.h PLANET_*): the header as shipped, or with one of its three switches the other way.
+//   PLANET_CLOUDLESS, `#define CLOUDS` (:63) gone: no clouds_march (:344-347), no clouds_shadow_march (:355-361).  `cloud` is the
+//     reference's static object that nothing writes: radiance and alpha are its +0, shadow is the literal 1, and the two mix of
+//     :363 / :365 run on those zeros as written — x * (1 - 0) + 0 * 0, of which the compiler folds what IEEE lets it fold (x * 1 and
+//     0 * 0; the + 0 stays, it turns a -0 into +0 before the abs).  Nothing is parked in slots 1-2.
+//   PLANET_UNLIT, `#define LIGHT` (:249) gone: N = w_normal.y (:254), ocean = water (:292), shoreline unlit; sdf_terrain_normal —
+//     the paired and unpaired detail maps — and setup_lights are compiled out, F.L is not read and no park area exists.
+//   PLANET_CLOSEUP, setup_camera's `#if 0` (:51) on: eye (0, 0, -1.93), look_at (-.1, .9, 2), written by build_planet.  The code is
+//     the shipped build's but for length() of a march position, which is the IEEE root in the SKIP kernel too (RS below; the note at
+//     PL_SQRT_RS says why).
+// None of the three is built with ATM.
+#ifndef PL_MIN_WAVES_UNLIT
+#define PL_MIN_WAVES_UNLIT PL_MIN_WAVES
+#endif
+constexpr int planet_min_waves(int build) { return build == PLANET_UNLIT ? PL_MIN_WAVES_UNLIT : PL_MIN_WAVES; }
+template <bool SKIP, bool ATM = false, int BUILD = PLANET_DEFAULT>
+__global__ void __launch_bounds__(WG_THREADS, planet_min_waves(BUILD)) k_planet(FramePlanet F, RowMap M, float* __restrict__ out) {
+    static_assert(!ATM || BUILD == PLANET_DEFAULT, "the builds of app_planet.h's switches are not combined with the atmosphere sky");
+    constexpr bool CLD = BUILD != PLANET_CLOUDLESS, LIT = BUILD != PLANET_UNLIT;
+    constexpr bool RS = SKIP && BUILD != PLANET_CLOSEUP;         // the short roots of pl_length: proved for the shipped eye only
     const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();      // (the dispatch order's cost table, RowMap.cost)
     __shared__ double etab[ATM ? 32 : 1];
     if (ATM) {
@@ -475,7 +503,7 @@ __global__ void __launch_bounds__(WG_THREADS, PL_MIN_WAVES) k_planet(FramePlanet
             if (!wave_any(tm)) break;
             const v3 o = hit_o + t * rd;
             const v3 p = mul(F.rot, o - V3(0, 0, 0));
-            const v2 d = terrain_map<3, SKIP>(S, p, tm, lane);
+            const v2 d = terrain_map<3, SKIP, RS>(S, p, tm, lane);
             if (tm) {
 #if PL_PARK && PL_PARK_MARCH && PL_TLAST
                 {
@@ -493,7 +521,7 @@ __global__ void __launch_bounds__(WG_THREADS, PL_MIN_WAVES) k_planet(FramePlanet
         }
         // clouds_march :121-141 on construct_volume(hit.origin)
         Vol cloud = make_vol(hit_o);
-        {
+        if constexpr (CLD) {
             const float t_step = PL_MAX_RAY_DIST / 75.f;
             float tc = 0.f;
             bool cm = hit_atm;
@@ -511,7 +539,7 @@ __global__ void __launch_bounds__(WG_THREADS, PL_MIN_WAVES) k_planet(FramePlanet
                     if (SKIP && !wave_any(cm && !(d2 > 1.5885f || d2 < 1.166f))) { tc += t_step; continue; }
                 }
                 const v3 cp = mul(F.rot_cloud, o - V3(0, 0, 0));
-                const float ch = PL_DIVK(pl_length<SKIP>(cp) - 1.f, PL_MAX_HEIGHT);
+                const float ch = PL_DIVK(pl_length<RS>(cp) - 1.f, PL_MAX_HEIGHT);
                 if (cm) { cloud.pos = cp; cloud.height = ch; }
                 tc += t_step;
                 clouds_map<SKIP>(S, cloud, t_step, cm, lane);
@@ -531,49 +559,55 @@ __global__ void __launch_bounds__(WG_THREADS, PL_MIN_WAVES) k_planet(FramePlanet
             // illuminate :238-298
             float h = df.y;
             const float e = 0.001f;
-            float g[3];                                            // sdf_terrain_normal :201-212
+            float g[3] = {0.f, 0.f, 0.f};                          // sdf_terrain_normal :201-212
+            if constexpr (LIT) {
 #if PL_PARK
             // 6 x (7 + 7)-octave terrain_map: the second register peak.  What it does not need — the hit point, its height
             // term, the ray, the cloud integrator (already in slots 1-2) — waits in LDS, and the three differences land there.
             float* const pk = &park[threadIdx.x >> 6][lane];
             pk[3 * 64] = pos.x; pk[4 * 64] = pos.y; pk[5 * 64] = pos.z; pk[6 * 64] = h;
-            pk[1 * 64] = cloud.radiance; pk[2 * 64] = cloud.alpha;
+            if constexpr (CLD) { pk[1 * 64] = cloud.radiance; pk[2 * 64] = cloud.alpha; }
             asm volatile("" ::: "memory");
             // (a zero coordinate of the hit point: pos.c + 0 and pos.c - 0 then differ in the sign of their zero — the unpaired path)
             const bool pairs = SKIP && PL_PAIRS && !wave_any(hitl && (pk[3 * 64] == 0.f || pk[4 * 64] == 0.f || pk[5 * 64] == 0.f));
             if (pairs) {
-                pk[7 * 64] = terrain_detail_difference<0, SKIP>(S, V3(pk[3 * 64], pk[4 * 64], pk[5 * 64]), e, hitl, lane);
+                pk[7 * 64] = terrain_detail_difference<0, SKIP, RS>(S, V3(pk[3 * 64], pk[4 * 64], pk[5 * 64]), e, hitl, lane);
                 asm volatile("" ::: "memory");
-                pk[8 * 64] = terrain_detail_difference<1, SKIP>(S, V3(pk[3 * 64], pk[4 * 64], pk[5 * 64]), e, hitl, lane);
+                pk[8 * 64] = terrain_detail_difference<1, SKIP, RS>(S, V3(pk[3 * 64], pk[4 * 64], pk[5 * 64]), e, hitl, lane);
                 asm volatile("" ::: "memory");
-                pk[9 * 64] = terrain_detail_difference<2, SKIP>(S, V3(pk[3 * 64], pk[4 * 64], pk[5 * 64]), e, hitl, lane);
+                pk[9 * 64] = terrain_detail_difference<2, SKIP, RS>(S, V3(pk[3 * 64], pk[4 * 64], pk[5 * 64]), e, hitl, lane);
                 asm volatile("" ::: "memory");
             } else {
 #pragma unroll 1
             for (int ax = 0; ax < 3; ++ax) {                       // one code copy for the three central differences
                 const v3 d = V3(ax == 0 ? e : 0.f, ax == 1 ? e : 0.f, ax == 2 ? e : 0.f);
-                const float va = terrain_map<7, SKIP>(S, V3(pk[3 * 64], pk[4 * 64], pk[5 * 64]) + d, hitl, lane).x;
+                const float va = terrain_map<7, SKIP, RS>(S, V3(pk[3 * 64], pk[4 * 64], pk[5 * 64]) + d, hitl, lane).x;
                 asm volatile("" ::: "memory");
-                const float vb = terrain_map<7, SKIP>(S, V3(pk[3 * 64], pk[4 * 64], pk[5 * 64]) - d, hitl, lane).x;
+                const float vb = terrain_map<7, SKIP, RS>(S, V3(pk[3 * 64], pk[4 * 64], pk[5 * 64]) - d, hitl, lane).x;
                 pk[(7 + ax) * 64] = va - vb;
                 asm volatile("" ::: "memory");
             }
             }
             pos = V3(pk[3 * 64], pk[4 * 64], pk[5 * 64]);
             h = pk[6 * 64];
-            cloud.radiance = pk[1 * 64]; cloud.alpha = pk[2 * 64];
+            if constexpr (CLD) { cloud.radiance = pk[1 * 64]; cloud.alpha = pk[2 * 64]; }
             g[0] = pk[7 * 64]; g[1] = pk[8 * 64]; g[2] = pk[9 * 64];
 #else
 #pragma unroll 1
             for (int ax = 0; ax < 3; ++ax) {                       // one code copy for the three central differences
                 const v3 d = V3(ax == 0 ? e : 0.f, ax == 1 ? e : 0.f, ax == 2 ? e : 0.f);
-                const float v = terrain_map<7, SKIP>(S, pos + d, hitl, lane).x - terrain_map<7, SKIP>(S, pos - d, hitl, lane).x;
+                const float v = terrain_map<7, SKIP, RS>(S, pos + d, hitl, lane).x - terrain_map<7, SKIP, RS>(S, pos - d, hitl, lane).x;
                 if (ax == 0) g[0] = v; else if (ax == 1) g[1] = v; else g[2] = v;
             }
 #endif
+            }
             const v3 w_normal = normalize(pos);
-            const v3 normal = normalize(V3(g[0], g[1], g[2]));
-            const float N = dot(normal, w_normal);
+            v3 normal = w_normal;                                  // (not read in the unlit build)
+            float N = w_normal.y;                                  // `#else` of LIGHT :254
+            if constexpr (LIT) {
+                normal = normalize(V3(g[0], g[1], g[2]));
+                N = dot(normal, w_normal);
+            }
             const v3 c_water = V3(.015f, .110f, .455f), c_grass = V3(.086f, .132f, .018f),
                      c_beach = V3(.153f, .172f, .121f), c_rock = V3(.080f, .050f, .030f),
                      c_snow = V3(.600f, .600f, .600f);
@@ -583,12 +617,17 @@ __global__ void __launch_bounds__(WG_THREADS, PL_MIN_WAVES) k_planet(FramePlanet
             const v3 grass = mix3(c_grass, rock, smoothstep_(l_grass, l_rock, h));
             v3 shoreline = mix3(c_beach, grass, smoothstep_(l_shore, l_grass, h));
             const v3 water = mix3(c_water / 2.f, c_water, smoothstep_(0.f, l_water, h));
-            shoreline = shoreline * setup_lights(F.L, normal);
-            const v3 ocean = setup_lights(F.L, w_normal) * water;
+            v3 ocean = water;                                      // `#else` of LIGHT :292
+            if constexpr (LIT) {
+                shoreline = shoreline * setup_lights(F.L, normal);
+                ocean = setup_lights(F.L, w_normal) * water;
+            }
             const v3 c_terr = mix3(ocean, shoreline, smoothstep_(l_water, l_shore, h));
 
             const float c_cld = cloud.radiance, alpha = cloud.alpha;
             // cloud shadow on the ground :355-360, clouds_shadow_march :143-160
+            float shadow = 1.f;                                    // :353
+            if constexpr (CLD) {
             const v3 lp = mul(F.rot_t, pos);
             Vol sh = make_vol(lp);
             const v3 local_up = normalize(lp);
@@ -598,12 +637,13 @@ __global__ void __launch_bounds__(WG_THREADS, PL_MIN_WAVES) k_planet(FramePlanet
                 for (int i = 0; i < 5; ++i) {
                     const v3 o = sh.origin + ts * local_up;
                     sh.pos = mul(F.rot_cloud, o - V3(0, 0, 0));
-                    sh.height = PL_DIVK(pl_length<SKIP>(sh.pos) - 1.f, PL_MAX_HEIGHT);
+                    sh.height = PL_DIVK(pl_length<RS>(sh.pos) - 1.f, PL_MAX_HEIGHT);
                     ts += t_step;
                     clouds_map<SKIP>(S, sh, t_step, hitl, lane);
                 }
             }
-            const float shadow = mix_(.7f, 1.f, step_(sh.alpha, 0.33f));
+            shadow = mix_(.7f, 1.f, step_(sh.alpha, 0.33f));
+            }
             c_hit = abs3(mix3(c_terr * shadow, V3s(c_cld), alpha));
         }
         cloud_sky = !hitl;
@@ -632,7 +672,23 @@ __global__ void __launch_bounds__(WG_THREADS, PL_MIN_WAVES) k_planet(FramePlanet
 
 dim3 planet_grid(const RowMap& M) { return grid_for<PL_TW>(M); }
 
-void launch_planet(const FramePlanet& F, const RowMap& M, float* out, hipStream_t s, int variant) {
+// build: PLANET_* (sbx_frame.h).  The plain kernel (variant 1: no skips, the IEEE forms) of PLANET_CLOSEUP is the shipped build's over
+// the frame block build_planet writes for it: with SKIP false no instantiation depends on RS.
+void launch_planet(const FramePlanet& F, const RowMap& M, float* out, hipStream_t s, int variant, int build) {
+    switch (F.atm_sky ? PLANET_DEFAULT : build) {
+    case PLANET_CLOUDLESS:
+        if (variant == 1) hipLaunchKernelGGL((k_planet<false, false, PLANET_CLOUDLESS>), grid_for<PL_TW>(M), dim3(WG_THREADS), 0, s, F, M, out);
+        else hipLaunchKernelGGL((k_planet<true, false, PLANET_CLOUDLESS>), grid_for<PL_TW>(M), dim3(WG_THREADS), 0, s, F, M, out);
+        return;
+    case PLANET_UNLIT:
+        if (variant == 1) hipLaunchKernelGGL((k_planet<false, false, PLANET_UNLIT>), grid_for<PL_TW>(M), dim3(WG_THREADS), 0, s, F, M, out);
+        else hipLaunchKernelGGL((k_planet<true, false, PLANET_UNLIT>), grid_for<PL_TW>(M), dim3(WG_THREADS), 0, s, F, M, out);
+        return;
+    case PLANET_CLOSEUP:
+        if (variant != 1) { hipLaunchKernelGGL((k_planet<true, false, PLANET_CLOSEUP>), grid_for<PL_TW>(M), dim3(WG_THREADS), 0, s, F, M, out); return; }
+        break;
+    default: break;
+    }
     if (F.atm_sky) {
         if (variant == 1) hipLaunchKernelGGL((k_planet<false, true>), grid_for<PL_TW>(M), dim3(WG_THREADS), 0, s, F, M, out);
         else hipLaunchKernelGGL((k_planet<true, true>), grid_for<PL_TW>(M), dim3(WG_THREADS), 0, s, F, M, out);

@@ -8,7 +8,7 @@
 
 namespace sbx {
 
-constexpr int SBX_APP_COUNT = SBX_APP_VINYL_NOSHADOW + 1;
+constexpr int SBX_APP_COUNT = SBX_APP_PLANET_UNLIT + 1;
 // sbx_debug_tile_order (include/sbx_test.h) answers for the apps up to SBX_APP_FUNC and says SBX_ERR_ARG for the later ones, as it
 // always has: none of those has an order grid below, so there is no table to show
 constexpr int TILE_ORDER_DEBUG_APPS = SBX_APP_FUNC + 1;
@@ -64,6 +64,9 @@ constexpr AppTraits kApps[] = {
     /* SBX_APP_VINYL_CLOSEUP     */ {AUX_NONE, false, false, vinyl_grid, TILE_SCENE_FREE},
     /* SBX_APP_VINYL_RIDGES      */ {AUX_NONE, false, false, vinyl_grid, TILE_SCENE_FREE},
     /* SBX_APP_VINYL_NOSHADOW    */ {AUX_NONE, false, false, vinyl_grid, TILE_SCENE_FREE},
+    /* SBX_APP_PLANET_CLOSEUP    */ {AUX_NONE, false, false, nullptr, TILE_SCENE_FREE},
+    /* SBX_APP_PLANET_CLOUDLESS  */ {AUX_NONE, false, false, nullptr, TILE_SCENE_FREE},
+    /* SBX_APP_PLANET_UNLIT      */ {AUX_NONE, false, false, nullptr, TILE_SCENE_FREE},
 };
 static_assert(sizeof(kApps) / sizeof(kApps[0]) == SBX_APP_COUNT, "every value of enum sbx_app needs its row in kApps");
 

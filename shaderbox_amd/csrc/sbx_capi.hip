@@ -260,6 +260,10 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     case SBX_APP_SDF_AO_NORMALS: launch_sdf_ao(build_sdf_ao(*uni, aux_sdf_ao(aux)), M, rgba, s, sdf_variant, 2); break;
     case SBX_APP_PLANET: launch_planet(build_planet(*uni), M, rgba, s, cull_variant); break;
     case SBX_APP_PLANET_ATMOSPHERE: launch_planet(build_planet(*uni, true), M, rgba, s, cull_variant); break;
+    // the builds of app_planet.h's three switches (include/sbx.h): kernel builds over the shipped frame, CLOSEUP over a frame of its own
+    case SBX_APP_PLANET_CLOSEUP: launch_planet(build_planet(*uni, false, PLANET_CLOSEUP), M, rgba, s, cull_variant, PLANET_CLOSEUP); break;
+    case SBX_APP_PLANET_CLOUDLESS: launch_planet(build_planet(*uni), M, rgba, s, cull_variant, PLANET_CLOUDLESS); break;
+    case SBX_APP_PLANET_UNLIT: launch_planet(build_planet(*uni), M, rgba, s, cull_variant, PLANET_UNLIT); break;
     case SBX_APP_VINYL: launch_vinyl(build_vinyl(*uni, 60), M, rgba, s, sdf_variant); break;
     case SBX_APP_VINYL_GPU: launch_vinyl(build_vinyl(*uni, 180), M, rgba, s, sdf_variant); break;
     // the builds of app_vinyl.h's three switches (include/sbx.h), 60 steps each: one frame of its own for the shipped kernels, two kernel

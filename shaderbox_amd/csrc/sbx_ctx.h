@@ -192,7 +192,7 @@ FrameAtmosphere build_atmosphere(const sbx_uniforms& U);
 FrameAtmosphere build_atmosphere_ground(const sbx_uniforms& U);
 FrameSdfAo build_sdf_ao(const sbx_uniforms& U, const sbx_aux_sdf_ao& A);
 FrameVinyl build_vinyl(const sbx_uniforms& U, int steps, int build = VINYL_DEFAULT);   // build: VINYL_* (sbx_frame.h); VINYL_CLOSEUP is the other camera
-FramePlanet build_planet(const sbx_uniforms& U, bool atm_sky = false);
+FramePlanet build_planet(const sbx_uniforms& U, bool atm_sky = false, int build = PLANET_DEFAULT);   // build: PLANET_* (sbx_frame.h); PLANET_CLOSEUP is the other camera
 FrameCloudsBest build_clouds_best(const sbx_uniforms& U);
 FrameCloudsUe4 build_clouds_ue4(const sbx_uniforms& U, const sbx_aux_clouds_ue4& A);
 Frame2d build_2d(const sbx_uniforms& U);

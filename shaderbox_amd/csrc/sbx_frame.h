@@ -217,6 +217,11 @@ struct FramePlanet {
     int atm_sky;                // 1: SBX_APP_PLANET_ATMOSPHERE — background() is APP_ATMOSPHERE's get_incident_light (kern_planet.hip)
     v3 atm_sun;                 // its sun: (0,1,0) * rotate_around_x(-|sin(t/2)|*90)   app_atmosphere.h:177-181
 };
+// The builds of app_planet.h's compile-time switches (include/sbx.h): SBX_APP_PLANET, _PLANET_CLOUDLESS (`#define CLOUDS` at :63 gone),
+// _PLANET_UNLIT (`#define LIGHT` at :249 gone), _PLANET_CLOSEUP (setup_camera's `#if 0` at :51 on).  All three are kernel template
+// parameters (kern_planet.hip); CLOSEUP is also another camera in the frame block (build_planet).  FramePlanet is the same type in
+// all four; none of the three is combined with atm_sky.
+enum { PLANET_DEFAULT = 0, PLANET_CLOUDLESS = 1, PLANET_UNLIT = 2, PLANET_CLOSEUP = 3 };
 
 // ---- "clouds_best" (src/app_clouds_best.h, the stand-alone cloud shader) ------
 // The march runs along projection = dir / dir.y, whose y component is exactly 1, from origin.y = eye.y + 100:

@@ -260,11 +260,12 @@ FrameVinyl build_vinyl(const sbx_uniforms& U, int steps, int build) {
     return F;
 }
 
-FramePlanet build_planet(const sbx_uniforms& U, bool atm_sky) {
+FramePlanet build_planet(const sbx_uniforms& U, bool atm_sky, int build) {
     FramePlanet F;
     F.atm_sky = atm_sky ? 1 : 0;
     F.atm_sun = build_atmosphere(U).sun_dir;
-    F.cam = make_camera(U.u_res[0], U.u_res[1], tan_(radians_(30.f)), V3(0, 0, -2.5f), V3(0, 0, 2));   // app_planet.h:47-58,368
+    if (build == PLANET_CLOSEUP) F.cam = make_camera(U.u_res[0], U.u_res[1], tan_(radians_(30.f)), V3(.0f, 0, -1.93f), V3(-.1f, .9f, 2));   // setup_camera's `#if` branch :52-53
+    else F.cam = make_camera(U.u_res[0], U.u_res[1], tan_(radians_(30.f)), V3(0, 0, -2.5f), V3(0, 0, 2));   // app_planet.h:47-58,368
     const m3 rot_y = rotate_around_y(27.f);                            // :307
     F.rot = mul(rotate_around_x(U.u_time * -12.f), rot_y);             // :308
     F.rot_cloud = mul(rotate_around_x(U.u_time * 8.f), rot_y);         // :309

@@ -82,7 +82,8 @@ static SpanProbe span_probe(int app, const sbx_uniforms& U, const void* aux) {
     case SBX_APP_CLOUDS: case SBX_APP_CLOUDS_TEX: case SBX_APP_CLOUDS_SKY: case SBX_APP_CLOUDS_HEIGHT: case SBX_APP_CLOUDS_LUMINANCE: P.cam = build_clouds(U, aux_clouds(aux)).cam; break;
     case SBX_APP_ATMOSPHERE: P.cam = build_atmosphere(U).cam; break;
     case SBX_APP_ATMOSPHERE_GROUND: P.cam = build_atmosphere_ground(U).cam; break;
-    case SBX_APP_PLANET: P.cam = build_planet(U).cam; break;
+    case SBX_APP_PLANET: case SBX_APP_PLANET_CLOUDLESS: case SBX_APP_PLANET_UNLIT: P.cam = build_planet(U).cam; break;
+    case SBX_APP_PLANET_CLOSEUP: P.cam = build_planet(U, false, PLANET_CLOSEUP).cam; break;
     default: P.model = false; P.cam = Camera{}; break;
     }
     return P;
@@ -131,7 +132,7 @@ static bool span_heavy(const SpanProbe& P, float fx, float fy) {
         const float t = 1.f / denom;
         return t < 0.f || t > 1e8f;
     }
-    case SBX_APP_PLANET: {                                         // intersect_sphere(eye, {0, 1 + max_height}), kern_planet.hip
+    case SBX_APP_PLANET: case SBX_APP_PLANET_CLOSEUP: case SBX_APP_PLANET_CLOUDLESS: case SBX_APP_PLANET_UNLIT: {   // intersect_sphere(eye, {0, 1 + max_height}), kern_planet.hip
         const v3 ro = P.cam.eye, rd = primary_dir(P.cam, pc);
         const float radius = 1.f + .4f;                            // planet.radius + max_height   app_planet.h:16-20,311-312
         const v3 rc = V3(0, 0, 0) - ro;

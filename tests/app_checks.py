@@ -1,7 +1,7 @@
 """What the GPU test files share, written once: the fixtures (`renderer`, `renderer8`, `volumes`, `variant_restored`), the comparisons
 (`compare`, `assert_same`, `same_tensor`, `bits_differ`), the app lists, and the checks every app's file makes of the layers above
 its kernel: rows, host rows, ranks and splits, the loopback exchanges, the 8-bit format, sbx_multi_render, the sbx_mainimage.hpp
-drop-in and host/sbx_render.  A test file states its app's name, sizes, times, aux block and expected frame and calls in here;
+drop-in, the app that header selects and host/sbx_render.  A test file states its app's name, sizes, times, aux block and expected frame and calls in here;
 what belongs to one app stays in its file.  A plain module (pytest does not collect it): a test module imports the fixtures it
 names.
 
@@ -257,6 +257,14 @@ int main(int argc, char** argv) {
     return 0;
 }
 '''
+
+
+def check_mainimage_selects(defines, want):
+    """include/sbx_mainimage.hpp, preprocessed with -D<define> for each of `defines`, renders the app `want` (its SBX_APP_* name)"""
+    r = subprocess.run(["g++", "-std=c++17", "-E", "-P", "-x", "c++"] + ["-D" + d for d in defines] +
+                       ["-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "include", "sbx_mainimage.hpp")],
+                       check=True, capture_output=True, text=True)
+    assert "sbx_main_image(ctx, %s, &u" % want in r.stdout
 
 
 def build_dropin(tmp_path, defines, exe_name):

@@ -9,11 +9,13 @@ march parameter t is the same for every pixel, so a step is one batch of density
 
 The definition is pinned from two sides (tests/test_clouds_builds_cpu.py): "default" equals the oracle in every bit, "height" and
 "luminance" equal the frames and points that the edited reference header itself rendered (tests/golden/clouds_builds/,
-tools/make_golden_clouds_builds.py)."""
+tools/make_golden_builds.py)."""
+import functools
+
 import numpy as np
 
 from oracle import aux_sets
-from tests.model_common import F, ONE, TWO, ZERO, _f, dot, fmax, fmin, get_primary_ray, oracle, point_cam, same_bits  # noqa: F401
+from tests.model_common import F, ONE, TWO, ZERO, _f, builds_fixture, dot, fmax, fmin, get_primary_ray, oracle, point_cam, same_bits  # noqa: F401
 
 BUILDS = ("default", "height", "luminance")
 APP_OF = {"default": "clouds", "height": "clouds_height", "luminance": "clouds_luminance"}
@@ -167,37 +169,4 @@ def frame(build, width, height, u_time, aux=None, mouse=(0.0, 0.0)):
     fx = (np.arange(width, dtype=F) + F(.5))[None, :]
     fy = (np.arange(height, dtype=F) + F(.5))[:, None]
     return main_image(build, width, height, u_time, fx, fy, aux, mouse)
-
-
-_FIXTURES = {}
-
-
-def fixture(build):
-    """tests/golden/clouds_builds/clouds_<build>.npz decoded (tools/make_golden_clouds_builds.py says how it is encoded): a dict with
-    `frames` = [(name, u_time, aux set name or None, float32 [H, W, 4])], `points` [n, 2], `points_uniforms`, `points_out` and
-    `points_shipped` [n, 4], `aux_counts` {set: pixels that differ from the shipped build's}.  A frame is stored as the XOR of its rgb
-    bits with the shipped build's frame, which is the oracle's SBX_APP_CLOUDS frame."""
-    import os
-    if build not in _FIXTURES:
-        z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clouds_builds", "clouds_%s.npz" % build))
-
-        def decode(xor, shipped):
-            out = np.ones(xor.shape[:-1] + (4,), dtype=F)
-            out[..., :3] = (xor ^ np.ascontiguousarray(shipped[..., :3]).view(np.uint32)).view(F)
-            return out
-
-        frames = []
-        for u in z["uniforms"]:
-            w, h, t = int(u[0]), int(u[1]), float(u[4])
-            frames.append(("t%g" % t, t, None, decode(z["x_t%g" % t], oracle().render(1, w, h, t))))
-        u = z["aux_uniforms"]
-        for s in z["aux_sets"]:
-            s = str(s)
-            shipped = oracle().render(1, int(u[0]), int(u[1]), float(u[4]), aux=aux_sets.block("clouds", aux_sets.load()["clouds"][s]))
-            frames.append(("aux_" + s, float(u[4]), s, decode(z["x_aux_" + s], shipped)))
-        shipped = np.ones((len(z["points"]), 4), dtype=F)
-        shipped[:, :3] = z["points_shipped"]
-        _FIXTURES[build] = dict(frames=frames, points=z["points"], points_uniforms=z["points_uniforms"], points_shipped=shipped,
-                                points_out=decode(z["points_xor"], shipped),
-                                aux_counts=dict(zip(map(str, z["aux_sets"]), map(int, z["aux_counts"]))))
-    return _FIXTURES[build]
+fixture = functools.partial(builds_fixture, "clouds")     # tests/golden/clouds_builds/ decoded: tests/model_common.py

@@ -6,7 +6,7 @@ The CPU oracle renders the shipped build only and is not to grow, so the GPU tes
 module.  It is pinned from two sides (tests/test_egg_builds_cpu.py): build "default" equals Oracle.render("egg") in every bit —
 which covers everything the three builds share: camera, turntable, pedals, IK, feet, wheel, ground, the unions, trace, shadow
 march, colours, depth, bars, epilogue — and builds "straight" / "oval" equal frames and points that the reference header itself
-rendered with the one line edited (tests/golden/egg_builds/, tools/make_golden_egg_builds.py).
+rendered with the one line edited (tests/golden/egg_builds/, tools/make_golden_builds.py).
 
 mainImage -> render -> render_scene -> sdf / shadowmarch, vectorised over pixels, in binary32 step by step in the oracle's
 operation order (oracle/ovec.h: dot = (x x + y y) + z z, normalize = three divisions by sqrtf, M * v = (c0 v.x + c1 v.y) + c2 v.z
@@ -16,11 +16,12 @@ alone (src/app_egg.h:40, 68-96, 120, 125) is evaluated once per frame (`scene`),
 oracle's hook `egg.sdf`.  The vector algebra and the camera are tests/model_common.py's.
 """
 import concurrent.futures
+import functools
 
 import numpy as np
 
-from tests.model_common import (F, ONE, TWO, ZERO, _const, _f, _sincos, cross, dot, fmax, fmin, get_primary_ray, normalize, op_add2,
-                                 oracle, point_cam, same_bits)
+from tests.model_common import (F, ONE, TWO, ZERO, _const, _f, _sincos, builds_fixture, cross, dot, fmax, fmin, get_primary_ray,
+                                 normalize, op_add2, oracle, point_cam, same_bits)
 
 HALF = F(.5)
 BUILDS = ("default", "straight", "oval")
@@ -322,3 +323,6 @@ def frame(build, width, height, u_time, rows=None, threads=8):
         return np.concatenate([one(b) for b in bands], axis=0)
     with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as ex:
         return np.concatenate(list(ex.map(one, bands)), axis=0)
+
+
+fixture = functools.partial(builds_fixture, "egg")     # tests/golden/egg_builds/ decoded: tests/model_common.py

@@ -1,8 +1,13 @@
 """The binary32 toolkit the numpy models of tests/*_model.py share: the oracle's vector algebra (oracle/ovec.h), its min / max and
 GLSL's mod, the camera of main.h and util.h, and the bit comparison every test of a model or a kernel rests on
 (tests/test_model_common.py).  Every value is an explicit np.float32 so that nothing widens to float64; a model imports what it
-uses from here and states only its own scene."""
+uses from here and states only its own scene.  builds_fixture() is the one decoder of the build families' fixtures
+(tests/build_families.py, tools/make_golden_builds.py)."""
+import os
+
 import numpy as np
+
+from tests.build_families import FAMILIES, fixture_path, frame_keys
 
 F = np.float32
 ZERO, ONE, TWO = F(0), F(1), F(2)
@@ -90,3 +95,80 @@ def get_primary_ray(pcx, pcy, eye, look_at):        # oracle/ref_lib.h:56-65 (ut
         up = cross(fwd, right)
         v = tuple((fwd[k] + up[k] * pcy) + right[k] * pcx for k in range(3))
         return normalize(v)
+
+
+# ---- the fixtures of the build families ------------------------------------------------------------------------------------------
+
+def _bits(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=F)[..., :3]).view(np.uint32)
+
+
+def _rgba(bits):
+    out = np.ones(bits.shape[:-1] + (4,), dtype=F)
+    out[..., :3] = np.ascontiguousarray(bits).view(F)
+    return out
+
+
+_FIXTURES = {}
+
+
+def builds_fixture(family, build):
+    """tests/golden/<family>_builds/<file of the build> decoded, as tests/build_families.py describes it and tools/make_golden_builds.py
+    wrote it: a dict with
+        uniforms [n, 5] (u_res, u_mouse, u_time per frame) and frames, a list with one float32 [H, W, 4] per frame or, by the family's
+        `frames_as`, one (w, h, u_time, u_mouse, frame) or one (name, u_time, aux set or None, frame), clouds' aux-set frames behind
+        the others, with aux_counts {set: pixels that differ from the shipped build's};
+        big_uniforms, big_frames: the larger set, empty for a build without one;
+        points [n, 2], points_uniforms [5], points_out and points_shipped [n, 4], where the family records points.
+    Where the file holds the XOR of every frame's rgb bits with the shipped build's frame, that frame is the oracle's under the same
+    uniforms, and alpha is 1.  The file's keys and uniforms are asserted to be the table's."""
+    if (family, build) in _FIXTURES:
+        return _FIXTURES[(family, build)]
+    fam = FAMILIES[family]
+    z = np.load(fixture_path(os.path.dirname(os.path.abspath(__file__)), family, build))
+    name, app = fam["shipped"]
+    xor, keys = fam["storage"] == "xor", {"uniforms"}
+
+    def decode(key, shipped):
+        keys.add(key)
+        if not xor:
+            return z[key]
+        shipped = shipped()
+        assert (shipped[..., 3] == 1).all()
+        return _rgba(z[key] ^ _bits(shipped))
+
+    def frame_set(size, uniforms, pattern, name_of_uniforms):
+        u = np.array([[size[0], size[1], m[0], m[1], t] for t, m in uniforms], dtype=F)
+        assert np.array_equal(z[name_of_uniforms], u), (family, build, name_of_uniforms)
+        return u, [decode(k, lambda: oracle().render(app, size[0], size[1], t, mouse=m)) for k, (t, m) in zip(frame_keys(pattern, uniforms), uniforms)]
+
+    fx = {}
+    fx["uniforms"], frames = frame_set(fam["size"], fam["uniforms"], fam["keys"], "uniforms")
+    if fam["frames_as"] == "whtm":
+        frames = [(int(u[0]), int(u[1]), float(u[4]), (float(u[2]), float(u[3])), f) for u, f in zip(fx["uniforms"], frames)]
+    elif fam["frames_as"] == "named":
+        frames = [(k[2:], float(u[4]), None, f) for k, u, f in zip(frame_keys(fam["keys"], fam["uniforms"]), fx["uniforms"], frames)]
+    if "aux_sets" in fam:
+        from oracle import aux_sets
+        (w, h), t = fam["size"], fam["aux_time"]
+        assert tuple(map(str, z["aux_sets"])) == fam["aux_sets"] and tuple(z["aux_uniforms"]) == (w, h, 0, 0, t)
+        for s in fam["aux_sets"]:
+            block = aux_sets.block(name, aux_sets.load()[name][s])
+            frames.append(("aux_" + s, float(z["aux_uniforms"][4]), s, decode("x_aux_" + s, lambda: oracle().render(app, w, h, t, aux=block))))
+        fx["aux_counts"] = dict(zip(fam["aux_sets"], map(int, z["aux_counts"])))
+        keys.update(("aux_sets", "aux_uniforms", "aux_counts"))
+    fx["frames"], fx["big_uniforms"], fx["big_frames"] = frames, np.zeros((0, 5), dtype=F), []
+    if "min_big" in fam["builds"][build]:
+        fx["big_uniforms"], fx["big_frames"] = frame_set(fam["big"]["size"], fam["big"]["uniforms"], fam["big_keys"], "big_uniforms")
+        keys.add("big_uniforms")
+    if fam["points"]:
+        p = fam["points"]
+        assert z["points"].shape == (p["count"], 2) and tuple(z["points_uniforms"]) == p["size"] + (0, 0, p["time"])
+        shipped = np.ones((p["count"], 4), dtype=F)
+        shipped[:, :z["points_shipped"].shape[1]] = z["points_shipped"]
+        fx.update(points=z["points"], points_uniforms=z["points_uniforms"], points_shipped=shipped,
+                  points_out=decode("points_xor" if xor else "points_out", lambda: shipped))
+        keys.update(("points", "points_uniforms", "points_shipped"))
+    assert set(z.files) == keys, (family, build, sorted(set(z.files) ^ keys))
+    _FIXTURES[(family, build)] = fx
+    return fx

@@ -8,7 +8,7 @@ The CPU oracle renders the shipped build only and is not to grow, so the GPU tes
 module.  It is pinned from two sides (tests/test_planet_builds_cpu.py): build "default" equals Oracle.render("planet") in every bit —
 which covers everything the four builds share: camera arithmetic, the atmosphere test, both terrain maps, the terrain march, the cloud
 integrator and its two marches, illuminate, background, epilogue — and the other three equal frames and points that the reference
-header itself rendered with the one line edited (tests/golden/planet_builds/, tools/make_golden_planet_builds.py), NaN pixels
+header itself rendered with the one line edited (tests/golden/planet_builds/, tools/make_golden_builds.py), NaN pixels
 included.
 
 mainImage -> render -> sdf_terrain_map / clouds_march / illuminate / clouds_shadow_march, vectorised over pixels, in binary32 step
@@ -17,13 +17,12 @@ by step in the oracle's operation order (oracle/ovec.h: dot = (x x + y y) + z z,
 e1 - e0), every value an explicit np.float32.  sin, cos, tan, exp, pow and noise_iq are the oracle's (Oracle.math, Oracle.noise).
 The vector algebra and the camera are tests/model_common.py's; matrices are tests/vinyl_builds_model.py's and tests/egg_builds_model.py's.
 """
-import os
+import functools
 
 import numpy as np
 
-from oracle.oracle import APP_PLANET
 from tests.egg_builds_model import clamp, mat_vec, mix
-from tests.model_common import F, ONE, RADIANS, TWO, ZERO, _f, dot, fmax, get_primary_ray, normalize, oracle, point_cam
+from tests.model_common import F, ONE, RADIANS, TWO, ZERO, _f, builds_fixture, dot, fmax, get_primary_ray, normalize, oracle, point_cam
 from tests.vinyl_builds_model import mat_mat, rotate_around_x, rotate_around_y
 
 BUILDS = ("default", "closeup", "cloudless", "unlit")
@@ -36,7 +35,6 @@ MAX_RAY_DIST = MAX_HEIGHT * F(4.)                   # :21
 TERR_STEPS, TERR_EPS = 120, F(.005)                 # :165-166
 ABSORB = F(30.034)                                  # :68
 HIT_T = F(F(1e8) + F(1e1))                          # no_hit.t def.h:78-83
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _math(fn, x, y=None):
@@ -324,44 +322,4 @@ def frame(build, width, height, u_time, mouse=(0.0, 0.0), parts=None):
     return main_image(build, width, height, u_time, fx, fy, parts)
 
 
-# ---- the fixtures --------------------------------------------------------------------------------------------------------
-
-def _bits(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=F)[..., :3]).view(np.uint32)
-
-
-def _rgba(bits):
-    out = np.ones(bits.shape[:-1] + (4,), dtype=F)
-    out[..., :3] = np.ascontiguousarray(bits).view(F)
-    return out
-
-
-_FIXTURES = {}
-
-
-def fixture(build):
-    """tests/golden/planet_builds/planet_<build>.npz decoded (tools/make_golden_planet_builds.py): a dict with
-    uniforms [4, 5] and frames (a list of [36, 64, 4]), big_uniforms / big_frames ([72, 128, 4]; cloudless and unlit only, else
-    empty), points [2048, 2], points_uniforms [5], points_out and points_shipped [2048, 4].  The files hold the XOR of every frame's
-    rgb bits with the shipped build's frame, which is the oracle's APP_PLANET frame under the same uniforms."""
-    if build not in _FIXTURES:
-        z = np.load(os.path.join(GOLDEN, "planet_builds", "planet_%s.npz" % build))
-        o = oracle()
-
-        def decode(uniforms, prefix):
-            frames = []
-            for i, u in enumerate(uniforms):
-                shipped = o.render(APP_PLANET, int(u[0]), int(u[1]), float(u[4]), mouse=(float(u[2]), float(u[3])))
-                assert (shipped[..., 3] == 1).all()
-                frames.append(_rgba(z["%s%d" % (prefix, i)] ^ _bits(shipped)))
-            return frames
-
-        fx = {"uniforms": z["uniforms"], "frames": decode(z["uniforms"], "x_frame"),
-              "big_uniforms": z["big_uniforms"] if "big_uniforms" in z else np.zeros((0, 5), dtype=F)}
-        fx["big_frames"] = decode(fx["big_uniforms"], "x_big")
-        shipped_pts = np.ones((len(z["points"]), 4), dtype=F)
-        shipped_pts[:, :3] = z["points_shipped"]
-        fx.update(points=z["points"], points_uniforms=z["points_uniforms"], points_shipped=shipped_pts,
-                  points_out=_rgba(z["points_xor"] ^ _bits(shipped_pts)))
-        _FIXTURES[build] = fx
-    return _FIXTURES[build]
+fixture = functools.partial(builds_fixture, "planet")     # tests/golden/planet_builds/ decoded: tests/model_common.py

@@ -11,12 +11,12 @@ Vectorised over the pixels: every pixel runs both bounces' arithmetic and masks 
 
 The definition is pinned from two sides (tests/test_raytracer_builds_cpu.py): "default" equals the oracle in every bit, the other
 three equal the frames and points that the edited reference header itself rendered (tests/golden/raytracer_builds/,
-tools/make_golden_raytracer_builds.py)."""
-import os
+tools/make_golden_builds.py)."""
+import functools
 
 import numpy as np
 
-from tests.model_common import F, ONE, RADIANS, TWO, ZERO, _f, _sincos, dot, fmax, fmin, get_primary_ray, oracle, point_cam, same_bits  # noqa: F401
+from tests.model_common import F, ONE, RADIANS, TWO, ZERO, _f, _sincos, builds_fixture, dot, fmax, fmin, get_primary_ray, oracle, point_cam, same_bits  # noqa: F401
 
 BUILDS = ("default", "phong", "noshadow", "static")
 APP_OF = {"default": "raytracer", "phong": "raytracer_phong", "noshadow": "raytracer_noshadow", "static": "raytracer_static"}
@@ -219,31 +219,4 @@ def frame(build, width, height, u_time, mouse=(0.0, 0.0)):
     fx = (np.arange(width, dtype=F) + F(.5))[None, :]
     fy = (np.arange(height, dtype=F) + F(.5))[:, None]
     return main_image(build, width, height, u_time, fx, fy, mouse)
-
-
-_FIXTURES = {}
-
-
-def fixture(build):
-    """tests/golden/raytracer_builds/raytracer_<build>.npz decoded (tools/make_golden_raytracer_builds.py says how it is encoded): a
-    dict with `frames` = [(width, height, u_time, u_mouse, float32 [H, W, 4])], `points` [n, 2], `points_uniforms` (u_res, u_mouse,
-    u_time), `points_out` and `points_shipped` [n, 4].  A frame is stored as the XOR of its rgb bits with the shipped build's frame
-    under the same uniforms, which is the oracle's SBX_APP_RAYTRACER frame; alpha is 1."""
-    if build not in _FIXTURES:
-        from oracle.oracle import APP_RAYTRACER
-        z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "raytracer_builds", "raytracer_%s.npz" % build))
-
-        def decode(xor, shipped):
-            out = np.ones(xor.shape[:-1] + (4,), dtype=F)
-            out[..., :3] = (xor ^ np.ascontiguousarray(shipped[..., :3]).view(np.uint32)).view(F)
-            return out
-
-        frames = []
-        for i, u in enumerate(z["uniforms"]):
-            w, h, mouse, t = int(u[0]), int(u[1]), (float(u[2]), float(u[3])), float(u[4])
-            frames.append((w, h, t, mouse, decode(z["x_frame%d" % i], oracle().render(APP_RAYTRACER, w, h, t, mouse=mouse))))
-        shipped = np.ones((len(z["points"]), 4), dtype=F)
-        shipped[:, :3] = z["points_shipped"]
-        _FIXTURES[build] = dict(frames=frames, points=z["points"], points_uniforms=z["points_uniforms"], points_shipped=shipped,
-                                points_out=decode(z["points_xor"], shipped))
-    return _FIXTURES[build]
+fixture = functools.partial(builds_fixture, "raytracer")     # tests/golden/raytracer_builds/ decoded: tests/model_common.py

@@ -6,7 +6,7 @@ The CPU oracle renders the shipped build only and is not to grow, so the GPU tes
 module.  It is pinned from two sides (tests/test_sdf_ao_builds_cpu.py): build "default" equals Oracle.render("sdf_ao") in every
 bit — which covers everything the three builds share: camera, march, sdf, normal, AO, lights, materials, fog, epilogue — and
 builds "shadow" / "normals" equal frames that the reference header itself rendered with the one `#if 0` turned to `#if 1`
-(tests/golden/sdf_ao_builds/, tools/make_golden_sdf_ao_builds.py).
+(tests/golden/sdf_ao_builds/, tools/make_golden_builds.py).
 
 mainImage -> render -> render_impl -> sdf_shadow / illuminate, vectorised over pixels, in binary32 step by step in the oracle's
 operation order (oracle/ovec.h: dot = (x x + y y) + z z, normalize = three divisions by sqrtf; oracle/sbx_math_ref.h: min / max as
@@ -15,12 +15,13 @@ and pow are the oracle's (Oracle.math).  sdf is restated here (a known-answer ho
 pinned against the hook `sdf_ao.sdf`; the vector algebra and the camera are tests/model_common.py's.
 """
 import concurrent.futures
+import functools
 import struct
 
 import numpy as np
 
-from tests.model_common import (F, ONE, TWO, ZERO, _const, _f, _sincos, dot, fmax, fmin, get_primary_ray, normalize, op_add2, oracle,
-                                 point_cam, same_bits)
+from tests.model_common import (F, ONE, TWO, ZERO, _const, _f, _sincos, builds_fixture, dot, fmax, fmin, get_primary_ray,
+                                 normalize, op_add2, oracle, point_cam, same_bits)
 
 BUILDS = ("default", "shadow", "normals")
 FOG_DENSITY, FOG_FALLOFF = F(.1), F(.5)             # src/uniform_buffer.h:56-60 (oracle/ref_lib.h sdf_ao_aux_t)
@@ -296,3 +297,6 @@ def frame(build, width, height, u_time, aux=None, rows=None, threads=8):
         return np.concatenate([one(b) for b in bands], axis=0)
     with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as ex:
         return np.concatenate(list(ex.map(one, bands)), axis=0)
+
+
+fixture = functools.partial(builds_fixture, "sdf_ao")     # tests/golden/sdf_ao_builds/ decoded: tests/model_common.py

@@ -1,7 +1,7 @@
 """SBX_APP_CLOUDS_HEIGHT and SBX_APP_CLOUDS_LUMINANCE without a GPU: the numpy definition of the three builds of
 src/app_clouds.h's illuminate_volume (tests/clouds_builds_model.py) pinned from two sides — its shipped build against the CPU oracle,
 its other two against what the edited reference header itself rendered (tests/golden/clouds_builds/) — the conditions those
-fixtures were recorded under, and the host-only layers: names, the span table."""
+fixtures were recorded under (tests/build_families.py), and the host-only span table.  The name tables: tests/test_build_families_cpu.py."""
 import os
 
 import numpy as np
@@ -9,10 +9,15 @@ import pytest
 
 from oracle import aux_sets
 from tests import clouds_builds_model as M
+from tests.build_families import FAMILIES, fixture_path, frame_keys
 from tests.model_common import same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("height", "luminance")
+FAMILY = FAMILIES["clouds"]
+CAPS = FAMILY["builds"]                             # per build: the caps that keep a fixture from saying nothing (tests/build_families.py)
+NEW = tuple(CAPS)
+W, H = FAMILY["size"]
+POINTS = FAMILY["points"]
 
 
 def assert_bits(got, want, what):
@@ -30,57 +35,48 @@ def test_shipped_build_of_the_model_is_the_oracle(oracle, t, aux_set):
 @pytest.mark.parametrize("build", NEW)
 def test_model_equals_the_reference_headers_frames(build):
     fx = M.fixture(build)
-    assert [f[0] for f in fx["frames"]] == ["t0", "t1.5", "t37.25", "aux_steer", "aux_yz", "aux_degenerate", "aux_zero"]
+    assert [f[0] for f in fx["frames"]] == [k[2:] for k in frame_keys(FAMILY["keys"], FAMILY["uniforms"])] + ["aux_" + s for s in FAMILY["aux_sets"]]
     for name, t, aux_set, want in fx["frames"]:
         over = None if aux_set is None else aux_sets.load()["clouds"][aux_set]
-        assert want.shape == (54, 96, 4)
-        assert_bits(M.frame(build, 96, 54, t, aux=over), want, (build, name))
+        assert want.shape == (H, W, 4)
+        assert_bits(M.frame(build, W, H, t, aux=over), want, (build, name))
 
 
 @pytest.mark.parametrize("build", NEW)
 def test_model_equals_the_reference_headers_points(build):
     fx = M.fixture(build)
     pts, u = fx["points"], fx["points_uniforms"]
-    assert pts.shape == (2048, 2) and (int(u[0]), int(u[1]), float(u[4])) == (1920, 1080, 1.5)
-    assert_bits(M.main_image(build, 1920, 1080, 1.5, pts[:, 0], pts[:, 1]), fx["points_out"], (build, "points"))
-    assert_bits(M.main_image("default", 1920, 1080, 1.5, pts[:, 0], pts[:, 1]), fx["points_shipped"], (build, "shipped points"))
+    assert pts.shape == (POINTS["count"], 2) and (int(u[0]), int(u[1]), float(u[4])) == POINTS["size"] + (POINTS["time"],)
+    assert_bits(M.main_image(build, int(u[0]), int(u[1]), float(u[4]), pts[:, 0], pts[:, 1]), fx["points_out"], (build, "points"))
+    assert_bits(M.main_image("default", int(u[0]), int(u[1]), float(u[4]), pts[:, 0], pts[:, 1]), fx["points_shipped"], (build, "shipped points"))
 
 
 @pytest.mark.parametrize("build", NEW)
 def test_fixture_conditions(build, oracle):
-    """what tools/make_golden_clouds_builds.py asserted when it recorded the files, of the committed files"""
-    path = os.path.join(ROOT, "tests", "golden", "clouds_builds", "clouds_%s.npz" % build)
+    """what tools/make_golden_builds.py asserted when it recorded the files, of the committed files"""
+    path = fixture_path(os.path.join(ROOT, "tests"), "clouds", build)
     largest = max(os.path.getsize(os.path.join(ROOT, "tests", "golden", f)) for f in os.listdir(os.path.join(ROOT, "tests", "golden"))
                   if f.endswith(".npz"))
-    assert os.path.getsize(path) <= largest
+    assert FAMILY["max_bytes"] == "largest" and os.path.getsize(path) <= largest
     fx = M.fixture(build)
     for name, t, aux_set, frame in fx["frames"]:
         assert not np.isnan(frame).any() and (frame[..., 3] == 1).all()
         over = None if aux_set is None else aux_sets.load()["clouds"][aux_set]
-        shipped = oracle.render(1, 96, 54, t, aux=None if over is None else aux_sets.block("clouds", over))
+        shipped = oracle.render(1, W, H, t, aux=None if over is None else aux_sets.block("clouds", over))
         n = int((~same_bits(frame, shipped).all(axis=-1)).sum())
         if aux_set is None:
-            assert n >= 1500, (build, name, n)
+            assert n >= CAPS[build]["min_pixels"], (build, name, n)
         else:
             assert n == fx["aux_counts"][aux_set] and ((n == 0) if aux_set == "zero" else (n > 0)), (build, name, n)
     pts = fx["points"]
-    assert (pts[:, 1] >= 648).all() and (pts != np.floor(pts) + .5).any(axis=1).all()      # above the horizon cut, off-centre
-    assert not np.isnan(fx["points_out"]).any()
-    assert int((~same_bits(fx["points_out"], fx["points_shipped"]).all(axis=-1)).sum()) >= 500
+    assert (pts[:, 1] >= POINTS["rect"][1]).all() and (pts != np.floor(pts) + .5).any(axis=1).all()      # above the horizon cut, off-centre
+    assert FAMILY["no_nan"] and not np.isnan(fx["points_out"]).any()
+    assert int((~same_bits(fx["points_out"], fx["points_shipped"]).all(axis=-1)).sum()) >= CAPS[build]["min_points"]
 
 
 def test_the_two_builds_differ_from_each_other():
     a, b = M.fixture("height"), M.fixture("luminance")
     assert not same_bits(a["frames"][1][3], b["frames"][1][3]).all()
-
-
-def test_names_and_values():
-    import shaderbox_amd
-    assert shaderbox_amd.APP_CLOUDS_HEIGHT == 21 == shaderbox_amd.app_id("clouds_height") == shaderbox_amd.ALL_APPS["APP_CLOUDS_HEIGHT"]
-    assert shaderbox_amd.APP_CLOUDS_LUMINANCE == 22 == shaderbox_amd.app_id("APP_CLOUDS_LUMINANCE")
-    assert sorted(shaderbox_amd.ALL_APPS.values()) == list(range(len(shaderbox_amd.ALL_APPS)))
-    hdr = open(os.path.join(ROOT, "include", "sbx.h")).read()
-    assert "SBX_APP_CLOUDS_HEIGHT = 21" in hdr and "SBX_APP_CLOUDS_LUMINANCE = 22" in hdr and "#define SBX_ABI_VERSION 2\n" in hdr
 
 
 @pytest.mark.parametrize("app", ["clouds_height", "clouds_luminance"])

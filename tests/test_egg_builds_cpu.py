@@ -1,36 +1,38 @@
 """CPU tests of the definition of SBX_APP_EGG_STRAIGHT and SBX_APP_EGG_OVAL (include/sbx.h):
 tests/egg_builds_model.py against the oracle (the shipped build, everything the three builds share) and against the frames and
-points the reference header rendered with one line edited (tests/golden/egg_builds/, tools/make_golden_egg_builds.py); the
-conditions on those fixtures; the model's sdf against the oracle's `egg.sdf` hook; and the name tables."""
+points the reference header rendered with one line edited (tests/golden/egg_builds/, tools/make_golden_builds.py); the
+conditions on those fixtures, which are tests/build_families.py's; and the model's sdf against the oracle's `egg.sdf` hook.  The name
+tables: tests/test_build_families_cpu.py, which also asks every
+family the header-selection cases at the end of this file."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import egg_builds_model as M
-from tests.app_checks import assert_same
+from tests.app_checks import assert_same, check_mainimage_selects
+from tests.build_families import FAMILIES, fixture_path
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "egg_builds")
 F = np.float32
-NEW = ("straight", "oval")
-MIN_PIXELS = {"straight": 90, "oval": 15}               # of a 96x54 frame, other than the shipped build's
-MIN_POINTS = 200                                        # of the 4096 points
+FAMILY = FAMILIES["egg"]
+CAPS = FAMILY["builds"]                             # per build: the caps that keep a fixture from saying nothing (tests/build_families.py)
+NEW = tuple(CAPS)
+W, H = FAMILY["size"]
+POINTS = FAMILY["points"]
 
 
 def golden(build):
     """(frames [(u_time, frame)], points [n, 2], their uniforms, the build's answers, the shipped build's answers) of one fixture"""
-    z = np.load(os.path.join(GOLDEN, "egg_%s.npz" % build))
-    keys = [k for k in z.files if k.startswith("t")]
-    assert len(keys) == len(z["uniforms"]) == 3
-    for k, u in zip(keys, z["uniforms"]):
-        assert (u[0], u[1], u[2], u[3]) == (96, 54, 0, 0) and k == "t%g" % u[4]
-        assert z[k].shape == (54, 96, 4) and z[k].dtype == np.float32
-    assert z["points"].shape == (4096, 2) and z["points"].dtype == np.float32
-    assert z["points_out"].shape == z["points_shipped"].shape == (4096, 4)
-    assert tuple(z["points_uniforms"][:4]) == (1920, 1080, 0, 0)
-    return [(float(u[4]), z[k]) for k, u in zip(keys, z["uniforms"])], z["points"], z["points_uniforms"], z["points_out"], z["points_shipped"]
+    z = M.fixture(build)                            # (which asserts the file's keys and uniforms to be the table's)
+    assert len(z["frames"]) == len(z["uniforms"]) == len(FAMILY["uniforms"])
+    for f, u in zip(z["frames"], z["uniforms"]):
+        assert (u[0], u[1], u[2], u[3]) == (W, H, 0, 0)
+        assert f.shape == (H, W, 4) and f.dtype == np.float32
+    assert z["points"].shape == (POINTS["count"], 2) and z["points"].dtype == np.float32
+    assert z["points_out"].shape == z["points_shipped"].shape == (POINTS["count"], 4)
+    assert tuple(z["points_uniforms"][:4]) == POINTS["size"] + (0, 0)
+    return [(float(u[4]), f) for f, u in zip(z["frames"], z["uniforms"])], z["points"], z["points_uniforms"], z["points_out"], z["points_shipped"]
 
 
 # ---- what the three builds share: the shipped build against the oracle --------------------------------------------------------
@@ -78,7 +80,7 @@ def test_sdf_equals_the_oracles_hook(oracle):
 @pytest.mark.parametrize("build", NEW)
 def test_builds_equal_the_reference_frames(build):
     for t, want in golden(build)[0]:
-        got = M.frame(build, 96, 54, t)
+        got = M.frame(build, W, H, t)
         assert not np.isnan(want).any()
         assert_same(got, want, (build, t))
 
@@ -96,16 +98,18 @@ def test_fixture_conditions(oracle, build):
     and 0.2 and 985 of the 4096 points; oval 20, 21 and 20 pixels and 297 points."""
     from oracle.oracle import APP_EGG
     frames, pts, u, want, shipped = golden(build)
-    assert [t for t, _ in frames] == [pytest.approx(x) for x in (0.0037, 0.02, 0.2)]
+    assert [t for t, _ in frames] == [pytest.approx(x) for x, _ in FAMILY["uniforms"]]
     for t, g in frames:
-        n = int((~M.same_bits(g, oracle.render(APP_EGG, 96, 54, t)).all(axis=2)).sum())
+        n = int((~M.same_bits(g, oracle.render(APP_EGG, W, H, t)).all(axis=2)).sum())
         print(build, t, n)
-        assert n >= MIN_PIXELS[build], (build, t, n)
+        assert n >= CAPS[build]["min_pixels"], (build, t, n)
     n = int((~M.same_bits(want, shipped).all(axis=1)).sum())
     print(build, "points", n)
-    assert n >= MIN_POINTS, (build, n)
-    assert (want[:, 3] == 1).all() and not np.isnan(want).any()
-    assert os.path.getsize(os.path.join(GOLDEN, "egg_%s.npz" % build)) < 100 * 1024
+    assert n >= CAPS[build]["min_points"], (build, n)
+    assert (want[:, 3] == 1).all() and FAMILY["no_nan"] and not np.isnan(want).any()
+    x0, y0, x1, y1 = CAPS[build]["rect"]
+    assert ((pts >= (x0, y0)) & (pts <= (x1, y1))).all()
+    assert os.path.getsize(fixture_path(os.path.join(ROOT, "tests"), "egg", build)) < FAMILY["max_bytes"]
 
 
 def test_what_the_builds_change():
@@ -131,32 +135,10 @@ def test_what_the_builds_change():
         assert (got["egg"] >= q / 1.5501 - 0.475 - 1e-6).all()
 
 
-# ---- names ---------------------------------------------------------------------------------------------------------------------
-
-def test_python_names():
-    import shaderbox_amd
-    assert shaderbox_amd.APP_EGG_STRAIGHT == 19 == shaderbox_amd.ALL_APPS["APP_EGG_STRAIGHT"]
-    assert shaderbox_amd.APP_EGG_OVAL == 20 == shaderbox_amd.ALL_APPS["APP_EGG_OVAL"]
-    assert shaderbox_amd.app_id("egg_straight") == 19 and shaderbox_amd.app_id("egg_oval") == 20
-    assert shaderbox_amd.app_id("APP_EGG_OVAL") == 20 and shaderbox_amd.app_id("egg") == 3
-    # appended: no value renumbered.  (APPS itself keeps the nineteen apps before them: an existing test pins it to those.)
-    assert sorted(shaderbox_amd.ALL_APPS.values()) == list(range(len(shaderbox_amd.ALL_APPS))) and len(shaderbox_amd.ALL_APPS) >= 21
-    assert all(shaderbox_amd.ALL_APPS[k] == v for k, v in shaderbox_amd.APPS.items())
-    assert shaderbox_amd.SBX_ABI_VERSION == 2
-
+# ---- the app include/sbx_mainimage.hpp selects (every family's, from the table: tests/test_build_families_cpu.py) --------------------
 
 @pytest.mark.parametrize("defines,want", [(["APP_EGG_STRAIGHT"], "SBX_APP_EGG_STRAIGHT"), (["APP_EGG_OVAL"], "SBX_APP_EGG_OVAL"),
                                           (["APP_EGG", "APP_EGG_STRAIGHT"], "SBX_APP_EGG_STRAIGHT"),
                                           (["APP_EGG_OVAL", "APP_EGG"], "SBX_APP_EGG_OVAL"), (["APP_EGG"], "SBX_APP_EGG")])
 def test_mainimage_header_selects_the_build(defines, want):
-    r = subprocess.run(["g++", "-std=c++17", "-E", "-P", "-x", "c++"] + ["-D" + d for d in defines] +
-                       ["-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "include", "sbx_mainimage.hpp")],
-                       check=True, capture_output=True, text=True)
-    assert "sbx_main_image(ctx, %s, &u" % want in r.stdout
-
-
-def test_enum_values_of_the_header(tmp_path):
-    src = tmp_path / "enum.cpp"
-    src.write_text('#include "sbx.h"\nstatic_assert(SBX_APP_EGG == 3 && SBX_APP_SDF_AO_NORMALS == 18 && SBX_APP_EGG_STRAIGHT == 19 && '
-                   'SBX_APP_EGG_OVAL == 20 && SBX_ABI_VERSION == 2, "appended");\n')
-    subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
+    check_mainimage_selects(defines, want)

@@ -1,8 +1,6 @@
 """GPU tests of SBX_APP_EGG_STRAIGHT and SBX_APP_EGG_OVAL (src/app_egg.h without its `#define BEZIER` / with its `#if 1` at :46 off;
 include/sbx.h): every layer bit for bit, NaN == NaN, all four channels, against tests/egg_builds_model.py — and
 against the frames and points the edited reference header rendered (tests/golden/egg_builds/)."""
-import os
-
 import numpy as np
 import pytest
 
@@ -13,7 +11,6 @@ from tests.app_checks import renderer  # noqa: F401 (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILDS = ["straight", "oval"]
 F = np.float32
 TIMES = (0.0037, 0.2, -0.41, 1.3)                                       # at 1.3 the turntable has carried the figure out of view
@@ -23,8 +20,8 @@ model_frame = frame_cache(lambda build, w, h, t: M.frame(build, w, h, t, threads
 
 
 def golden(build):
-    z = np.load(os.path.join(ROOT, "tests", "golden", "egg_builds", "egg_%s.npz" % build))
-    return [(float(u[4]), z["t%g" % u[4]]) for u in z["uniforms"]], z["points"], z["points_uniforms"], z["points_out"]
+    z = M.fixture(build)
+    return [(float(u[4]), f) for u, f in zip(z["uniforms"], z["frames"])], z["points"], z["points_uniforms"], z["points_out"]
 
 
 @pytest.mark.parametrize("build", BUILDS)

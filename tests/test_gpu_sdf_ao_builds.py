@@ -1,8 +1,6 @@
 """GPU tests of SBX_APP_SDF_AO_SHADOW and SBX_APP_SDF_AO_NORMALS (src/app_sdf_ao.h with one of its `#if 0` blocks on; include/sbx.h,
 DESIGN.md §5.11): every layer bit for bit, NaN == NaN, all four channels, against tests/sdf_ao_builds_model.py — and, at 64x36,
 against the frames the edited reference header rendered (tests/golden/sdf_ao_builds/)."""
-import os
-
 import numpy as np
 import pytest
 
@@ -13,7 +11,6 @@ from tests.app_checks import renderer  # noqa: F401 (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILDS = ["shadow", "normals"]
 F = np.float32
 
@@ -35,8 +32,8 @@ def aux_block(aux):
 
 
 def golden(build):
-    z = np.load(os.path.join(ROOT, "tests", "golden", "sdf_ao_builds", "sdf_ao_%s_64x36.npz" % build))
-    return [(float(u[4]), z["t%g" % u[4]]) for u in z["uniforms"]]
+    z = M.fixture(build)
+    return [(float(u[4]), f) for u, f in zip(z["uniforms"], z["frames"])]
 
 
 # u_mouse does not enter app_sdf_ao.h: every mouse value gives the frame of (0, 0).  Fog falloff 0 makes the factor 0 / 0: a NaN frame.

@@ -1,31 +1,28 @@
 """CPU tests of the definition of SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS and SBX_APP_PLANET_UNLIT (include/sbx.h,
 DESIGN.md §5.16): tests/planet_builds_model.py against the oracle (the shipped build, everything the four builds share) and against
 the frames and points the reference header rendered with one line edited (tests/golden/planet_builds/,
-tools/make_golden_planet_builds.py); the conditions on those fixtures; and the name tables."""
+tools/make_golden_builds.py); and the conditions on those fixtures, which are tests/build_families.py's.  The name tables:
+tests/test_build_families_cpu.py, which also asks every
+family the header-selection cases at the end of this file."""
 import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import planet_builds_model as M
-from tests.app_checks import assert_same
+from tests.app_checks import assert_same, check_mainimage_selects
+from tests.build_families import FAMILIES, fixture_path
 from tests.model_common import same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "planet_builds")
-NEW = ("closeup", "cloudless", "unlit")
-TIMES = (0.37, 2.5, -3.7, 7.25)                     # u_time of the fixtures' 64x36 frames
-BIG_TIMES = (-3.7, 7.25)                            # u_time of the 128x72 frames (cloudless, unlit)
-# caps that keep a fixture from saying nothing: pixels of a 64x36 frame and of a 128x72 frame other than the shipped build's; the most
-# NaN pixels a frame may hold (the 0 / 0 of :273 is one source); and the points of the 2048 other than the shipped build's that
-# tools/make_golden_planet_builds.py printed when it wrote the files (its docstring), of which 80 % are asked for
-MIN_PIXELS = {"closeup": 2250, "cloudless": 750, "unlit": 580}
-MIN_BIG = {"cloudless": 3000, "unlit": 2300}
-MAX_NAN = {"closeup": 150, "cloudless": 100, "unlit": 0}
-MAX_NAN_BIG = {"cloudless": 300, "unlit": 0}
-PRINTED_POINTS = {"closeup": 2047, "cloudless": 796, "unlit": 659}
+FAMILY = FAMILIES["planet"]
+CAPS = FAMILY["builds"]                             # per build: the caps that keep a fixture from saying nothing (tests/build_families.py)
+NEW = tuple(CAPS)
+(W, H), (BW, BH) = FAMILY["size"], FAMILY["big"]["size"]
+TIMES = tuple(t for t, _ in FAMILY["uniforms"])     # u_time of the fixtures' frames
+BIG_TIMES = tuple(t for t, _ in FAMILY["big"]["uniforms"])      # u_time of the larger frames, of the builds that state a min_big
+POINTS = FAMILY["points"]
 
 
 def _differ(a, b):
@@ -38,7 +35,7 @@ def _nan_pixels(a):
 
 # ---- what the four builds share: the shipped build against the oracle ----------------------------------------------------------
 
-@pytest.mark.parametrize("w,h,times", [(64, 36, TIMES), (97, 55, (2.5,))])
+@pytest.mark.parametrize("w,h,times", [(W, H, TIMES), (97, 55, (2.5,))])
 def test_default_build_equals_the_oracle(oracle, w, h, times):
     from oracle.oracle import APP_PLANET
     for t in times:
@@ -52,22 +49,22 @@ def test_default_build_equals_the_oracle(oracle, w, h, times):
 @pytest.mark.parametrize("build", NEW)
 def test_builds_equal_the_reference_frames(build):
     fx = M.fixture(build)
-    assert [tuple(u) for u in fx["uniforms"]] == [(64, 36, 0, 0, np.float32(t)) for t in TIMES]
+    assert [tuple(u) for u in fx["uniforms"]] == [(W, H, 0, 0, np.float32(t)) for t in TIMES]
     for u, want in zip(fx["uniforms"], fx["frames"]):
-        assert want.shape == (36, 64, 4) and want.dtype == np.float32
-        assert_same(M.frame(build, 64, 36, u[4]), want, (build, float(u[4])))
+        assert want.shape == (H, W, 4) and want.dtype == np.float32
+        assert_same(M.frame(build, W, H, u[4]), want, (build, float(u[4])))
     big = [tuple(u) for u in fx["big_uniforms"]]
-    assert big == ([(128, 72, 0, 0, np.float32(t)) for t in BIG_TIMES] if build in MIN_BIG else [])
+    assert big == ([(BW, BH, 0, 0, np.float32(t)) for t in BIG_TIMES] if "min_big" in CAPS[build] else [])
     for u, want in zip(fx["big_uniforms"], fx["big_frames"]):
-        assert want.shape == (72, 128, 4)
-        assert_same(M.frame(build, 128, 72, u[4]), want, (build, "128x72", float(u[4])))
+        assert want.shape == (BH, BW, 4)
+        assert_same(M.frame(build, BW, BH, u[4]), want, (build, "big", float(u[4])))
 
 
 @pytest.mark.parametrize("build", NEW)
 def test_builds_equal_the_reference_points(build):
     fx = M.fixture(build)
     pts, u = fx["points"], fx["points_uniforms"]
-    assert pts.shape == (2048, 2) and pts.dtype == np.float32 and tuple(u) == (1920, 1080, 0, 0, 2.5)
+    assert pts.shape == (POINTS["count"], 2) and pts.dtype == np.float32 and tuple(u) == POINTS["size"] + (0, 0, POINTS["time"])
     assert (pts != np.floor(pts) + .5).any(axis=1).all()                  # off-centre
     assert_same(M.main_image(build, u[0], u[1], u[4], pts[:, 0], pts[:, 1]), fx["points_out"], (build, "points"))
     assert_same(M.main_image("default", u[0], u[1], u[4], pts[:, 0], pts[:, 1]), fx["points_shipped"], (build, "the shipped build's answers"))
@@ -83,23 +80,23 @@ def test_fixture_conditions(oracle, build):
     fx = M.fixture(build)
     for u, g in zip(fx["uniforms"], fx["frames"]):
         assert (g[..., 3] == 1).all()
-        n, nans = _differ(g, oracle.render(APP_PLANET, 64, 36, float(u[4]))), _nan_pixels(g)
+        n, nans = _differ(g, oracle.render(APP_PLANET, W, H, float(u[4]))), _nan_pixels(g)
         print(build, float(u[4]), n, "NaN pixels", nans)
-        assert n >= MIN_PIXELS[build], (build, float(u[4]), n)
-        assert nans <= MAX_NAN[build], (build, float(u[4]), nans)
+        assert n >= CAPS[build]["min_pixels"], (build, float(u[4]), n)
+        assert nans <= CAPS[build]["max_nan"], (build, float(u[4]), nans)
     for u, g in zip(fx["big_uniforms"], fx["big_frames"]):
         assert (g[..., 3] == 1).all()
-        n, nans = _differ(g, oracle.render(APP_PLANET, 128, 72, float(u[4]))), _nan_pixels(g)
-        print(build, "128x72", float(u[4]), n, "NaN pixels", nans)
-        assert n >= MIN_BIG[build], (build, float(u[4]), n)
-        assert nans <= MAX_NAN_BIG[build], (build, float(u[4]), nans)
+        n, nans = _differ(g, oracle.render(APP_PLANET, BW, BH, float(u[4]))), _nan_pixels(g)
+        print(build, "big", float(u[4]), n, "NaN pixels", nans)
+        assert n >= CAPS[build]["min_big"], (build, float(u[4]), n)
+        assert nans <= CAPS[build]["max_nan_big"], (build, float(u[4]), nans)
     want, shipped = fx["points_out"], fx["points_shipped"]
     assert (want[:, 3] == 1).all() and (shipped[:, 3] == 1).all()
     n = _differ(want, shipped)
     print(build, "points", n)
-    assert n >= .8 * PRINTED_POINTS[build], (build, n)
+    assert n >= .8 * CAPS[build]["printed_points"], (build, n)             # 80 % of what the fixture tool printed
     bound = max(os.path.getsize(p) for p in glob.glob(os.path.join(ROOT, "tests", "golden", "*.npz")))
-    assert os.path.getsize(os.path.join(GOLDEN, "planet_%s.npz" % build)) <= bound
+    assert FAMILY["max_bytes"] == "largest" and os.path.getsize(fixture_path(os.path.join(ROOT, "tests"), "planet", build)) <= bound
 
 
 def test_the_builds_differ_from_one_another():
@@ -152,30 +149,7 @@ def test_unlit_is_the_shipped_build_off_the_ground():
     assert not np.isnan(a).any()
 
 
-# ---- names ---------------------------------------------------------------------------------------------------------------------
-
-def test_python_names():
-    import shaderbox_amd
-    for build, value in (("closeup", 29), ("cloudless", 30), ("unlit", 31)):
-        name = "APP_PLANET_" + build.upper()
-        assert getattr(shaderbox_amd, name) == value == shaderbox_amd.ALL_APPS[name] == shaderbox_amd.MORE_APPS[name]
-        assert shaderbox_amd.app_id("planet_" + build) == value == shaderbox_amd.app_id(name)
-        assert shaderbox_amd.app_id(M.APP_OF[build]) == value
-        assert name not in shaderbox_amd.APPS
-    assert shaderbox_amd.app_id("planet") == 0 == shaderbox_amd.app_id("APP_PLANET") and shaderbox_amd.app_id("planet_atmosphere") == 12
-    # appended: no value renumbered, the table dense
-    assert sorted(shaderbox_amd.ALL_APPS.values()) == list(range(len(shaderbox_amd.ALL_APPS))) and len(shaderbox_amd.ALL_APPS) >= 32
-    assert all(shaderbox_amd.ALL_APPS[k] == v for k, v in shaderbox_amd.APPS.items())
-    assert max(shaderbox_amd.APPS.values()) < 19 and len(shaderbox_amd.APPS) == 19          # APPS keeps its pinned entries
-    assert shaderbox_amd.SBX_ABI_VERSION == 2
-
-
-def test_enum_values_of_the_header(tmp_path):
-    src = tmp_path / "enum.cpp"
-    src.write_text('#include "sbx.h"\nstatic_assert(SBX_APP_PLANET == 0 && SBX_APP_PLANET_ATMOSPHERE == 12 && SBX_APP_VINYL_NOSHADOW == 28 && '
-                   'SBX_APP_PLANET_CLOSEUP == 29 && SBX_APP_PLANET_CLOUDLESS == 30 && SBX_APP_PLANET_UNLIT == 31 && SBX_ABI_VERSION == 2, "appended");\n')
-    subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
-
+# ---- the app include/sbx_mainimage.hpp selects (every family's, from the table: tests/test_build_families_cpu.py) --------------------
 
 @pytest.mark.parametrize("defines,want", [(["APP_PLANET_CLOSEUP"], "SBX_APP_PLANET_CLOSEUP"), (["APP_PLANET_CLOUDLESS"], "SBX_APP_PLANET_CLOUDLESS"),
                                           (["APP_PLANET_UNLIT"], "SBX_APP_PLANET_UNLIT"),
@@ -185,7 +159,4 @@ def test_enum_values_of_the_header(tmp_path):
                                           (["APP_PLANET_ATMOSPHERE"], "SBX_APP_PLANET_ATMOSPHERE"),
                                           (["APP_PLANET"], "SBX_APP_PLANET")])
 def test_mainimage_header_selects_the_build(defines, want):
-    r = subprocess.run(["g++", "-std=c++17", "-E", "-P", "-x", "c++"] + ["-D" + d for d in defines] +
-                       ["-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "include", "sbx_mainimage.hpp")],
-                       check=True, capture_output=True, text=True)
-    assert "sbx_main_image(ctx, %s, &u" % want in r.stdout
+    check_mainimage_selects(defines, want)

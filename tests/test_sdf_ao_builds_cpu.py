@@ -1,30 +1,29 @@
 """CPU tests of the definition of SBX_APP_SDF_AO_SHADOW and SBX_APP_SDF_AO_NORMALS (include/sbx.h):
 tests/sdf_ao_builds_model.py against the oracle (the shipped build, everything the three builds share), against the frames the
-reference header rendered with one `#if 0` turned on (tests/golden/sdf_ao_builds/, tools/make_golden_sdf_ao_builds.py) and,
-for the shadow term alone, against a scalar step-by-step march over the oracle's sdf hook; and the name tables."""
-import os
-import subprocess
-
+reference header rendered with one `#if 0` turned on (tests/golden/sdf_ao_builds/, tools/make_golden_builds.py) and,
+for the shadow term alone, against a scalar step-by-step march over the oracle's sdf hook.  The name tables:
+tests/test_build_families_cpu.py, which also asks every
+family the header-selection cases at the end of this file."""
 import numpy as np
 import pytest
 
 from tests import sdf_ao_builds_model as M
-from tests.app_checks import assert_same
+from tests.app_checks import assert_same, check_mainimage_selects
+from tests.build_families import FAMILIES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "sdf_ao_builds")
+FAMILY = FAMILIES["sdf_ao"]
+W, H = FAMILY["size"]
 F = np.float32
 
 
 def golden(build):
     """[(u_time, frame)] of one fixture; the uniforms are u_res, u_mouse, u_time per frame, in the order of the frames"""
-    z = np.load(os.path.join(GOLDEN, "sdf_ao_%s_64x36.npz" % build))
-    keys = [k for k in z.files if k != "uniforms"]
-    assert len(keys) == len(z["uniforms"]) == 3
-    for k, u in zip(keys, z["uniforms"]):
-        assert (u[0], u[1], u[2], u[3]) == (64, 36, 0, 0) and k == "t%g" % u[4]
-        assert z[k].shape == (36, 64, 4) and z[k].dtype == np.float32
-    return [(float(u[4]), z[k]) for k, u in zip(keys, z["uniforms"])]
+    z = M.fixture(build)                            # (which asserts the file's keys and uniforms to be the table's)
+    assert len(z["frames"]) == len(z["uniforms"]) == len(FAMILY["uniforms"]) and "points" not in z
+    for f, u in zip(z["frames"], z["uniforms"]):
+        assert (u[0], u[1], u[2], u[3]) == (W, H, 0, 0)
+        assert f.shape == (H, W, 4) and f.dtype == np.float32
+    return [(float(u[4]), f) for f, u in zip(z["frames"], z["uniforms"])]
 
 
 def hits(build, w, h, t):
@@ -80,7 +79,7 @@ def test_sdf_normal_and_ao_equal_the_oracles_hooks(oracle):
 @pytest.mark.parametrize("build", ["shadow", "normals"])
 def test_builds_equal_the_reference_frames(build):
     for t, want in golden(build):
-        assert_same(M.frame(build, 64, 36, t), want, (build, t))
+        assert_same(M.frame(build, W, H, t), want, (build, t))
 
 
 def scalar_shadow(oracle, o, trace):
@@ -140,30 +139,10 @@ def test_shadow_frames_differ_from_the_shipped_build():
             assert share > 0, (build, t, share)
 
 
-# ---- names ---------------------------------------------------------------------------------------------------------------------
-
-def test_python_names():
-    import shaderbox_amd
-    assert shaderbox_amd.APP_SDF_AO_SHADOW == 17 == shaderbox_amd.APPS["APP_SDF_AO_SHADOW"]
-    assert shaderbox_amd.APP_SDF_AO_NORMALS == 18 == shaderbox_amd.APPS["APP_SDF_AO_NORMALS"]
-    assert shaderbox_amd.app_id("sdf_ao_shadow") == 17 and shaderbox_amd.app_id("sdf_ao_normals") == 18
-    assert shaderbox_amd.app_id("APP_SDF_AO_SHADOW") == 17 and shaderbox_amd.app_id("sdf_ao") == 6
-    assert sorted(shaderbox_amd.APPS.values()) == list(range(19))       # appended: no value renumbered
-    assert shaderbox_amd.SBX_ABI_VERSION == 2
-
+# ---- the app include/sbx_mainimage.hpp selects (every family's, from the table: tests/test_build_families_cpu.py) --------------------
 
 @pytest.mark.parametrize("defines,want", [(["APP_SDF_AO_SHADOW"], "SBX_APP_SDF_AO_SHADOW"), (["APP_SDF_AO_NORMALS"], "SBX_APP_SDF_AO_NORMALS"),
                                           (["APP_SDF_AO", "APP_SDF_AO_SHADOW"], "SBX_APP_SDF_AO_SHADOW"),
                                           (["APP_SDF_AO_NORMALS", "APP_SDF_AO"], "SBX_APP_SDF_AO_NORMALS"), (["APP_SDF_AO"], "SBX_APP_SDF_AO")])
 def test_mainimage_header_selects_the_build(defines, want):
-    r = subprocess.run(["g++", "-std=c++17", "-E", "-P", "-x", "c++"] + ["-D" + d for d in defines] +
-                       ["-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "include", "sbx_mainimage.hpp")],
-                       check=True, capture_output=True, text=True)
-    assert "sbx_main_image(ctx, %s, &u" % want in r.stdout
-
-
-def test_enum_values_of_the_header(tmp_path):
-    src = tmp_path / "enum.cpp"
-    src.write_text('#include "sbx.h"\nstatic_assert(SBX_APP_SDF_AO == 6 && SBX_APP_ATMOSPHERE_GROUND == 16 && SBX_APP_SDF_AO_SHADOW == 17 && '
-                   'SBX_APP_SDF_AO_NORMALS == 18 && SBX_ABI_VERSION == 2, "appended");\n')
-    subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
+    check_mainimage_selects(defines, want)

@@ -7,7 +7,7 @@ The CPU oracle renders the shipped build only and is not to grow, so the GPU tes
 module.  It is pinned from two sides (tests/test_vinyl_builds_cpu.py): build "default" equals Oracle.render("vinyl") in every bit —
 which covers everything the four builds share: camera arithmetic, sdf_logo, platter, tonearm, the unions, the march, sdf_shadow,
 sdf_normal, both shading branches, epilogue — and the other three equal frames and points that the reference header itself rendered
-with the one line edited (tests/golden/vinyl_builds/, tools/make_golden_vinyl_builds.py), NaN pixels included.
+with the one line edited (tests/golden/vinyl_builds/, tools/make_golden_builds.py), NaN pixels included.
 
 mainImage -> render -> sdf / sdf_shadow / illuminate, vectorised over pixels, in binary32 step by step in the oracle's operation
 order (oracle/ovec.h: dot = (x x + y y) + z z, normalize = three divisions by sqrtf, v * M = the three dots with M's columns,
@@ -16,14 +16,13 @@ np.float32.  sin, cos, exp, pow and noise_iq are the oracle's (Oracle.math, Orac
 and wobble rotations) and on nothing (the tonearm's constant frames) is evaluated once (`scene`), in the same operations.  The vector
 algebra and the camera are tests/model_common.py's; the primitives sd_cylinder and sd_bezier are tests/egg_builds_model.py's.
 """
-import os
+import functools
 
 import numpy as np
 
-from oracle.oracle import APP_VINYL
 from tests.egg_builds_model import add3, clamp, length3, mat_vec, sd_bezier_x, sd_cylinder, sub3
-from tests.model_common import (F, ONE, RADIANS, TWO, ZERO, _const, _f, cross, dot, fmax, fmin, get_primary_ray, normalize, op_add2,
-                                 oracle, point_cam, same_bits)
+from tests.model_common import (F, ONE, RADIANS, TWO, ZERO, _const, _f, builds_fixture, cross, dot, fmax, fmin, get_primary_ray,
+                                 normalize, op_add2, oracle, point_cam, same_bits)
 
 BUILDS = ("default", "closeup", "ridges", "noshadow")
 APP_OF = {"default": "vinyl", "closeup": "vinyl_closeup", "ridges": "vinyl_ridges", "noshadow": "vinyl_noshadow"}
@@ -36,7 +35,6 @@ MAT_GROOVE, MAT_DEAD_WAX, MAT_LABEL, MAT_LOGO, MAT_SHINY = 1, 2, 3, 4, 5      # 
 BASE_COLOR = {0: (F(1), F(1), F(1)), MAT_GROOVE: (F(.01), F(.01), F(.01)), MAT_DEAD_WAX: (F(.05), F(.05), F(.05)),
               MAT_LABEL: (F(.5), F(.5), F(.0)), MAT_LOGO: (F(0), F(0), F(.7)), MAT_SHINY: (F(.7), F(.7), F(.7))}   # setup_scene :40-54
 PI = F(3.14159265359)                               # def.h:51
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _sincos_rad(a):
@@ -428,45 +426,4 @@ def frame(build, width, height, u_time, mouse=(0.0, 0.0), parts=None):
     return main_image(build, width, height, u_time, fx, fy, parts)
 
 
-# ---- the fixtures --------------------------------------------------------------------------------------------------------
-
-def _bits(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=F)[..., :3]).view(np.uint32)
-
-
-def _rgba(bits):
-    out = np.ones(bits.shape[:-1] + (4,), dtype=F)
-    out[..., :3] = np.ascontiguousarray(bits).view(F)
-    return out
-
-
-_FIXTURES = {}
-
-
-def fixture(build):
-    """tests/golden/vinyl_builds/vinyl_<build>.npz decoded (tools/make_golden_vinyl_builds.py): a dict with
-    uniforms [4, 5] and frames (a list of [36, 64, 4]), big_uniforms / big_frames ([72, 128, 4]; ridges and noshadow only, else empty),
-    points [2048, 2], points_uniforms [5], points_out and points_shipped [2048, 4].  The files hold the XOR of every frame's rgb
-    bits with the shipped build's frame, which is the oracle's APP_VINYL frame under the same uniforms."""
-    if build not in _FIXTURES:
-        z = np.load(os.path.join(GOLDEN, "vinyl_builds", "vinyl_%s.npz" % build))
-        o = oracle()
-
-        def decode(uniforms, prefix):
-            frames = []
-            for i, u in enumerate(uniforms):
-                shipped = o.render(APP_VINYL, int(u[0]), int(u[1]), float(u[4]), mouse=(float(u[2]), float(u[3])))
-                assert (shipped[..., 3] == 1).all()
-                frames.append(_rgba(z["%s%d" % (prefix, i)] ^ _bits(shipped)))
-            return frames
-
-        fx = {"uniforms": z["uniforms"], "frames": decode(z["uniforms"], "x_frame"),
-              "big_uniforms": z["big_uniforms"] if "big_uniforms" in z else np.zeros((0, 5), dtype=F)}
-        fx["big_frames"] = decode(fx["big_uniforms"], "x_big")
-        shipped_pts = np.ones((len(z["points"]), 4), dtype=F)
-        shipped_pts[:, :3] = z["points_shipped"]
-        fx.update(points=z["points"], points_uniforms=z["points_uniforms"], points_shipped=shipped_pts,
-                  points_out=_rgba(z["points_xor"] ^ _bits(shipped_pts)))
-        _FIXTURES[build] = fx
-    return _FIXTURES[build]
-
+fixture = functools.partial(builds_fixture, "vinyl")     # tests/golden/vinyl_builds/ decoded: tests/model_common.py

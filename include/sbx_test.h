@@ -78,8 +78,15 @@ int sbx_model_landing(sbx_ctx* ctx, const void* src, void* dst, size_t bytes, in
 /* The dispatch-order table of an app (csrc/sbx_tile_order.h TileOrder: a full launch's tiles sorted by the cost earlier frames measured,
  * longest first — a hint about cost, never about pixels): tables built so far for the current launch shape (0 = the launches still
  * run in plain order), launches since the last one, and — if `table` is not NULL and one exists — the current table copied to the
- * host (`capacity` words; returns the number of tiles, or a negative sbx_status).  For the test that every table is a permutation. */
+ * host (`capacity` words; returns the number of tiles, or a negative sbx_status).  For the test that every table is a permutation.
+ * Answers for every app; one without a dispatch order (csrc/sbx_apps.h kApps) never has a table. */
 int sbx_debug_tile_order(sbx_ctx* ctx, int app, int* tables_built, int* launches_since, unsigned* table, size_t capacity);
+
+/* The sort behind that table (csrc/kern_util.hip launch_order_build: k_order_count / _scan / _place) run once on `gx * gy` cost words
+ * of the caller's (host memory), the table of `gx * gy` words x | y << 16 copied back to `table_host`; synchronous.  Device buffers
+ * of its own, nothing of the context's tables is touched.  gx, gy outside 1 ... 0xffff (the bound of a launch that takes a table): SBX_ERR_ARG.
+ * For the test that the table is a permutation, longest cost class first, whatever the words hold (tests/test_gpu_tile_order.py). */
+int sbx_debug_order_build(sbx_ctx* ctx, const unsigned* cost_host, int gx, int gy, unsigned* table_host, void* stream);
 
 #ifdef __cplusplus
 }

@@ -210,6 +210,7 @@ def load_library(path=None):
     lib.sbx_shared_frame.restype = vp
     lib.sbx_debug_tile_order.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint),
                                          ctypes.c_size_t]
+    lib.sbx_debug_order_build.argtypes = [vp, vp, ci, ci, vp, vp]
     lib.sbx_shared_bytes.argtypes = [vp]
     lib.sbx_shared_bytes.restype = ctypes.c_size_t
     lib.sbx_shared_frame_begin.argtypes = [vp, ci, vp]
@@ -669,6 +670,18 @@ class Renderer:
         n = self.lib.sbx_debug_tile_order(self.ctx, app_id(app), ctypes.byref(built), ctypes.byref(since), buf, int(capacity))
         self._check(min(n, 0))
         return built.value, since.value, (np.frombuffer(buf, dtype=np.uint32, count=n).copy() if n > 0 else None)
+
+    def order_build(self, cost, gx, gy):
+        """include/sbx_test.h sbx_debug_order_build: the dispatch order's sort (csrc/kern_util.hip launch_order_build) run on the
+        `gx * gy` cost words `cost` -> the table, a numpy array of gx * gy words x | y << 16"""
+        import numpy as np
+        cost = np.ascontiguousarray(cost, dtype=np.uint32)
+        n = int(gx) * int(gy)
+        assert cost.size == n, (cost.size, gx, gy)
+        table = np.empty(max(n, 1), dtype=np.uint32)
+        self._check(self.lib.sbx_debug_order_build(self.ctx, ctypes.c_void_p(cost.ctypes.data), int(gx), int(gy),
+                                                   ctypes.c_void_p(table.ctypes.data), self._stream()))
+        return table[:n]
 
     def set_timing(self, enabled=True):
         self._check(self.lib.sbx_set_timing(self.ctx, 1 if enabled else 0))

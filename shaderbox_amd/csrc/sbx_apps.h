@@ -9,9 +9,8 @@
 namespace sbx {
 
 constexpr int SBX_APP_COUNT = SBX_APP_PLANET_UNLIT + 1;
-// sbx_debug_tile_order (include/sbx_test.h) answers for the apps up to SBX_APP_FUNC and says SBX_ERR_ARG for the later ones, as it
-// always has: none of those has an order grid below, so there is no table to show
-constexpr int TILE_ORDER_DEBUG_APPS = SBX_APP_FUNC + 1;
+// (sbx_debug_tile_order, include/sbx_test.h, answers for every app — the builds after SBX_APP_FUNC that have an order grid below
+// included; an app without one never has a table: 0 tables, 0 launches, nothing to copy)
 
 // What a MOVING scene means for an app's dispatch-order table (sbx_tile_order.h; measured on animated frames,
 // profiles/r06_tile_order.txt section 11):

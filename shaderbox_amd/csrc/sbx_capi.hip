@@ -465,7 +465,7 @@ int sbx_debug_raise_fault(sbx_ctx* ctx, void* stream) {
 }
 
 int sbx_debug_tile_order(sbx_ctx* ctx, int app, int* tables_built, int* launches_since, unsigned* table, size_t capacity) {
-    if (!ctx || app < 0 || app >= TILE_ORDER_DEBUG_APPS) return SBX_ERR_ARG;
+    if (!ctx || !app_valid(app)) return SBX_ERR_ARG;
     TileOrder& T = tile_order_latest(ctx->tile_orders, app);   // the shape used last
     if (tables_built) *tables_built = T.built;
     if (launches_since) *launches_since = T.age;
@@ -477,6 +477,33 @@ int sbx_debug_tile_order(sbx_ctx* ctx, int app, int* tables_built, int* launches
     if (e == hipSuccess) e = hipMemcpy(table, T.mem + T.cap * (size_t)(2 + T.cur), n * 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "sbx_debug_tile_order", e);
     return (int)n;
+}
+
+// The sort of the dispatch order on cost words of the caller's: launch_order_build itself (kern_util.hip), over buffers laid out as
+// tile_order_begin lays them out (cost | classes | one table | the histograms), for the test that the table is a permutation
+// whatever the words hold.  gx, gy within 1 ... 0xffff as there (a table entry is x | y << 16), gx * gy within the sort's int index.
+int sbx_debug_order_build(sbx_ctx* ctx, const unsigned* cost_host, int gx, int gy, unsigned* table_host, void* stream) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!cost_host || !table_host) return fail(ctx, SBX_ERR_ARG, "sbx_debug_order_build: NULL cost words or table");
+    if (gx < 1 || gx > 0xffff || gy < 1 || gy > 0xffff || (long long)gx * gy > 0x7fffffffll)
+        return fail(ctx, SBX_ERR_ARG, "sbx_debug_order_build: gx, gy must lie in 1 ... 65535 (and gx * gy below 2^31)");
+    const int rc = use_device(ctx);
+    if (rc != SBX_OK) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)gx * (size_t)gy;
+    unsigned* mem = nullptr;
+    hipError_t e = hipMalloc((void**)&mem, (n * 3 + order_build_scratch_words()) * 4);
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "sbx_debug_order_build: hipMalloc", e);
+    e = hipMemcpy(mem, cost_host, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_order_build(mem, mem + n, mem + n * 3, mem + n * 2, gx, gy, s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpy(table_host, mem + n * 2, n * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(mem);
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "sbx_debug_order_build", e);
+    return SBX_OK;
 }
 
 const char* sbx_last_error(sbx_ctx* ctx) {

@@ -121,6 +121,8 @@ def test_full_frames_alternate_between_the_builds(renderer):
                 if b not in first:
                     first[b] = got.clone()
             assert_same(got, first[b].cpu().numpy(), (b, "round", rnd))
+            if rnd == 1:                                                    # (round 1's launches had finished when round 2 began: the
+                assert renderer.tile_order(M.APP_OF[b])[0] >= 1, b         # table is due behind round 2's first launch at the latest)
     for b in BUILDS:
         assert_same(first[b], model_frame(b, w, h, t), (b, "vs model"))
         assert not M.same_bits(first[b].cpu().numpy(), first["default"].cpu().numpy()).all()

@@ -129,6 +129,22 @@ def test_shipped_builds_between_and_after_the_new_apps(renderer):
             assert_same(renderer.render("vinyl_gpu", 64, 36, t), zg[key], ("vinyl_gpu after", build, t))
     for build in BUILDS:
         assert_same(renderer.render(M.APP_OF[build], 64, 36, 2.5), model_frame(build, 64, 36, 2.5), (build, "at the end"))
+    # the same at a shape that takes a table (32 x 132 tiles of 32 x 8 pixels; 64 x 36 is below the 4096 tiles one needs): runs long
+    # enough for each app's table to be built and used, the apps taking turns twice — every frame is that app's first, a table IS there
+    import torch
+    w, h, t = 1000, 1051, 2.5
+    first = {}
+    for rnd in range(2):
+        for app in [M.APP_OF[b] for b in BUILDS] + ["vinyl", "vinyl_gpu"]:
+            for k in range(5):
+                got = renderer.render(app, w, h, t)
+                torch.cuda.synchronize()
+                if app not in first:
+                    first[app] = got.cpu().numpy()
+                assert_same(got, first[app], (app, "round", rnd, "launch", k))
+            assert renderer.tile_order(app)[0] >= 1, (app, rnd)
+    for build in BUILDS:
+        assert not M.same_bits(first[M.APP_OF[build]], first["vinyl"]).all(), build
 
 
 def test_noshadow_equals_the_default_build_where_nothing_is_shadowed(renderer):

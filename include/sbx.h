@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT and sbx_noise_eval's "worley_fbm": new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm" and sbx_atmosphere_eval: new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -539,6 +539,21 @@ int sbx_last_kernel_ms(sbx_ctx* ctx, float* ms);
  * (include/sbx_test.h documents three more names that exist for the parity tests of the recorded-domain forms.) */
 int sbx_noise_eval(sbx_ctx* ctx, const char* fn, const float* xyz, const float* params, float* out,
                    size_t n, void* stream);
+/* The Rayleigh/Mie scattering solver (src/app_atmosphere.h:50-160) as standalone functions over n rays of the caller's and a sun
+ * of the caller's: what the reference reaches only through its cameras and u_time.  `rays`: device memory, n x 6 floats (origin
+ * xyz, direction xyz; metres, planet centre at 0, earth_radius 6360e3, atmosphere_radius 6420e3); `out`: device memory, n x 3 floats,
+ * not overlapping `rays`; both need only 4-byte alignment.  `sun_dir`: HOST memory, 3 floats, read during the call and used as
+ * given — never normalised, as the reference never normalises its rotated (0, 1, 0).
+ *   "get_incident_light" (:78-160): out = the linear RGB along the ray (no camera, no sRGB, no alpha); (0, 0, 0) where isect_sphere
+ *       is false (:85-88).
+ *   "get_sun_light" (:50-76): out = {overground ? 1 : 0, optical_depthR, optical_depthM} along the ray itself, both depths starting
+ *       at 0; where the march returns early (:66-67) the depths are the partial sums the reference leaves in its _inout
+ *       arguments.  sun_dir is not read and may be NULL.
+ * Exact for every bit pattern of input: NaN and inf are data.  Asynchronous on `stream` and capturable (no allocation, no wait); not
+ * counted in sbx_stats.render_launches; sbx_set_precision does not enter.  n == 0 returns SBX_OK and touches nothing;
+ * SBX_ERR_ARG for a NULL ctx / fn / rays / out, a NULL sun_dir with "get_incident_light", an unknown name, n > 2^31. */
+int sbx_atmosphere_eval(sbx_ctx* ctx, const char* fn, const float* rays, const float* sun_dir, float* out,
+                        size_t n, void* stream);
 /* The size^3 RGBA32F noise volume util/ddsvolgen bakes (ddsvolgen.cpp:101-117): R =
  * fbm_worley_tile((xyz + .5)/size, 2, 1, .5), G = B = A = 0, x fastest.  `rgba`: size^3 * 4 floats. */
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream);

@@ -31,8 +31,17 @@ extern "C" {
  * raytrace_iteration; 2 = the witness's test edge; 3 = the IEEE roots and normalisations; each over the build's own code and frame.
  * SBX_APP_VINYL_CLOSEUP / _RIDGES / _NOSHADOW: every value as for APP_VINYL, over the build's own code and frame.
  * SBX_APP_PLANET_CLOSEUP / _CLOUDLESS / _UNLIT: as for APP_PLANET, 1 = the build without its exact skips.
+ * sbx_atmosphere_eval: 1 = the plain statement of src/app_atmosphere.h:50-160 lane by lane for every wave (no class test, guarded exp,
+ * sqrt_n_, division by the exact reciprocal); 0 runs it only on the waves whose rays are outside the class of csrc/sbx_atmosphere.h.
  * All variants are specified to produce identical bits (tests/test_gpu_parity.py sweeps them against each other). */
 int sbx_set_variant(sbx_ctx* ctx, int variant);
+
+/* sbx_atmosphere_eval (sbx.h) with a count: the same launch (the context's variant included), after which the call waits and
+ * stores in `fast_waves_host` the number of 64-lane waves that ran the fast forms (0 under variant 1, and for a sun direction the
+ * host refuses).  It allocates and synchronises, so it is not capturable.  For the test that the fast forms run where the default
+ * kernel is compared with the plain one (tests/test_gpu_atmosphere_eval.py) and for tools/time_atmosphere_eval.py. */
+int sbx_debug_atmosphere_eval(sbx_ctx* ctx, const char* fn, const float* rays, const float* sun_dir, float* out, size_t n,
+                              unsigned* fast_waves_host, void* stream);
 
 /* Device evaluation of the math spec, elementwise over device arrays (for parity tests):
  * fn in {"sin","cos","tan","exp","pow","acos","atan2","hash","div","div_rd","exp_h13","pow_h","sqrt_n","sqrt_ieee","exp_reg","exp_reg_plain","exp_reg64","exp_reg64_plain","exp_small","exp_small_plain","exp_reg4k","sin_b40","div3","sqrt_rs","divn","srgb_pow","pow_spec"}; b may be NULL

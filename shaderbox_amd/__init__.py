@@ -171,6 +171,8 @@ def load_library(path=None):
     lib.sbx_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     lib.sbx_math_eval.argtypes = [vp, ctypes.c_char_p, fp, fp, fp, ctypes.c_size_t, vp]
     lib.sbx_noise_eval.argtypes = [vp, ctypes.c_char_p, fp, fp, fp, ctypes.c_size_t, vp]
+    lib.sbx_atmosphere_eval.argtypes = [vp, ctypes.c_char_p, fp, fp, fp, ctypes.c_size_t, vp]
+    lib.sbx_debug_atmosphere_eval.argtypes = [vp, ctypes.c_char_p, fp, fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
     lib.sbx_worley_volume.argtypes = [vp, ci, fp, vp]
     lib.sbx_render_split_in_place.argtypes = [vp, ci, ctypes.POINTER(Uniforms), vp, ci, ci, ci, ci, ci, fp, vp]
     lib.sbx_multi_create.argtypes = [ci, ctypes.POINTER(ci), ctypes.POINTER(vp)]
@@ -699,6 +701,29 @@ class Renderer:
         self._check(self.lib.sbx_noise_eval(self.ctx, fn.encode(), ctypes.c_void_p(xyz.data_ptr()),
                                             ctypes.cast(par, ctypes.c_void_p), ctypes.c_void_p(out.data_ptr()),
                                             xyz.shape[0], self._stream()))
+        return out
+
+    def atmosphere_eval(self, fn, rays, sun_dir=(0.0, 1.0, 0.0)):
+        """The Rayleigh/Mie solver over rays[n, 6] (origin xyz, direction xyz; include/sbx.h sbx_atmosphere_eval) -> [n, 3]:
+        fn 'get_incident_light' = linear RGB for the sun direction `sun_dir` (used as given), 'get_sun_light' = (overground,
+        optical_depthR, optical_depthM) along the ray (sun_dir may be None)."""
+        return self._atmosphere_eval(fn, rays, sun_dir, None)
+
+    def atmosphere_eval_counted(self, fn, rays, sun_dir=(0.0, 1.0, 0.0)):
+        """include/sbx_test.h sbx_debug_atmosphere_eval: atmosphere_eval that waits -> (out, waves that ran the fast forms)"""
+        waves = ctypes.c_uint(0)
+        return self._atmosphere_eval(fn, rays, sun_dir, waves), waves.value
+
+    def _atmosphere_eval(self, fn, rays, sun_dir, waves):
+        rays = rays.to(self.tdev, self.torch.float32).contiguous().view(rays.numel() // 6, 6)
+        sun = None if sun_dir is None else (ctypes.c_float * 3)(*[float(v) for v in sun_dir])
+        sun_p = None if sun is None else ctypes.cast(sun, ctypes.c_void_p)
+        out = self.torch.empty((rays.shape[0], 3), dtype=self.torch.float32, device=self.tdev)
+        args = (self.ctx, fn.encode(), ctypes.c_void_p(rays.data_ptr()), sun_p, ctypes.c_void_p(out.data_ptr()), rays.shape[0])
+        if waves is None:
+            self._check(self.lib.sbx_atmosphere_eval(*args, self._stream()))
+        else:
+            self._check(self.lib.sbx_debug_atmosphere_eval(*args, ctypes.byref(waves), self._stream()))
         return out
 
     def worley_volume(self, size=128):

@@ -110,6 +110,84 @@ __global__ void __launch_bounds__(64 * ATM_TX, ATM_MIN_WAVES) k_atmosphere_groun
     store_rgba(M, out, px.idx, to_srgb(col));
 }
 
+// ---- the solver over the caller's rays: sbx_atmosphere_eval ------------------------------------------------------------------------
+// One thread per ray (rays: n x {origin, direction}, out: n x 3, both only 4-byte aligned), FN 0 = get_incident_light (:78-160),
+// FN 1 = get_sun_light (:50-76; out = {overground, optical_depthR, optical_depthM}, the partial sums where the march returns early).
+// The plain statement, lane by lane, is the definition (SELECT = false).  SELECT = true carries both bodies: a wave whose 64 rays all
+// lie in sbx_atmosphere.h's class ("CALLER'S RAYS": the test is made here, on the loaded rays, wave-uniformly) runs the FIN forms,
+// every other wave the plain one.  (The same selection as TWO launches, in each of which the waves of the other class leave after
+// the test: measured against the one kernel and not taken, profiles/atmosphere_eval_timing.txt.)
+// fast_waves: NULL, or a counter of the waves that took the FIN forms (sbx_test.h).
+static_assert(!ATM_BATCH, "get_sun_light's partial sums are those of the sample-by-sample march");
+template <int FN, bool SELECT>
+__global__ void __launch_bounds__(64, ATM_MIN_WAVES) k_atmosphere_eval(const float* __restrict__ rays, v3 sun_dir, float* __restrict__ out,
+                                                                       size_t n, unsigned* fast_waves) {
+    constexpr bool T64 = ATM_EXP_REG && ATM_EXP64 && !ATM_EXP4K;
+    __shared__ double etab[32];
+    __shared__ double etab64[T64 ? 64 : 1];
+    if (threadIdx.x < 32) etab[threadIdx.x] = kExp2Tab[threadIdx.x];
+    if (T64 && threadIdx.x < 64) etab64[threadIdx.x] = kExp2Tab64[threadIdx.x];
+    __builtin_amdgcn_wave_barrier();
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const bool live = i < n;
+    // a lane past n holds a ray of the class, so that it neither keeps its wave from the FIN forms nor disturbs their wave-wide tests
+    v3 ro = V3(0.f, ATM_EARTH_R + 1.f, 0.f), rd = V3(1.f, 0.f, 0.f);
+    if (live) {
+        const float* p = rays + 6 * i;
+        ro = V3(p[0], p[1], p[2]);
+        rd = V3(p[3], p[4], p[5]);
+    }
+    const bool fast = SELECT && __builtin_amdgcn_ballot_w64(!atm_eval_class(ro, rd)) == 0ull;   // wave-uniform
+    v3 r;
+    if (fast) {
+        if (fast_waves && threadIdx.x == 0) atomicAdd(fast_waves, 1u);
+        if (FN == 0) {
+            r = atm_incident_light<true, 0, true>(ro, rd, sun_dir, etab, etab64);
+        } else {
+            AtmDiv K{ATM_HR, 1.0f / ATM_HR, ATM_HM, 1.0f / ATM_HM};
+            if (ATM_DIV3) asm volatile("" : "+v"(K.hr), "+v"(K.rhr), "+v"(K.hm), "+v"(K.rhm));
+            float odR = 0.f, odM = 0.f;
+            const bool over = sun_light<true>(ro, rd, odR, odM, etab, etab64, K);
+            r = V3(over ? 1.f : 0.f, odR, odM);
+        }
+    } else {
+        if (!live) return;
+        if (FN == 0) {
+            r = atm_incident_light<false, 0, false>(ro, rd, sun_dir, etab, etab64);
+        } else {
+            const AtmDiv K{ATM_HR, 1.0f / ATM_HR, ATM_HM, 1.0f / ATM_HM};
+            float odR = 0.f, odM = 0.f;
+            const bool over = sun_light<false>(ro, rd, odR, odM, etab, etab64, K);
+            r = V3(over ? 1.f : 0.f, odR, odM);
+        }
+    }
+    if (live) {
+        float* q = out + 3 * i;
+        q[0] = r.x; q[1] = r.y; q[2] = r.z;
+    }
+}
+
+// the host's part of the class: a sun direction that is finite and a unit vector to ATM_EVAL_UNIT_TOL (sbx_atmosphere.h)
+static bool atm_eval_sun_ok(v3 s) {
+    const float ss = (s.x * s.x + s.y * s.y) + s.z * s.z;
+    return std::isfinite(s.x) && std::isfinite(s.y) && std::isfinite(s.z) && std::fabs(ss - 1.0f) <= ATM_EVAL_UNIT_TOL;
+}
+
+template <int FN>
+static void launch_atmosphere_eval_fn(bool select, const float* rays, v3 sun, float* out, size_t n, unsigned* fast_waves, hipStream_t s) {
+    const dim3 g((unsigned)((n + 63) / 64)), b(64);
+    if (select) hipLaunchKernelGGL((k_atmosphere_eval<FN, true>), g, b, 0, s, rays, sun, out, n, fast_waves);
+    else hipLaunchKernelGGL((k_atmosphere_eval<FN, false>), g, b, 0, s, rays, sun, out, n, fast_waves);
+}
+
+// plain: the plain kernel for every wave (sbx_set_variant 1); a sun the class does not admit makes the launch plain by itself.  n in 1 ... 2^31.
+void launch_atmosphere_eval(int fn, bool plain, const float* rays, const float* sun_dir, float* out, size_t n, unsigned* fast_waves, hipStream_t s) {
+    const v3 sun = fn == 0 ? V3(sun_dir[0], sun_dir[1], sun_dir[2]) : V3(0.f, 1.f, 0.f);   // get_sun_light reads no sun
+    const bool select = !plain && ATM_NO_FIN == 0 && atm_eval_sun_ok(sun);
+    if (fn == 0) launch_atmosphere_eval_fn<0>(select, rays, sun, out, n, fast_waves, s);
+    else launch_atmosphere_eval_fn<1>(select, rays, sun, out, n, fast_waves, s);
+}
+
 // exp_reg4k_ as a standalone function (sbx_math_eval "exp_reg4k"): the same table, read from global memory, the same instruction
 // sequence as inside k_atmosphere — for the exhaustive comparison with exp_
 __global__ void __launch_bounds__(256) k_exp4k_eval(const float* __restrict__ a, float* __restrict__ out, size_t n) {

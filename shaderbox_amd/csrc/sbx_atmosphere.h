@@ -75,6 +75,60 @@ __device__ __forceinline__ bool isect_atmosphere(v3 ro, v3 rd, float& t1) {
 //   * ATM_TAU4K tests its own precondition on the wave, whatever the rays are.
 //   * DEAD RAYS (atm_incident_light below): no optical depth can overflow (every density term is <= e^.001 * step), so the test is
 //     never true for these rays; k_atmosphere_ground compiles it OUT (DEAD = false) rather than carry a ballot per view sample.
+// CALLER'S RAYS (k_atmosphere_eval, sbx_atmosphere_eval: any origin, any direction, any sun).  Nothing above holds for a ray the
+// kernel has not looked at, so the FIN forms run only on a wave whose 64 rays ALL pass atm_eval_class() below, and only in a launch
+// whose sun direction the host has found finite with |dot(sun, sun) - 1| <= 1e-4 (atm_eval_sun_ok); every other wave, and every wave
+// of every other launch, runs the plain statement (FIN = false), which is correct for every bit pattern.  The class, in the binary32
+// values isect_atmosphere itself computes (oo = dot(rc, rc), tca, d2 = oo - tca^2; R = atmosphere_radius, Re = earth_radius):
+//     oo <= R^2   and   d2 >= 1e12   and   |dot(rd, rd) - 1| <= 1e-4
+// A NaN fails each comparison and an inf component makes oo or dot(rd, rd) inf or NaN, so all six components are finite; |rd|^2 and
+// |sun|^2 are within 1.01e-4 of 1 in exact arithmetic (the binary32 dots carry 2e-7).  Roundings of the quantities of magnitude R^2 =
+// 4.1e13 (ulp 4.2e6) and of the positions (ulp .5 m at 6.4e6 m) add up to E <= 2e8 m^2 in every squared distance below.  Three facts:
+//   (a) NO SAMPLE IS FAR OUTSIDE THE SPHERE.  Along p(t) = o + d t the squared distance f(t) = |o|^2 - 2 t tca + t^2 |d|^2 is convex,
+//       and t1 = tca + thc with thc^2 = R^2 - oo + tca^2 gives f(t1) = R^2 + t1^2 (|d|^2 - 1).  |t1| <= 2.0006 R (|tca| <= 1.0001 R;
+//       d2 >= -1.01e-4 oo, so thc <= 1.0001 R), hence every sample of a march whose origin has |o|^2 <= R^2 + 1.7e10 has
+//       |p|^2 <= max(f(0), f(t1)) <= R^2 + 1.7e10 + E, i.e. |p| <= R + 1.4 km — whatever the sign of t1, for the view march (origin in
+//       the class) and then for every light march (origin a view sample, direction the checked sun).
+//   (b) EVERY VIEW SAMPLE IS FAR FROM THE CENTRE.  The ray's line passes the centre at squared distance oo - tca^2 / |d|^2, which
+//       differs from d2 by at most 1.01e-4 oo + E <= 4.4e9: every view sample has |s| >= sqrt(1e12 - 4.4e9) - 2 > 9.97e5 m.
+//   (c) A VIEW SAMPLE OF A LONG CHORD IS INSIDE THE SPHERE.  At t = lambda t1, lambda in [1/32, 31/32] (sixteen mid-points; the
+//       accumulated march_pos moves lambda by 1e-6), the identity t1^2 - 2 t1 tca = R^2 - oo gives
+//       f = (1 - lambda) oo + lambda R^2 - lambda (1 - lambda |d|^2) t1^2 <= R^2 - .03 t1^2: strictly inside, with room for E, once
+//       t1 >= 140 km (.03 t1^2 >= 5.9e8).  The light ray of such a sample has a t1 that is a number: isect_atmosphere computes its
+//       d2' = oo' - tca'^2 <= oo' (a square is subtracted and rounding is monotone), oo' is within E of |s|^2 <= R^2 - 5.9e8, so
+//       R^2 - d2' >= 5.9e8 - E > 0 and the root is taken of a positive number.
+// The shortcuts, one by one:
+//   * ATM_SQRT_RS (|s|^2 in [2^-102, inf)).  View samples: (b) and (a), 9.9e11 <= |s|^2 <= 4.2e13.  Light samples: the first one lies
+//     |t1'| / 16 * |sun| <= 2.0006 R / 16 * 1.0001 = 8.03e5 m from its view sample, so it is >= 9.97e5 - 8.03e5 = 1.9e5 m from the centre;
+//     every later one is reached only if the one before it was above the ground (:65-67) and lies <= 1.61e6 m from that, >= 4.7e6 m
+//     from the centre; (a) bounds them above.  A light ray that MISSES the sphere — possible only from a view sample that (a) lets lie
+//     up to 1.4 km outside it — has t1' = NaN: every position, length, quotient, exp and sum of that march is NaN in both forms
+//     (sqrt_rs_, div3_ and exp_reg4k_ each return NaN for a NaN: sbx_math.h; exp_reg4k_'s table index is masked), height < 0 is false
+//     in both, the sample is "lit" in both, tau is NaN, the ATM_TAU4K ballot sends the wave to the guarded exp, and the pixel is NaN.
+//   * ATM_DIV3 (dividend 0 or in [2^-100, 2^100]; the quotient only feeds exp, so the sign of a zero is not used).  View samples:
+//     |s| >= 2^19 by (b), so |s| and Re are multiples of 1/16 and height = RN(|s| - Re) is 0 or has 1/16 <= |height| <= 5.4e6.  Light
+//     samples reach the division only with height >= 0: |s| >= Re, height 0 or a multiple of .5 up to 61.4e3 (or NaN, above).
+//   * exp_reg4k_ on -height / H (arguments in [-80, 2^18]).  By (a) height <= 61.4e3: -height / H >= -51.2.  By (b) a view sample has
+//     height >= -5.37e6: -height / H <= 4475; a light sample's argument is <= 0.
+//   * ATM_TAU4K tests its own precondition on the wave, whatever the rays are.
+//   * DEAD RAYS: compiled IN (DEAD = true) — callers' rays do look below the horizon (half of a dome of them), and those are the rays
+//     the exit was written for.  Its argument needs, for every sample after the overflow, (1) the light march's t1' a number (a NaN
+//     tau would make the reference's pixel NaN where the exit adds nothing) and (2) hr, hm finite where the sample is lit.  An
+//     optical depth overflows only with a sample more than 80 km under the ground (sixteen terms of e^(-height / hM) * step,
+//     step <= 8.1e5), which is more than 140 km from the sphere: t1 >= 140 km and (c) gives (1) for every sample of the ray.  (2): the
+//     height along the light ray is convex in t (a norm along a line) and is <= 61.4e3 at t1' by (a), so the first light sample, at
+//     t1' / 16, is above the ground only if 15 / 16 of the view sample's depth is <= 61.4e3 / 16: a lit sample is at most 4.1 km
+//     under the ground, hr and hm <= e^3.5 * step.  Lanes that do not enter the march (d2 < R^2 false: (0, 0, 0)) are not counted
+//     by its ballots; lanes past n march (0, Re + 1, 0) + t (1, 0, 0), a ray of the class, and drop the result.
+// get_sun_light alone (the entry's second function: sun_light<FIN> along the caller's ray) uses the same class: its samples are view
+// samples in the sense of (a) and (b), its t1 is a number (d2 <= oo <= R^2), and it divides and exponentiates only with height >= 0.
+constexpr float ATM_EVAL_D2_MIN = 1e12f, ATM_EVAL_UNIT_TOL = 1e-4f;
+__device__ __forceinline__ bool atm_eval_class(v3 ro, v3 rd) {
+    const v3 rc = V3(0, 0, 0) - ro;
+    const float oo = dot(rc, rc), tca = dot(rc, rd);
+    const float d2 = oo - tca * tca;
+    return oo <= ATM_ATMOS_R * ATM_ATMOS_R && d2 >= ATM_EVAL_D2_MIN && fabsf(dot(rd, rd) - 1.0f) <= ATM_EVAL_UNIT_TOL;
+}
 // PREC = 1: the TOLERANCE tier (include/sbx.h sbx_set_precision, SBX_PRECISION_1E4; opt-in, never the default, never in bench.py's
 // `value`).  north_star's bar is 1e-4 per channel, not bit-equality, and this kernel — 336 exp per in-dome pixel, each 15 instructions
 // of binary64 table arithmetic — has no threshold that turns a rounding difference into a different pixel: every exp becomes

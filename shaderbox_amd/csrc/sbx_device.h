@@ -200,6 +200,8 @@ size_t func_table_bytes();
 int launch_noise_eval(int fn, const float* xyz, const float* par, float* out, size_t n, hipStream_t s);
 void launch_worley_volume(int size, float* out, hipStream_t s);
 void launch_exp4k_eval(const float* a, float* out, size_t n, hipStream_t s);
+// sbx_atmosphere_eval (kern_atmosphere.hip): fn 0 get_incident_light / 1 get_sun_light; plain = the plain kernel for every wave
+void launch_atmosphere_eval(int fn, bool plain, const float* rays, const float* sun_dir, float* out, size_t n, unsigned* fast_waves, hipStream_t s);
 int launch_math_eval(int fn, const float* a, const float* b, float* out, size_t n, hipStream_t s);
 void launch_cl_exp_eval(const float* a, float* out, size_t n, hipStream_t s, int form);   // exp_reg_ / exp_reg128_ forms (kern_clouds.hip)
 

@@ -53,6 +53,50 @@ int sbx_noise_eval(sbx_ctx* ctx, const char* fn, const float* xyz, const float* 
     return launched(ctx, "noise_eval launch");
 }
 
+// the checks sbx_atmosphere_eval and its test hook share: SBX_OK with fn_id set, or the failure
+static int atmosphere_eval_args(sbx_ctx* ctx, const char* fn, const float* rays, const float* sun_dir, const float* out, size_t n, int& fn_id) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!fn) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    fn_id = std::strcmp(fn, "get_incident_light") == 0 ? 0 : std::strcmp(fn, "get_sun_light") == 0 ? 1 : -1;
+    if (fn_id < 0) return fail(ctx, SBX_ERR_ARG, "unknown atmosphere function");
+    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 rays");
+    if (n == 0) return SBX_OK;
+    if (!rays || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    if (fn_id == 0 && !sun_dir) return fail(ctx, SBX_ERR_ARG, "get_incident_light needs sun_dir");
+    return SBX_OK;
+}
+
+int sbx_atmosphere_eval(sbx_ctx* ctx, const char* fn, const float* rays, const float* sun_dir, float* out, size_t n, void* stream) {
+    int id = -1;
+    int rc = atmosphere_eval_args(ctx, fn, rays, sun_dir, out, n, id);
+    if (rc != SBX_OK || n == 0) return rc;
+    if ((rc = use_device(ctx)) != SBX_OK) return rc;
+    launch_atmosphere_eval(id, ctx->variant == 1, rays, sun_dir, out, n, nullptr, (hipStream_t)stream);
+    return launched(ctx, "atmosphere_eval launch");
+}
+
+int sbx_debug_atmosphere_eval(sbx_ctx* ctx, const char* fn, const float* rays, const float* sun_dir, float* out, size_t n,
+                              unsigned* fast_waves_host, void* stream) {
+    int id = -1;
+    int rc = atmosphere_eval_args(ctx, fn, rays, sun_dir, out, n, id);
+    if (rc != SBX_OK) return rc;
+    if (!fast_waves_host) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    *fast_waves_host = 0;
+    if (n == 0) return SBX_OK;
+    if ((rc = use_device(ctx)) != SBX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned* counter = nullptr;
+    hipError_t e = hipMalloc((void**)&counter, sizeof(unsigned));
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
+    if ((e = hipMemsetAsync(counter, 0, sizeof(unsigned), s)) == hipSuccess) {
+        launch_atmosphere_eval(id, ctx->variant == 1, rays, sun_dir, out, n, counter, s);
+        if ((e = hipGetLastError()) == hipSuccess && (e = hipMemcpyAsync(fast_waves_host, counter, sizeof(unsigned), hipMemcpyDeviceToHost, s)) == hipSuccess)
+            e = hipStreamSynchronize(s);
+    }
+    (void)hipFree(counter);
+    return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "atmosphere_eval (counted)", e);
+}
+
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream) {
     if (!ctx) return SBX_ERR_ARG;
     if (!rgba || size <= 0 || size > 1024) return fail(ctx, SBX_ERR_ARG, "bad volume arguments");

@@ -19,6 +19,9 @@
 //              its `#if 0` at :357 on (the ridge of label and logo) / its `#if 1` at :445 off (no shadow march); 60 march steps each
 //     app "planet_closeup" / "planet_cloudless" / "planet_unlit": src/app_planet.h with its `#if 0` at :51 on (the camera of :52-53) /
 //              without its `#define CLOUDS` at :63 (no cloud march, no cloud shadow) / without its `#define LIGHT` at :249 (unlit terrain)
+//     app "raytracer_scene": src/app_raytracer.h's render over the caller's scene (SBX_APP_RAYTRACER_SCENE, include/sbx.h):
+//              --scene-bin FILE   the raw 1376 bytes of an sbx_aux_raytracer_scene (any other size is refused); without it the
+//              Cornell box of --time and --mouse (sbx_raytracer_scene_cornell), SBX_APP_RAYTRACER's frame
 //     app "2d" / "2d_tex": src/app_2d.h (its alpha is not 1: the .f32 frames carry it; single GPU only), the USE_TEXTURE build
 //              reading hlsltoy's default 128x128 checkerboard at t0
 //     app "func": src/app_func.h, the tiled Worley fBm of its compiled 2D branch (grey, alpha 1; u_time and --mouse do not enter)
@@ -46,8 +49,8 @@ static int app_from_name(const std::string& s) {
     const char* names[] = {"planet", "clouds", "vinyl", "egg", "raytracer", "atmosphere", "sdf_ao", "clouds_best", "clouds_tex", "clouds_ue4",
                            "clouds_sky", "vinyl_gpu", "planet_atmosphere", "2d", "2d_tex", "func", "atmosphere_ground", "sdf_ao_shadow", "sdf_ao_normals",
                            "egg_straight", "egg_oval", "clouds_height", "clouds_luminance", "raytracer_phong", "raytracer_noshadow", "raytracer_static",
-                           "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow", "planet_closeup", "planet_cloudless", "planet_unlit"};
-    const int n = 32;
+                           "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow", "planet_closeup", "planet_cloudless", "planet_unlit", "raytracer_scene"};
+    const int n = 33;
     std::string low;
     for (char c : s) low += (char)tolower(c);
     for (int i = 0; i < n; ++i)
@@ -101,7 +104,7 @@ static bool read_dds_volume(const std::string& path, int& size, std::vector<floa
 }
 
 int main(int argc, char** argv) {
-    std::string app = "clouds", ppm, f32, noise_tex;
+    std::string app = "clouds", ppm, f32, noise_tex, scene_bin;
     int W = 1280, H = 720, frames = 1, gpus = 1, exchange = SBX_MULTI_EXCHANGE_SPANS;
     float t = 0.37f, dt = 1.f / 30.f, mx = 0, my = 0;
     sbx_aux_clouds ac;
@@ -129,6 +132,7 @@ int main(int argc, char** argv) {
         else if (a == "--f32") f32 = next();
         else if (a == "--rgba8") rgba8_out = true;
         else if (a == "--noise-tex") noise_tex = next();
+        else if (a == "--scene-bin") scene_bin = next();
         else if (a == "--wind") { vec3(ac.wind_dir); have_ac = true; }
         else if (a == "--sun") { vec3(ac.sun_dir); have_ac = true; }
         else if (a == "--sun-color") { vec3(ac.sun_color); have_ac = true; }
@@ -153,6 +157,17 @@ int main(int argc, char** argv) {
     const void* aux = nullptr;
     if ((id == SBX_APP_CLOUDS || id == SBX_APP_CLOUDS_TEX || id == SBX_APP_CLOUDS_SKY || id == SBX_APP_CLOUDS_HEIGHT || id == SBX_APP_CLOUDS_LUMINANCE) && have_ac) aux = &ac;
     if ((id == SBX_APP_SDF_AO || id == SBX_APP_SDF_AO_SHADOW || id == SBX_APP_SDF_AO_NORMALS) && have_as) aux = &as;
+    sbx_aux_raytracer_scene scene;
+    if (!scene_bin.empty()) {
+        if (id != SBX_APP_RAYTRACER_SCENE) { fprintf(stderr, "--scene-bin belongs to --app raytracer_scene\n"); return 2; }
+        FILE* fp = fopen(scene_bin.c_str(), "rb");
+        if (!fp) { perror(scene_bin.c_str()); return 1; }
+        char extra;
+        const bool ok = fread(&scene, 1, sizeof(scene), fp) == sizeof(scene) && fread(&extra, 1, 1, fp) == 0;
+        fclose(fp);
+        if (!ok) { fprintf(stderr, "%s: a scene file holds the %zu bytes of an sbx_aux_raytracer_scene and nothing else\n", scene_bin.c_str(), sizeof(scene)); return 2; }
+        aux = &scene;
+    }
 
     sbx_ctx* ctx = nullptr;
     int rc = sbx_create(0, &ctx);

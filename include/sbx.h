@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm" and sbx_atmosphere_eval: new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell: new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -252,7 +252,35 @@ typedef enum sbx_app {
        evaluated.  Clouds and their ground shadow as shipped.  No NaN pixel in any recorded frame (N == 1 needs a hit on the planet's
        y axis).  Everything else, the output forms, the variant and what is not offered as SBX_APP_PLANET_CLOSEUP says; the camera is
        the shipped one. */
-    SBX_APP_PLANET_UNLIT = 31
+    SBX_APP_PLANET_UNLIT = 31,
+    /* The raytracer over the CALLER'S scene: what the reference's README lists as its "minimal raytracer framework" and "minimal
+       Cook-Torrance lighting and material setup".  mainImage of src/main.h:6-53 over render of src/app_raytracer.h:88-136, with the
+       scene, the camera and the FOV taken from the aux block sbx_aux_raytracer_scene (below) instead of setup_scene / setup_camera /
+       :138.  u_res is read; u_time and u_mouse are not.  aux == NULL means sbx_raytracer_scene_cornell(uni, 0, .): SBX_APP_RAYTRACER's
+       frame.  Alpha is 1, so every output form holds it (rows, host rows, points, sbx_main_image*, ranks, splits, rgb, the exchanges
+       with whole rows: sbx_span_table has no model for it; SBX_FORMAT_RGBA8, sbx_multi_render).
+       SEMANTICS, all as the reference's code has them (tests/raytracer_scene_model.py is the definition):
+         - planes and spheres are taken in array order, as raytrace_iteration does (:75-83); a later primitive replaces an earlier one
+           at equal t.  Planes are never skipped.  In the shadow trace spheres whose material is 0 are skipped (mat_to_ignore =
+           mat_debug, :116): a material-0 sphere is the reference's light bulb, drawn flat with materials[0].base_color (:51-53), and
+           it casts no shadow.  A sphere whose material is -1 (mat_invalid, the mat_to_ignore of :97) is never intersected;
+         - a material id outside 0..7 gives the zero material (get_material's loop finds nothing, material.h:19-36);
+         - metallic, translucency and light_color are carried but not read;
+         - normals and light_L are never normalised: intersect_plane (src/intersect.h:61-77) uses `direction` as given, with its
+           P0 = (distance, distance, distance), its `denom < 1e-6` and its `t < 0 || t > hit.t`;
+         - with LIGHT_DIR, illuminate takes L = light_L as given (light.h:22-23); the shadow ray still uses light_L - hit.origin (:109,
+           the reference's TODO);
+         - the background is black (:13-16);
+         - the shadow ray is cast on bounce 0 only; illuminate takes the PRIMARY origin on every bounce (:105); reflect's swapped
+           arguments are kept (:127);
+         - every float bit pattern is data: NaN, inf, denormals, a zero radius or normal flow through as the reference's operations
+           make them.
+       SBX_ERR_ARG, before anything is enqueued, for n_planes or n_spheres outside 0..16, bounces outside 1..8, or a light_type /
+       lighting / shadow outside the values listed at the block.
+       sbx_set_variant as for SBX_APP_RAYTRACER: 1 and 3 select the IEEE roots and normalisations, 2 forces the witness re-run.
+       NOT OFFERED: more than one light (the reference reads lights[0]), refraction, other primitives, more than 16 + 16 primitives,
+       an acceleration structure, and the drop-in header sbx_mainimage.hpp, which has no way to state a scene. */
+    SBX_APP_RAYTRACER_SCENE = 32
 } sbx_app;
 
 typedef enum sbx_status {
@@ -304,6 +332,29 @@ typedef struct sbx_aux_clouds_ue4 {
     float wind_dir[3];   int32_t use_dirs;              /* c2   use_dirs = 0: SUN_DIR / WIND_DIR of the shader */
 } sbx_aux_clouds_ue4;
 void sbx_aux_clouds_ue4_defaults(sbx_aux_clouds_ue4* aux);
+
+/* the scene of SBX_APP_RAYTRACER_SCENE: plain data, 1376 bytes, in 16-byte registers like the other blocks */
+#define SBX_RT_MAX_PLANES 16
+#define SBX_RT_MAX_SPHERES 16
+typedef struct sbx_rt_material { float base_color[3]; float metallic, roughness, ior, reflectivity, translucency; } sbx_rt_material; /* material.h:5-12; 32 B */
+typedef struct sbx_rt_plane  { float direction[3]; float distance; int32_t material; int32_t _pad[3]; } sbx_rt_plane;   /* 32 B */
+typedef struct sbx_rt_sphere { float origin[3];    float radius;   int32_t material; int32_t _pad[3]; } sbx_rt_sphere;  /* 32 B */
+typedef struct sbx_aux_raytracer_scene {
+    float eye[3];         float fov;            /* c0  fov = the FOV factor of main.h:45, used as given */
+    float look_at[3];     int32_t bounces;      /* c1  the `2` of app_raytracer.h:96; 1..8 */
+    float light_L[3];     int32_t light_type;   /* c2  lights[0]: 1 = LIGHT_POINT, 2 = LIGHT_DIR (light.h:5-12) */
+    float light_color[3]; int32_t lighting;     /* c3  0 = illum_cook_torrance, 1 = illum_blinn_phong's Phong branch (:61) */
+    float ambient[3];     int32_t shadow;       /* c4  ambient_light (light.h:16); shadow 1 = the `#if 1` of :107, 0 = off */
+    int32_t n_planes, n_spheres, _pad[2];       /* c5  0..16 each */
+    sbx_rt_material materials[8];               /* num_materials slots; id 0 is mat_debug */
+    sbx_rt_plane planes[SBX_RT_MAX_PLANES];     /* taken in array order, as raytrace_iteration does */
+    sbx_rt_sphere spheres[SBX_RT_MAX_SPHERES];
+} sbx_aux_raytracer_scene;
+/* Host only, no context: what setup_scene + setup_camera + :138 of src/app_raytracer.h make of these uniforms — the u_mouse rotation
+ * of the eye, the u_time animation of the left sphere, the right sphere and the light (unless at_rest: the `#if 0` of :29, u_time not
+ * read), fov = tan(radians(30.)) of the math spec, bounces 2, point light, Cook-Torrance, shadow on, ambient .01, 6 planes, 3 spheres.
+ * The block SBX_APP_RAYTRACER_SCENE renders when aux is NULL is this one with at_rest = 0. */
+void sbx_raytracer_scene_cornell(const sbx_uniforms* uni, int at_rest, sbx_aux_raytracer_scene* out);
 
 typedef struct sbx_ctx sbx_ctx;
 

@@ -29,6 +29,7 @@ extern "C" {
  * SBX_APP_CLOUDS_HEIGHT / SBX_APP_CLOUDS_LUMINANCE: as for APP_CLOUDS, 1 = the per-lane kernel of the build.
  * APP_RAYTRACER and SBX_APP_RAYTRACER_PHONG / _NOSHADOW / _STATIC alike: 1 = the IEEE roots and normalisations with the six-plane loop of
  * raytrace_iteration; 2 = the witness's test edge; 3 = the IEEE roots and normalisations; each over the build's own code and frame.
+ * SBX_APP_RAYTRACER_SCENE: 1 and 3 = the IEEE roots, normalisations and sphere-normal quotients; 2 = the witness's test edge.
  * SBX_APP_VINYL_CLOSEUP / _RIDGES / _NOSHADOW: every value as for APP_VINYL, over the build's own code and frame.
  * SBX_APP_PLANET_CLOSEUP / _CLOUDLESS / _UNLIT: as for APP_PLANET, 1 = the build without its exact skips.
  * sbx_atmosphere_eval: 1 = the plain statement of src/app_atmosphere.h:50-160 lane by lane for every wave (no class test, guarded exp,
@@ -96,6 +97,10 @@ int sbx_debug_tile_order(sbx_ctx* ctx, int app, int* tables_built, int* launches
  * of its own, nothing of the context's tables is touched.  gx, gy outside 1 ... 0xffff (the bound of a launch that takes a table): SBX_ERR_ARG.
  * For the test that the table is a permutation, longest cost class first, whatever the words hold (tests/test_gpu_tile_order.py). */
 int sbx_debug_order_build(sbx_ctx* ctx, const unsigned* cost_host, int gx, int gy, unsigned* table_host, void* stream);
+
+/* Launches of k_raytracer_scene (SBX_APP_RAYTRACER_SCENE's kernel, csrc/kern_raytracer.hip) this context has enqueued since its
+ * creation: for the test that a scene block equal to the Cornell box is rendered by the scene kernel, not handed to k_raytracer. */
+int sbx_debug_raytracer_scene_launches(sbx_ctx* ctx, uint64_t* launches);
 
 #ifdef __cplusplus
 }

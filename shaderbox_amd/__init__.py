@@ -17,7 +17,7 @@ from . import shard  # noqa: F401  (pure-python row-block arithmetic, no GPU nee
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsbx.so")
 
-APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW, APP_PLANET_CLOSEUP, APP_PLANET_CLOUDLESS, APP_PLANET_UNLIT = range(32)
+APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW, APP_PLANET_CLOSEUP, APP_PLANET_CLOUDLESS, APP_PLANET_UNLIT, APP_RAYTRACER_SCENE = range(33)
 APPS = {"APP_PLANET": APP_PLANET, "APP_CLOUDS": APP_CLOUDS, "APP_VINYL": APP_VINYL, "APP_EGG": APP_EGG,
         "APP_RAYTRACER": APP_RAYTRACER, "APP_ATMOSPHERE": APP_ATMOSPHERE, "APP_SDF_AO": APP_SDF_AO,
         "APP_CLOUDS_BEST": APP_CLOUDS_BEST,    # src/app_clouds_best.h (stand-alone shader, not an APP_* define)
@@ -46,7 +46,8 @@ MORE_APPS = {"APP_EGG_STRAIGHT": APP_EGG_STRAIGHT,  # APP_EGG without `#define B
              "APP_VINYL_NOSHADOW": APP_VINYL_NOSHADOW,  # APP_VINYL with the `#if 1` at src/app_vinyl.h:445 off: no sdf_shadow march
              "APP_PLANET_CLOSEUP": APP_PLANET_CLOSEUP,      # APP_PLANET with the `#if 0` at src/app_planet.h:51 on: the camera of :52-53
              "APP_PLANET_CLOUDLESS": APP_PLANET_CLOUDLESS,  # APP_PLANET without the `#define CLOUDS` of src/app_planet.h:63: no cloud march, no cloud shadow
-             "APP_PLANET_UNLIT": APP_PLANET_UNLIT}          # APP_PLANET without the `#define LIGHT` of src/app_planet.h:249: N = w_normal.y, ocean = water
+             "APP_PLANET_UNLIT": APP_PLANET_UNLIT,          # APP_PLANET without the `#define LIGHT` of src/app_planet.h:249: N = w_normal.y, ocean = water
+             "APP_RAYTRACER_SCENE": APP_RAYTRACER_SCENE}    # src/app_raytracer.h's render over the caller's scene: aux = a RaytracerScene (cornell_scene, raytracer_scene)
 ALL_APPS = {**APPS, **MORE_APPS}
 
 SBX_OK, SBX_ERR_ARG, SBX_ERR_UNSUPPORTED, SBX_ERR_HIP, SBX_ERR_NO_DEVICE, SBX_ERR_FAULT = 0, -1, -2, -3, -4, -5
@@ -83,6 +84,36 @@ class AuxCloudsUe4(ctypes.Structure):       # sbx_aux_clouds_ue4
 
 class AuxSdfAo(ctypes.Structure):           # sbx_aux_sdf_ao (cbuffer b1, APP_SDF_AO)
     _fields_ = [("fog_density", ctypes.c_float), ("fog_falloff", ctypes.c_float), ("_pad", ctypes.c_float * 2)]
+
+
+class RtMaterial(ctypes.Structure):         # sbx_rt_material (material.h:5-12)
+    _fields_ = [("base_color", ctypes.c_float * 3), ("metallic", ctypes.c_float), ("roughness", ctypes.c_float),
+                ("ior", ctypes.c_float), ("reflectivity", ctypes.c_float), ("translucency", ctypes.c_float)]
+
+
+class RtPlane(ctypes.Structure):            # sbx_rt_plane
+    _fields_ = [("direction", ctypes.c_float * 3), ("distance", ctypes.c_float), ("material", ctypes.c_int32),
+                ("_pad", ctypes.c_int32 * 3)]
+
+
+class RtSphere(ctypes.Structure):           # sbx_rt_sphere
+    _fields_ = [("origin", ctypes.c_float * 3), ("radius", ctypes.c_float), ("material", ctypes.c_int32),
+                ("_pad", ctypes.c_int32 * 3)]
+
+
+RT_MAX_PLANES = RT_MAX_SPHERES = 16          # SBX_RT_MAX_PLANES, SBX_RT_MAX_SPHERES
+LIGHT_POINT, LIGHT_DIR = 1, 2                # light.h:5-6
+LIGHTING_COOK_TORRANCE, LIGHTING_PHONG = 0, 1
+
+
+class RaytracerScene(ctypes.Structure):     # sbx_aux_raytracer_scene (the aux block of APP_RAYTRACER_SCENE, 1376 bytes)
+    _fields_ = [("eye", ctypes.c_float * 3), ("fov", ctypes.c_float),
+                ("look_at", ctypes.c_float * 3), ("bounces", ctypes.c_int32),
+                ("light_L", ctypes.c_float * 3), ("light_type", ctypes.c_int32),
+                ("light_color", ctypes.c_float * 3), ("lighting", ctypes.c_int32),
+                ("ambient", ctypes.c_float * 3), ("shadow", ctypes.c_int32),
+                ("n_planes", ctypes.c_int32), ("n_spheres", ctypes.c_int32), ("_pad", ctypes.c_int32 * 2),
+                ("materials", RtMaterial * 8), ("planes", RtPlane * RT_MAX_PLANES), ("spheres", RtSphere * RT_MAX_SPHERES)]
 
 
 class Stats(ctypes.Structure):              # sbx_stats
@@ -137,6 +168,9 @@ def load_library(path=None):
     lib.sbx_aux_sdf_ao_defaults.restype = None
     lib.sbx_aux_clouds_ue4_defaults.argtypes = [ctypes.POINTER(AuxCloudsUe4)]
     lib.sbx_aux_clouds_ue4_defaults.restype = None
+    lib.sbx_raytracer_scene_cornell.argtypes = [ctypes.POINTER(Uniforms), ci, ctypes.POINTER(RaytracerScene)]
+    lib.sbx_raytracer_scene_cornell.restype = None
+    lib.sbx_debug_raytracer_scene_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.sbx_create.argtypes = [ci, ctypes.POINTER(vp)]
     lib.sbx_destroy.argtypes = [vp]
     lib.sbx_destroy.restype = None
@@ -236,6 +270,51 @@ def sdf_ao_defaults(lib=None):
     lib = lib or load_library()
     a = AuxSdfAo()
     lib.sbx_aux_sdf_ao_defaults(ctypes.byref(a))
+    return a
+
+
+def cornell_scene(width, height, time, mouse=(0.0, 0.0), at_rest=False, lib=None):
+    """sbx_raytracer_scene_cornell (host only, no GPU needed): the RaytracerScene that src/app_raytracer.h's setup_scene, setup_camera
+    and FOV make of these uniforms — what APP_RAYTRACER_SCENE renders when aux is None.  at_rest: the `#if 1` of :29 off, `time`
+    is not read."""
+    lib = lib or load_library()
+    u = uniforms(width, height, time, mouse)
+    a = RaytracerScene()
+    lib.sbx_raytracer_scene_cornell(ctypes.byref(u), 1 if at_rest else 0, ctypes.byref(a))
+    return a
+
+
+def raytracer_scene(planes=(), spheres=(), materials=(), light=(0.0, 3.8, 1.5), eye=(0.0, 2.0, 4.666), look_at=(0.0, 2.0, 0.0),
+                    fov=0.57735026, bounces=2, light_type=LIGHT_POINT, lighting=LIGHTING_COOK_TORRANCE, shadow=True,
+                    ambient=(0.01, 0.01, 0.01), light_color=(1.0, 1.0, 1.0)):
+    """A RaytracerScene (the aux block of APP_RAYTRACER_SCENE) from plain Python values; the counts are filled from the lists.
+        planes     [(direction xyz, distance, material id)]            at most 16; used as given, never normalised
+        spheres    [(origin xyz, radius, material id)]                 at most 16; material 0 = the light bulb (flat, casts no shadow)
+        materials  {id: dict(base_color=.., roughness=.., ior=.., reflectivity=.., metallic=.., translucency=..)} or a list of
+                   such dicts for the ids 0, 1, ...; missing fields default to base_color (0, 0, 0), roughness .5, ior 1, the others 0;
+                   slots not given stay zero
+        light      lights[0].L: the position (LIGHT_POINT) or the direction to the light (LIGHT_DIR), used as given
+        fov        the FOV factor of main.h:45 (tan of half the vertical angle); the default is tan(30 degrees)
+    Values outside the ranges of include/sbx.h are refused by the render call (SBX_ERR_ARG), not here."""
+    if len(planes) > RT_MAX_PLANES or len(spheres) > RT_MAX_SPHERES:
+        raise ValueError("a scene holds at most %d planes and %d spheres" % (RT_MAX_PLANES, RT_MAX_SPHERES))
+    a = RaytracerScene()
+    a.eye[:], a.look_at[:], a.light_L[:] = [float(v) for v in eye], [float(v) for v in look_at], [float(v) for v in light]
+    a.light_color[:], a.ambient[:] = [float(v) for v in light_color], [float(v) for v in ambient]
+    a.fov, a.bounces, a.light_type, a.lighting, a.shadow = float(fov), int(bounces), int(light_type), int(lighting), int(bool(shadow))
+    a.n_planes, a.n_spheres = len(planes), len(spheres)
+    items = materials.items() if hasattr(materials, "items") else enumerate(materials)
+    for i, m in items:
+        if not 0 <= int(i) < 8:
+            raise ValueError("material ids are 0..7")
+        s = a.materials[int(i)]
+        s.base_color[:] = [float(v) for v in m.get("base_color", (0.0, 0.0, 0.0))]
+        s.roughness, s.ior = float(m.get("roughness", 0.5)), float(m.get("ior", 1.0))
+        s.reflectivity, s.metallic, s.translucency = float(m.get("reflectivity", 0.0)), float(m.get("metallic", 0.0)), float(m.get("translucency", 0.0))
+    for i, (n, d, mat) in enumerate(planes):
+        a.planes[i].direction[:], a.planes[i].distance, a.planes[i].material = [float(v) for v in n], float(d), int(mat)
+    for i, (o, r, mat) in enumerate(spheres):
+        a.spheres[i].origin[:], a.spheres[i].radius, a.spheres[i].material = [float(v) for v in o], float(r), int(mat)
     return a
 
 
@@ -577,6 +656,12 @@ class Renderer:
         st = Stats()
         self._check(self.lib.sbx_get_stats(self.ctx, ctypes.byref(st)))
         return {k: int(getattr(st, k)) for k in ("render_launches", "main_image_hits", "main_image_frames", "main_image_points")}
+
+    def raytracer_scene_launches(self):
+        """include/sbx_test.h sbx_debug_raytracer_scene_launches: launches of APP_RAYTRACER_SCENE's own kernel by this context"""
+        n = ctypes.c_uint64(0)
+        self._check(self.lib.sbx_debug_raytracer_scene_launches(self.ctx, ctypes.byref(n)))
+        return int(n.value)
 
     def reset_stats(self):
         self._check(self.lib.sbx_reset_stats(self.ctx))

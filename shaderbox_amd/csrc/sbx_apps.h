@@ -8,7 +8,7 @@
 
 namespace sbx {
 
-constexpr int SBX_APP_COUNT = SBX_APP_PLANET_UNLIT + 1;
+constexpr int SBX_APP_COUNT = SBX_APP_RAYTRACER_SCENE + 1;
 // (sbx_debug_tile_order, include/sbx_test.h, answers for every app — the builds after SBX_APP_FUNC that have an order grid below
 // included; an app without one never has a table: 0 tables, 0 launches, nothing to copy)
 
@@ -22,7 +22,7 @@ constexpr int SBX_APP_COUNT = SBX_APP_PLANET_UNLIT + 1;
 //                      the table's key — a scene that stands still gets its table, a moving one never does
 enum { TILE_SCENE_FREE = 0, TILE_SCENE_REFRESH = 1, TILE_SCENE_KEYED = 2 };
 
-enum AuxKind { AUX_NONE, AUX_CLOUDS, AUX_SDF_AO, AUX_CLOUDS_UE4 };   // which block `aux` points to: sbx_aux_clouds, sbx_aux_sdf_ao, sbx_aux_clouds_ue4
+enum AuxKind { AUX_NONE, AUX_CLOUDS, AUX_SDF_AO, AUX_CLOUDS_UE4, AUX_RT_SCENE };   // which block `aux` points to: sbx_aux_clouds, sbx_aux_sdf_ao, sbx_aux_clouds_ue4, sbx_aux_raytracer_scene
 
 struct AppTraits {
     AuxKind aux;
@@ -66,6 +66,7 @@ constexpr AppTraits kApps[] = {
     /* SBX_APP_PLANET_CLOSEUP    */ {AUX_NONE, false, false, nullptr, TILE_SCENE_FREE},
     /* SBX_APP_PLANET_CLOUDLESS  */ {AUX_NONE, false, false, nullptr, TILE_SCENE_FREE},
     /* SBX_APP_PLANET_UNLIT      */ {AUX_NONE, false, false, nullptr, TILE_SCENE_FREE},
+    /* SBX_APP_RAYTRACER_SCENE   */ {AUX_RT_SCENE, false, false, nullptr, TILE_SCENE_FREE},
 };
 static_assert(sizeof(kApps) / sizeof(kApps[0]) == SBX_APP_COUNT, "every value of enum sbx_app needs its row in kApps");
 
@@ -77,6 +78,7 @@ inline int app_aux_bytes(int app) {
     case AUX_CLOUDS: return (int)sizeof(sbx_aux_clouds);
     case AUX_SDF_AO: return (int)sizeof(sbx_aux_sdf_ao);
     case AUX_CLOUDS_UE4: return (int)sizeof(sbx_aux_clouds_ue4);
+    case AUX_RT_SCENE: return (int)sizeof(sbx_aux_raytracer_scene);
     default: return 0;
     }
 }
@@ -89,5 +91,11 @@ template <class A> inline A aux_or(const void* aux, void (*defaults)(A*)) {
 inline sbx_aux_clouds aux_clouds(const void* aux) { return aux_or<sbx_aux_clouds>(aux, sbx_aux_clouds_defaults); }
 inline sbx_aux_sdf_ao aux_sdf_ao(const void* aux) { return aux_or<sbx_aux_sdf_ao>(aux, sbx_aux_sdf_ao_defaults); }
 inline sbx_aux_clouds_ue4 aux_clouds_ue4(const void* aux) { return aux_or<sbx_aux_clouds_ue4>(aux, sbx_aux_clouds_ue4_defaults); }
+// SBX_APP_RAYTRACER_SCENE: the caller's scene, or the Cornell box of these uniforms (its defaults depend on them)
+inline sbx_aux_raytracer_scene aux_raytracer_scene(const void* aux, const sbx_uniforms& uni) {
+    sbx_aux_raytracer_scene a;
+    if (aux) a = *(const sbx_aux_raytracer_scene*)aux; else sbx_raytracer_scene_cornell(&uni, 0, &a);
+    return a;
+}
 
 }  // namespace sbx

@@ -193,6 +193,16 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
         AC = aux_clouds(aux);
         if (AC.cld_march_steps < 0 || AC.illum_march_steps < 0) return fail(ctx, SBX_ERR_ARG, "negative march steps");
     }
+    sbx_aux_raytracer_scene RS;
+    if (T.aux == AUX_RT_SCENE) {
+        RS = aux_raytracer_scene(aux, *uni);
+        if (RS.n_planes < 0 || RS.n_planes > SBX_RT_MAX_PLANES || RS.n_spheres < 0 || RS.n_spheres > SBX_RT_MAX_SPHERES)
+            return fail(ctx, SBX_ERR_ARG, "raytracer scene: n_planes and n_spheres must lie in 0..16");
+        if (RS.bounces < 1 || RS.bounces > 8) return fail(ctx, SBX_ERR_ARG, "raytracer scene: bounces must lie in 1..8");
+        if (RS.light_type != 1 && RS.light_type != 2) return fail(ctx, SBX_ERR_ARG, "raytracer scene: light_type must be 1 (LIGHT_POINT) or 2 (LIGHT_DIR)");
+        if (RS.lighting != 0 && RS.lighting != 1) return fail(ctx, SBX_ERR_ARG, "raytracer scene: lighting must be 0 (Cook-Torrance) or 1 (Phong)");
+        if (RS.shadow != 0 && RS.shadow != 1) return fail(ctx, SBX_ERR_ARG, "raytracer scene: shadow must be 0 or 1");
+    }
     if (T.noise_volumes && !ctx->noise.shape) return fail(ctx, SBX_ERR_ARG, "APP_CLOUDS with USE_NOISE_TEX needs sbx_set_noise_volume first");
     const bool capturing = stream_is_capturing(s);
     TimingPair* tp = nullptr;
@@ -252,6 +262,11 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     case SBX_APP_RAYTRACER_PHONG: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots, RT_PHONG); break;
     case SBX_APP_RAYTRACER_NOSHADOW: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots, RT_NOSHADOW); break;
     case SBX_APP_RAYTRACER_STATIC: launch_raytracer(build_raytracer(*uni, RT_STATIC), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots, RT_STATIC); break;
+    // the caller's scene (validated above), always through its own kernel: a block equal to the Cornell box is no special case
+    case SBX_APP_RAYTRACER_SCENE:
+        launch_raytracer_scene(build_raytracer_scene(*uni, RS), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots);
+        ctx->stats.rt_scene_launches.fetch_add(1, std::memory_order_relaxed);
+        break;
     case SBX_APP_ATMOSPHERE: launch_atmosphere(build_atmosphere(*uni), M, rgba, s, ctx->precision); break;
     case SBX_APP_ATMOSPHERE_GROUND: launch_atmosphere_ground(build_atmosphere_ground(*uni), M, rgba, s, ctx->precision, ctx->variant); break;
     // one scene, three builds of app_sdf_ao.h (include/sbx.h)
@@ -503,6 +518,12 @@ int sbx_debug_order_build(sbx_ctx* ctx, const unsigned* cost_host, int gx, int g
     if (e == hipSuccess) e = hipMemcpy(table_host, mem + n * 2, n * 4, hipMemcpyDeviceToHost);
     (void)hipFree(mem);
     if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "sbx_debug_order_build", e);
+    return SBX_OK;
+}
+
+int sbx_debug_raytracer_scene_launches(sbx_ctx* ctx, uint64_t* launches) {
+    if (!ctx || !launches) return SBX_ERR_ARG;
+    *launches = ctx->stats.rt_scene_launches.load(std::memory_order_relaxed);
     return SBX_OK;
 }
 

@@ -93,7 +93,9 @@ struct Texture2d {
 // The key words are relaxed atomics because readers look at them while a writer may be storing.
 struct FrameCache {
     static constexpr int FRAMES = 2;
-    static constexpr int KEY_WORDS = 2 + (int)(sizeof(sbx_uniforms) + sizeof(sbx_aux_clouds)) / 4;   // (the largest aux block)
+    static constexpr int KEY_WORDS = 2 + (int)(sizeof(sbx_uniforms) + sizeof(sbx_aux_raytracer_scene)) / 4;   // (the largest aux block)
+    static_assert(sizeof(sbx_aux_raytracer_scene) >= sizeof(sbx_aux_clouds) && sizeof(sbx_aux_raytracer_scene) >= sizeof(sbx_aux_clouds_ue4) &&
+                  sizeof(sbx_aux_raytracer_scene) >= sizeof(sbx_aux_sdf_ao), "KEY_WORDS holds the largest aux block (mi_make_key copies app_aux_bytes of it)");
     struct Entry {
         std::atomic<uint64_t> gen{0};
         std::atomic<float*> host{nullptr};       // pinned (hipHostMalloc): the frame comes back with one asynchronous copy
@@ -118,6 +120,7 @@ struct Stats {
     struct alignas(64) Stripe { std::atomic<uint64_t> n{0}; };
     Stripe hits[16];
     std::atomic<uint64_t> launches{0}, frames{0}, points{0};
+    std::atomic<uint64_t> rt_scene_launches{0};   // k_raytracer_scene launches (sbx_debug_raytracer_scene_launches; never reset)
 };
 
 // sbx_render_rows_host: device staging of a host frame, the stream its strips are copied out on, one event per strip.
@@ -188,6 +191,7 @@ int render_rows(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const void* aux,
 FrameClouds build_clouds(const sbx_uniforms& U, const sbx_aux_clouds& A, bool sky_sphere = false);
 FrameEggStraight build_egg(const sbx_uniforms& U, int build = EGG_DEFAULT);   // (the other builds read its FrameEgg part)
 FrameRaytracer build_raytracer(const sbx_uniforms& U, int build = RT_DEFAULT);   // build: RT_* (sbx_frame.h); RT_STATIC is the scene at rest
+FrameRtScene build_raytracer_scene(const sbx_uniforms& U, const sbx_aux_raytracer_scene& A);   // SBX_APP_RAYTRACER_SCENE: a validated block
 FrameAtmosphere build_atmosphere(const sbx_uniforms& U);
 FrameAtmosphere build_atmosphere_ground(const sbx_uniforms& U);
 FrameSdfAo build_sdf_ao(const sbx_uniforms& U, const sbx_aux_sdf_ao& A);

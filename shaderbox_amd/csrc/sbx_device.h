@@ -162,6 +162,7 @@ void launch_extract_r(const float* rgba, float* r, size_t n, hipStream_t s);
 void launch_tex3d_eval(int size, const float* rgba, const float* xyz, float* out, size_t n, hipStream_t s);
 void launch_egg(const FrameEggStraight& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = EGG_DEFAULT);   // build: EGG_* (sbx_frame.h), the one F was built for
 void launch_raytracer(const FrameRaytracer& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = RT_DEFAULT);   // build: RT_* (sbx_frame.h)
+void launch_raytracer_scene(const FrameRtScene& F, const RowMap& M, float* out, hipStream_t s, int variant);   // SBX_APP_RAYTRACER_SCENE (kern_raytracer.hip)
 void launch_atmosphere(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision = 0);
 void launch_atmosphere_ground(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision, int variant);   // kern_atmosphere.hip
 void launch_sdf_ao(const FrameSdfAo& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = 0);   // build: 1 / 2 = the shadow / normals builds (kern_sdf_ao.hip)

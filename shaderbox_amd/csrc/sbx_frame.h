@@ -193,6 +193,23 @@ struct FrameRaytracer {
 // The first two are kernel template parameters (kern_raytracer.hip); the third is another frame block for the shipped kernels
 // (build_raytracer).  FrameRaytracer is the same type in all four.
 enum { RT_DEFAULT = 0, RT_PHONG = 1, RT_NOSHADOW = 2, RT_STATIC = 3 };
+// SBX_APP_RAYTRACER_SCENE (include/sbx.h sbx_aux_raytracer_scene): the caller's scene.  A type of its own, so that k_raytracer takes the
+// arguments it always took.  What the file's compile-time switches are for the Cornell box are run-time values here; the counts are
+// validated on the host (0..16 each, bounces 1..8) before a launch, so every array index of the kernel is in range.
+constexpr int RT_MAX_PLANES = 16, RT_MAX_SPHERES = 16;
+struct FrameRtScene {
+    Camera cam;
+    int n_planes, n_spheres;
+    int bounces;          // the `2` of app_raytracer.h:96
+    int lighting;         // 0 illum_cook_torrance, 1 illum_blinn_phong (:61)
+    int shadow;           // the `#if 1` of :107
+    int light_type;       // 1 LIGHT_POINT, 2 LIGHT_DIR (light.h:5-6)
+    v3 light;             // lights[0].L
+    v3 ambient;           // ambient_light light.h:16
+    RtMaterial mats[8];
+    RtPlane planes[RT_MAX_PLANES];
+    RtSphere spheres[RT_MAX_SPHERES];
+};
 
 // ---- APP_ATMOSPHERE (src/app_atmosphere.h) --------------------------------------------------
 struct FrameAtmosphere {

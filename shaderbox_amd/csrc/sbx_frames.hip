@@ -145,46 +145,95 @@ FrameEggStraight build_egg(const sbx_uniforms& U, int build) {
     return F;
 }
 
-FrameRaytracer build_raytracer(const sbx_uniforms& U, int build) {
-    FrameRaytracer F;
+// The Cornell box of app_raytracer.h as a scene block (include/sbx.h sbx_aux_raytracer_scene): setup_scene :18-36 over setup_cornell_box
+// cornell_box.h:39-87, setup_camera :38-44 and the FOV of :138.  The ONE statement of that scene: build_raytracer (the four builds of
+// SBX_APP_RAYTRACER) and sbx_raytracer_scene_cornell (SBX_APP_RAYTRACER_SCENE's default block) both read it.
+static void cornell_block(const sbx_uniforms& U, bool at_rest, sbx_aux_raytracer_scene& A) {
+    std::memset(&A, 0, sizeof(A));
     const float cb = 2.f;                                              // cb_plane_dist cornell_box.h:62
+    auto put = [](float* d, v3 v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; };
     // setup_camera app_raytracer.h:38-44
     v2 mouse = V2(0, 0);
     if (!(U.u_mouse[0] < 1e-4f)) mouse = V2(2.f * (U.u_res[0] / U.u_mouse[0]) - 1.f, 2.f * (U.u_res[1] / U.u_mouse[1]) - 1.f);
     const m3 rot_y = rotate_around_y(mouse.x * 30.f);
-    const v3 eye = mul(rot_y, V3(0, cb, 2.333f * cb));
-    F.cam = make_camera(U.u_res[0], U.u_res[1], tan_(radians_(30.f)), eye, V3(0, cb, 0));   // FOV :138
+    put(A.eye, mul(rot_y, V3(0, cb, 2.333f * cb)));
+    put(A.look_at, V3(0, cb, 0));
+    A.fov = tan_(radians_(30.f));                                      // FOV :138
+    A.bounces = 2;                                                     // :96
+    A.light_type = 1;                                                  // LIGHT_POINT cornell_box.h:83
+    A.lighting = 0;                                                    // illum_cook_torrance :64
+    A.shadow = 1;                                                      // :107
+    put(A.light_color, V3(1.f, 1.f, 1.f));                             // cornell_box.h:85
+    put(A.ambient, V3(.01f, .01f, .01f));                              // light.h:16
     // materials: zero-initialised slots (App. B5), mat_debug :20-25, cornell box cornell_box.h:47-55
-    for (int i = 0; i < 8; ++i) F.mats[i] = RtMaterial{V3(0, 0, 0), 0.f, 0.f, 0.f, 0.f};
-    F.mats[0] = RtMaterial{V3(1.f, 1.f, 1.f), 0.f, 1.f, 0.f, 0.f};
-    F.mats[1] = RtMaterial{V3(0.7913f, 0.7913f, 0.7913f), .5f, 1.f, 0.f, 0.f};
-    F.mats[2] = RtMaterial{V3(0.6795f, 0.0612f, 0.0529f), .5f, 1.f, 0.f, 0.f};
-    F.mats[3] = RtMaterial{V3(0.1878f, 0.1274f, 0.4287f), .5f, 1.f, 0.f, 0.f};
-    F.mats[4] = RtMaterial{V3(0.95f, 0.64f, 0.54f), .1f, 1.f, 1.f, 0.f};
-    F.mats[5] = RtMaterial{V3(1.f, 0.77f, 0.345f), .05f, 1.333f, 1.f, 0.f};
-    for (int i = 0; i < 8; ++i) {                                      // util_optics.h:10-11 with n1 = 1, per material
-        const float Rn = (1.f - F.mats[i].ior) / (1.f + F.mats[i].ior);
-        F.mats[i].r0 = Rn * Rn;
-    }
+    auto material = [&](int i, v3 c, float metallic, float roughness, float ior, float reflectivity) {
+        put(A.materials[i].base_color, c);
+        A.materials[i].metallic = metallic; A.materials[i].roughness = roughness; A.materials[i].ior = ior;
+        A.materials[i].reflectivity = reflectivity; A.materials[i].translucency = 0.f;
+    };
+    material(0, V3(1.f, 1.f, 1.f), 0.f, 0.f, 1.f, 0.f);
+    material(1, V3(0.7913f, 0.7913f, 0.7913f), .0f, .5f, 1.f, 0.f);
+    material(2, V3(0.6795f, 0.0612f, 0.0529f), 0.f, .5f, 1.f, 0.f);
+    material(3, V3(0.1878f, 0.1274f, 0.4287f), 0.f, .5f, 1.f, 0.f);
+    material(4, V3(0.95f, 0.64f, 0.54f), 1.f, .1f, 1.f, 1.f);
+    material(5, V3(1.f, 0.77f, 0.345f), 1.f, .05f, 1.333f, 1.f);
     // planes, in array-index order ground, behind, front, ceiling, left, right  cornell_box.h:57-69
-    F.planes[0] = RtPlane{V3(0, -1, 0), 0.f, 1};
-    F.planes[1] = RtPlane{V3(0, 0, -1), -cb, 1};
-    F.planes[2] = RtPlane{V3(0, 0, 1), cb, 1};
-    F.planes[3] = RtPlane{V3(0, 1, 0), 2.f * cb, 1};
-    F.planes[4] = RtPlane{V3(1, 0, 0), cb, 2};
-    F.planes[5] = RtPlane{V3(-1, 0, 0), -cb, 3};
-    // spheres and light as cornell_box.h:71-85 puts them: the whole scene of RT_STATIC (the `#if 1` at app_raytracer.h:29 off), which
+    auto plane = [&](int i, v3 n, float d, int mat) { put(A.planes[i].direction, n); A.planes[i].distance = d; A.planes[i].material = mat; };
+    A.n_planes = 6;
+    plane(0, V3(0, -1, 0), 0.f, 1);
+    plane(1, V3(0, 0, -1), -cb, 1);
+    plane(2, V3(0, 0, 1), cb, 1);
+    plane(3, V3(0, 1, 0), 2.f * cb, 1);
+    plane(4, V3(1, 0, 0), cb, 2);
+    plane(5, V3(-1, 0, 0), -cb, 3);
+    // spheres and light as cornell_box.h:71-85 puts them: the whole scene at rest (the `#if 1` at app_raytracer.h:29 off), which
     // reads no u_time
-    F.spheres[0] = RtSphere{V3(0, 2.5f * cb + 0.4f, 0), 1.5f, 0, recip64(1.5f)};
-    F.spheres[1] = RtSphere{V3(0.75f, 1, -0.75f), 0.75f, 4, recip64(0.75f)};
-    F.spheres[2] = RtSphere{V3(-0.75f, 0.75f, 0.75f), 0.75f, 5, recip64(0.75f)};
-    F.light = V3(0, 2.f * cb - 0.2f, 0);
-    if (build != RT_STATIC) {                                          // the animation app_raytracer.h:29-35
+    auto sphere = [&](int i, v3 o, float r, int mat) { put(A.spheres[i].origin, o); A.spheres[i].radius = r; A.spheres[i].material = mat; };
+    A.n_spheres = 3;
+    sphere(0, V3(0, 2.5f * cb + 0.4f, 0), 1.5f, 0);
+    v3 left = V3(0.75f, 1, -0.75f), right = V3(-0.75f, 0.75f, 0.75f), light = V3(0, 2.f * cb - 0.2f, 0);
+    if (!at_rest) {                                                    // the animation app_raytracer.h:29-35
         const float s = sin_(U.u_time), c = cos_(U.u_time);
-        F.spheres[1].o = F.spheres[1].o + V3(0, abs_(s), c + 1.f);
-        F.spheres[2].o.z = 0.f;
-        F.light.z = 1.5f;
+        left = left + V3(0, abs_(s), c + 1.f);
+        right.z = 0.f;
+        light.z = 1.5f;
     }
+    sphere(1, left, 0.75f, 4);
+    sphere(2, right, 0.75f, 5);
+    put(A.light_L, light);
+}
+static v3 v3_of(const float* p) { return V3(p[0], p[1], p[2]); }
+static RtMaterial rt_material(const sbx_rt_material& m) {
+    const float Rn = (1.f - m.ior) / (1.f + m.ior);                    // util_optics.h:10-11 with n1 = 1, per material
+    return RtMaterial{v3_of(m.base_color), m.roughness, m.ior, m.reflectivity, Rn * Rn};
+}
+static RtPlane rt_plane(const sbx_rt_plane& p) { return RtPlane{v3_of(p.direction), p.distance, p.material}; }
+static RtSphere rt_sphere(const sbx_rt_sphere& s) { return RtSphere{v3_of(s.origin), s.radius, s.material, recip64(s.radius)}; }
+
+FrameRaytracer build_raytracer(const sbx_uniforms& U, int build) {
+    sbx_aux_raytracer_scene A;
+    cornell_block(U, build == RT_STATIC, A);
+    FrameRaytracer F;
+    F.cam = make_camera(U.u_res[0], U.u_res[1], A.fov, v3_of(A.eye), v3_of(A.look_at));
+    for (int i = 0; i < 8; ++i) F.mats[i] = rt_material(A.materials[i]);
+    for (int i = 0; i < 6; ++i) F.planes[i] = rt_plane(A.planes[i]);
+    for (int i = 0; i < 3; ++i) F.spheres[i] = rt_sphere(A.spheres[i]);
+    F.light = v3_of(A.light_L);
+    return F;
+}
+
+// SBX_APP_RAYTRACER_SCENE: the caller's block (validated by render_mapped: the counts are within the arrays) as the kernel reads it.
+// The slots past the counts are copied as they are; the kernel never reads them.
+FrameRtScene build_raytracer_scene(const sbx_uniforms& U, const sbx_aux_raytracer_scene& A) {
+    FrameRtScene F;
+    F.cam = make_camera(U.u_res[0], U.u_res[1], A.fov, v3_of(A.eye), v3_of(A.look_at));
+    F.n_planes = A.n_planes; F.n_spheres = A.n_spheres;
+    F.bounces = A.bounces; F.lighting = A.lighting; F.shadow = A.shadow; F.light_type = A.light_type;
+    F.light = v3_of(A.light_L);
+    F.ambient = v3_of(A.ambient);
+    for (int i = 0; i < 8; ++i) F.mats[i] = rt_material(A.materials[i]);
+    for (int i = 0; i < RT_MAX_PLANES; ++i) F.planes[i] = rt_plane(A.planes[i]);
+    for (int i = 0; i < RT_MAX_SPHERES; ++i) F.spheres[i] = rt_sphere(A.spheres[i]);
     return F;
 }
 
@@ -344,6 +393,11 @@ void sbx_checkerboard_texture(int size, int freq, uint32_t* out) {    // hlsltoy
     for (int y = 0; y < size; ++y)
         for (int x = 0; x < size; ++x)
             out[(size_t)y * size + x] = ((x & freq) == (y & freq)) ? 0xff000000u : 0xffffffffu;
+}
+
+void sbx_raytracer_scene_cornell(const sbx_uniforms* uni, int at_rest, sbx_aux_raytracer_scene* out) {
+    if (!uni || !out) return;
+    cornell_block(*uni, at_rest != 0, *out);
 }
 
 void sbx_aux_clouds_ue4_defaults(sbx_aux_clouds_ue4* a) {              // app_clouds.usf:4-7

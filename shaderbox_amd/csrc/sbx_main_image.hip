@@ -95,8 +95,10 @@ int sbx_main_image_batch(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const v
 
 // ---- sbx_main_image: the per-pixel entry over cached frames ----------------------------------------------------------------
 // the cache key of a frame as words: app, aux size, the uniforms, the aux block (zero padded)
+// Only the words in use are written — 2 + the uniforms + the block, what mi_lookup compares and what mi_key_words() counts: the hit path
+// of an app without a block does not clear the 344 words the largest block would take.
+static int mi_key_words(const uint32_t* key) { return 2 + (int)(sizeof(sbx_uniforms) / 4) + (int)(key[1] / 4); }
 static void mi_make_key(int app, const sbx_uniforms* uni, const void* aux, uint32_t key[FrameCache::KEY_WORDS]) {
-    std::memset(key, 0, sizeof(uint32_t) * FrameCache::KEY_WORDS);
     const int ab = aux ? app_aux_bytes(app) : 0;   // (no block: the defaults, one frame whoever asks)
     key[0] = (uint32_t)app; key[1] = (uint32_t)ab;
     std::memcpy(key + 2, uni, sizeof(*uni));
@@ -108,7 +110,10 @@ static bool mi_lookup(sbx_ctx* ctx, const uint32_t* key, size_t pixel, float out
         const uint64_t g1 = en.gen.load(std::memory_order_acquire);
         if (g1 & 1u) continue;                                                   // being rewritten
         bool same = true;
-        for (int i = 0; i < FrameCache::KEY_WORDS && same; ++i) same = en.key[i].load(std::memory_order_relaxed) == key[i];
+        // (words 0 and 1 are the app and the aux block's size: keys that agree in them have the same length, and an unused entry's
+        // 0xffffffff differs in word 0)
+        const int words = mi_key_words(key);
+        for (int i = 0; i < words && same; ++i) same = en.key[i].load(std::memory_order_relaxed) == key[i];
         if (!same) continue;
         const float* h = en.host.load(std::memory_order_relaxed);
         if (!h) continue;
@@ -192,7 +197,7 @@ int sbx_main_image(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const void* a
         return fail(ctx, SBX_ERR_HIP, "frame render", e);
     }
     ctx->stats.frames.fetch_add(1, std::memory_order_relaxed);
-    for (int i = 0; i < FrameCache::KEY_WORDS; ++i) en->key[i].store(key[i], std::memory_order_relaxed);
+    for (int i = 0, words = mi_key_words(key); i < FrameCache::KEY_WORDS; ++i) en->key[i].store(i < words ? key[i] : 0u, std::memory_order_relaxed);
     en->used = true; en->born = ++ctx->mi.clock;
     en->gen.store(g0 + 2, std::memory_order_release);                            // even again: published
     std::memcpy(fragColor, host + pixel * 4, 4 * sizeof(float));

@@ -57,8 +57,8 @@ SBX_HD float smoothstep_(float e0, float e1, float x) {
 SBX_HD float radians_(float deg) { return deg * 0.017453292519943295f; }
 
 // Exact binary32 division by a denominator whose binary64 reciprocal is already known (a frame constant or
-// a literal): n / d == (float)((double)n * RN64(1 / (double)d)) for ALL binary32 n, d, bit for bit with the
-// IEEE quotient.  Proof sketch: the exact quotient Q of two 24-bit significands is never a rounding midpoint
+// a literal): n / d == (float)((double)n * RN64(1 / (double)d)), bit for bit with the IEEE quotient, for all binary32
+// n, d WHOSE QUOTIENT IS NOT IN THE BINARY32 SUBNORMAL RANGE (see the end of this comment).  Proof sketch: the exact quotient Q of two 24-bit significands is never a rounding midpoint
 // of binary32 (m * d with m an odd 25-bit integer has >= 25 significant bits) and, unless it is exactly
 // representable, lies at relative distance >= 2^-49 from the nearest midpoint; the computed product carries a
 // relative error < 2^-51.9 (one rounding in the reciprocal, one in the product), less than half that gap, so
@@ -66,6 +66,13 @@ SBX_HD float radians_(float deg) { return deg * 0.017453292519943295f; }
 // both sides.  On MI355X this is v_cvt_f64_f32 + v_mul_f64 + v_cvt_f32_f64 (~13 issue cycles) against ~42
 // for the v_div_scale/v_rcp/v_fma.../v_div_fixup sequence (profiles/r01_ubench_valu.txt).  The oracle keeps
 // the plain division; tests/test_gpu_parity.py::test_division_by_reciprocal_is_exact checks the identity.
+// SUBNORMAL QUOTIENTS ARE OUTSIDE THE CLAIM.  The midpoint argument is about the 25-bit midpoints of normal numbers.  Below 2^-126 the
+// rounding points are multiples of 2^-149, their midpoints have few bits, and a quotient can BE one: 5 * 2^-149 / 10 = 2^-150 exactly,
+// which IEEE division rounds to even, 0, while RN64(1 / 10) > 1 / 10 puts the product above the tie and the conversion gives 2^-149.
+// So a caller must show |n / d| >= 2^-126 (or n == 0, or d a power of two) or treat a result of magnitude <= 2^-126 as unproved, as
+// k_raytracer_scene does (kern_raytracer.hip "CALLER'S NUMBERS").  The callers older than that kernel — point_cam's fragCoord / u_res,
+// k_raytracer's hit_sphere, the smoothstep_rd forms — were written under the stronger sentence and have not been re-examined for
+// dividends that small (a fragCoord below 2^-126 * u_res given to sbx_render_points is one): DESIGN.md §6 keeps that as an open item.
 SBX_HD double recip64(float d) { return 1.0 / (double)d; }
 SBX_HD float div_by(float n, double rd) { return (float)((double)n * rd); }
 // smoothstep(e0, e1, x) with rd = recip64(e1 - e0)

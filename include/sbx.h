@@ -364,7 +364,12 @@ void sbx_aux_sdf_ao_defaults(sbx_aux_sdf_ao* aux);
 
 /* Create / destroy a context bound to HIP device `device`.  Owns only small device scratch
  * (APP_CLOUDS' per-frame y tables, timing events, the cached frame of sbx_main_image); the
- * framebuffer of the render calls always belongs to the caller. */
+ * framebuffer of the render calls always belongs to the caller.
+ * APP_CLOUDS (and its HEIGHT / LUMINANCE builds) also allocates, on the first eager launch that can use it, a table of the lattice
+ * hashes its frames index: 2 MB for frames whose noise lattice indices stay below 2^18 (the default frame: 6.4e4), a larger one —
+ * the next power of two — when a frame's bound outgrows it, at most 32 MB (indices below 2^22; frames beyond that keep the kernels
+ * that hash per wave).  Tables are never rebuilt; all of them together stay below 64 MB and are freed by sbx_destroy.  Nothing is
+ * allocated inside a stream capture. */
 int sbx_create(int device, sbx_ctx** out);
 void sbx_destroy(sbx_ctx* ctx);
 

@@ -102,6 +102,16 @@ int sbx_debug_order_build(sbx_ctx* ctx, const unsigned* cost_host, int gx, int g
  * creation: for the test that a scene block equal to the Cornell box is rendered by the scene kernel, not handed to k_raytracer. */
 int sbx_debug_raytracer_scene_launches(sbx_ctx* ctx, uint64_t* launches);
 
+/* APP_CLOUDS' lattice-hash tables (csrc/sbx_ctx.h HashTables; csrc/kern_clouds.hip GTab): the newest — largest — table's size in entries and
+ * its bias (entry i holds hash(float(i - bias))), 0 / 0 before the first one; how many tables this context has built; and whether its last
+ * launch of APP_CLOUDS or of its HEIGHT / LUMINANCE builds took a hash-table kernel (1) or the kernels with the per-wave cache (0).  Any
+ * pointer may be NULL.  For the tests that the table kernels run where their frames are compared with the per-lane kernel's, and that
+ * the launches which must not touch a table do not (tests/test_gpu_clouds_hashtab.py). */
+int sbx_debug_clouds_hashtab(sbx_ctx* ctx, int* entries, int* bias, int* tables_built, int* last_launch_used_table);
+
+/* `count` entries of the newest table from entry `first` on, copied to host memory after waiting for its build. */
+int sbx_debug_clouds_hashtab_read(sbx_ctx* ctx, size_t first, size_t count, float* host);
+
 #ifdef __cplusplus
 }
 #endif

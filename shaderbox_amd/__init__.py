@@ -247,6 +247,8 @@ def load_library(path=None):
     lib.sbx_debug_tile_order.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint),
                                          ctypes.c_size_t]
     lib.sbx_debug_order_build.argtypes = [vp, vp, ci, ci, vp, vp]
+    lib.sbx_debug_clouds_hashtab.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int)] * 4
+    lib.sbx_debug_clouds_hashtab_read.argtypes = [vp, ctypes.c_size_t, ctypes.c_size_t, vp]
     lib.sbx_shared_bytes.argtypes = [vp]
     lib.sbx_shared_bytes.restype = ctypes.c_size_t
     lib.sbx_shared_frame_begin.argtypes = [vp, ci, vp]
@@ -757,6 +759,20 @@ class Renderer:
         n = self.lib.sbx_debug_tile_order(self.ctx, app_id(app), ctypes.byref(built), ctypes.byref(since), buf, int(capacity))
         self._check(min(n, 0))
         return built.value, since.value, (np.frombuffer(buf, dtype=np.uint32, count=n).copy() if n > 0 else None)
+
+    def clouds_hashtab(self):
+        """include/sbx_test.h sbx_debug_clouds_hashtab: (entries, bias) of the newest lattice-hash table, tables built so far, and
+        whether the last APP_CLOUDS launch took a hash-table kernel"""
+        v = [ctypes.c_int() for _ in range(4)]
+        self._check(self.lib.sbx_debug_clouds_hashtab(self.ctx, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def clouds_hashtab_read(self, first, count):
+        """include/sbx_test.h sbx_debug_clouds_hashtab_read: entries [first, first + count) of the newest table, a numpy float32 array"""
+        import numpy as np
+        out = np.empty(max(int(count), 1), dtype=np.float32)
+        self._check(self.lib.sbx_debug_clouds_hashtab_read(self.ctx, int(first), int(count), ctypes.c_void_p(out.ctypes.data)))
+        return out[:int(count)]
 
     def order_build(self, cost, gx, gy):
         """include/sbx_test.h sbx_debug_order_build: the dispatch order's sort (csrc/kern_util.hip launch_order_build) run on the

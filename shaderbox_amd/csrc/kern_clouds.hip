@@ -73,6 +73,24 @@
                            // 7 waves = 72 VGPRs spill 6 and lose 4 %)
 #endif
 
+#ifndef CL_GTAB
+#define CL_GTAB 1          // 1: the y-table REG kernels with the z-only or the y-z light march read the lattice hashes of octaves CL_GTAB_OCT ... 3
+                           //    from the context's hash table in device memory (GTab below): no tag, no miss path, no cross-lane step for them;
+                           //    0: every launch takes the LDS cache for every octave (A/B; the same bits either way)
+#endif
+#ifndef CL_GTAB_OCT
+#define CL_GTAB_OCT 2      // the first octave read from the table.  2: octaves 0-1 keep the per-wave LDS cache — 73 % of a march's lookups, which all
+                           // but always hit, and an LDS read returns its 32 bytes per lane at twice the rate of the vector L1 — and octaves 2-3,
+                           // the ones that miss, read the table: 3840x2160 2.22 -> 1.96 ms.  0 (no cache in the kernel at all: 58 VGPRs, 3 KB of
+                           // LDS, 8 waves): 2.23 ms, the L1's return path is the limit.  3: 2.03 ms.  (profiles/clouds_gtab_timing.txt)
+#endif
+#ifndef CL_MIN_WAVES_GTAB
+#define CL_MIN_WAVES_GTAB 6    // waves per SIMD the hash-table instantiations with the z-only light march are held to: 78 VGPRs, no scratch, 5.4 KB
+#endif                         // of LDS as the cache kernels (7: 2.04 ms against 1.96; 5: 1.96; profiles/clouds_gtab_resources.txt)
+#ifndef CL_MIN_WAVES_GTAB_YZ
+#define CL_MIN_WAVES_GTAB_YZ 5 // the same with the y-z light march
+#endif
+
 #ifndef CL_MIN_WAVES_HEIGHT
 #define CL_MIN_WAVES_HEIGHT 8   // the HEIGHT build's y-table instantiations (no light march): 55-60 VGPRs of the 64, no scratch
 #endif
@@ -351,13 +369,70 @@ __device__ __forceinline__ void hc_blend_xy(float4 lo, float4 hi, float fx, floa
     cd = c * gy + d * fy;
 }
 
+// ---- the context's hash table (CL_GTAB; host side: sbx_ytab.hip clouds_hash_table) ------------------------------------------
+// hash(n) is a pure function of the integer lattice index, the same for every wave, frame and launch.  The context keeps
+//     T[i] = hash1((float)(i - bias)),  0 <= i < entries,
+// built once by k_clouds_hashtab with the binary32 argument a lane forms (lattice indices below 2^24 are exact integers, so the
+// corner arguments n + 1, n + 157, ... are exact too): the bits of a table entry are the bits the cache would hold.  A lookup is
+// idx = (int)n + bias and four 8-byte loads at the corner offsets 0 / 157 / 113 / 270 from the table's base (a kernel argument);
+// there is no tag, no miss path and no cross-lane step.  What keeps idx inside the table: the host takes these kernels only when
+// the frame's index bound (clouds_index_bound) lies within the table's range, every coordinate of a marching lane is bounded by
+// it or is NaN (v_cvt_i32_f32 of NaN is 0), and the lanes that do not march are given the straight-up ray before the march
+// (k_clouds); the table has CLOUDS_HASHTAB_GUARD entries of slack at both ends on top.
+struct GTab { const float* tab; unsigned bias4; };        // bias4 = 4 * bias: the byte offset of lattice index 0
+typedef float gt_f2 __attribute__((ext_vector_type(2), aligned(4)));
+__device__ __forceinline__ unsigned gt_off(float n, unsigned bias4) { return ((unsigned)(int)n << 2) + bias4; }
+__device__ __forceinline__ H8 gt_load(const GTab& g, unsigned off) {
+    const char* p = reinterpret_cast<const char*>(g.tab) + (unsigned long long)off;     // uniform base + 32-bit lane offset + immediates
+    const gt_f2 a = *reinterpret_cast<const gt_f2*>(p), b = *reinterpret_cast<const gt_f2*>(p + 157 * 4);
+    const gt_f2 c = *reinterpret_cast<const gt_f2*>(p + 113 * 4), d = *reinterpret_cast<const gt_f2*>(p + 270 * 4);
+    H8 h;
+    h.lo = make_float4(a.x, a.y, b.x, b.y);              // the cache's corner order: +0, +1, +157, +158, +113, +114, +270, +271
+    h.hi = make_float4(c.x, c.y, d.x, d.y);
+    return h;
+}
+__global__ void __launch_bounds__(256) k_clouds_hashtab(float* __restrict__ tab, int entries, int bias) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < entries) tab[i] = hash1((float)(i - bias));
+}
+void launch_clouds_hashtab(float* tab, int entries, int bias, hipStream_t s) {
+    hipLaunchKernelGGL(k_clouds_hashtab, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, tab, entries, bias);
+}
+
 // Octaves [K0, K1) of a main sample's fBm: lattice terms, tag checks, ONE wave-uniform all-hit test, reads, blends.
-template <int K0, int K1, bool B40>
+// GT (0: never; else 1 + the first octave the kernel reads from the context's table): for K0 >= GT - 1 the hashes come from the table
+// instead (all loads of the stage first, then the same blends)
+template <int K0, int K1, bool B40, int GT = 0>
 __device__ __forceinline__ void row_octaves(const float (&rfy)[4], const float (&rgy)[4], const float (&rpy)[4], float& qx, float& qz,
                                             float& t, float& H, bool active, unsigned long long active_mask, WaveCache& S,
                                             int lane, float (&fx)[4], float (&nxy)[4], float (&mab)[4], float (&mcd)[4],
-                                            float (&mpz)[4]) {
+                                            float (&mpz)[4], const GTab& g) {
     float fz[4];
+    if constexpr (GT != 0 && K0 >= GT - 1) {
+        unsigned off[4];
+#pragma unroll
+        for (int k = K0; k < K1; ++k) {
+            const float px = floor_(qx), pz = floor_(qz);
+            const float ax = qx - px, az = qz - pz;
+            fx[k] = ax * ax * tm2_(ax);
+            fz[k] = az * az * tm2_(az);
+            nxy[k] = px + rpy[k];
+            mpz[k] = pz;
+            const float n = nxy[k] + 113.0f * pz;            // p.x + p.y*157 + 113*p.z, noise_iq.h:19
+            off[k] = gt_off(n, g.bias4);
+            qx = qx * 2.64f; qz = qz * 2.64f;
+        }
+        H8 h[4];
+#pragma unroll
+        for (int k = K0; k < K1; ++k) h[k] = gt_load(g, off[k]);
+#pragma unroll
+        for (int k = K0; k < K1; ++k) {
+            hc_blend_xy(h[k].lo, h[k].hi, fx[k], rfy[k], rgy[k], mab[k], mcd[k]);
+            t += CL_PRESCALE ? (mab[k] * (1.0f - fz[k]) + mcd[k] * fz[k]) : (mab[k] * (1.0f - fz[k]) + mcd[k] * fz[k]) * H;
+            H *= .5f;
+        }
+        return;
+    }
     unsigned nbits[4];
     int slot[4];
     bool ne[4];
@@ -433,11 +508,11 @@ __device__ __forceinline__ void row_octaves(const float (&rfy)[4], const float (
 // = 2e-4 per end point (s3: 4e-4): the 1e-3 in the gaps covers both ends, the 1 % in c the rounding of t and D.  Positions
 // are eye + proj * 150 + wind_dir * u_time * 1000 + t * proj with |proj.x|, |proj.z| <= 20 (dir.y >= .05) — unbounded in
 // u_time and wind_dir, both caller-set: at |wind_off| = 2e7 (ulp 2) the bound fails numerically, hence the check.
-template <bool LIP, bool B40, bool D3>          // D3: the coverage smoothstep through div3_ (vcd, vcr = F.cov_d, F.cov_r in VGPRs)
+template <bool LIP, bool B40, bool D3, int GT = 0>          // GT: see row_octaves; D3: the coverage smoothstep through div3_ (vcd, vcr = F.cov_d, F.cov_r in VGPRs)
 __device__ __forceinline__ float coop_density_row(const FrameClouds& F, v3 pos_in, const YRow& row, bool active,
                                                   unsigned long long active_mask, WaveCache& S, int lane,
                                                   float (&fx)[4], float (&nxy)[4], float (&mab)[4], float (&mcd)[4],
-                                                  float (&mpz)[4], const float* lip_slot, int& skip, float vcd, float vcr) {
+                                                  float (&mpz)[4], const float* lip_slot, int& skip, float vcd, float vcr, const GTab& g) {
     float qx = (pos_in.x * .001f) * 2.03f, qz = (pos_in.z * .001f) * 2.03f;
     const float rfy[4] = {row.fy.x, row.fy.y, row.fy.z, row.fy.w};
     const float rgy[4] = {row.gy.x, row.gy.y, row.gy.z, row.gy.w};
@@ -445,7 +520,7 @@ __device__ __forceinline__ float coop_density_row(const FrameClouds& F, v3 pos_i
     float t = 0.f, H = .5f;
     float lip_inv = 0.f;
     if (LIP) lip_inv = *lip_slot;                        // 1 / c of this lane, kept in LDS (read early, used after the first stage)
-    row_octaves<0, 2, B40>(rfy, rgy, rpy, qx, qz, t, H, active, active_mask, S, lane, fx, nxy, mab, mcd, mpz);
+    row_octaves<0, 2, B40, GT>(rfy, rgy, rpy, qx, qz, t, H, active, active_mask, S, lane, fx, nxy, mab, mcd, mpz, g);
     // (t + .1876 < cov written as t < cov - .1876 with the right side a frame constant: one instruction; the 1e-4 of slack over
     //  .1875 covers the half ulp by which the two forms can differ, and a skipped sample is exactly 0 either way)
     if (!wave_any_mask(active_mask & wave_mask(!(t < F.thr1)))) {                        // NaN compares false: goes on
@@ -467,7 +542,7 @@ __device__ __forceinline__ float coop_density_row(const FrameClouds& F, v3 pos_i
 #ifdef SBX_CL_STATS
     if (lane == 0) S.stat[4] += 1.f;
 #endif
-    row_octaves<2, 3, B40>(rfy, rgy, rpy, qx, qz, t, H, active, active_mask, S, lane, fx, nxy, mab, mcd, mpz);
+    row_octaves<2, 3, B40, GT>(rfy, rgy, rpy, qx, qz, t, H, active, active_mask, S, lane, fx, nxy, mab, mcd, mpz, g);
     if (!wave_any_mask(active_mask & wave_mask(!(t < F.thr2)))) {
 #if CL_LIPSKIP2
         if (LIP) {
@@ -491,7 +566,7 @@ __device__ __forceinline__ float coop_density_row(const FrameClouds& F, v3 pos_i
 #ifdef SBX_CL_STATS
     if (lane == 0) S.stat[5] += 1.f;
 #endif
-    row_octaves<3, 4, B40>(rfy, rgy, rpy, qx, qz, t, H, active, active_mask, S, lane, fx, nxy, mab, mcd, mpz);
+    row_octaves<3, 4, B40, GT>(rfy, rgy, rpy, qx, qz, t, H, active, active_mask, S, lane, fx, nxy, mab, mcd, mpz, g);
     return D3 ? t * smoothstep_d3(F.cov, vcd, vcr, t) : t * smoothstep_rd(F.cov, F.cov_rd, t);        // :83-84
 }
 
@@ -512,12 +587,12 @@ __device__ __forceinline__ float coop_density_row(const FrameClouds& F, v3 pos_i
 // unsigned compare of az's bits against those of 1.0f replaces v_floor + v_cmp (both half-rate instructions on gfx950,
 // profiles/r02_ubench_issue.txt).  The test is conservative (a fract that rounds up to 1.0 is treated as a move);
 // a move recomputes floor / fract / lookups exactly as the general form does.
-template <bool YTAB, bool REG, bool SM>
+template <bool YTAB, bool REG, bool SM, int GT = 0>
 __device__ __forceinline__ float light_march_z(const FrameClouds& F, v3 lp, v3 lstep, bool lit, unsigned long long lit_mask,
                                                WaveCache& S, int lane, const YRow& row, const float (&mfx)[4],
                                                const float (&mnxy)[4], const float (&mab)[4], const float (&mcd)[4],
                                                const float (&mpz)[4], const double* etab, float vsigma, float vdt,
-                                               float vcov, float vcd, float vcr) {       // vcd, vcr: F.cov_d, F.cov_r in VGPRs (SM)
+                                               float vcov, float vcd, float vcr, const GTab& g) {       // vcd, vcr: F.cov_d, F.cov_r in VGPRs (SM)
     float fx[4], fy[4], gy[4], nxy[4], ab[4], cd[4], curz[4];
     if (YTAB) {
         // lp.x = pos.x + 0 and lp.y = pos.y + 0: the x terms are the main sample's own (same operations on
@@ -609,16 +684,20 @@ __device__ __forceinline__ float light_march_z(const FrameClouds& F, v3 lp, v3 l
                     az[k] = qzv[k] - pzv[k];
                 }
                 const float n = nxy[k] + 113.0f * pzv[k];
-                const unsigned nbits = f2u(n);
-                const int slot = (int)n & (HC_SLOTS - 1);
-                const bool ne = (S.tag[k][slot] != nbits);
                 curz[k] = pzv[k];
                 H8 h;
-                if (wave_any(lit && ne)) {
-                    h = hc_slow<SM>(S, k, nbits, slot, lit, lane);
+                if (GT != 0 && k >= GT - 1) {                     // (k: a constant of the unrolled loop)
+                    h = gt_load(g, gt_off(n, g.bias4));
                 } else {
-                    h.lo = *reinterpret_cast<const float4*>(&S.h[k][slot][0]);
-                    h.hi = *reinterpret_cast<const float4*>(&S.h[k][slot][4]);
+                    const unsigned nbits = f2u(n);
+                    const int slot = (int)n & (HC_SLOTS - 1);
+                    const bool ne = (S.tag[k][slot] != nbits);
+                    if (wave_any(lit && ne)) {
+                        h = hc_slow<SM>(S, k, nbits, slot, lit, lane);
+                    } else {
+                        h.lo = *reinterpret_cast<const float4*>(&S.h[k][slot][0]);
+                        h.hi = *reinterpret_cast<const float4*>(&S.h[k][slot][4]);
+                    }
                 }
                 hc_blend_xy(h.lo, h.hi, fx[k], fy[k], gy[k], ab[k], cd[k]);
                 if (!YTAB) { ab[k] *= hk_(k); cd[k] *= hk_(k); }          // (the table's fy, gy carry the gain already)
@@ -662,10 +741,10 @@ __device__ __forceinline__ float light_march_z(const FrameClouds& F, v3 lp, v3 l
 // is decided as in light_march_z, for y and z: a = q - cur is the reference's fract iff 0 <= RN(q - cur) < 1, one unsigned compare
 // of the larger bit pattern against 1.0f.  The kept x-mixes are register values: nothing the cache does can invalidate them.
 // A sample that leaves a cell looks that octave up in the general form (floor / index / tag check / cooperative insert).
-template <bool REG, bool SM>
+template <bool REG, bool SM, int GT = 0>
 __device__ __forceinline__ float light_march_yz(const FrameClouds& F, v3 lp, v3 lstep, bool lit, unsigned long long lit_mask,
                                                 WaveCache& S, int lane, const float (&mfx)[4], const double* etab,
-                                                float vsigma, float vdt, float vcov, float vcd, float vcr) {
+                                                float vsigma, float vdt, float vcov, float vcd, float vcr, const GTab& g) {
     float xa[4], xb[4], xc[4], xd[4], cy[4], cz[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) { cy[k] = cz[k] = u2f(0x7fc00001u); xa[k] = xb[k] = xc[k] = xd[k] = 0.f; }
@@ -700,15 +779,19 @@ __device__ __forceinline__ float light_march_yz(const FrameClouds& F, v3 lp, v3 
                 ay[k] = qyv[k] - py; az[k] = qzv[k] - pz;
                 cy[k] = py; cz[k] = pz;
                 const float n = px + py * 157.0f + 113.0f * pz;
-                const unsigned nbits = f2u(n);
-                const int slot = (int)n & (HC_SLOTS - 1);
-                const bool ne = (S.tag[k][slot] != nbits);
                 H8 h;
-                if (wave_any(lit && ne)) {
-                    h = hc_slow<SM>(S, k, nbits, slot, lit, lane);
+                if (GT != 0 && k >= GT - 1) {                     // (k: a constant of the unrolled loop)
+                    h = gt_load(g, gt_off(n, g.bias4));
                 } else {
-                    h.lo = *reinterpret_cast<const float4*>(&S.h[k][slot][0]);
-                    h.hi = *reinterpret_cast<const float4*>(&S.h[k][slot][4]);
+                    const unsigned nbits = f2u(n);
+                    const int slot = (int)n & (HC_SLOTS - 1);
+                    const bool ne = (S.tag[k][slot] != nbits);
+                    if (wave_any(lit && ne)) {
+                        h = hc_slow<SM>(S, k, nbits, slot, lit, lane);
+                    } else {
+                        h.lo = *reinterpret_cast<const float4*>(&S.h[k][slot][0]);
+                        h.hi = *reinterpret_cast<const float4*>(&S.h[k][slot][4]);
+                    }
                 }
                 const float fx = mfx[k], gx = 1.0f - fx;
                 xa[k] = h.lo.x * gx + h.lo.y * fx;
@@ -804,7 +887,19 @@ __device__ __forceinline__ v3 clouds_sky(const FrameClouds& F, v3 dir) {
 // with SGPRs spilled to VGPR lanes.  ClArgs mirrors the kernel's argument list: the kernarg segment lays the arguments out in
 // order at their natural alignment, exactly like this struct.  (Passing ONE struct argument instead made every use in the
 // march a scalar load: 3.5 -> 4.0 ms.)
-struct ClArgs { FrameClouds F; RowMap M; float* out; const YRow* ytab; };
+struct ClArgs { FrameClouds F; RowMap M; float* out; const YRow* ytab; const float* htab; unsigned hbias4; };
+// offset of argument I in the kernarg segment of a kernel with the parameter types A...
+template <size_t I, class... A>
+constexpr size_t kernarg_off(void (*)(A...)) {
+    constexpr size_t sz[] = {sizeof(A)...}, al[] = {alignof(A)...};
+    static_assert(sizeof...(A) == 6, "ClArgs mirrors six kernel arguments");
+    size_t o = 0;
+    for (size_t i = 0; i <= I; ++i) {
+        o = (o + al[i] - 1) / al[i] * al[i];
+        if (i < I) o += sz[i];
+    }
+    return o;
+}
 // LM, the light march (decided on the host from L * dt): 1 = no x and no y component (light_march_z), 2 = no x component
 // (light_march_yz; YTAB kernels only), 0 = general (coop_density per light sample)
 // BUILD (CLOUDS_* of sbx_frame.h): CLOUDS_DEFAULT is app_clouds.h as shipped.  CLOUDS_LUMINANCE (`#if 0` of :118 on) runs the same light
@@ -813,11 +908,17 @@ struct ClArgs { FrameClouds F; RowMap M; float* out; const YRow* ytab; };
 // k_clouds_lumtab's table behind the y rows, by the wave-uniform step index (a scalar load); the table-less kernels evaluate
 // clouds_height_lum in place — and integrates.  Nothing is parked, so its park area is the five slots that hold the integrator state,
 // the phase and the skip bound (1.25 KB instead of 3 KB), and its register budget is its own (CL_MIN_WAVES_HEIGHT).
-template <bool YTAB, bool REG, int LM, bool SM = false, int BUILD = CLOUDS_DEFAULT>   // SM: exp_small_ (launch_clouds: the frame's exp arguments lie in its domain)
-__global__ void __launch_bounds__(64 * CL_TX, BUILD == CLOUDS_HEIGHT ? (YTAB ? CL_MIN_WAVES_HEIGHT : CL_MIN_WAVES_HEIGHT_NOTAB) : (LM == 1 && (YTAB || !CL_NOTAB_GEN)) ? CL_MIN_WAVES : (LM == 2 ? CL_MIN_WAVES_YZ : CL_MIN_WAVES_GEN)) k_clouds(FrameClouds F, RowMap M, float* __restrict__ out_arg,
-                                                          const YRow* __restrict__ ytab) {
+// GT (CL_GTAB; YTAB && REG && LM != 0 only; 1 + CL_GTAB_OCT): the lattice hashes of octaves GT - 1 ... 3 come from the context's table
+// `htab` (GTab above), in the main sample and in the light march; the lower octaves keep the per-wave cache (GT = 1: the kernel has no
+// cache in LDS and no cross-lane step).  Lanes that do not march are given the straight-up ray, whose indices are in the table.
+template <bool YTAB, bool REG, int LM, bool SM = false, int BUILD = CLOUDS_DEFAULT, int GT = 0>   // SM: exp_small_ (launch_clouds: the frame's exp arguments lie in its domain)
+__global__ void __launch_bounds__(64 * CL_TX, BUILD == CLOUDS_HEIGHT ? (YTAB ? CL_MIN_WAVES_HEIGHT : CL_MIN_WAVES_HEIGHT_NOTAB) : GT != 0 ? (LM == 2 ? CL_MIN_WAVES_GTAB_YZ : CL_MIN_WAVES_GTAB) : (LM == 1 && (YTAB || !CL_NOTAB_GEN)) ? CL_MIN_WAVES : (LM == 2 ? CL_MIN_WAVES_YZ : CL_MIN_WAVES_GEN)) k_clouds(FrameClouds F, RowMap M, float* __restrict__ out_arg,
+                                                          const YRow* __restrict__ ytab, const float* __restrict__ htab, unsigned hbias4) {
+    static_assert(GT == 0 || GT == 1 || GT == 3 || GT == 4, "a stage of the main sample reads all its octaves from one place: the table starts at octave 0, 2 or 3");
+    static_assert(!GT || (YTAB && REG && LM != 0), "the hash-table kernels are the y-table REG kernels with the z-only or the y-z light march");
     const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();        // (for the dispatch order's cost table, RowMap.cost)
-    __shared__ WaveCache cache[CL_TX];
+    __shared__ WaveCache cache[CL_TX];                       // (GT = 1: never touched, so no LDS is allocated for it)
+    const GTab gtab{htab, hbias4};
 #if CL_PARK
     // the march state a lit step does not need while its light march runs, parked in LDS for that time (a manual spill to
     // the fast memory: what the register allocator would otherwise send to scratch when the kernel is held to 96 VGPRs)
@@ -837,7 +938,7 @@ __global__ void __launch_bounds__(64 * CL_TX, BUILD == CLOUDS_HEIGHT ? (YTAB ? C
     WaveCache& S = cache[threadIdx.x >> 6];
     if (!NOTAB) for (int i = threadIdx.x; i < ETAB_N; i += 64 * CL_TX) etab[i] = (ETAB_N == 64) ? kExp2Tab64[i] : kExp2Tab[i];
     if (CL_TX > 1) __syncthreads();
-    for (int i = lane; i < 4 * HC_SLOTS; i += 64) (&S.tag[0][0])[i] = 0x7fc00001u;   // empty
+    if constexpr (GT != 1) for (int i = lane; i < 4 * HC_SLOTS; i += 64) (&S.tag[0][0])[i] = 0x7fc00001u;   // empty
 #ifdef SBX_CL_STATS
     if (lane < 8) S.stat[lane] = 0.f;
 #endif
@@ -880,6 +981,15 @@ __global__ void __launch_bounds__(64 * CL_TX, BUILD == CLOUDS_HEIGHT ? (YTAB ? C
                 const v3 impact = F.cam.eye + dir * t0;
                 projection = dir;
                 origin = mul(F.sky_rot, impact - ac);
+            }
+            if constexpr (GT != 0) {
+                // A lane of this wave that does not march (below the horizon cut, or outside the frame) still runs every lookup of
+                // the march, with dir / dir.y huge, infinite or NaN: it takes the straight-up ray instead, once, here — positions the
+                // host's index bound covers.  Its results are never used (alive = lit = false).  Marching lanes keep their own ray.
+                if (!marches) {
+                    projection = V3(0.f, 1.f, 0.f);
+                    origin = (F.cam.eye + V3(0.f, 150.f, 0.f)) + F.wind_off;
+                }
             }
 #if CL_PARK
             if (BUILD != CLOUDS_LUMINANCE) pk[(8 - PARK_0) * 64] = hg_phase(clamp_(dot(F.sun_dir, dir), 0.f, 1.f), .2f);
@@ -930,7 +1040,7 @@ __global__ void __launch_bounds__(64 * CL_TX, BUILD == CLOUDS_HEIGHT ? (YTAB ? C
                 float mfx[4] = {0.f, 0.f, 0.f, 0.f}, mnxy[4] = {0.f, 0.f, 0.f, 0.f};
                 float mab[4] = {0.f, 0.f, 0.f, 0.f}, mcd[4] = {0.f, 0.f, 0.f, 0.f};
                 float mpz[4] = {u2f(0x7fc00001u), u2f(0x7fc00001u), u2f(0x7fc00001u), u2f(0x7fc00001u)};
-                float density = YTAB ? coop_density_row<LIP, SM, D3>(F, pos, row, alive, alive_mask, S, lane, mfx, mnxy, mab, mcd, mpz, lip_slot, skip, vcd, vcr)
+                float density = YTAB ? coop_density_row<LIP, SM, D3, GT>(F, pos, row, alive, alive_mask, S, lane, mfx, mnxy, mab, mcd, mpz, lip_slot, skip, vcd, vcr, gtab)
                                            : coop_density<false, SM>(F, pos, alive, S, lane);
                 const bool lit = alive && !(density < .005f);     // integrate_volume :132
                 const unsigned long long lit_mask = alive_mask & wave_mask(!(density < .005f));
@@ -954,8 +1064,8 @@ __global__ void __launch_bounds__(64 * CL_TX, BUILD == CLOUDS_HEIGHT ? (YTAB ? C
                         asm volatile("" ::: "memory");     // the reloads below cannot be forwarded from these stores: the values
                                                            // are dead across the light march
 #endif
-                        if (LM == 1) ltrans = light_march_z<YTAB, REG, SM>(F, lp, lstep, lit, lit_mask, S, lane, row, mfx, mnxy, mab, mcd, mpz, etab, vsigma, vdt, vcov, vcd, vcr);
-                        else ltrans = light_march_yz<REG, SM>(F, lp, lstep, lit, lit_mask, S, lane, mfx, etab, vsigma, vdt, vcov, vcd, vcr);
+                        if (LM == 1) ltrans = light_march_z<YTAB, REG, SM, GT>(F, lp, lstep, lit, lit_mask, S, lane, row, mfx, mnxy, mab, mcd, mpz, etab, vsigma, vdt, vcov, vcd, vcr, gtab);
+                        else ltrans = light_march_yz<REG, SM, GT>(F, lp, lstep, lit, lit_mask, S, lane, mfx, etab, vsigma, vdt, vcov, vcd, vcr, gtab);
 #if CL_PARK
                         asm volatile("" ::: "memory");
                         origin.x = pk[(0 - PARK_0) * 64]; origin.z = pk[(1 - PARK_0) * 64]; projection.x = pk[(2 - PARK_0) * 64]; projection.z = pk[(3 - PARK_0) * 64];
@@ -1085,14 +1195,44 @@ static bool clouds_div3_domain(const FrameClouds& F) {
     return std::isfinite(F.cov) && std::isfinite(F.cov_d) && std::isfinite(F.cov_r) && c >= 0x1p-20 && c <= 0x1p20 && d >= 0x1p-60 &&
            d <= 0x1p60 && F.cov_d == F.cov_hi - F.cov && F.cov_r == 1.0f / F.cov_d;
 }
-static bool clouds_index_domain(const FrameClouds& F) {
+// (the bound itself: every lattice index, corner offsets included, of every main and light sample of the frame is below it in
+//  magnitude — what the context's hash table is sized by; inf / NaN if anything it is made of is)
+static double clouds_index_bound(const FrameClouds& F) {
     auto m3 = [](v3 v) { return std::fmax(std::fabs((double)v.x), std::fmax(std::fabs((double)v.y), std::fabs((double)v.z))); };
     const double reach = 21.0 * 150.0 + 22.0 * std::fabs((double)F.dt) * (double)F.steps;
     const double light = ((double)F.lsteps + 1.0) * m3(F.sun_dir) * std::fabs((double)F.dt);
     const double sky = F.sky ? std::fabs((double)F.atm_r) + std::fabs((double)F.atm_y) : 0.0;
     const double P = m3(F.cam.eye) + m3(F.wind_off) + reach + light + sky;
-    const double n = 271.0 * (P * std::fabs((double)F.nf) * 2.03 * 18.4 + 2.0);
+    return 271.0 * (P * std::fabs((double)F.nf) * 2.03 * 18.4 + 2.0);
+}
+static bool clouds_index_domain(const FrameClouds& F) {
+    const double n = clouds_index_bound(F);
     return std::isfinite(n) && n <= 549755813888.0;                  // 2^39; NaN compares false
+}
+// The hash-table kernels' launch condition, and the table range R the frame needs: the table holds the lattice indices [-R, R + 271].
+// 0: the launch takes the cache kernels (CL_GTAB off, a point list, SKY_SPHERE, not a regular frame, the general light march, a bound
+// beyond CLOUDS_HASHTAB_MAX_RANGE or not finite).  R is the power of two at or above the bound, at least CLOUDS_HASHTAB_MIN_RANGE: a
+// slowly growing wind_off asks for a larger table O(log) times.
+// The bound takes |dir / dir.y| <= 21 for a marching lane, i.e. dir = normalize(v) a unit vector or NaN: so the camera is checked
+// here as well — finite, and so small that |v| cannot overflow (a NaN direction indexes entry `bias`: v_cvt_i32_f32(NaN) = 0).
+int clouds_hashtab_range(const FrameClouds& F, const RowMap& M, int build) {
+#if !CL_GTAB
+    return 0;
+#endif
+    if (F.sky || M.frag || F.steps <= 0 || !clouds_regular(F)) return 0;
+    const v3 lstep = F.sun_dir * F.dt;
+    const bool zl = build == CLOUDS_HEIGHT || (lstep.x == 0.f && lstep.y == 0.f);
+    const bool yz = !zl && lstep.x == 0.f && CL_YZ_MARCH;
+    if (!zl && !yz) return 0;
+    const Camera& c = F.cam;
+    const float cv[] = {c.fwd.x, c.fwd.y, c.fwd.z, c.up.x, c.up.y, c.up.z, c.right.x, c.right.y, c.right.z};
+    for (float v : cv) if (!(std::fabs(v) <= 4.f)) return 0;                                       // NaN compares false
+    if (!(std::fabs(c.fov) <= 1e6f) || !(std::fabs(c.aspect_x * c.fov) <= 1e6f)) return 0;
+    const double n = clouds_index_bound(F);
+    if (!(n <= (double)CLOUDS_HASHTAB_MAX_RANGE)) return 0;
+    int R = CLOUDS_HASHTAB_MIN_RANGE;
+    while ((double)R < n) R *= 2;
+    return R;
 }
 
 dim3 clouds_grid(const RowMap& M) { return grid_for<CL_TW, CL_TX>(M); }
@@ -1101,8 +1241,8 @@ dim3 clouds_grid(const RowMap& M) { return grid_for<CL_TW, CL_TX>(M); }
 // instantiations.  The HEIGHT build has no light march, so the form of L * dt selects nothing there (its instantiations carry LM = 1
 // for the one thing LM decides outside the light march: the SM kernels' div3_ smoothstep in the main sample).
 template <int BUILD>
-static void launch_clouds_build(const FrameClouds& F_in, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
-                                bool build_table) {
+static bool launch_clouds_build(const FrameClouds& F_in, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
+                                bool build_table, const CloudsHashTab* ht) {
     constexpr bool HT = BUILD == CLOUDS_HEIGHT;
     FrameClouds F = F_in;
     F.lip_ok = clouds_lip_domain(F) ? 1 : 0;
@@ -1132,38 +1272,65 @@ static void launch_clouds_build(const FrameClouds& F_in, const RowMap& M, float*
         // (the caller rebuilds a table that has no luminances before the HEIGHT build reads it: sbx_ytab.hip)
         if (build_table && HT) hipLaunchKernelGGL(k_clouds_lumtab, dim3((F.steps + 63) / 64), dim3(64), 0, s, F.steps, const_cast<float*>(lum_of(tab, F.steps)));
         const YRow* ct = tab;
+        const float* const hnull = nullptr;
         // SM kernels: exp_small_'s domain AND lattice indices below 2^40 for sin_b40_
         const bool sm = F.exp_small && clouds_index_domain(F) && (!CL_DIV3 || clouds_div3_domain(F)) && CL_EXP_SMALL && CL_EXP_ASM && CL_EXP64;
-        if (reg && zl && sm) hipLaunchKernelGGL((k_clouds<true, true, 1, true, BUILD>), grid, block, pad, s, F, M, out, ct);
-        else if (reg && zl) hipLaunchKernelGGL((k_clouds<true, true, 1, false, BUILD>), grid, block, pad, s, F, M, out, ct);
-        else if (zl) hipLaunchKernelGGL((k_clouds<true, false, 1, false, BUILD>), grid, block, 0, s, F, M, out, ct);
+#if CL_GTAB
+        // the hash-table kernels: iff a ready table of the context covers the frame's bound (clouds_hashtab_range has the other conditions)
+        const int need = (ht && ht->tab) ? clouds_hashtab_range(F, M, BUILD) : 0;
+        if (need > 0 && need <= ht->range) {
+            const float* const htab = ht->tab;
+            const unsigned hb4 = 4u * (unsigned)ht->bias;
+            const bool yzsm = sm && CL_YZ_SM;
+            if (zl && sm) hipLaunchKernelGGL((k_clouds<true, true, 1, true, BUILD, CL_GTAB_OCT + 1>), grid, block, 0, s, F, M, out, ct, htab, hb4);
+            else if (zl) hipLaunchKernelGGL((k_clouds<true, true, 1, false, BUILD, CL_GTAB_OCT + 1>), grid, block, 0, s, F, M, out, ct, htab, hb4);
+            else if constexpr (!HT) {
+                if (yzsm) hipLaunchKernelGGL((k_clouds<true, true, 2, true, BUILD, CL_GTAB_OCT + 1>), grid, block, 0, s, F, M, out, ct, htab, hb4);
+                else hipLaunchKernelGGL((k_clouds<true, true, 2, false, BUILD, CL_GTAB_OCT + 1>), grid, block, 0, s, F, M, out, ct, htab, hb4);
+            }
+            return true;
+        }
+#endif
+        if (reg && zl && sm) hipLaunchKernelGGL((k_clouds<true, true, 1, true, BUILD>), grid, block, pad, s, F, M, out, ct, hnull, 0u);
+        else if (reg && zl) hipLaunchKernelGGL((k_clouds<true, true, 1, false, BUILD>), grid, block, pad, s, F, M, out, ct, hnull, 0u);
+        else if (zl) hipLaunchKernelGGL((k_clouds<true, false, 1, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
         else if constexpr (!HT) {
-            if (reg && yz && sm && CL_YZ_SM) hipLaunchKernelGGL((k_clouds<true, true, 2, true, BUILD>), grid, block, 0, s, F, M, out, ct);
-            else if (reg && yz) hipLaunchKernelGGL((k_clouds<true, true, 2, false, BUILD>), grid, block, 0, s, F, M, out, ct);
-            else if (reg && sm) hipLaunchKernelGGL((k_clouds<true, true, 0, true, BUILD>), grid, block, 0, s, F, M, out, ct);
-            else if (reg) hipLaunchKernelGGL((k_clouds<true, true, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct);
-            else if (yz) hipLaunchKernelGGL((k_clouds<true, false, 2, false, BUILD>), grid, block, 0, s, F, M, out, ct);
-            else hipLaunchKernelGGL((k_clouds<true, false, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct);
+            if (reg && yz && sm && CL_YZ_SM) hipLaunchKernelGGL((k_clouds<true, true, 2, true, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
+            else if (reg && yz) hipLaunchKernelGGL((k_clouds<true, true, 2, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
+            else if (reg && sm) hipLaunchKernelGGL((k_clouds<true, true, 0, true, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
+            else if (reg) hipLaunchKernelGGL((k_clouds<true, true, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
+            else if (yz) hipLaunchKernelGGL((k_clouds<true, false, 2, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
+            else hipLaunchKernelGGL((k_clouds<true, false, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
         }
     } else {
         const YRow* ct = nullptr;
+        const float* const hnull = nullptr;
         const bool sm = F.exp_small && clouds_index_domain(F) && (!CL_DIV3 || clouds_div3_domain(F)) && CL_EXP_SMALL && CL_EXP_ASM && CL_EXP64;
-        if (reg && zl && sm) hipLaunchKernelGGL((k_clouds<false, true, 1, true, BUILD>), grid, block, 0, s, F, M, out, ct);
-        else if (reg && zl) hipLaunchKernelGGL((k_clouds<false, true, 1, false, BUILD>), grid, block, 0, s, F, M, out, ct);
-        else if (zl && !reg) hipLaunchKernelGGL((k_clouds<false, false, 1, false, BUILD>), grid, block, 0, s, F, M, out, ct);
+        if (reg && zl && sm) hipLaunchKernelGGL((k_clouds<false, true, 1, true, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
+        else if (reg && zl) hipLaunchKernelGGL((k_clouds<false, true, 1, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
+        else if (zl && !reg) hipLaunchKernelGGL((k_clouds<false, false, 1, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
         else if constexpr (!HT) {
-            if (reg && sm) hipLaunchKernelGGL((k_clouds<false, true, 0, true, BUILD>), grid, block, 0, s, F, M, out, ct);
-            else if (reg) hipLaunchKernelGGL((k_clouds<false, true, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct);
-            else hipLaunchKernelGGL((k_clouds<false, false, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct);
+            if (reg && sm) hipLaunchKernelGGL((k_clouds<false, true, 0, true, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
+            else if (reg) hipLaunchKernelGGL((k_clouds<false, true, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
+            else hipLaunchKernelGGL((k_clouds<false, false, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
         }
     }
+    return false;
 }
 
-void launch_clouds(const FrameClouds& F, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
-                   bool build_table, int build) {
-    if (build == CLOUDS_HEIGHT) launch_clouds_build<CLOUDS_HEIGHT>(F, M, out, s, variant, ytab, ytab_rows, build_table);
-    else if (build == CLOUDS_LUMINANCE) launch_clouds_build<CLOUDS_LUMINANCE>(F, M, out, s, variant, ytab, ytab_rows, build_table);
-    else launch_clouds_build<CLOUDS_DEFAULT>(F, M, out, s, variant, ytab, ytab_rows, build_table);
+// ClArgs against the kernel's own argument list (the epilogue reloads F, M and out through it)
+typedef decltype(&k_clouds<true, true, 1>) KCloudsFn;
+static_assert(kernarg_off<0>(KCloudsFn(nullptr)) == offsetof(ClArgs, F) && kernarg_off<1>(KCloudsFn(nullptr)) == offsetof(ClArgs, M) &&
+              kernarg_off<2>(KCloudsFn(nullptr)) == offsetof(ClArgs, out) && kernarg_off<3>(KCloudsFn(nullptr)) == offsetof(ClArgs, ytab) &&
+              kernarg_off<4>(KCloudsFn(nullptr)) == offsetof(ClArgs, htab) && kernarg_off<5>(KCloudsFn(nullptr)) == offsetof(ClArgs, hbias4) &&
+              offsetof(ClArgs, hbias4) + sizeof(unsigned) <= sizeof(ClArgs) && sizeof(ClArgs) < offsetof(ClArgs, hbias4) + sizeof(unsigned) + alignof(ClArgs),
+              "ClArgs must mirror k_clouds' argument list, argument for argument");
+
+bool launch_clouds(const FrameClouds& F, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
+                   bool build_table, int build, const CloudsHashTab* ht) {
+    if (build == CLOUDS_HEIGHT) return launch_clouds_build<CLOUDS_HEIGHT>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht);
+    if (build == CLOUDS_LUMINANCE) return launch_clouds_build<CLOUDS_LUMINANCE>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht);
+    return launch_clouds_build<CLOUDS_DEFAULT>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht);
 }
 
 hipError_t bind_fault_clouds(unsigned* word) { return hc_bind_fault_word(word); }

@@ -89,6 +89,7 @@ static void release(HostStaging& S) {
 static void destroy_ctx(sbx_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     release(ctx->ytab);
+    release(ctx->hashtab);
     release(ctx->mi);
     tile_order_destroy(ctx->tile_orders);
     release(ctx->hs);
@@ -518,6 +519,29 @@ int sbx_debug_order_build(sbx_ctx* ctx, const unsigned* cost_host, int gx, int g
     if (e == hipSuccess) e = hipMemcpy(table_host, mem + n * 2, n * 4, hipMemcpyDeviceToHost);
     (void)hipFree(mem);
     if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "sbx_debug_order_build", e);
+    return SBX_OK;
+}
+
+int sbx_debug_clouds_hashtab(sbx_ctx* ctx, int* entries, int* bias, int* tables_built, int* last_launch_used_table) {
+    if (!ctx) return SBX_ERR_ARG;
+    const HashTables& H = ctx->hashtab;
+    if (entries) *entries = H.tabs.empty() ? 0 : H.tabs.back().entries;
+    if (bias) *bias = H.tabs.empty() ? 0 : H.tabs.back().bias;
+    if (tables_built) *tables_built = (int)H.tabs.size();
+    if (last_launch_used_table) *last_launch_used_table = H.last_used;
+    return SBX_OK;
+}
+
+int sbx_debug_clouds_hashtab_read(sbx_ctx* ctx, size_t first, size_t count, float* host) {
+    if (!ctx) return SBX_ERR_ARG;
+    const HashTables& H = ctx->hashtab;
+    if (H.tabs.empty()) return fail(ctx, SBX_ERR_ARG, "sbx_debug_clouds_hashtab_read: no table has been built");
+    const HashTables::Tab& t = H.tabs.back();
+    if (!host || first > (size_t)t.entries || count > (size_t)t.entries - first) return fail(ctx, SBX_ERR_ARG, "sbx_debug_clouds_hashtab_read: range outside the table");
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess) e = hipEventSynchronize(t.ready);
+    if (e == hipSuccess) e = hipMemcpy(host, t.dev + first, count * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "sbx_debug_clouds_hashtab_read", e);
     return SBX_OK;
 }
 

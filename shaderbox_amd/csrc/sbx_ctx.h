@@ -3,7 +3,7 @@
 // release function that tolerates a half-built (null) member; sbx_destroy, and a failed sbx_create, is the sequence of them.
 //   sbx_capi.hip        create / destroy, render_mapped (the one place a render kernel is launched), rows, setters, the fault word
 //   sbx_frames.hip      the per-frame constant blocks of every app (pure host math), the aux defaults
-//   sbx_ytab.hip        APP_CLOUDS' y tables
+//   sbx_ytab.hip        APP_CLOUDS' y tables and lattice-hash tables
 //   sbx_main_image.hip  sbx_main_image over cached frames, the point lists, the stats
 //   sbx_split.hip       the multi-GPU split: row arithmetic, the span model and its tables, split / span / assemble entry points
 //   sbx_eval.hip        the eval and test hooks, texture and noise-volume binding
@@ -56,6 +56,23 @@ struct YTables {
     bool big_lum = false;
     hipEvent_t big_ready{};
     bool have_big_ready = false;
+};
+
+// APP_CLOUDS lattice-hash tables (sbx_ytab.hip clouds_hash_table; kern_clouds.hip GTab).  A table is built lazily, on the stream of the
+// first eager launch that wants it, and NEVER changes afterwards: a frame whose index bound outgrows the largest one gets a new,
+// larger table (ranges are powers of two between CLOUDS_HASHTAB_MIN_RANGE and _MAX_RANGE, so all of them together stay below twice
+// the largest); the old ones may still be read by launches in flight and are freed by release().  Of the building stream only the
+// `ready` event is kept: a launch waits for it (a no-op on the building stream) until the host has once seen it complete.
+// INVARIANT: a Tab in `tabs` has its build kernel ENQUEUED and `ready` recorded behind it; tabs is ascending in range.
+struct HashTables {
+    struct Tab {
+        float* dev = nullptr;
+        int range = 0, entries = 0, bias = 0;
+        hipEvent_t ready{};
+        bool seen_complete = false;
+    };
+    std::vector<Tab> tabs;
+    int last_used = 0;                     // the last APP_CLOUDS launch of the context took a hash-table kernel (sbx_debug_clouds_hashtab)
 };
 
 // per-stream timing events (sbx_set_timing): a pair brackets the last launch on its stream
@@ -152,6 +169,7 @@ struct sbx_ctx {
     int precision = 0;                     // sbx_set_precision: 0 bit-exact (default), 1 = SBX_PRECISION_1E4 (APP_ATMOSPHERE only)
     int sdf_roots = 0;                     // sbx_set_variant 2 / 3: the SDF kernels' square-root witness test build / IEEE roots
     YTables ytab;
+    HashTables hashtab;
     Timers timers;
     NoiseVolumes noise;
     Texture2d tex2d;
@@ -204,6 +222,7 @@ Frame2d build_2d(const sbx_uniforms& U);
 // ---- sbx_ytab.hip
 int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rgba, hipStream_t s, bool capturing, int build = CLOUDS_DEFAULT);
 void release(YTables& Y);
+void release(HashTables& H);
 
 // ---- sbx_main_image.hip
 void mi_invalidate(sbx_ctx* ctx);          // forget the cached frames (something they were rendered with changed)

@@ -143,9 +143,19 @@ __device__ __forceinline__ void store_rgba4(const RowMap& M, float* out, size_t 
 }
 
 // launchers (one per app), defined next to their kernels
-void launch_clouds(const FrameClouds& F, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
-                   bool build_table, int build = CLOUDS_DEFAULT);   // build: CLOUDS_* (sbx_frame.h); build_table with CLOUDS_HEIGHT also
-                                                                    // writes the steps' luminances behind the y rows
+// APP_CLOUDS' lattice-hash table (kern_clouds.hip GTab; owned by the context, sbx_ytab.hip): tab[i] = hash1((float)(i - bias)) for
+// 0 <= i < entries, covering the lattice indices [-range, range + 271] with CLOUDS_HASHTAB_GUARD entries of slack at both ends
+struct CloudsHashTab { const float* tab = nullptr; int entries = 0, bias = 0, range = 0; };
+constexpr int CLOUDS_HASHTAB_MIN_RANGE = 1 << 18;   // the smallest table (2 MB; the default frame's bound is 6.4e4)
+constexpr int CLOUDS_HASHTAB_MAX_RANGE = 1 << 22;   // the largest (32 MB); a frame whose bound is beyond it keeps the LDS hash cache
+constexpr int CLOUDS_HASHTAB_GUARD = 512;
+constexpr int clouds_hashtab_entries(int range) { return 2 * range + 272 + 2 * CLOUDS_HASHTAB_GUARD; }
+int clouds_hashtab_range(const FrameClouds& F, const RowMap& M, int build);   // the range the launch needs; 0: it does not take the table kernels
+void launch_clouds_hashtab(float* tab, int entries, int bias, hipStream_t s);
+// returns whether the launch took a hash-table kernel (only with `ht`: a READY table; taken iff it covers the frame's index bound)
+bool launch_clouds(const FrameClouds& F, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
+                   bool build_table, int build = CLOUDS_DEFAULT,    // build: CLOUDS_* (sbx_frame.h); build_table with CLOUDS_HEIGHT also
+                   const CloudsHashTab* ht = nullptr);              // writes the steps' luminances behind the y rows
 constexpr int CLOUDS_YTAB_ROWS = 4096;      // march steps covered by a y table of the ring (208 KB per table; beyond it the one big
                                             // table below, or in a capture the table-less kernels: 1100 steps at 4K took 48 ms without a table)
 constexpr int CLOUDS_YTAB_STEP_BYTES = 48 + 4;   // per march step: its YRow and, behind the frame's rows, the HEIGHT build's luminance

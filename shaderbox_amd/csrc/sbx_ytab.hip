@@ -1,5 +1,5 @@
 // shaderbox_amd/csrc/sbx_ytab.hip — APP_CLOUDS' y tables (YTables, sbx_ctx.h): which table a launch of k_clouds reads, when one
-// is rebuilt, and who has to wait for whom.
+// is rebuilt, and who has to wait for whom; and its lattice-hash tables (HashTables), which are built once and never rebuilt.
 #include "sbx_ctx.h"
 #include <cstring>
 
@@ -14,7 +14,54 @@ namespace sbx {
 // build (CLOUDS_*): the three builds share the tables.  The HEIGHT build also reads the steps' luminances, which lie behind the y rows
 // and are written only by a rebuild made for it: a table without them counts as stale for that build (`lum`, `big_lum`), a table
 // with them serves the other builds unchanged.
+// The lattice-hash table of a launch that reads a y table (kern_clouds.hip GTab): the smallest of the context's tables that covers
+// the frame's index bound, made ready for stream `s` — or none (tab == nullptr), and the launch takes the LDS hash cache:
+//   the launch does not want one (clouds_hashtab_range: CL_GTAB off, a point list, the general light march, a bound beyond the cap
+//   or not finite, ...);
+//   the stream is being captured and no table the host has seen complete covers the frame: nothing is allocated, built, queried
+//   or waited for inside a capture;
+//   the allocation or the event failed (the error is dropped: the cache kernels render the same frame).
+// A new table is built on `s` in front of the launch.  A table never changes, so its only ordering is "built before read": until the
+// host has once seen `ready` complete (hipEventQuery), every launch waits for it on its own stream.
+static CloudsHashTab clouds_hash_table(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, hipStream_t s, bool capturing, int build) {
+    CloudsHashTab none;
+    const int need = clouds_hashtab_range(F, M, build);
+    if (need <= 0) return none;
+    HashTables& H = ctx->hashtab;
+    HashTables::Tab* t = nullptr;
+    for (auto& c : H.tabs) if (c.range >= need) { t = &c; break; }       // ascending: the smallest that covers
+    if (t && !t->seen_complete) {
+        if (capturing) return none;
+        if (hipEventQuery(t->ready) == hipSuccess) t->seen_complete = true;
+        else {
+            (void)hipGetLastError();                                     // (hipErrorNotReady)
+            if (hipStreamWaitEvent(s, t->ready, 0) != hipSuccess) { (void)hipGetLastError(); return none; }
+        }
+    }
+    if (!t) {
+        if (capturing) return none;
+        HashTables::Tab n;
+        n.range = need;
+        n.entries = clouds_hashtab_entries(need);
+        n.bias = need + CLOUDS_HASHTAB_GUARD;
+        if (hipMalloc((void**)&n.dev, (size_t)n.entries * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return none; }
+        if (hipEventCreateWithFlags(&n.ready, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(n.dev); return none; }
+        launch_clouds_hashtab(n.dev, n.entries, n.bias, s);
+        if (hipGetLastError() != hipSuccess || hipEventRecord(n.ready, s) != hipSuccess) {
+            // (nothing reads the table: freeing it waits for whatever was enqueued)
+            (void)hipGetLastError(); (void)hipEventDestroy(n.ready); (void)hipFree(n.dev);
+            return none;
+        }
+        H.tabs.push_back(n);                                             // (a new table is larger than every older one: still ascending)
+        t = &H.tabs.back();
+    }
+    CloudsHashTab r;
+    r.tab = t->dev; r.entries = t->entries; r.bias = t->bias; r.range = t->range;
+    return r;
+}
+
 int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rgba, hipStream_t s, bool capturing, int build) {
+    ctx->hashtab.last_used = 0;
     const bool need_lum = build == CLOUDS_HEIGHT;
     const bool uses_table = ctx->variant == 0 && F.steps > 0 && F.steps <= CLOUDS_YTAB_ROWS;
     if (!uses_table && ctx->variant == 0 && F.steps > CLOUDS_YTAB_ROWS && F.steps <= CLOUDS_YTAB_BIG_MAX && !capturing) {
@@ -42,7 +89,8 @@ int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rg
         } else {
             (void)hipStreamWaitEvent(s, ctx->ytab.big_ready, 0);
         }
-        launch_clouds(F, M, rgba, s, 0, ctx->ytab.big, ctx->ytab.big_rows, rebuild, build);
+        const CloudsHashTab ht = clouds_hash_table(ctx, F, M, s, capturing, build);
+        ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, ctx->ytab.big, ctx->ytab.big_rows, rebuild, build, &ht) ? 1 : 0;
         if (rebuild) {
             (void)hipEventRecord(ctx->ytab.big_ready, s);
             std::memcpy(ctx->ytab.big_key, key, sizeof(key));
@@ -58,7 +106,8 @@ int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rg
     }
     if (capturing) {
         char* tab = ctx->ytab.ring + (size_t)(CLOUDS_YTAB_RING + (ctx->ytab.cap_next++ % CLOUDS_YTAB_CAPTURE)) * CLOUDS_YTAB_BYTES;
-        launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, true, build);
+        const CloudsHashTab ht = clouds_hash_table(ctx, F, M, s, capturing, build);
+        ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, true, build, &ht) ? 1 : 0;
         return SBX_OK;
     }
     const float key[3] = {F.cam.eye.y, F.wind_off.y, F.dt};
@@ -91,7 +140,8 @@ int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rg
         (void)hipStreamWaitEvent(s, ctx->ytab.ready, 0);           // table was built on another stream
     }
     char* tab = ctx->ytab.ring + (size_t)slot * CLOUDS_YTAB_BYTES;
-    launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, rebuild, build);
+    const CloudsHashTab ht = clouds_hash_table(ctx, F, M, s, capturing, build);
+    ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, rebuild, build, &ht) ? 1 : 0;
     if (rebuild) {
         (void)hipEventRecord(ctx->ytab.ready, s);                  // the build is enqueued: now the cache state is true
         std::memcpy(ctx->ytab.key, key, sizeof(key));
@@ -120,6 +170,14 @@ void release(YTables& Y) {
     if (Y.have_ready) (void)hipEventDestroy(Y.ready);
     for (auto& sl : Y.slots) for (auto& u : sl.users) (void)hipEventDestroy(u.second);
     Y = YTables();
+}
+
+void release(HashTables& H) {
+    for (auto& t : H.tabs) {
+        if (t.dev) (void)hipFree(t.dev);
+        (void)hipEventDestroy(t.ready);
+    }
+    H = HashTables();
 }
 
 }  // namespace sbx

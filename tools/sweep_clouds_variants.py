@@ -106,6 +106,7 @@ def one(path, N):
     R = shaderbox_amd.Renderer(0)
     rng = np.random.default_rng(123)
     bad = 0
+    tab = 0                                           # frames whose default launch took a hash-table kernel (CL_GTAB)
     for i in range(N):
         aux = shaderbox_amd.clouds_defaults(R.lib)
         t = float(rng.uniform(0, 50)) if i % 3 else float(rng.uniform(0, 3))
@@ -124,12 +125,14 @@ def one(path, N):
             aux.sun_dir[0] = 0.0                      # a sun in the y-z plane: the y-z light march
         W, H = (640, 360) if i % 4 else (333, 187)
         R.set_variant(0); a = R.render("clouds", W, H, t, mouse=mouse, aux=aux).clone()
+        tab += R.clouds_hashtab()[3]
         R.set_variant(1); b = R.render("clouds", W, H, t, mouse=mouse, aux=aux)
         same = (a.view(torch.int32) == b.view(torch.int32)) | (torch.isnan(a) & torch.isnan(b))
         if not bool(same.all()):
             bad += 1
     R.set_variant(0)
-    print("%-44s frames %d, with a differing pixel: %d%s" % (os.path.basename(path), N, bad, "" if bad == 0 else "   <-- DIFFERENT"))
+    print("%-44s frames %d (hash-table kernels: %d), with a differing pixel: %d%s"
+          % (os.path.basename(path), N, tab, bad, "" if bad == 0 else "   <-- DIFFERENT"))
 
 
 if __name__ == "__main__":
@@ -162,3 +165,5 @@ if __name__ == "__main__":
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", p, "--frames", str(N)], capture_output=True, text=True)
         out = [l for l in r.stdout.splitlines() if "frames" in l]
         print(out[-1] if out else "%-44s FAILED: %s" % (os.path.basename(p), r.stderr.strip().splitlines()[-1] if r.stderr.strip() else "?"))
+        if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
+            sys.exit("a sweep process died (status %d): nothing more is started on this GPU" % r.returncode)

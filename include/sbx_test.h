@@ -104,13 +104,44 @@ int sbx_debug_raytracer_scene_launches(sbx_ctx* ctx, uint64_t* launches);
 
 /* APP_CLOUDS' lattice-hash tables (csrc/sbx_ctx.h HashTables; csrc/kern_clouds.hip GTab): the newest — largest — table's size in entries and
  * its bias (entry i holds hash(float(i - bias))), 0 / 0 before the first one; how many tables this context has built; and whether its last
- * launch of APP_CLOUDS or of its HEIGHT / LUMINANCE builds took a hash-table kernel (1) or the kernels with the per-wave cache (0).  Any
+ * launch of APP_CLOUDS, of its HEIGHT / LUMINANCE builds or of CLOUDS_SKY took a hash-table kernel (1) or another one (0): `gt != 0` of
+ * sbx_debug_clouds_last_selection's record.  Any
  * pointer may be NULL.  For the tests that the table kernels run where their frames are compared with the per-lane kernel's, and that
  * the launches which must not touch a table do not (tests/test_gpu_clouds_hashtab.py). */
 int sbx_debug_clouds_hashtab(sbx_ctx* ctx, int* entries, int* bias, int* tables_built, int* last_launch_used_table);
 
 /* `count` entries of the newest table from entry `first` on, copied to host memory after waiting for its build. */
 int sbx_debug_clouds_hashtab_read(sbx_ctx* ctx, size_t first, size_t count, float* host);
+
+/* WHICH KERNEL a launch of APP_CLOUDS, of its HEIGHT / LUMINANCE builds or of CLOUDS_SKY took (csrc/kern_clouds.hip: clouds_select is
+ * the host's choice, launch_form<> the one place a k_clouds / k_clouds_perlane launch is made — it writes perlane, ytab_used, reg, lm,
+ * sm, gt and build from its own template arguments). */
+typedef struct sbx_clouds_selection {
+    int build;          /* 0 the shipped build, 1 HEIGHT, 2 LUMINANCE */
+    int perlane;        /* 1: k_clouds_perlane<build>; every field of the next line is 0 then */
+    int ytab_used, reg, lm, sm, gt;   /* k_clouds<YTAB, REG, LM, SM, BUILD, GT> as instantiated (gt: 0, or 1 + the first octave read from the hash table) */
+    int ytab;           /* the y table the launch read: 0 none, 1 a slot of the eager ring, 2 the context's big table, 3 a slot of the capture ring
+                           (sbx_debug_clouds_select, which has no context: 1 for a table of up to 4096 rows, 2 for a longer one) */
+    int sky;            /* the frame is SKY_SPHERE's (CLOUDS_SKY) */
+    /* the host predicates as evaluated for the frame, whether or not the choice came to depend on them */
+    int regular, exp_small, index_domain, div3_domain, lip_ok;
+    int light;          /* the form of sun_dir * dt: 1 z-only (x == 0 and y == 0), 2 y-z (x == 0), 0 general (NaN included) */
+    int need_range;     /* clouds_hashtab_range: the hash-table range the frame needs, 0: it takes no table kernel */
+    int table_range;    /* the range of the ready table the launch was given, 0: none */
+    int reserved;
+    uint64_t launches;  /* launches of these apps by the context so far, this one included (sbx_debug_clouds_select: 0) */
+} sbx_clouds_selection;
+
+/* The record of the context's last launch of APP_CLOUDS, SBX_APP_CLOUDS_HEIGHT / _LUMINANCE or SBX_APP_CLOUDS_SKY (all zero before the
+ * first one).  `last_launch_used_table` of sbx_debug_clouds_hashtab is `gt != 0` of this record. */
+int sbx_debug_clouds_last_selection(sbx_ctx* ctx, sbx_clouds_selection* out);
+
+/* The choice alone: host only, no context, no device, nothing launched (callable on a machine without a GPU, like sbx_span_table).
+ * app: one of the four apps above; variant as sbx_set_variant; "a y table of `ytab_rows` rows is at hand" (0: none), "a ready hash
+ * table of range `table_range` is at hand" (0: none); point_list != 0: the launch is a point list's (sbx_render_points).  Returns
+ * SBX_OK, or SBX_ERR_ARG for another app, a NULL pointer or negative march steps. */
+int sbx_debug_clouds_select(int app, const sbx_uniforms* uni, const void* aux, int variant, int ytab_rows, int table_range, int point_list,
+                            sbx_clouds_selection* out);
 
 #ifdef __cplusplus
 }

@@ -76,6 +76,15 @@ class AuxClouds(ctypes.Structure):          # sbx_aux_clouds (cbuffer b1, APP_CL
                 ("atm_radius", ctypes.c_float), ("atm_ground_y", ctypes.c_float)]
 
 
+class CloudsSelection(ctypes.Structure):    # sbx_clouds_selection (include/sbx_test.h): the kernel a launch of APP_CLOUDS took
+    _fields_ = [(n, ctypes.c_int) for n in ("build", "perlane", "ytab_used", "reg", "lm", "sm", "gt", "ytab", "sky", "regular", "exp_small",
+                                            "index_domain", "div3_domain", "lip_ok", "light", "need_range", "table_range", "reserved")] + \
+               [("launches", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class AuxCloudsUe4(ctypes.Structure):       # sbx_aux_clouds_ue4
     _fields_ = [("coverage", ctypes.c_float), ("thickness", ctypes.c_float), ("absorbtion", ctypes.c_float),
                 ("fuzziness", ctypes.c_float), ("sun_dir", ctypes.c_float * 3), ("_pad1", ctypes.c_float),
@@ -249,6 +258,8 @@ def load_library(path=None):
     lib.sbx_debug_order_build.argtypes = [vp, vp, ci, ci, vp, vp]
     lib.sbx_debug_clouds_hashtab.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int)] * 4
     lib.sbx_debug_clouds_hashtab_read.argtypes = [vp, ctypes.c_size_t, ctypes.c_size_t, vp]
+    lib.sbx_debug_clouds_last_selection.argtypes = [vp, ctypes.POINTER(CloudsSelection)]
+    lib.sbx_debug_clouds_select.argtypes = [ci, ctypes.POINTER(Uniforms), vp, ci, ci, ci, ci, ctypes.POINTER(CloudsSelection)]
     lib.sbx_shared_bytes.argtypes = [vp]
     lib.sbx_shared_bytes.restype = ctypes.c_size_t
     lib.sbx_shared_frame_begin.argtypes = [vp, ci, vp]
@@ -336,6 +347,22 @@ def uniforms(width, height, time, mouse=(0.0, 0.0)):
     u.u_mouse[0], u.u_mouse[1] = float(mouse[0]), float(mouse[1])
     u.u_time = float(time)
     return u
+
+
+def clouds_select(app, width, height, time, mouse=(0.0, 0.0), aux=None, variant=0, ytab_rows=4096, table_range=0, point_list=False,
+                  lib=None):
+    """include/sbx_test.h sbx_debug_clouds_select (host only, no GPU needed): the kernel a launch of APP_CLOUDS, of its HEIGHT /
+    LUMINANCE builds or of CLOUDS_SKY would take with a y table of `ytab_rows` rows and a ready hash table of range `table_range` at
+    hand (0: none), as a dict of sbx_clouds_selection's fields"""
+    lib = lib or load_library()
+    u = uniforms(width, height, time, mouse)
+    auxp = ctypes.cast(ctypes.byref(aux), ctypes.c_void_p) if aux is not None else None
+    out = CloudsSelection()
+    rc = lib.sbx_debug_clouds_select(app_id(app), ctypes.byref(u), auxp, int(variant), int(ytab_rows), int(table_range),
+                                     1 if point_list else 0, ctypes.byref(out))
+    if rc < 0:
+        raise SbxError(rc, "sbx_debug_clouds_select: bad arguments")
+    return out.as_dict()
 
 
 def span_table(app, width, height, time, block_rows, nranks, root_rounds=1, rounds=1, mouse=(0.0, 0.0), aux=None, lib=None):
@@ -766,6 +793,13 @@ class Renderer:
         v = [ctypes.c_int() for _ in range(4)]
         self._check(self.lib.sbx_debug_clouds_hashtab(self.ctx, *[ctypes.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+    def clouds_last_selection(self):
+        """include/sbx_test.h sbx_debug_clouds_last_selection: the kernel the context's last launch of APP_CLOUDS, of its HEIGHT /
+        LUMINANCE builds or of CLOUDS_SKY took, as a dict of sbx_clouds_selection's fields"""
+        out = CloudsSelection()
+        self._check(self.lib.sbx_debug_clouds_last_selection(self.ctx, ctypes.byref(out)))
+        return out.as_dict()
 
     def clouds_hashtab_read(self, first, count):
         """include/sbx_test.h sbx_debug_clouds_hashtab_read: entries [first, first + count) of the newest table, a numpy float32 array"""

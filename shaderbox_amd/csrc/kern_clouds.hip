@@ -1198,7 +1198,12 @@ static bool clouds_div3_domain(const FrameClouds& F) {
 // (the bound itself: every lattice index, corner offsets included, of every main and light sample of the frame is below it in
 //  magnitude — what the context's hash table is sized by; inf / NaN if anything it is made of is)
 static double clouds_index_bound(const FrameClouds& F) {
-    auto m3 = [](v3 v) { return std::fmax(std::fabs((double)v.x), std::fmax(std::fabs((double)v.y), std::fabs((double)v.z))); };
+    // (std::fmax drops a NaN operand: a vector with ONE NaN component gave a finite bound until the selection's fuzz compared it with the
+    //  sentence above — tests/test_clouds_selection_cpu.py; such a frame now takes the cache kernels and no SM kernel)
+    auto m3 = [](v3 v) {
+        const double x = std::fabs((double)v.x), y = std::fabs((double)v.y), z = std::fabs((double)v.z);
+        return (x != x || y != y || z != z) ? (double)NAN : std::fmax(x, std::fmax(y, z));
+    };
     const double reach = 21.0 * 150.0 + 22.0 * std::fabs((double)F.dt) * (double)F.steps;
     const double light = ((double)F.lsteps + 1.0) * m3(F.sun_dir) * std::fabs((double)F.dt);
     const double sky = F.sky ? std::fabs((double)F.atm_r) + std::fabs((double)F.atm_y) : 0.0;
@@ -1237,22 +1242,87 @@ int clouds_hashtab_range(const FrameClouds& F, const RowMap& M, int build) {
 
 dim3 clouds_grid(const RowMap& M) { return grid_for<CL_TW, CL_TX>(M); }
 
-// One build's launch: the kernel selection is the same for every build (REG / SM / y table / light-march form), over the build's own
-// instantiations.  The HEIGHT build has no light march, so the form of L * dt selects nothing there (its instantiations carry LM = 1
-// for the one thing LM decides outside the light march: the SM kernels' div3_ smoothstep in the main sample).
+// exp_small_'s domain: x = -density * sigma * dt with 0 <= density <= .9375 (1 + 1e-6) (a blend of hashes in [0, 1] with weights
+// in [0, 1], gains .5 + .25 + .125 + .0625, times a smoothstep in [0, 1]) lies in [-.205, -0] when sigma, dt >= 0 and:
+static bool clouds_exp_small(const FrameClouds& F) {
+    return F.sigma >= 0.f && F.dt >= 0.f && .94 * (double)F.sigma * (double)F.dt <= .2049;   // NaN: false
+}
+
+// THE SELECTION (sbx_test.h sbx_clouds_selection): which of k_clouds' instantiations, or the per-lane kernel, a launch takes — the same
+// rules for every build (REG / SM / y table / light-march form / hash table), over the build's own instantiations.  The HEIGHT build has
+// no light march, so the form of L * dt selects nothing there (its instantiations carry LM = 1 for the one thing LM decides outside the
+// light march: the SM kernels' div3_ smoothstep in the main sample).  A pure function of its arguments: no device, no context.
+sbx_clouds_selection clouds_select(const FrameClouds& F, const RowMap& M, int variant, int build, int ytab_rows, int table_range) {
+    const bool HT = build == CLOUDS_HEIGHT;
+    sbx_clouds_selection S{};
+    S.build = build;
+    S.sky = F.sky ? 1 : 0;
+    S.regular = clouds_regular(F) ? 1 : 0;
+    S.exp_small = clouds_exp_small(F) ? 1 : 0;
+    S.index_domain = clouds_index_domain(F) ? 1 : 0;
+    S.div3_domain = clouds_div3_domain(F) ? 1 : 0;
+    S.lip_ok = clouds_lip_domain(F) ? 1 : 0;
+    const v3 lstep = F.sun_dir * F.dt;                          // the kernel's own expression
+    S.light = (lstep.x == 0.f && lstep.y == 0.f) ? 1 : lstep.x == 0.f ? 2 : 0;   // NaN compares false: the general march
+    S.need_range = clouds_hashtab_range(F, M, build);
+    S.table_range = table_range > 0 ? table_range : 0;
+    const bool reg = S.regular != 0;
+    const bool zl = HT || S.light == 1;
+    const bool yz = !zl && S.light == 2 && CL_YZ_MARCH;
+    // SM kernels: exp_small_'s domain AND lattice indices below 2^40 for sin_b40_ AND div3_'s domain
+    const bool sm = S.exp_small && S.index_domain && (!CL_DIV3 || S.div3_domain) && CL_EXP_SMALL && CL_EXP_ASM && CL_EXP64;
+    if (variant == 1) { S.perlane = 1; return S; }
+    // (SKY_SPHERE frames: the march does not run along dir / dir.y, so no y table — the table-less kernels, F.nf, F.sky)
+    if (!F.sky && ytab_rows > 0 && F.steps <= ytab_rows && F.steps > 0) {
+        S.ytab_used = 1;
+        S.ytab = ytab_rows <= CLOUDS_YTAB_ROWS ? 1 : 2;
+        // the hash-table kernels: iff a ready table of the context covers the frame's bound (clouds_hashtab_range has the other conditions:
+        // a regular frame, the z-only or the y-z march among them)
+        if (CL_GTAB && S.table_range > 0 && S.need_range > 0 && S.need_range <= S.table_range) {
+            S.reg = 1; S.lm = zl ? 1 : 2; S.sm = (zl ? sm : sm && CL_YZ_SM) ? 1 : 0; S.gt = CL_GTAB_OCT + 1;
+        } else if (zl) { S.reg = reg; S.lm = 1; S.sm = reg && sm; }
+        else if (reg && yz) { S.reg = 1; S.lm = 2; S.sm = sm && CL_YZ_SM; }
+        else if (reg) { S.reg = 1; S.lm = 0; S.sm = sm; }
+        else { S.reg = 0; S.lm = yz ? 2 : 0; S.sm = 0; }
+    } else {
+        if (zl) { S.reg = reg; S.lm = 1; S.sm = reg && sm; }
+        else { S.reg = reg; S.lm = 0; S.sm = reg && sm; }
+    }
+    return S;
+}
+
+// THE LAUNCHER: every launch of k_clouds and of k_clouds_perlane goes through here, and the record's kernel fields are written from the
+// template arguments of the kernel that is launched — the record cannot name another kernel than the one that ran.
+struct ClLaunch { dim3 grid, block; unsigned lds; hipStream_t s; const FrameClouds* F; const RowMap* M; float* out; const YRow* ct; const float* htab; unsigned hb4; };
+template <bool YTAB, bool REG, int LM, bool SM, int BUILD, int GT>
+static void launch_form(sbx_clouds_selection& R, const ClLaunch& L) {
+    R.build = BUILD; R.perlane = 0; R.ytab_used = YTAB; R.reg = REG; R.lm = LM; R.sm = SM; R.gt = GT;
+    hipLaunchKernelGGL((k_clouds<YTAB, REG, LM, SM, BUILD, GT>), L.grid, L.block, L.lds, L.s, *L.F, *L.M, L.out, L.ct, L.htab, L.hb4);
+}
+template <int BUILD>
+static void launch_perlane(sbx_clouds_selection& R, const ClLaunch& L) {
+    R.build = BUILD; R.perlane = 1; R.ytab_used = 0; R.reg = 0; R.lm = 0; R.sm = 0; R.gt = 0;
+    hipLaunchKernelGGL(k_clouds_perlane<BUILD>, grid_for<32>(*L.M), dim3(WG_THREADS), 0, L.s, *L.F, *L.M, L.out);
+}
+
+// One build's launch: the selection above, mapped onto the build's instantiations — 19 for the shipped build and for LUMINANCE (4 with
+// the hash table, 9 with the y table and the LDS cache, 6 table-less), 8 for HEIGHT (LM = 1 only: 2 + 3 + 3), and the per-lane kernel.
+// A selection outside the list would be a bug of clouds_select: nothing is launched and the record says perlane = -1.
 template <int BUILD>
 static bool launch_clouds_build(const FrameClouds& F_in, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
-                                bool build_table, const CloudsHashTab* ht) {
+                                bool build_table, const CloudsHashTab* ht, sbx_clouds_selection& R, int ytab_kind) {
     constexpr bool HT = BUILD == CLOUDS_HEIGHT;
+    constexpr int G = CL_GTAB_OCT + 1;
+    const int table_range = (CL_GTAB && ht && ht->tab) ? ht->range : 0;
+    const sbx_clouds_selection S = clouds_select(F_in, M, variant, BUILD, ytab ? ytab_rows : 0, table_range);
+    const uint64_t launches = R.launches;
+    R = S;
+    R.launches = launches;
     FrameClouds F = F_in;
-    F.lip_ok = clouds_lip_domain(F) ? 1 : 0;
-    // exp_small_'s domain: x = -density * sigma * dt with 0 <= density <= .9375 (1 + 1e-6) (a blend of hashes in [0, 1] with weights
-    // in [0, 1], gains .5 + .25 + .125 + .0625, times a smoothstep in [0, 1]) lies in [-.205, -0] when sigma, dt >= 0 and:
-    F.exp_small = (F.sigma >= 0.f && F.dt >= 0.f && .94 * (double)F.sigma * (double)F.dt <= .2049) ? 1 : 0;   // NaN: 0
+    F.lip_ok = S.lip_ok;
+    F.exp_small = S.exp_small;
     F.thr1 = F.cov - .1876f;                                     // coop_density_row's stage cut-offs
     F.thr2 = F.cov - .06255f;
-    const bool reg = clouds_regular(F);
-    const dim3 grid = grid_for<CL_TW, CL_TX>(M), block(64 * CL_TX);
 #ifdef SBX_CL_OCC_SWEEP
     // experiment only (tools/ab_time.py): extra dynamic LDS per workgroup lowers the waves resident per SIMD
     const char* pad_env = std::getenv("SBX_DEBUG_LDS_PAD");
@@ -1260,61 +1330,32 @@ static bool launch_clouds_build(const FrameClouds& F_in, const RowMap& M, float*
 #else
     const unsigned pad = 0;
 #endif
-    const v3 lstep = F.sun_dir * F.dt;                          // the kernel's own expression
-    const bool zl = HT || (lstep.x == 0.f && lstep.y == 0.f);
-    const bool yz = !zl && lstep.x == 0.f && CL_YZ_MARCH;        // NaN compares false: the general march
-    // (SKY_SPHERE frames: the march does not run along dir / dir.y, so no y table — the table-less kernels, F.nf, F.sky)
-    if (variant == 1) {
-        hipLaunchKernelGGL(k_clouds_perlane<BUILD>, grid_for<32>(M), dim3(WG_THREADS), 0, s, F, M, out);
-    } else if (!F.sky && ytab && F.steps <= ytab_rows && F.steps > 0) {
+    ClLaunch L{grid_for<CL_TW, CL_TX>(M), dim3(64 * CL_TX), 0u, s, &F, &M, out, nullptr, nullptr, 0u};
+    if (S.perlane) { launch_perlane<BUILD>(R, L); return false; }
+    if (S.ytab_used) {
         YRow* tab = reinterpret_cast<YRow*>(ytab);
         if (build_table) hipLaunchKernelGGL(k_clouds_ytab, dim3((F.steps + 63) / 64), dim3(64), 0, s, F, tab);
         // (the caller rebuilds a table that has no luminances before the HEIGHT build reads it: sbx_ytab.hip)
         if (build_table && HT) hipLaunchKernelGGL(k_clouds_lumtab, dim3((F.steps + 63) / 64), dim3(64), 0, s, F.steps, const_cast<float*>(lum_of(tab, F.steps)));
-        const YRow* ct = tab;
-        const float* const hnull = nullptr;
-        // SM kernels: exp_small_'s domain AND lattice indices below 2^40 for sin_b40_
-        const bool sm = F.exp_small && clouds_index_domain(F) && (!CL_DIV3 || clouds_div3_domain(F)) && CL_EXP_SMALL && CL_EXP_ASM && CL_EXP64;
-#if CL_GTAB
-        // the hash-table kernels: iff a ready table of the context covers the frame's bound (clouds_hashtab_range has the other conditions)
-        const int need = (ht && ht->tab) ? clouds_hashtab_range(F, M, BUILD) : 0;
-        if (need > 0 && need <= ht->range) {
-            const float* const htab = ht->tab;
-            const unsigned hb4 = 4u * (unsigned)ht->bias;
-            const bool yzsm = sm && CL_YZ_SM;
-            if (zl && sm) hipLaunchKernelGGL((k_clouds<true, true, 1, true, BUILD, CL_GTAB_OCT + 1>), grid, block, 0, s, F, M, out, ct, htab, hb4);
-            else if (zl) hipLaunchKernelGGL((k_clouds<true, true, 1, false, BUILD, CL_GTAB_OCT + 1>), grid, block, 0, s, F, M, out, ct, htab, hb4);
-            else if constexpr (!HT) {
-                if (yzsm) hipLaunchKernelGGL((k_clouds<true, true, 2, true, BUILD, CL_GTAB_OCT + 1>), grid, block, 0, s, F, M, out, ct, htab, hb4);
-                else hipLaunchKernelGGL((k_clouds<true, true, 2, false, BUILD, CL_GTAB_OCT + 1>), grid, block, 0, s, F, M, out, ct, htab, hb4);
-            }
-            return true;
-        }
-#endif
-        if (reg && zl && sm) hipLaunchKernelGGL((k_clouds<true, true, 1, true, BUILD>), grid, block, pad, s, F, M, out, ct, hnull, 0u);
-        else if (reg && zl) hipLaunchKernelGGL((k_clouds<true, true, 1, false, BUILD>), grid, block, pad, s, F, M, out, ct, hnull, 0u);
-        else if (zl) hipLaunchKernelGGL((k_clouds<true, false, 1, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
-        else if constexpr (!HT) {
-            if (reg && yz && sm && CL_YZ_SM) hipLaunchKernelGGL((k_clouds<true, true, 2, true, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
-            else if (reg && yz) hipLaunchKernelGGL((k_clouds<true, true, 2, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
-            else if (reg && sm) hipLaunchKernelGGL((k_clouds<true, true, 0, true, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
-            else if (reg) hipLaunchKernelGGL((k_clouds<true, true, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
-            else if (yz) hipLaunchKernelGGL((k_clouds<true, false, 2, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
-            else hipLaunchKernelGGL((k_clouds<true, false, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
-        }
-    } else {
-        const YRow* ct = nullptr;
-        const float* const hnull = nullptr;
-        const bool sm = F.exp_small && clouds_index_domain(F) && (!CL_DIV3 || clouds_div3_domain(F)) && CL_EXP_SMALL && CL_EXP_ASM && CL_EXP64;
-        if (reg && zl && sm) hipLaunchKernelGGL((k_clouds<false, true, 1, true, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
-        else if (reg && zl) hipLaunchKernelGGL((k_clouds<false, true, 1, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
-        else if (zl && !reg) hipLaunchKernelGGL((k_clouds<false, false, 1, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
-        else if constexpr (!HT) {
-            if (reg && sm) hipLaunchKernelGGL((k_clouds<false, true, 0, true, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
-            else if (reg) hipLaunchKernelGGL((k_clouds<false, true, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
-            else hipLaunchKernelGGL((k_clouds<false, false, 0, false, BUILD>), grid, block, 0, s, F, M, out, ct, hnull, 0u);
-        }
+        L.ct = tab;
+        R.ytab = ytab_kind;
+        if (S.gt) { L.htab = ht->tab; L.hb4 = 4u * (unsigned)ht->bias; }
+        else if (S.reg && S.lm == 1) L.lds = pad;
     }
+    const int key = S.ytab_used << 12 | S.reg << 8 | S.lm << 4 | S.sm << 1 | (S.gt ? 1 : 0);
+#define CL_FORM(Y, RG, LMV, SMV, GTV) \
+    if (key == ((Y) << 12 | (RG) << 8 | (LMV) << 4 | (SMV) << 1 | ((GTV) ? 1 : 0))) { \
+        if constexpr ((LMV) == 1 || !HT) { launch_form<(Y) != 0, (RG) != 0, (LMV), (SMV) != 0, BUILD, (GTV)>(R, L); return (GTV) != 0; } }
+    // the y-table kernels that read the lattice-hash table
+    CL_FORM(1, 1, 1, 1, G) CL_FORM(1, 1, 1, 0, G) CL_FORM(1, 1, 2, 1, G) CL_FORM(1, 1, 2, 0, G)
+    // the y-table kernels with the per-wave LDS cache
+    CL_FORM(1, 1, 1, 1, 0) CL_FORM(1, 1, 1, 0, 0) CL_FORM(1, 0, 1, 0, 0)
+    CL_FORM(1, 1, 2, 1, 0) CL_FORM(1, 1, 2, 0, 0) CL_FORM(1, 1, 0, 1, 0) CL_FORM(1, 1, 0, 0, 0) CL_FORM(1, 0, 2, 0, 0) CL_FORM(1, 0, 0, 0, 0)
+    // the table-less kernels
+    CL_FORM(0, 1, 1, 1, 0) CL_FORM(0, 1, 1, 0, 0) CL_FORM(0, 0, 1, 0, 0)
+    CL_FORM(0, 1, 0, 1, 0) CL_FORM(0, 1, 0, 0, 0) CL_FORM(0, 0, 0, 0, 0)
+#undef CL_FORM
+    R.perlane = -1;                                              // unreachable: clouds_select names listed forms only
     return false;
 }
 
@@ -1327,10 +1368,13 @@ static_assert(kernarg_off<0>(KCloudsFn(nullptr)) == offsetof(ClArgs, F) && kerna
               "ClArgs must mirror k_clouds' argument list, argument for argument");
 
 bool launch_clouds(const FrameClouds& F, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
-                   bool build_table, int build, const CloudsHashTab* ht) {
-    if (build == CLOUDS_HEIGHT) return launch_clouds_build<CLOUDS_HEIGHT>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht);
-    if (build == CLOUDS_LUMINANCE) return launch_clouds_build<CLOUDS_LUMINANCE>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht);
-    return launch_clouds_build<CLOUDS_DEFAULT>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht);
+                   bool build_table, int build, const CloudsHashTab* ht, sbx_clouds_selection* rec, int ytab_kind) {
+    sbx_clouds_selection local{};
+    sbx_clouds_selection& R = rec ? *rec : local;
+    R.launches += 1;
+    if (build == CLOUDS_HEIGHT) return launch_clouds_build<CLOUDS_HEIGHT>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht, R, ytab_kind);
+    if (build == CLOUDS_LUMINANCE) return launch_clouds_build<CLOUDS_LUMINANCE>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht, R, ytab_kind);
+    return launch_clouds_build<CLOUDS_DEFAULT>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht, R, ytab_kind);
 }
 
 hipError_t bind_fault_clouds(unsigned* word) { return hc_bind_fault_word(word); }

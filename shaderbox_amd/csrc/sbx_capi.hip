@@ -248,7 +248,10 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     // the builds of illuminate_volume's two switches (include/sbx.h): the same frame constants and the same y tables
     case SBX_APP_CLOUDS_HEIGHT: rc = render_clouds(ctx, build_clouds(*uni, AC), M, rgba, s, capturing, CLOUDS_HEIGHT); break;
     case SBX_APP_CLOUDS_LUMINANCE: rc = render_clouds(ctx, build_clouds(*uni, AC), M, rgba, s, capturing, CLOUDS_LUMINANCE); break;
-    case SBX_APP_CLOUDS_SKY: launch_clouds(build_clouds(*uni, AC, true), M, rgba, s, ctx->variant, nullptr, 0, false); break;
+    case SBX_APP_CLOUDS_SKY:
+        ctx->hashtab.last_used = 0;
+        launch_clouds(build_clouds(*uni, AC, true), M, rgba, s, ctx->variant, nullptr, 0, false, CLOUDS_DEFAULT, nullptr, &ctx->hashtab.last_selection);
+        break;
     case SBX_APP_CLOUDS_TEX: launch_clouds_tex(build_clouds(*uni, AC), M, rgba, s, ctx->noise.shape, ctx->noise.shape_size, ctx->noise.detail, ctx->noise.detail_size,
                                                     // a captured launch is replayed later, possibly over volumes re-bound in place with
                                                     // other texel ranges: no bounds baked into a graph (the plain exp_ / IEEE divide)
@@ -529,6 +532,30 @@ int sbx_debug_clouds_hashtab(sbx_ctx* ctx, int* entries, int* bias, int* tables_
     if (bias) *bias = H.tabs.empty() ? 0 : H.tabs.back().bias;
     if (tables_built) *tables_built = (int)H.tabs.size();
     if (last_launch_used_table) *last_launch_used_table = H.last_used;
+    return SBX_OK;
+}
+
+int sbx_debug_clouds_last_selection(sbx_ctx* ctx, sbx_clouds_selection* out) {
+    if (!ctx || !out) return SBX_ERR_ARG;
+    *out = ctx->hashtab.last_selection;
+    return SBX_OK;
+}
+
+// the choice alone (kern_clouds.hip clouds_select) over the frame render_mapped would build: host code only
+int sbx_debug_clouds_select(int app, const sbx_uniforms* uni, const void* aux, int variant, int ytab_rows, int table_range, int point_list,
+                            sbx_clouds_selection* out) {
+    if (!uni || !out) return SBX_ERR_ARG;
+    int build = CLOUDS_DEFAULT;
+    if (app == SBX_APP_CLOUDS_HEIGHT) build = CLOUDS_HEIGHT;
+    else if (app == SBX_APP_CLOUDS_LUMINANCE) build = CLOUDS_LUMINANCE;
+    else if (app != SBX_APP_CLOUDS && app != SBX_APP_CLOUDS_SKY) return SBX_ERR_ARG;
+    const sbx_aux_clouds AC = aux_clouds(aux);
+    if (AC.cld_march_steps < 0 || AC.illum_march_steps < 0) return SBX_ERR_ARG;
+    const bool sky = app == SBX_APP_CLOUDS_SKY;
+    static const float one_point[2] = {.5f, .5f};
+    RowMap M{};                                                        // (the choice reads `frag` alone: a point list or not)
+    if (point_list) { M.frag = one_point; M.npoints = 1; }
+    *out = clouds_select(build_clouds(*uni, AC, sky), M, variant, build, sky ? 0 : ytab_rows, sky ? 0 : table_range);
     return SBX_OK;
 }
 

@@ -73,6 +73,8 @@ struct HashTables {
     };
     std::vector<Tab> tabs;
     int last_used = 0;                     // the last APP_CLOUDS launch of the context took a hash-table kernel (sbx_debug_clouds_hashtab)
+    sbx_clouds_selection last_selection{}; // what the context's last launch of k_clouds / k_clouds_perlane took, CLOUDS_SKY included
+                                           // (sbx_debug_clouds_last_selection; written by the launcher, kern_clouds.hip launch_form)
 };
 
 // per-stream timing events (sbx_set_timing): a pair brackets the last launch on its stream

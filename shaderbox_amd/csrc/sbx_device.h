@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "sbx_frame.h"
+#include "../../include/sbx_test.h"   // sbx_clouds_selection: the record launch_clouds fills
 
 namespace sbx {
 
@@ -152,10 +153,15 @@ constexpr int CLOUDS_HASHTAB_GUARD = 512;
 constexpr int clouds_hashtab_entries(int range) { return 2 * range + 272 + 2 * CLOUDS_HASHTAB_GUARD; }
 int clouds_hashtab_range(const FrameClouds& F, const RowMap& M, int build);   // the range the launch needs; 0: it does not take the table kernels
 void launch_clouds_hashtab(float* tab, int entries, int bias, hipStream_t s);
-// returns whether the launch took a hash-table kernel (only with `ht`: a READY table; taken iff it covers the frame's index bound)
+// The kernel a launch takes, as a pure function of the frame (kern_clouds.hip): "a y table of ytab_rows rows is at hand" (0: none),
+// "a ready hash table of range table_range is at hand" (0: none).  No device, no context; launch_clouds launches what this returns.
+sbx_clouds_selection clouds_select(const FrameClouds& F, const RowMap& M, int variant, int build, int ytab_rows, int table_range);
+// returns whether the launch took a hash-table kernel (only with `ht`: a READY table; taken iff it covers the frame's index bound).
+// rec: the record of what was launched (sbx_test.h), written by the launcher itself; its `ytab` is ytab_kind where a y table was read
 bool launch_clouds(const FrameClouds& F, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
                    bool build_table, int build = CLOUDS_DEFAULT,    // build: CLOUDS_* (sbx_frame.h); build_table with CLOUDS_HEIGHT also
-                   const CloudsHashTab* ht = nullptr);              // writes the steps' luminances behind the y rows
+                   const CloudsHashTab* ht = nullptr,               // writes the steps' luminances behind the y rows
+                   sbx_clouds_selection* rec = nullptr, int ytab_kind = 0);
 constexpr int CLOUDS_YTAB_ROWS = 4096;      // march steps covered by a y table of the ring (208 KB per table; beyond it the one big
                                             // table below, or in a capture the table-less kernels: 1100 steps at 4K took 48 ms without a table)
 constexpr int CLOUDS_YTAB_STEP_BYTES = 48 + 4;   // per march step: its YRow and, behind the frame's rows, the HEIGHT build's luminance

@@ -62,6 +62,7 @@ static CloudsHashTab clouds_hash_table(sbx_ctx* ctx, const FrameClouds& F, const
 
 int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rgba, hipStream_t s, bool capturing, int build) {
     ctx->hashtab.last_used = 0;
+    sbx_clouds_selection* const rec = &ctx->hashtab.last_selection;       // (sbx_debug_clouds_last_selection; launch_clouds counts)
     const bool need_lum = build == CLOUDS_HEIGHT;
     const bool uses_table = ctx->variant == 0 && F.steps > 0 && F.steps <= CLOUDS_YTAB_ROWS;
     if (!uses_table && ctx->variant == 0 && F.steps > CLOUDS_YTAB_ROWS && F.steps <= CLOUDS_YTAB_BIG_MAX && !capturing) {
@@ -90,7 +91,7 @@ int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rg
             (void)hipStreamWaitEvent(s, ctx->ytab.big_ready, 0);
         }
         const CloudsHashTab ht = clouds_hash_table(ctx, F, M, s, capturing, build);
-        ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, ctx->ytab.big, ctx->ytab.big_rows, rebuild, build, &ht) ? 1 : 0;
+        ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, ctx->ytab.big, ctx->ytab.big_rows, rebuild, build, &ht, rec, 2) ? 1 : 0;
         if (rebuild) {
             (void)hipEventRecord(ctx->ytab.big_ready, s);
             std::memcpy(ctx->ytab.big_key, key, sizeof(key));
@@ -101,13 +102,13 @@ int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rg
         return SBX_OK;
     }
     if (!uses_table) {
-        launch_clouds(F, M, rgba, s, ctx->variant, nullptr, 0, false, build);
+        launch_clouds(F, M, rgba, s, ctx->variant, nullptr, 0, false, build, nullptr, rec);
         return SBX_OK;
     }
     if (capturing) {
         char* tab = ctx->ytab.ring + (size_t)(CLOUDS_YTAB_RING + (ctx->ytab.cap_next++ % CLOUDS_YTAB_CAPTURE)) * CLOUDS_YTAB_BYTES;
         const CloudsHashTab ht = clouds_hash_table(ctx, F, M, s, capturing, build);
-        ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, true, build, &ht) ? 1 : 0;
+        ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, true, build, &ht, rec, 3) ? 1 : 0;
         return SBX_OK;
     }
     const float key[3] = {F.cam.eye.y, F.wind_off.y, F.dt};
@@ -141,7 +142,7 @@ int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rg
     }
     char* tab = ctx->ytab.ring + (size_t)slot * CLOUDS_YTAB_BYTES;
     const CloudsHashTab ht = clouds_hash_table(ctx, F, M, s, capturing, build);
-    ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, rebuild, build, &ht) ? 1 : 0;
+    ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, rebuild, build, &ht, rec, 1) ? 1 : 0;
     if (rebuild) {
         (void)hipEventRecord(ctx->ytab.ready, s);                  // the build is enqueued: now the cache state is true
         std::memcpy(ctx->ytab.key, key, sizeof(key));

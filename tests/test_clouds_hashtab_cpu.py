@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from tests import clouds_builds_model as M
+from tests import clouds_selection_cases as C
 from tests.model_common import F, ONE, ZERO, _f, get_primary_ray, point_cam
 
 MIN_RANGE, MAX_RANGE = 1 << 18, 1 << 22             # csrc/sbx_device.h CLOUDS_HASHTAB_MIN_RANGE / _MAX_RANGE
@@ -103,3 +104,27 @@ def test_default_frame_and_grown_frame_ranges():
     assert table_range(b1) == 2 * MIN_RANGE
     assert table_range(index_bound((0, -.5, 0), (0, 0, .2 * 3000.0 * 1000.0), (0, 0, -1), 1.25, 100, 6)) == 0
     assert table_range(float("inf")) == 0 and table_range(float("nan")) == 0
+
+
+# ---- every frame the GPU suite sends through a hash-table kernel (tests/clouds_selection_cases.py) --------------------------------------
+# No case goes to the GPU that has not passed this enumeration: tests/test_gpu_clouds_selection.py renders exactly these frames (the
+# table's GT cases, the frames either side of every table-range edge, the ragged frames of the default build's GT forms and the
+# sides of the predicate edges that take a table).
+GT_FRAMES = ([c for c in C.CASES if c["kernel"] != "perlane" and c["kernel"][4]] +
+             [c for sun in ("z", "yz") for _, a, b in C.range_edge_cases(sun) for c in (a, b) if c["kernel"][4]] +
+             [dict(c, name=c["name"] + "_33x3", w=33, h=3) for c in C.CASES if c["name"] in C.RAGGED_GT] +
+             [C._c("%s_%s" % (e[0], side), "clouds", None, 1, aux) for e in C.PREDICATE_EDGES for side, aux in (("in", e[2]), ("out", e[3]))
+              if C.hashtab_range(C.frame_of("clouds", C.W, C.H, C.T, (0.0, 0.0), aux), 0)])
+
+
+@pytest.mark.parametrize("case", GT_FRAMES, ids=lambda c: c["name"])
+def test_selection_cases_stay_inside_their_table(case):
+    f = C.frame_of(case["app"], case["w"], case["h"], case["t"], case["mouse"], case["aux"])
+    R = C.hashtab_range(f, C.BUILD_OF[case["app"]])
+    lo, hi, bound = frame_extremes(case["w"], case["h"], case["t"], case["mouse"], case["aux"] or None)
+    # (index_bound above takes the noise factor as .001; the host, and C.index_bound, as the binary32 nearest to it: 5e-8 apart)
+    host = C.index_bound(f)
+    assert abs(bound - host) <= 1e-7 * host and R == table_range(host) and R >= MIN_RANGE, (bound, host, R)
+    bound = min(bound, host)
+    assert -bound < lo and hi < bound, (lo, hi, bound)
+    assert -R < lo and hi < R + 271

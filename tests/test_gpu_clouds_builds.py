@@ -58,6 +58,15 @@ def test_odd_frame_equals_the_model(renderer, build):
 VARIANT_CASES = [(None, {}, 256, 144), ("yz", {}, 256, 144), ("steer", {}, 256, 144), ("exp_on", {}, 256, 144), ("exp_off", {}, 256, 144),
                  ("exp_off", {"sun_dir": (0.0, 0.6, -0.8)}, 256, 144), ("steer", {"sigma_scattering": 30.0}, 256, 144),
                  ("long", {"cld_march_steps": 4200}, 64, 36)]
+# the kernel each case is meant to reach, (YTAB, REG, LM, SM, GT) of k_clouds as the launch's record names it (sbx_debug_clouds_last_selection;
+# GT 3: the hash-table kernels), for the HEIGHT build (no light march: LM 1 whatever the sun) and for the LUMINANCE build
+VARIANT_KERNELS = [((1, 1, 1, 1, 3), (1, 1, 1, 1, 3)), ((1, 1, 1, 1, 3), (1, 1, 2, 1, 3)), ((1, 1, 1, 0, 3), (1, 1, 0, 0, 0)),
+                   ((1, 1, 1, 1, 3), (1, 1, 1, 1, 3)), ((1, 1, 1, 0, 3), (1, 1, 1, 0, 3)), ((1, 1, 1, 0, 3), (1, 1, 2, 0, 3)),
+                   ((1, 0, 1, 0, 0), (1, 0, 0, 0, 0)), ((1, 1, 1, 1, 3), (1, 1, 1, 1, 3))]
+
+
+def kernel_of(rec):
+    return (rec["ytab_used"], rec["reg"], rec["lm"], rec["sm"], rec["gt"])
 
 
 @pytest.mark.parametrize("build", BUILDS)
@@ -72,7 +81,11 @@ def test_plain_and_default_kernels_agree(renderer, build, case):
         want = renderer.render(M.APP_OF[build], w, h, t, aux=aux).cpu().numpy()
     finally:
         renderer.set_variant(0)
+    assert renderer.clouds_last_selection()["perlane"] == 1
     assert_same(renderer.render(M.APP_OF[build], w, h, t, aux=aux), want, (build, name, over))
+    rec = renderer.clouds_last_selection()
+    assert rec["perlane"] == 0 and rec["build"] == BUILDS.index(build) + 1 and kernel_of(rec) == VARIANT_KERNELS[case][BUILDS.index(build)], rec
+    assert rec["ytab"] == (2 if name == "long" else 1)                   # the one big table / a slot of the ring
     other = renderer.render("clouds", w, h, t, aux=aux).cpu().numpy()
     assert not M.same_bits(other, want).all()                            # and the build is not the shipped one
 
@@ -98,6 +111,7 @@ def test_captured_launch(renderer, build):
 # kernels) up to sigma 2443: (sun, sigma) below reach SM, REG and the plain form under a z-only and under a general sun.
 NOTAB_SUNS = {"z": {}, "general": {"sun_dir": (0.3, 0.2, -0.9)}}
 NOTAB_SIGMAS = {"sm": 0.15, "reg": 30.0, "plain": 3000.0}
+NOTAB_FORMS = {"sm": (1, 1), "reg": (1, 0), "plain": (0, 0)}            # (REG, SM) of the kernel the sigma is meant to reach
 
 
 @pytest.mark.parametrize("sigma", list(NOTAB_SIGMAS))
@@ -118,10 +132,17 @@ def test_captured_long_march_runs_the_table_less_kernels(renderer, build, sun, s
     with torch.cuda.stream(s):
         with torch.cuda.graph(g, stream=s):
             renderer.render(M.APP_OF[build], w, h, t, aux=aux, out=out)
+    # the record of the captured launch: no y table, no hash table, the light march of the sun (HEIGHT has none: LM 1), REG / SM by sigma
+    rec = renderer.clouds_last_selection()
+    lm = 1 if build == "height" or sun == "z" else 0
+    assert (rec["perlane"], rec["ytab"]) == (0, 0) and kernel_of(rec) == (0, NOTAB_FORMS[sigma][0], lm, NOTAB_FORMS[sigma][1], 0), rec
     g.replay()
     torch.cuda.synchronize()
     assert_same(out, want, (build, sun, sigma, "table-less"))
     assert_same(renderer.render(M.APP_OF[build], w, h, t, aux=aux), want, (build, sun, sigma, "big table"))   # the same frame, eagerly
+    rec = renderer.clouds_last_selection()
+    assert (rec["ytab_used"], rec["ytab"], rec["reg"], rec["lm"], rec["sm"]) == (1, 2, NOTAB_FORMS[sigma][0], lm, NOTAB_FORMS[sigma][1]), rec
+    assert (rec["gt"] != 0) == (lm == 1 and sigma != "plain")           # the z forms of a regular frame read the hash table as well
     if sigma != "plain":                                                 # (there no light reaches a lit sample: LUMINANCE's 0 is the shipped build's 0)
         other = renderer.render("clouds", w, h, t, aux=aux).cpu().numpy()
         assert not M.same_bits(other, want).all()

@@ -55,7 +55,16 @@ def perlane(r, app, w, h, t, **kw):
 
 
 def used_table(r):
-    return r.clouds_hashtab()[3]
+    """sbx_debug_clouds_hashtab's `last_launch_used_table`, which is `gt != 0` of the launch's record"""
+    used = r.clouds_hashtab()[3]
+    assert used == (1 if r.clouds_last_selection()["gt"] else 0)
+    return used
+
+
+def kernel_of(rec):
+    """(YTAB, REG, LM, SM, GT) of the k_clouds instantiation the record names"""
+    assert rec["perlane"] == 0
+    return (rec["ytab_used"], rec["reg"], rec["lm"], rec["sm"], rec["gt"])
 
 
 @pytest.fixture
@@ -148,6 +157,10 @@ def test_frames_outside_the_table_keep_the_cache_kernels(fresh, t):
     w, h = 96, 54
     got = launch(fresh, "clouds", w, h, t)
     assert fresh.clouds_hashtab() == (0, 0, 0, 0)
+    # the cache kernel it keeps: y table (a ring slot), REG, the z-only light march; a wind that is not finite is outside sin_b40_'s
+    # domain as well, so no SM there
+    rec = fresh.clouds_last_selection()
+    assert kernel_of(rec) == (1, 1, 1, 1 if t == 3000.0 else 0, 0) and (rec["ytab"], rec["need_range"], rec["table_range"]) == (1, 0, 0), rec
     assert_same(got, perlane(fresh, "clouds", w, h, t), ("fallback", t))
 
 
@@ -155,10 +168,14 @@ def test_general_sun_and_point_lists_keep_the_cache_kernels(fresh):
     import torch
     launch(fresh, "clouds", 96, 54, T, aux=aux_of((0.3, 0.2, -0.9)))
     assert fresh.clouds_hashtab()[2:] == (0, 0)
+    rec = fresh.clouds_last_selection()
+    assert kernel_of(rec) == (1, 1, 0, 1, 0) and (rec["light"], rec["need_range"]) == (0, 0), rec      # the general light march, LDS cache
     pts = torch.tensor([[10.5, 40.5], [3.25, 50.0]], dtype=torch.float32, device=fresh.tdev)
     fresh.render_points("clouds", 96, 54, T, pts)
     torch.cuda.synchronize()
     assert fresh.clouds_hashtab()[2:] == (0, 0)
+    rec = fresh.clouds_last_selection()
+    assert kernel_of(rec) == (1, 1, 1, 1, 0) and (rec["light"], rec["need_range"], rec["launches"]) == (1, 0, 2), rec   # the z-only march, LDS cache
 
 
 def test_captured_launch_without_a_table_builds_none(fresh):

@@ -412,15 +412,22 @@ def test_clouds_exp_small_domain_edges(renderer, oracle):
     import shaderbox_amd
     from oracle.oracle import APP_CLOUDS
     w, h = 256, 144
-    cases = [dict(sigma_scattering=.1743), dict(sigma_scattering=.1744), dict(sigma_scattering=.17445), dict(cld_thick=145.3),
-             dict(cld_thick=145.4), dict(sigma_scattering=-.15), dict(cld_thick=-125.0), dict(sigma_scattering=0.0),
-             dict(cld_thick=0.0), dict(sigma_scattering=.2, cld_march_steps=150, illum_march_steps=4)]
-    for kw in cases:
+    # (aux fields, inside exp_small_'s domain): the record of the launch (sbx_debug_clouds_last_selection) must name the SM kernel
+    # inside the bound and the REG kernel without SM outside of it — REG, the z-only light march and the y table on both sides
+    cases = [(dict(sigma_scattering=.1743), 1), (dict(sigma_scattering=.1744), 0), (dict(sigma_scattering=.17445), 0), (dict(cld_thick=145.3), 1),
+             (dict(cld_thick=145.4), 0), (dict(sigma_scattering=-.15), 0), (dict(cld_thick=-125.0), 0), (dict(sigma_scattering=0.0), 1),
+             (dict(cld_thick=0.0), 1), (dict(sigma_scattering=.2, cld_march_steps=150, illum_march_steps=4), 1)]
+    for kw, inside in cases:
         aux = shaderbox_amd.clouds_defaults()
         for k, v in kw.items():
             setattr(aux, k, v)
         for t in (.37, 2.5):
+            renderer.render("clouds", w, h, t, aux=aux)
+            rec = renderer.clouds_last_selection()
+            assert (rec["exp_small"], rec["sm"]) == (inside, inside), (kw, t, rec)
+            assert (rec["perlane"], rec["ytab_used"], rec["reg"], rec["lm"]) == (0, 1, 1, 1), (kw, t, rec)
             a, b = both_variants(renderer, "clouds", w, h, t, aux=aux)
+            assert renderer.clouds_last_selection()["perlane"] == 1
             assert compare(a, b) == (0.0, 0), (kw, t)
             assert compare(a, oracle.render(APP_CLOUDS, w, h, t, aux=aux)) == (0.0, 0), (kw, t)
 

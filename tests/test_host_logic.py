@@ -32,7 +32,8 @@ def test_every_declared_symbol_is_exported(lib):
             assert hasattr(lib, n), "libsbx.so does not export %s (%s)" % (n, name)
     assert len(declared["sbx.h"]) >= 50 and len(declared["sbx_test.h"]) >= 6
     hooks = {"sbx_set_variant", "sbx_math_eval", "sbx_tex3d_eval", "sbx_debug_raise_fault", "sbx_multi_set_variant",
-             "sbx_shared_set_timeout_ms", "sbx_model_landing", "sbx_debug_tile_order", "sbx_debug_order_build"}
+             "sbx_shared_set_timeout_ms", "sbx_model_landing", "sbx_debug_tile_order", "sbx_debug_order_build",
+             "sbx_debug_clouds_last_selection", "sbx_debug_clouds_select"}
     assert hooks <= declared["sbx_test.h"] and not (hooks & declared["sbx.h"])
 
 

@@ -22,6 +22,9 @@
 //     app "raytracer_scene": src/app_raytracer.h's render over the caller's scene (SBX_APP_RAYTRACER_SCENE, include/sbx.h):
 //              --scene-bin FILE   the raw 1376 bytes of an sbx_aux_raytracer_scene (any other size is refused); without it the
 //              Cornell box of --time and --mouse (sbx_raytracer_scene_cornell), SBX_APP_RAYTRACER's frame
+//     app "sdf_scene": src/app_sdf_ao.h's renderer over the caller's field (SBX_APP_SDF_SCENE, include/sbx.h):
+//              --scene-bin FILE   the raw 2784 bytes of an sbx_aux_sdf_scene (any other size is refused); without it the ramp block
+//              of --time (sbx_sdf_scene_ramp)
 //     app "2d" / "2d_tex": src/app_2d.h (its alpha is not 1: the .f32 frames carry it; single GPU only), the USE_TEXTURE build
 //              reading hlsltoy's default 128x128 checkerboard at t0
 //     app "func": src/app_func.h, the tiled Worley fBm of its compiled 2D branch (grey, alpha 1; u_time and --mouse do not enter)
@@ -49,8 +52,8 @@ static int app_from_name(const std::string& s) {
     const char* names[] = {"planet", "clouds", "vinyl", "egg", "raytracer", "atmosphere", "sdf_ao", "clouds_best", "clouds_tex", "clouds_ue4",
                            "clouds_sky", "vinyl_gpu", "planet_atmosphere", "2d", "2d_tex", "func", "atmosphere_ground", "sdf_ao_shadow", "sdf_ao_normals",
                            "egg_straight", "egg_oval", "clouds_height", "clouds_luminance", "raytracer_phong", "raytracer_noshadow", "raytracer_static",
-                           "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow", "planet_closeup", "planet_cloudless", "planet_unlit", "raytracer_scene"};
-    const int n = 33;
+                           "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow", "planet_closeup", "planet_cloudless", "planet_unlit", "raytracer_scene", "sdf_scene"};
+    const int n = 34;
     std::string low;
     for (char c : s) low += (char)tolower(c);
     for (int i = 0; i < n; ++i)
@@ -158,15 +161,18 @@ int main(int argc, char** argv) {
     if ((id == SBX_APP_CLOUDS || id == SBX_APP_CLOUDS_TEX || id == SBX_APP_CLOUDS_SKY || id == SBX_APP_CLOUDS_HEIGHT || id == SBX_APP_CLOUDS_LUMINANCE) && have_ac) aux = &ac;
     if ((id == SBX_APP_SDF_AO || id == SBX_APP_SDF_AO_SHADOW || id == SBX_APP_SDF_AO_NORMALS) && have_as) aux = &as;
     sbx_aux_raytracer_scene scene;
+    sbx_aux_sdf_scene sdf_scene;
     if (!scene_bin.empty()) {
-        if (id != SBX_APP_RAYTRACER_SCENE) { fprintf(stderr, "--scene-bin belongs to --app raytracer_scene\n"); return 2; }
+        if (id != SBX_APP_RAYTRACER_SCENE && id != SBX_APP_SDF_SCENE) { fprintf(stderr, "--scene-bin belongs to --app raytracer_scene or --app sdf_scene\n"); return 2; }
+        void* dst = id == SBX_APP_SDF_SCENE ? (void*)&sdf_scene : (void*)&scene;
+        const size_t bytes = id == SBX_APP_SDF_SCENE ? sizeof(sdf_scene) : sizeof(scene);
         FILE* fp = fopen(scene_bin.c_str(), "rb");
         if (!fp) { perror(scene_bin.c_str()); return 1; }
         char extra;
-        const bool ok = fread(&scene, 1, sizeof(scene), fp) == sizeof(scene) && fread(&extra, 1, 1, fp) == 0;
+        const bool ok = fread(dst, 1, bytes, fp) == bytes && fread(&extra, 1, 1, fp) == 0;
         fclose(fp);
-        if (!ok) { fprintf(stderr, "%s: a scene file holds the %zu bytes of an sbx_aux_raytracer_scene and nothing else\n", scene_bin.c_str(), sizeof(scene)); return 2; }
-        aux = &scene;
+        if (!ok) { fprintf(stderr, "%s: a scene file holds the %zu bytes of an %s and nothing else\n", scene_bin.c_str(), bytes, id == SBX_APP_SDF_SCENE ? "sbx_aux_sdf_scene" : "sbx_aux_raytracer_scene"); return 2; }
+        aux = dst;
     }
 
     sbx_ctx* ctx = nullptr;

@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell: new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell, SBX_APP_SDF_SCENE with sbx_aux_sdf_scene, sbx_sdf_scene_ramp and sbx_sdf_eval: new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -280,7 +280,38 @@ typedef enum sbx_app {
        sbx_set_variant as for SBX_APP_RAYTRACER: 1 and 3 select the IEEE roots and normalisations, 2 forces the witness re-run.
        NOT OFFERED: more than one light (the reference reads lights[0]), refraction, other primitives, more than 16 + 16 primitives,
        an acceleration structure, and the drop-in header sbx_mainimage.hpp, which has no way to state a scene. */
-    SBX_APP_RAYTRACER_SCENE = 32
+    SBX_APP_RAYTRACER_SCENE = 32,
+    /* The sphere tracer of src/app_sdf_ao.h over the CALLER'S field: what the reference's README lists as its "signed distance field
+       functions and operators" (src/sdf.h).  mainImage of src/main.h:6-53 over render / render_impl / sdf_normal / sdf_ao / sdf_shadow /
+       illuminate of src/app_sdf_ao.h exactly as written, with sdf(pos) a small postfix PROGRAM of the aux block sbx_aux_sdf_scene
+       (below) and the block's values in place of the literals its comments name.  u_res is read; u_time and u_mouse are not.
+       aux == NULL means sbx_sdf_scene_ramp(uni, .).  Alpha is 1, so every output form holds it (rows, host rows, points,
+       sbx_main_image*, ranks, splits, rgb, the exchanges with whole rows: sbx_span_table has no model for it; SBX_FORMAT_RGBA8,
+       sbx_multi_render).
+       SEMANTICS (tests/sdf_scene_model.py is the definition).  The program's instructions run in array order over a stack of floats:
+         - a PRIMITIVE computes q = pos - offset, then, if rot_axis != 0, q = mul(q, rotate_around_{x,y,z}(rot_deg)) — the matrices of
+           util.h:44-69, the row-vector product with every zero term kept, sin / cos of radians(rot_deg) evaluated by the math spec on
+           the host once per frame — and pushes the float the reference's function returns: sd_plane(q, a.xyz, a.w), sd_sphere(q, a.x),
+           sd_box(q, a.xyz), sd_torus(q, a.x, a.y), sd_y_cylinder(q, a.x, a.y), sd_cylinder(q, a.xyz, b.xyz, a.w),
+           sd_capsule(q, a.xyz, b.xyz, a.w), sd_bezier(a.xyz, b.xyz, c.xyz, q, a.w).x (sdf.h:49-171);
+         - an OPERATOR pops d2 (the top), then d1, and pushes op_add(d1, d2), op_sub(d1, d2), op_intersect(d1, d2) or
+           op_blend(d1, d2, a.x) (the float forms, sdf.h:13-47);
+         - OBJECT pops d and folds vec2(d, float(material)) into the scene's result with the vec2 op_add (sdf.h:5-11):
+           acc = first ? v : op_add(acc, v), that is acc.x < v.x ? acc : v — at equal distance, or with a NaN, the LATER object wins.
+           This is how the reference's apps build scenes: float CSG per object, a material per object, a union of objects;
+         - sdf(pos) is acc after the last instruction; the hit's material is int(acc.y).
+       The hit threshold .005, sdf_shadow's 20 steps / end 20 / .05 offset / factor 32 / darkest .05, the AO's five taps, the three
+       light colours, the checker scale .5, the abs, the fog formula, linear_to_srgb and alpha 1 stay the reference's.  sun_dir is used
+       as given, never normalised.  Every float bit pattern is data: NaN, inf, denormals, a zero k, a zero-length cylinder, a collinear
+       Bezier flow through as the reference's operations make them; every loop has a validated bound.
+       SBX_ERR_ARG, before anything is enqueued and with nothing written, for: n_instr outside 1..32, an unknown op, rot_axis outside
+       0..3, material outside 0..7 on an OBJECT (get_material leaves its result uninitialised outside the table), checker_material
+       outside -1..7, march_steps outside 1..512, shadow or view outside {0, 1}, a stack that underflows, that exceeds
+       SBX_SDF_MAX_STACK, that is not empty at an OBJECT after its pop or at the end, and a last instruction that is not OBJECT.
+       sbx_set_variant as for SBX_APP_SDF_AO: 1 and 3 select the IEEE roots, 2 forces the witness re-run.
+       NOT OFFERED: nested frames (a host composes its offsets itself), scaling, per-object light or AO settings, more than 32
+       instructions, and the drop-in header sbx_mainimage.hpp, which has no way to state a scene. */
+    SBX_APP_SDF_SCENE = 33
 } sbx_app;
 
 typedef enum sbx_status {
@@ -355,6 +386,43 @@ typedef struct sbx_aux_raytracer_scene {
  * read), fov = tan(radians(30.)) of the math spec, bounces 2, point light, Cook-Torrance, shadow on, ambient .01, 6 planes, 3 spheres.
  * The block SBX_APP_RAYTRACER_SCENE renders when aux is NULL is this one with at_rest = 0. */
 void sbx_raytracer_scene_cornell(const sbx_uniforms* uni, int at_rest, sbx_aux_raytracer_scene* out);
+
+/* the field and the renderer settings of SBX_APP_SDF_SCENE: plain data, 2784 bytes.  (app_sdf_ao.h:N names the line of
+ * src/app_sdf_ao.h whose literal the value replaces.) */
+#define SBX_SDF_MAX_INSTR 32
+#define SBX_SDF_MAX_STACK 4
+enum { SBX_SDF_PLANE = 1, SBX_SDF_SPHERE, SBX_SDF_BOX, SBX_SDF_TORUS, SBX_SDF_Y_CYLINDER, SBX_SDF_CYLINDER, SBX_SDF_CAPSULE, SBX_SDF_BEZIER,
+       SBX_SDF_ADD = 16, SBX_SDF_SUB, SBX_SDF_INTERSECT, SBX_SDF_BLEND,
+       SBX_SDF_OBJECT = 32 };
+typedef struct sbx_sdf_instr {            /* 80 B */
+    int32_t op, rot_axis;                 /* rot_axis 0 none, 1 x, 2 y, 3 z */
+    float rot_deg; int32_t material;      /* material: SBX_SDF_OBJECT only, 0..7 */
+    float offset[3]; float _pad;
+    float a[4], b[4], c[4];
+} sbx_sdf_instr;
+typedef struct sbx_aux_sdf_scene {        /* 2784 B */
+    float eye[3];        float fov;               /* main.h's FOV factor, as given (app_sdf_ao.h:313 has 1.) */
+    float look_at[3];    int32_t march_steps;     /* :249, 1..512 (70) */
+    float sun_dir[3];    float march_end;         /* :209 USED AS GIVEN, never normalised; :250 (20.) */
+    float background[3]; int32_t shadow;          /* :11; the `#if 0` of :269: 0 | 1 */
+    float fog_density, fog_falloff; int32_t view, checker_material;   /* view 0 shaded, 1 = the `#if 0` of :217 (normals); checker: the id that gets :237-240, -1 none */
+    int32_t n_instr, _pad[3];
+    float materials[8][4];                        /* rgb, pad */
+    sbx_sdf_instr program[SBX_SDF_MAX_INSTR];
+} sbx_aux_sdf_scene;
+/* Host only, no context: the block SBX_APP_SDF_SCENE renders when aux is NULL.  app_sdf_ao.h's camera for u_time (setup_camera :45-50),
+ * FOV 1, sun = normalize(1, 2, 1) of the math spec, the six shipped materials (slots 6 and 7 zero), background (.1, .1, .7), fog
+ * .1 / .5, 70 steps, end 20, shadow 0, view 0, checker material 1, and as the program ONE ramp of sdf_pipe (:54-113) in sdf_pipe's own
+ * coordinates plus the ground plane, 20 instructions:
+ *     box (0,1,0) size; y-cylinder rotated x -90 at (0 + .7, 1 + .5, 0 + 0); SUB; OBJECT 2          the ramp
+ *     y-cylinder rotated x -90 at (0 + (-1.3 + .525), 1 + 1, 0 + 0); OBJECT 5                       the coping bar
+ *     rail box, bars 1 2 ADD 3 ADD 4 5 ADD ADD, ADD; OBJECT 4                                        the deck railing (stack depth 4)
+ *     plane (0, 1, 0), 0; OBJECT 1                                                                   the ground
+ * Each offset is the binary32 value (o1 - o2) of the reference's two successive offsets `p = pos - o1; p + o2` or (o1 + o2) of
+ * `p = pos - o1; p -= o2`, component by component — ONE subtraction per primitive where the reference makes two, so the frame is
+ * a new one, not SBX_APP_SDF_AO's; that frame's nested rotate_around_y(180) (:134) and its tree of vec2 unions (:108-110, :137,
+ * :147-149) are not expressible in this block either. */
+void sbx_sdf_scene_ramp(const sbx_uniforms* uni, sbx_aux_sdf_scene* out);
 
 typedef struct sbx_ctx sbx_ctx;
 
@@ -610,6 +678,15 @@ int sbx_noise_eval(sbx_ctx* ctx, const char* fn, const float* xyz, const float* 
  * SBX_ERR_ARG for a NULL ctx / fn / rays / out, a NULL sun_dir with "get_incident_light", an unknown name, n > 2^31. */
 int sbx_atmosphere_eval(sbx_ctx* ctx, const char* fn, const float* rays, const float* sun_dir, float* out,
                         size_t n, void* stream);
+/* The SDF library on its own (src/sdf.h): sdf(pos) of SBX_APP_SDF_SCENE's program over the caller's points — the field's value
+ * without a renderer: collision queries, a mesher's samples, another renderer's march.  `scene`: HOST memory, read during the call;
+ * ONLY n_instr and program are read, and they are validated as SBX_APP_SDF_SCENE validates them (SBX_ERR_ARG, nothing written).
+ * `xyz`: device memory, n x 3 floats; `out`: device memory, n x 2 floats — the distance, then the nearest object's material id as a
+ * float — not overlapping `xyz`; both need only 4-byte alignment.  Exact for every bit pattern of input: NaN and inf are data.
+ * Asynchronous on `stream` and capturable (no allocation, no wait); not counted in sbx_stats.render_launches; sbx_set_variant 1 / 3
+ * select the IEEE roots as for the app.  n == 0 returns SBX_OK and touches nothing; SBX_ERR_ARG also for a NULL ctx / scene / xyz /
+ * out and n > 2^31. */
+int sbx_sdf_eval(sbx_ctx* ctx, const sbx_aux_sdf_scene* scene, const float* xyz, float* out, size_t n, void* stream);
 /* The size^3 RGBA32F noise volume util/ddsvolgen bakes (ddsvolgen.cpp:101-117): R =
  * fbm_worley_tile((xyz + .5)/size, 2, 1, .5), G = B = A = 0, x fastest.  `rgba`: size^3 * 4 floats. */
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream);

@@ -30,6 +30,7 @@ extern "C" {
  * APP_RAYTRACER and SBX_APP_RAYTRACER_PHONG / _NOSHADOW / _STATIC alike: 1 = the IEEE roots and normalisations with the six-plane loop of
  * raytrace_iteration; 2 = the witness's test edge; 3 = the IEEE roots and normalisations; each over the build's own code and frame.
  * SBX_APP_RAYTRACER_SCENE: 1 and 3 = the IEEE roots, normalisations and sphere-normal quotients; 2 = the witness's test edge.
+ * SBX_APP_SDF_SCENE and sbx_sdf_eval: 1 and 3 = the IEEE roots; 2 = the witness's test edge.
  * SBX_APP_VINYL_CLOSEUP / _RIDGES / _NOSHADOW: every value as for APP_VINYL, over the build's own code and frame.
  * SBX_APP_PLANET_CLOSEUP / _CLOUDLESS / _UNLIT: as for APP_PLANET, 1 = the build without its exact skips.
  * sbx_atmosphere_eval: 1 = the plain statement of src/app_atmosphere.h:50-160 lane by lane for every wave (no class test, guarded exp,

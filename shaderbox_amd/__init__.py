@@ -17,7 +17,7 @@ from . import shard  # noqa: F401  (pure-python row-block arithmetic, no GPU nee
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsbx.so")
 
-APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW, APP_PLANET_CLOSEUP, APP_PLANET_CLOUDLESS, APP_PLANET_UNLIT, APP_RAYTRACER_SCENE = range(33)
+APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW, APP_PLANET_CLOSEUP, APP_PLANET_CLOUDLESS, APP_PLANET_UNLIT, APP_RAYTRACER_SCENE, APP_SDF_SCENE = range(34)
 APPS = {"APP_PLANET": APP_PLANET, "APP_CLOUDS": APP_CLOUDS, "APP_VINYL": APP_VINYL, "APP_EGG": APP_EGG,
         "APP_RAYTRACER": APP_RAYTRACER, "APP_ATMOSPHERE": APP_ATMOSPHERE, "APP_SDF_AO": APP_SDF_AO,
         "APP_CLOUDS_BEST": APP_CLOUDS_BEST,    # src/app_clouds_best.h (stand-alone shader, not an APP_* define)
@@ -47,7 +47,8 @@ MORE_APPS = {"APP_EGG_STRAIGHT": APP_EGG_STRAIGHT,  # APP_EGG without `#define B
              "APP_PLANET_CLOSEUP": APP_PLANET_CLOSEUP,      # APP_PLANET with the `#if 0` at src/app_planet.h:51 on: the camera of :52-53
              "APP_PLANET_CLOUDLESS": APP_PLANET_CLOUDLESS,  # APP_PLANET without the `#define CLOUDS` of src/app_planet.h:63: no cloud march, no cloud shadow
              "APP_PLANET_UNLIT": APP_PLANET_UNLIT,          # APP_PLANET without the `#define LIGHT` of src/app_planet.h:249: N = w_normal.y, ocean = water
-             "APP_RAYTRACER_SCENE": APP_RAYTRACER_SCENE}    # src/app_raytracer.h's render over the caller's scene: aux = a RaytracerScene (cornell_scene, raytracer_scene)
+             "APP_RAYTRACER_SCENE": APP_RAYTRACER_SCENE,    # src/app_raytracer.h's render over the caller's scene: aux = a RaytracerScene (cornell_scene, raytracer_scene)
+             "APP_SDF_SCENE": APP_SDF_SCENE}                # src/app_sdf_ao.h's renderer over the caller's field, a program of src/sdf.h's primitives and operators: aux = an SdfScene (sdf_ramp_scene, SdfSceneBuilder)
 ALL_APPS = {**APPS, **MORE_APPS}
 
 SBX_OK, SBX_ERR_ARG, SBX_ERR_UNSUPPORTED, SBX_ERR_HIP, SBX_ERR_NO_DEVICE, SBX_ERR_FAULT = 0, -1, -2, -3, -4, -5
@@ -125,6 +126,173 @@ class RaytracerScene(ctypes.Structure):     # sbx_aux_raytracer_scene (the aux b
                 ("materials", RtMaterial * 8), ("planes", RtPlane * RT_MAX_PLANES), ("spheres", RtSphere * RT_MAX_SPHERES)]
 
 
+SDF_MAX_INSTR, SDF_MAX_STACK = 32, 4         # SBX_SDF_MAX_INSTR, SBX_SDF_MAX_STACK
+SDF_PLANE, SDF_SPHERE, SDF_BOX, SDF_TORUS, SDF_Y_CYLINDER, SDF_CYLINDER, SDF_CAPSULE, SDF_BEZIER = range(1, 9)
+SDF_ADD, SDF_SUB, SDF_INTERSECT, SDF_BLEND = range(16, 20)
+SDF_OBJECT = 32
+
+
+class SdfInstr(ctypes.Structure):           # sbx_sdf_instr, 80 bytes
+    _fields_ = [("op", ctypes.c_int32), ("rot_axis", ctypes.c_int32), ("rot_deg", ctypes.c_float), ("material", ctypes.c_int32),
+                ("offset", ctypes.c_float * 3), ("_pad", ctypes.c_float),
+                ("a", ctypes.c_float * 4), ("b", ctypes.c_float * 4), ("c", ctypes.c_float * 4)]
+
+
+class SdfScene(ctypes.Structure):           # sbx_aux_sdf_scene (the aux block of APP_SDF_SCENE, 2784 bytes)
+    _fields_ = [("eye", ctypes.c_float * 3), ("fov", ctypes.c_float),
+                ("look_at", ctypes.c_float * 3), ("march_steps", ctypes.c_int32),
+                ("sun_dir", ctypes.c_float * 3), ("march_end", ctypes.c_float),
+                ("background", ctypes.c_float * 3), ("shadow", ctypes.c_int32),
+                ("fog_density", ctypes.c_float), ("fog_falloff", ctypes.c_float), ("view", ctypes.c_int32), ("checker_material", ctypes.c_int32),
+                ("n_instr", ctypes.c_int32), ("_pad", ctypes.c_int32 * 3),
+                ("materials", (ctypes.c_float * 4) * 8),
+                ("program", SdfInstr * SDF_MAX_INSTR)]
+
+
+assert ctypes.sizeof(SdfInstr) == 80 and ctypes.sizeof(SdfScene) == 2784 and SdfScene.program.offset == 224 and SdfScene.materials.offset == 96
+
+
+def sdf_scene_check(scene, program_only=False):
+    """The refusals of include/sbx.h for an SdfScene, on the host and in the C side's order: None if the block would be accepted,
+    else a sentence saying what is wrong.  program_only: what sbx_sdf_eval checks (n_instr and the program)."""
+    if not 1 <= scene.n_instr <= SDF_MAX_INSTR:
+        return "n_instr must lie in 1..32"
+    if not program_only:
+        if not -1 <= scene.checker_material <= 7:
+            return "checker_material must lie in -1..7"
+        if not 1 <= scene.march_steps <= 512:
+            return "march_steps must lie in 1..512"
+        if scene.shadow not in (0, 1):
+            return "shadow must be 0 or 1"
+        if scene.view not in (0, 1):
+            return "view must be 0 or 1"
+    depth = 0
+    for i in range(scene.n_instr):
+        I = scene.program[i]
+        prim, oper = SDF_PLANE <= I.op <= SDF_BEZIER, SDF_ADD <= I.op <= SDF_BLEND
+        if not (prim or oper or I.op == SDF_OBJECT):
+            return "unknown op"
+        if not 0 <= I.rot_axis <= 3:
+            return "rot_axis must lie in 0..3"
+        if prim:
+            depth += 1
+            if depth > SDF_MAX_STACK:
+                return "the stack exceeds SDF_MAX_STACK"
+        elif oper:
+            if depth < 2:
+                return "the stack underflows at an operator"
+            depth -= 1
+        else:
+            if not 0 <= I.material <= 7:
+                return "an OBJECT's material must lie in 0..7"
+            if depth < 1:
+                return "the stack underflows at an OBJECT"
+            depth -= 1
+            if depth:
+                return "the stack is not empty at an OBJECT after its pop"
+    if scene.program[scene.n_instr - 1].op != SDF_OBJECT:
+        return "the last instruction must be an OBJECT"
+    return None
+
+
+class SdfSceneBuilder:
+    """Appends instructions to an SdfScene (the aux block of APP_SDF_SCENE; include/sbx.h has the semantics) and checks the block on
+    the host the way the C side does.  Starts from sdf_ramp_scene's renderer settings with an empty program:
+
+        b = SdfSceneBuilder(eye=(0, 3, 5))
+        b.box((0, 1, 0), (1, 1, 1)).sphere((0, 1.5, 0), .8).sub().object(2)        # postfix: box, sphere, box minus sphere
+        b.plane((0, 1, 0), 0).object(1)
+        frame = renderer.render("sdf_scene", w, h, 0, aux=b.scene())
+
+    Every primitive takes offset=, rot_axis= (0 none, 1 x, 2 y, 3 z) and rot_deg=.  scene() raises ValueError where the block would be
+    refused."""
+
+    def __init__(self, **settings):
+        s = self.s = SdfScene()
+        s.eye[:], s.look_at[:], s.fov = (0.0, 3.0, 5.0), (0.0, 0.0, 0.0), 1.0
+        s.march_steps, s.march_end = 70, 20.0
+        s.sun_dir[:] = (0.40824828, 0.81649655, 0.40824828)
+        s.background[:] = (0.1, 0.1, 0.7)
+        s.fog_density, s.fog_falloff, s.checker_material = 0.1, 0.5, 1
+        for i, m in enumerate(((1, 1, 1), (0, .2, 0), (.1, .1, .1), (.1, .1, .1), (.1, .1, .1), (.4, .4, .4))):
+            s.materials[i][:3] = m
+        self.set(**settings)
+
+    def set(self, **settings):
+        for k, v in settings.items():
+            if k == "materials":
+                for i, m in (v.items() if hasattr(v, "items") else enumerate(v)):
+                    self.s.materials[int(i)][:3] = [float(x) for x in m]
+            elif k in ("eye", "look_at", "sun_dir", "background"):
+                getattr(self.s, k)[:] = [float(x) for x in v]
+            elif k in ("fov", "march_end", "fog_density", "fog_falloff"):
+                setattr(self.s, k, float(v))
+            elif k in ("march_steps", "shadow", "view", "checker_material"):
+                setattr(self.s, k, int(v))
+            else:
+                raise ValueError("unknown setting %r" % k)
+        return self
+
+    def _add(self, op, offset=(0, 0, 0), a=(), b=(), c=(), rot_axis=0, rot_deg=0.0, material=0):
+        if self.s.n_instr >= SDF_MAX_INSTR:
+            raise ValueError("a program holds at most %d instructions" % SDF_MAX_INSTR)
+        I = self.s.program[self.s.n_instr]
+        I.op, I.rot_axis, I.rot_deg, I.material = int(op), int(rot_axis), float(rot_deg), int(material)
+        I.offset[:] = [float(x) for x in offset]
+        for dst, src in ((I.a, a), (I.b, b), (I.c, c)):
+            dst[:] = [float(x) for x in tuple(src) + (0.0,) * (4 - len(tuple(src)))]
+        self.s.n_instr += 1
+        return self
+
+    def plane(self, normal, d, **kw):
+        return self._add(SDF_PLANE, a=tuple(normal) + (d,), **kw)
+
+    def sphere(self, offset, r, **kw):
+        return self._add(SDF_SPHERE, offset, (r,), **kw)
+
+    def box(self, offset, half, **kw):
+        return self._add(SDF_BOX, offset, tuple(half), **kw)
+
+    def torus(self, offset, R, r, **kw):
+        return self._add(SDF_TORUS, offset, (R, r), **kw)
+
+    def y_cylinder(self, offset, r, h, **kw):
+        return self._add(SDF_Y_CYLINDER, offset, (r, h), **kw)
+
+    def cylinder(self, offset, p0, p1, r, **kw):
+        return self._add(SDF_CYLINDER, offset, tuple(p0) + (r,), tuple(p1), **kw)
+
+    def capsule(self, offset, a, b, r, **kw):
+        return self._add(SDF_CAPSULE, offset, tuple(a) + (r,), tuple(b), **kw)
+
+    def bezier(self, offset, a, b, c, thickness, **kw):
+        return self._add(SDF_BEZIER, offset, tuple(a) + (thickness,), tuple(b), tuple(c), **kw)
+
+    def add(self):
+        return self._add(SDF_ADD)
+
+    def sub(self):
+        return self._add(SDF_SUB)
+
+    def intersect(self):
+        return self._add(SDF_INTERSECT)
+
+    def blend(self, k):
+        return self._add(SDF_BLEND, a=(k,))
+
+    def object(self, material):
+        return self._add(SDF_OBJECT, material=material)
+
+    def check(self, program_only=False):
+        return sdf_scene_check(self.s, program_only)
+
+    def scene(self):
+        why = self.check()
+        if why:
+            raise ValueError("sdf scene: " + why)
+        return SdfScene.from_buffer_copy(self.s)
+
+
 class Stats(ctypes.Structure):              # sbx_stats
     _fields_ = [("render_launches", ctypes.c_uint64), ("main_image_hits", ctypes.c_uint64),
                 ("main_image_frames", ctypes.c_uint64), ("main_image_points", ctypes.c_uint64),
@@ -179,6 +347,9 @@ def load_library(path=None):
     lib.sbx_aux_clouds_ue4_defaults.restype = None
     lib.sbx_raytracer_scene_cornell.argtypes = [ctypes.POINTER(Uniforms), ci, ctypes.POINTER(RaytracerScene)]
     lib.sbx_raytracer_scene_cornell.restype = None
+    lib.sbx_sdf_scene_ramp.argtypes = [ctypes.POINTER(Uniforms), ctypes.POINTER(SdfScene)]
+    lib.sbx_sdf_scene_ramp.restype = None
+    lib.sbx_sdf_eval.argtypes = [vp, ctypes.POINTER(SdfScene), fp, fp, ctypes.c_size_t, vp]
     lib.sbx_debug_raytracer_scene_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.sbx_create.argtypes = [ci, ctypes.POINTER(vp)]
     lib.sbx_destroy.argtypes = [vp]
@@ -328,6 +499,16 @@ def raytracer_scene(planes=(), spheres=(), materials=(), light=(0.0, 3.8, 1.5), 
         a.planes[i].direction[:], a.planes[i].distance, a.planes[i].material = [float(v) for v in n], float(d), int(mat)
     for i, (o, r, mat) in enumerate(spheres):
         a.spheres[i].origin[:], a.spheres[i].radius, a.spheres[i].material = [float(v) for v in o], float(r), int(mat)
+    return a
+
+
+def sdf_ramp_scene(width, height, time, lib=None):
+    """sbx_sdf_scene_ramp (host only, no GPU needed): the SdfScene that APP_SDF_SCENE renders when aux is None — app_sdf_ao.h's camera
+    for `time`, its lights, materials and fog, and one ramp of its sdf_pipe plus the ground as a 20-instruction program."""
+    lib = lib or load_library()
+    u = uniforms(width, height, time)
+    a = SdfScene()
+    lib.sbx_sdf_scene_ramp(ctypes.byref(u), ctypes.byref(a))
     return a
 
 
@@ -859,6 +1040,15 @@ class Renderer:
             self._check(self.lib.sbx_atmosphere_eval(*args, self._stream()))
         else:
             self._check(self.lib.sbx_debug_atmosphere_eval(*args, ctypes.byref(waves), self._stream()))
+        return out
+
+    def sdf_eval(self, scene, xyz):
+        """sdf(pos) of an SdfScene's program over points xyz[n, 3] (include/sbx.h sbx_sdf_eval) -> [n, 2]: the distance and the
+        nearest object's material id as a float.  Only the program of `scene` is read."""
+        xyz = xyz.to(self.tdev, self.torch.float32).contiguous().view(xyz.numel() // 3, 3)
+        out = self.torch.empty((xyz.shape[0], 2), dtype=self.torch.float32, device=self.tdev)
+        self._check(self.lib.sbx_sdf_eval(self.ctx, ctypes.byref(scene), ctypes.c_void_p(xyz.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                          xyz.shape[0], self._stream()))
         return out
 
     def worley_volume(self, size=128):

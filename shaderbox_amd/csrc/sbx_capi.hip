@@ -204,6 +204,11 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
         if (RS.lighting != 0 && RS.lighting != 1) return fail(ctx, SBX_ERR_ARG, "raytracer scene: lighting must be 0 (Cook-Torrance) or 1 (Phong)");
         if (RS.shadow != 0 && RS.shadow != 1) return fail(ctx, SBX_ERR_ARG, "raytracer scene: shadow must be 0 or 1");
     }
+    sbx_aux_sdf_scene SS;
+    if (T.aux == AUX_SDF_SCENE) {
+        SS = aux_sdf_scene(aux, *uni);
+        if (const char* why = sdf_scene_check(SS, false)) return fail(ctx, SBX_ERR_ARG, why);
+    }
     if (T.noise_volumes && !ctx->noise.shape) return fail(ctx, SBX_ERR_ARG, "APP_CLOUDS with USE_NOISE_TEX needs sbx_set_noise_volume first");
     const bool capturing = stream_is_capturing(s);
     TimingPair* tp = nullptr;
@@ -277,6 +282,8 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     case SBX_APP_SDF_AO: launch_sdf_ao(build_sdf_ao(*uni, aux_sdf_ao(aux)), M, rgba, s, sdf_variant, 0); break;
     case SBX_APP_SDF_AO_SHADOW: launch_sdf_ao(build_sdf_ao(*uni, aux_sdf_ao(aux)), M, rgba, s, sdf_variant, 1); break;
     case SBX_APP_SDF_AO_NORMALS: launch_sdf_ao(build_sdf_ao(*uni, aux_sdf_ao(aux)), M, rgba, s, sdf_variant, 2); break;
+    // the caller's field (validated above) through app_sdf_ao.h's renderer
+    case SBX_APP_SDF_SCENE: launch_sdf_scene(build_sdf_scene(*uni, SS), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots); break;
     case SBX_APP_PLANET: launch_planet(build_planet(*uni), M, rgba, s, cull_variant); break;
     case SBX_APP_PLANET_ATMOSPHERE: launch_planet(build_planet(*uni, true), M, rgba, s, cull_variant); break;
     // the builds of app_planet.h's three switches (include/sbx.h): kernel builds over the shipped frame, CLOSEUP over a frame of its own

@@ -112,9 +112,10 @@ struct Texture2d {
 // The key words are relaxed atomics because readers look at them while a writer may be storing.
 struct FrameCache {
     static constexpr int FRAMES = 2;
-    static constexpr int KEY_WORDS = 2 + (int)(sizeof(sbx_uniforms) + sizeof(sbx_aux_raytracer_scene)) / 4;   // (the largest aux block)
-    static_assert(sizeof(sbx_aux_raytracer_scene) >= sizeof(sbx_aux_clouds) && sizeof(sbx_aux_raytracer_scene) >= sizeof(sbx_aux_clouds_ue4) &&
-                  sizeof(sbx_aux_raytracer_scene) >= sizeof(sbx_aux_sdf_ao), "KEY_WORDS holds the largest aux block (mi_make_key copies app_aux_bytes of it)");
+    static constexpr int KEY_WORDS = 2 + (int)(sizeof(sbx_uniforms) + sizeof(sbx_aux_sdf_scene)) / 4;   // (the largest aux block)
+    static_assert(sizeof(sbx_aux_sdf_scene) >= sizeof(sbx_aux_clouds) && sizeof(sbx_aux_sdf_scene) >= sizeof(sbx_aux_clouds_ue4) &&
+                  sizeof(sbx_aux_sdf_scene) >= sizeof(sbx_aux_sdf_ao) && sizeof(sbx_aux_sdf_scene) >= sizeof(sbx_aux_raytracer_scene),
+                  "KEY_WORDS holds the largest aux block (mi_make_key copies app_aux_bytes of it)");
     struct Entry {
         std::atomic<uint64_t> gen{0};
         std::atomic<float*> host{nullptr};       // pinned (hipHostMalloc): the frame comes back with one asynchronous copy
@@ -212,6 +213,10 @@ FrameClouds build_clouds(const sbx_uniforms& U, const sbx_aux_clouds& A, bool sk
 FrameEggStraight build_egg(const sbx_uniforms& U, int build = EGG_DEFAULT);   // (the other builds read its FrameEgg part)
 FrameRaytracer build_raytracer(const sbx_uniforms& U, int build = RT_DEFAULT);   // build: RT_* (sbx_frame.h); RT_STATIC is the scene at rest
 FrameRtScene build_raytracer_scene(const sbx_uniforms& U, const sbx_aux_raytracer_scene& A);   // SBX_APP_RAYTRACER_SCENE: a validated block
+// SBX_APP_SDF_SCENE / sbx_sdf_eval: NULL if the block passes the checks of include/sbx.h, else what is wrong (program_only: n_instr and
+// the program alone, what sbx_sdf_eval reads); build_sdf_scene takes a block that passed
+const char* sdf_scene_check(const sbx_aux_sdf_scene& A, bool program_only);
+FrameSdfScene build_sdf_scene(const sbx_uniforms& U, const sbx_aux_sdf_scene& A);
 FrameAtmosphere build_atmosphere(const sbx_uniforms& U);
 FrameAtmosphere build_atmosphere_ground(const sbx_uniforms& U);
 FrameSdfAo build_sdf_ao(const sbx_uniforms& U, const sbx_aux_sdf_ao& A);

@@ -182,6 +182,8 @@ void launch_raytracer_scene(const FrameRtScene& F, const RowMap& M, float* out, 
 void launch_atmosphere(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision = 0);
 void launch_atmosphere_ground(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision, int variant);   // kern_atmosphere.hip
 void launch_sdf_ao(const FrameSdfAo& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = 0);   // build: 1 / 2 = the shadow / normals builds (kern_sdf_ao.hip)
+void launch_sdf_scene(const FrameSdfScene& F, const RowMap& M, float* out, hipStream_t s, int variant);   // SBX_APP_SDF_SCENE (kern_sdf_scene.hip)
+void launch_sdf_scene_eval(const FrameSdfScene& F, const float* xyz, float* out, size_t n, hipStream_t s, int variant);   // sbx_sdf_eval
 void launch_vinyl(const FrameVinyl& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = VINYL_DEFAULT);   // build: VINYL_* (sbx_frame.h)
 void launch_clouds_best(const FrameCloudsBest& F, const RowMap& M, float* out, hipStream_t s);
 void launch_clouds_ue4(const FrameCloudsUe4& F, const RowMap& M, float* out, hipStream_t s);

@@ -97,6 +97,25 @@ int sbx_debug_atmosphere_eval(sbx_ctx* ctx, const char* fn, const float* rays, c
     return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "atmosphere_eval (counted)", e);
 }
 
+int sbx_sdf_eval(sbx_ctx* ctx, const sbx_aux_sdf_scene* scene, const float* xyz, float* out, size_t n, void* stream) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!scene) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    if (const char* why = sdf_scene_check(*scene, true)) return fail(ctx, SBX_ERR_ARG, why);
+    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 points");
+    if (n == 0) return SBX_OK;
+    if (!xyz || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    const int rc = use_device(ctx);
+    if (rc != SBX_OK) return rc;
+    // only the program of the block is read: the renderer's settings are taken from the ramp block, whatever the caller's hold
+    sbx_aux_sdf_scene A;
+    const sbx_uniforms U = {{1.f, 1.f}, {0.f, 0.f}, 0.f, {0.f, 0.f, 0.f}};
+    sbx_sdf_scene_ramp(&U, &A);
+    A.n_instr = scene->n_instr;
+    std::memcpy(A.program, scene->program, sizeof(A.program));
+    launch_sdf_scene_eval(build_sdf_scene(U, A), xyz, out, n, (hipStream_t)stream, ctx->variant == 1 ? 1 : ctx->sdf_roots);
+    return launched(ctx, "sdf_eval launch");
+}
+
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream) {
     if (!ctx) return SBX_ERR_ARG;
     if (!rgba || size <= 0 || size > 1024) return fail(ctx, SBX_ERR_ARG, "bad volume arguments");

@@ -226,6 +226,37 @@ struct FrameSdfAo {
     float fog_density, fog_falloff;
 };
 
+// SBX_APP_SDF_SCENE (include/sbx.h sbx_aux_sdf_scene): app_sdf_ao.h's renderer over the caller's field, a postfix program.  One
+// instruction as the kernel reads it: the point-independent part of its primitive evaluated on the host, each host operation the same
+// binary32 operation the reference performs per call (the rotation's sin / cos; sd_cylinder's dir, length(P1), length(P0) sdf.h:104-107;
+// sd_capsule's ab and dot(ab, ab) :168-169; sd_bezier's w, u, v, a2, c2 :147-153 — normalisations with IEEE quotients, sbx_frames.hip).
+//   p[]:  PLANE n d | SPHERE r | BOX b | TORUS R r | Y_CYLINDER r h | CYLINDER dir len1 len0 P0 R | CAPSULE a ab dot(ab,ab) r |
+//         BEZIER b u v w a2 c2 thickness | BLEND k | OBJECT float(material)
+// 32 x 92 B: the frame, RowMap and the output pointer are 3288 B of the 4 KB a kernel may take by value — no buffer, no allocation.
+constexpr int SDF_MAX_INSTR = 32;
+// SBX_SDF_* as a bit number: primitives 1..8 -> 0..7, operators 16..19 -> 8..11, OBJECT 32 -> 12.  One bit per op, so that the
+// interpreter tests bits one after the other and the compiler cannot fold the tests back into a switch tree
+constexpr int sdf_op_bit(int op) { return op < 16 ? op - 1 : op < 32 ? op - 8 : 12; }
+struct SdfOp {
+    int ctl;              // what steers the interpreter, one scalar load per instruction: 1 << sdf_op_bit(op) | rot_axis << 16
+    float s, c;           // sin / cos of radians(rot_deg)
+    v3 off;
+    float p[17];
+};
+struct FrameSdfScene {
+    Camera cam;
+    int n_instr;          // 1..32, validated with the program's stack discipline before a launch (sbx_frames.hip sdf_scene_check)
+    int steps;            // app_sdf_ao.h:249, 1..512
+    int shadow, view;     // the `#if 0` of :269 and of :217
+    int checker;          // the material id that gets :237-240
+    float end;            // :250
+    float fog_density, fog_falloff;
+    v3 sun_dir;           // :209, as given
+    v3 background;        // :11
+    v3 mats[8];
+    SdfOp prog[SDF_MAX_INSTR];
+};
+
 // ---- APP_PLANET (src/app_planet.h) ----------------------------------------------------------
 struct FramePlanet {
     Camera cam;

@@ -265,6 +265,161 @@ FrameSdfAo build_sdf_ao(const sbx_uniforms& U, const sbx_aux_sdf_ao& A) {
     return F;
 }
 
+// ---- SBX_APP_SDF_SCENE (include/sbx.h sbx_aux_sdf_scene) -------------------------------------------------------------------------
+// The checks of include/sbx.h, in its order: the renderer's settings (unless program_only), then the program walked once with its
+// stack depth.  After it every loop of k_sdf_scene has a bound and every stack slot is written before it is read.
+const char* sdf_scene_check(const sbx_aux_sdf_scene& A, bool program_only) {
+    if (A.n_instr < 1 || A.n_instr > SBX_SDF_MAX_INSTR) return "sdf scene: n_instr must lie in 1..32";
+    if (!program_only) {
+        if (A.checker_material < -1 || A.checker_material > 7) return "sdf scene: checker_material must lie in -1..7";
+        if (A.march_steps < 1 || A.march_steps > 512) return "sdf scene: march_steps must lie in 1..512";
+        if (A.shadow != 0 && A.shadow != 1) return "sdf scene: shadow must be 0 or 1";
+        if (A.view != 0 && A.view != 1) return "sdf scene: view must be 0 or 1";
+    }
+    int depth = 0;
+    for (int i = 0; i < A.n_instr; ++i) {
+        const sbx_sdf_instr& I = A.program[i];
+        if (I.op >= SBX_SDF_PLANE && I.op <= SBX_SDF_BEZIER) {
+            if (I.rot_axis < 0 || I.rot_axis > 3) return "sdf scene: rot_axis must lie in 0..3";
+            if (++depth > SBX_SDF_MAX_STACK) return "sdf scene: the stack exceeds SBX_SDF_MAX_STACK";
+        } else if (I.op >= SBX_SDF_ADD && I.op <= SBX_SDF_BLEND) {
+            if (I.rot_axis < 0 || I.rot_axis > 3) return "sdf scene: rot_axis must lie in 0..3";
+            if (depth < 2) return "sdf scene: the stack underflows at an operator";
+            --depth;
+        } else if (I.op == SBX_SDF_OBJECT) {
+            if (I.rot_axis < 0 || I.rot_axis > 3) return "sdf scene: rot_axis must lie in 0..3";
+            if (I.material < 0 || I.material > 7) return "sdf scene: an OBJECT's material must lie in 0..7";
+            if (depth < 1) return "sdf scene: the stack underflows at an OBJECT";
+            if (--depth != 0) return "sdf scene: the stack is not empty at an OBJECT after its pop";
+        } else {
+            return "sdf scene: unknown op";
+        }
+    }
+    if (A.program[A.n_instr - 1].op != SBX_SDF_OBJECT) return "sdf scene: the last instruction must be an OBJECT";
+    return nullptr;                                                    // (depth is 0 here: the last OBJECT left it so)
+}
+
+// normalize(v) with three IEEE quotients: sbx_vec.h's form divides through a binary64 reciprocal, which is not the IEEE quotient where
+// the quotient is subnormal (sbx_math.h) — the caller's numbers can be anything
+static v3 normalize_ieee(v3 v) {
+    const float l = length(v);
+    return V3(v.x / l, v.y / l, v.z / l);
+}
+static v3 v3_at(const float* p) { return V3(p[0], p[1], p[2]); }
+
+FrameSdfScene build_sdf_scene(const sbx_uniforms& U, const sbx_aux_sdf_scene& A) {
+    FrameSdfScene F;
+    std::memset(&F, 0, sizeof(F));
+    {                                                                  // make_camera (sbx_frame.h), util.h:10-13, IEEE quotients
+        const v3 eye = v3_at(A.eye), look_at = v3_at(A.look_at);
+        Camera& c = F.cam;
+        c.res_x = U.u_res[0]; c.res_y = U.u_res[1];
+        c.aspect_x = U.u_res[0] / U.u_res[1];
+        c.fov = A.fov;
+        c.rres_x = recip64(U.u_res[0]); c.rres_y = recip64(U.u_res[1]);
+        c.eye = eye;
+        c.fwd = normalize_ieee(look_at - eye);
+        c.right = cross(V3(0, 1, 0), c.fwd);
+        c.up = cross(c.fwd, c.right);
+    }
+    F.n_instr = A.n_instr; F.steps = A.march_steps; F.shadow = A.shadow; F.view = A.view; F.checker = A.checker_material;
+    F.end = A.march_end; F.fog_density = A.fog_density; F.fog_falloff = A.fog_falloff;
+    F.sun_dir = v3_at(A.sun_dir); F.background = v3_at(A.background);
+    for (int i = 0; i < 8; ++i) F.mats[i] = v3_at(A.materials[i]);
+    for (int i = 0; i < A.n_instr; ++i) {                              // (the slots past n_instr stay zero; the kernel never reads them)
+        const sbx_sdf_instr& I = A.program[i];
+        SdfOp& O = F.prog[i];
+        O.ctl = (int)(1u << sdf_op_bit(I.op) | (unsigned)I.rot_axis << 16);
+        const float ang = radians_(I.rot_deg);                         // util.h:44-69
+        O.s = sin_(ang); O.c = cos_(ang);
+        O.off = v3_at(I.offset);
+        auto put = [&O](int k, v3 v) { O.p[k] = v.x; O.p[k + 1] = v.y; O.p[k + 2] = v.z; };
+        switch (I.op) {
+        case SBX_SDF_PLANE: case SBX_SDF_BOX: for (int k = 0; k < 4; ++k) O.p[k] = I.a[k]; break;
+        case SBX_SDF_SPHERE: O.p[0] = I.a[0]; break;
+        case SBX_SDF_TORUS: case SBX_SDF_Y_CYLINDER: O.p[0] = I.a[0]; O.p[1] = I.a[1]; break;
+        case SBX_SDF_CYLINDER: {                                       // sdf.h:104,106-107
+            const v3 P0 = v3_at(I.a), P1 = v3_at(I.b);
+            put(0, normalize_ieee(P1 - P0));
+            O.p[3] = length(P1); O.p[4] = length(P0);
+            put(5, P0);
+            O.p[8] = I.a[3];
+            break;
+        }
+        case SBX_SDF_CAPSULE: {                                        // sdf.h:168-169
+            const v3 a = v3_at(I.a), ab = v3_at(I.b) - a;
+            put(0, a); put(3, ab);
+            O.p[6] = dot(ab, ab);
+            O.p[7] = I.a[3];
+            break;
+        }
+        case SBX_SDF_BEZIER: {                                         // sdf.h:147-153
+            const v3 a = v3_at(I.a), b = v3_at(I.b), c = v3_at(I.c);
+            const v3 w = normalize_ieee(cross(c - b, a - b));
+            const v3 u = normalize_ieee(c - b);
+            const v3 v = normalize_ieee(cross(w, u));
+            put(0, b); put(3, u); put(6, v); put(9, w);
+            O.p[12] = dot(a - b, u); O.p[13] = dot(a - b, v);
+            O.p[14] = dot(c - b, u); O.p[15] = dot(c - b, v);
+            O.p[16] = I.a[3];
+            break;
+        }
+        case SBX_SDF_BLEND: O.p[0] = I.a[0]; break;
+        case SBX_SDF_OBJECT: O.p[0] = (float)I.material; break;
+        default: break;
+        }
+    }
+    return F;
+}
+
+// The default block of SBX_APP_SDF_SCENE (include/sbx.h sbx_sdf_scene_ramp): one ramp of sdf_pipe (app_sdf_ao.h:54-113) and the ground
+static void sdf_ramp_block(const sbx_uniforms& U, sbx_aux_sdf_scene& A) {
+    std::memset(&A, 0, sizeof(A));
+    auto put = [](float* d, v3 v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; };
+    const m3 rot = rotate_around_y(U.u_time * 50.f);                   // setup_camera :45-50
+    put(A.eye, mul(rot, V3(0, 3, 5)));
+    put(A.look_at, V3(0, 0, 0));
+    A.fov = 1.f;                                                       // :313
+    A.march_steps = 70; A.march_end = 20.f;                            // :249-250
+    put(A.sun_dir, normalize(V3(1, 2, 1)));                            // :209
+    put(A.background, V3(.1f, .1f, .7f));                              // :11
+    A.shadow = 0; A.view = 0; A.checker_material = 1;
+    A.fog_density = .1f; A.fog_falloff = .5f;                          // uniform_buffer.h:56-60
+    const v3 mats[6] = {V3(1, 1, 1), V3(0, .2f, 0), V3(.1f, .1f, .1f), V3(.1f, .1f, .1f), V3(.1f, .1f, .1f), V3(.4f, .4f, .4f)};   // :35-43
+    for (int i = 0; i < 6; ++i) put(A.materials[i], mats[i]);
+    int n = 0;
+    auto prim = [&](int op, v3 off, float a0, float a1, float a2, float a3, int axis = 0, float deg = 0.f) {
+        sbx_sdf_instr& I = A.program[n++];
+        I.op = op; I.rot_axis = axis; I.rot_deg = deg;
+        put(I.offset, off);
+        I.a[0] = a0; I.a[1] = a1; I.a[2] = a2; I.a[3] = a3;
+    };
+    auto oper = [&](int op) { A.program[n++].op = op; };
+    auto object = [&](int material) { sbx_sdf_instr& I = A.program[n++]; I.op = SBX_SDF_OBJECT; I.material = material; };
+    const v3 size = V3(1.3f, 1.f, 1.25f);                              // :52
+    const v3 o1 = V3(0, size.y, 0);                                    // :58, :74
+    prim(SBX_SDF_BOX, o1, size.x, size.y, size.z, 0.f);                // :60
+    prim(SBX_SDF_Y_CYLINDER, o1 + V3(.7f, .5f, 0), size.y + .55f, 2.f * size.z + .1f, 0.f, 0.f, 1, -90.f);   // :62-66
+    oper(SBX_SDF_SUB);                                                 // :69
+    object(2);                                                         // mat_pipe
+    prim(SBX_SDF_Y_CYLINDER, o1 + V3(-size.x + .525f, size.y, 0), .025f, 2.f * size.z, 0.f, 0.f, 1, -90.f);   // :76-81
+    object(5);                                                         // mat_coping
+    const v3 o2 = V3(0, size.y * 2.f, 0);                              // :86
+    prim(SBX_SDF_BOX, o2 - V3(size.x, -.25f, 0), .025f, .05f, size.z, 0.f);   // rail :88-90
+    const float H = -.125f;
+    const float bz[5] = {0.f, size.z / 2.f, size.z, -size.z / 2.f, -size.z};   // :94-98
+    auto bar = [&](int k) { prim(SBX_SDF_BOX, o2 - V3(size.x, H, bz[k]), .025f, .125f, .025f, 0.f); };
+    bar(0); bar(1); oper(SBX_SDF_ADD);                                 // b_a :99
+    bar(2); oper(SBX_SDF_ADD);                                         // b_b :100
+    bar(3); bar(4); oper(SBX_SDF_ADD);                                 // b_c :101
+    oper(SBX_SDF_ADD);                                                 // b_d :102
+    oper(SBX_SDF_ADD);                                                 // op_add(rail, bars) :106
+    object(4);                                                         // mat_deck
+    prim(SBX_SDF_PLANE, V3(0, 0, 0), 0.f, 1.f, 0.f, 0.f);              // ground :143-145
+    object(1);                                                         // mat_ground
+    A.n_instr = n;
+}
+
 static Capsule capsule(v3 a, v3 b) {                                   // sdf.h:168-169
     Capsule c;
     c.a = a;
@@ -398,6 +553,11 @@ void sbx_checkerboard_texture(int size, int freq, uint32_t* out) {    // hlsltoy
 void sbx_raytracer_scene_cornell(const sbx_uniforms* uni, int at_rest, sbx_aux_raytracer_scene* out) {
     if (!uni || !out) return;
     cornell_block(*uni, at_rest != 0, *out);
+}
+
+void sbx_sdf_scene_ramp(const sbx_uniforms* uni, sbx_aux_sdf_scene* out) {
+    if (!uni || !out) return;
+    sdf_ramp_block(*uni, *out);
 }
 
 void sbx_aux_clouds_ue4_defaults(sbx_aux_clouds_ue4* a) {              // app_clouds.usf:4-7

@@ -8,6 +8,11 @@
 //     APP_CLOUDS aux block (the ImGui panel of hlsltoy, util/hlsltoy/src/hlsltoy.cpp:466-483):
 //              [--wind x,y,z] [--sun x,y,z] [--sun-color r,g,b] [--sun-power P] [--sky-radius R] [--sky-height Y]
 //              [--sigma S] [--coverage C] [--thick T] [--steps N] [--light-steps N]
+//     --clouds-panorama W H [--eye X Y Z]: instead of an app's frame, an equirectangular sky of W x H pixels seen from the eye (default
+//              0 -.5 0, setup_camera's): every azimuth, elevations from the horizon (row 0) to the zenith, through sbx_clouds_eval
+//              "render" (include/sbx.h) with the APP_CLOUDS aux flags and --time / --frames / --dt.  Pixel (x, y) looks along
+//              (cos e sin a, sin e, -cos e cos a) with a = 2 pi (x + .5) / W and e = (pi / 2) (y + .5) / H, evaluated in binary64 and
+//              rounded.  The frame holds what the entry returns: LINEAR rgb and the clouds' alpha.  One GPU, float pixels.
 //     APP_SDF_AO aux block (:484-487):  [--fog-density D] [--fog-falloff F]
 //     app "sdf_ao_shadow" / "sdf_ao_normals": src/app_sdf_ao.h with its `#if 0` at :269 (soft shadows) / :217 (normals view) on; same fog flags
 //     app "egg_straight" / "egg_oval": src/app_egg.h without its `#define BEZIER` (:37, cylinder legs) / with its `#if 1` at :46 off (one scaled sphere)
@@ -39,6 +44,7 @@
 // before the extension when N > 1).  --gpus N shards every frame over N GPUs inside the library (sbx_multi_*).
 #include <hip/hip_runtime_api.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -114,7 +120,8 @@ int main(int argc, char** argv) {
     sbx_aux_sdf_ao as;
     sbx_aux_clouds_defaults(&ac);
     sbx_aux_sdf_ao_defaults(&as);
-    bool have_ac = false, have_as = false, rgba8_out = false;
+    bool have_ac = false, have_as = false, rgba8_out = false, panorama = false;
+    float eye[3] = {0.f, -.5f, 0.f};
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -136,6 +143,8 @@ int main(int argc, char** argv) {
         else if (a == "--rgba8") rgba8_out = true;
         else if (a == "--noise-tex") noise_tex = next();
         else if (a == "--scene-bin") scene_bin = next();
+        else if (a == "--clouds-panorama") { W = atoi(next()); H = atoi(next()); panorama = true; }
+        else if (a == "--eye") { for (float& v : eye) v = (float)atof(next()); }
         else if (a == "--wind") { vec3(ac.wind_dir); have_ac = true; }
         else if (a == "--sun") { vec3(ac.sun_dir); have_ac = true; }
         else if (a == "--sun-color") { vec3(ac.sun_color); have_ac = true; }
@@ -155,6 +164,8 @@ int main(int argc, char** argv) {
     if (id < 0) { fprintf(stderr, "unknown app %s\n", app.c_str()); return 2; }
     if (frames < 1 || gpus < 1) { fprintf(stderr, "--frames and --gpus must be >= 1\n"); return 2; }
     if (rgba8_out && !f32.empty()) { fprintf(stderr, "--rgba8 renders 8-bit pixels: there is no float frame for --f32\n"); return 2; }
+    if (panorama && (W < 1 || H < 1)) { fprintf(stderr, "--clouds-panorama W H\n"); return 2; }
+    if (panorama && (gpus > 1 || rgba8_out)) { fprintf(stderr, "--clouds-panorama renders float pixels on one GPU\n"); return 2; }
     for (const std::string* p : {&ppm, &f32})
         if (!pattern_ok(*p)) { fprintf(stderr, "bad file pattern %s: one %%d / %%0Nd conversion at most, a literal percent as %%%%\n", p->c_str()); return 2; }
     const void* aux = nullptr;
@@ -229,19 +240,34 @@ int main(int argc, char** argv) {
     if (!ppm.empty() && !rgba8_out && hipMalloc((void**)&dev8, npx * 4) != hipSuccess) { fprintf(stderr, "hipMalloc failed\n"); return 1; }
     std::vector<float> host(f32.empty() ? 0 : n);
     std::vector<unsigned char> rgba8(ppm.empty() ? 0 : npx * 4), rgb(ppm.empty() ? 0 : npx * 3);
+    float* rays = nullptr;
+    if (panorama) {
+        std::vector<float> hr(npx * 6);
+        const double pi = 3.14159265358979323846;
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x) {
+                const double az = 2.0 * pi * (x + .5) / W, el = .5 * pi * (y + .5) / H;
+                float* r = &hr[((size_t)y * W + x) * 6];
+                r[0] = eye[0]; r[1] = eye[1]; r[2] = eye[2];
+                r[3] = (float)(cos(el) * sin(az)); r[4] = (float)sin(el); r[5] = (float)(-cos(el) * cos(az));
+            }
+        if (hipMalloc((void**)&rays, hr.size() * sizeof(float)) != hipSuccess ||
+            hipMemcpy(rays, hr.data(), hr.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "hipMalloc failed\n"); return 1; }
+    }
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     for (int f = 0; f < frames; ++f) {
         sbx_uniforms u{};
         u.u_res[0] = (float)W; u.u_res[1] = (float)H; u.u_mouse[0] = mx; u.u_mouse[1] = my; u.u_time = t + f * dt;   // hlsltoy.cpp:502-504
         (void)hipEventRecord(e0, nullptr);
-        rc = multi ? sbx_multi_render(multi, id, &u, aux, dev, nullptr) : sbx_render_rows(ctx, id, &u, aux, 0, H, dev, nullptr);
+        if (panorama) rc = sbx_clouds_eval(ctx, "render", have_ac ? &ac : nullptr, u.u_time, rays, dev, npx, nullptr);
+        else rc = multi ? sbx_multi_render(multi, id, &u, aux, dev, nullptr) : sbx_render_rows(ctx, id, &u, aux, 0, H, dev, nullptr);
         if (rc != SBX_OK) { fprintf(stderr, "render: %s\n", multi ? sbx_multi_last_error(multi) : sbx_last_error(ctx)); return 1; }
         (void)hipEventRecord(e1, nullptr);
         (void)hipEventSynchronize(e1);
         float ms = 0;
         (void)hipEventElapsedTime(&ms, e0, e1);
-        printf("frame %d  u_time %.4f  %s %dx%d  %.3f ms  %.1f Mpix/s\n", f, u.u_time, app.c_str(), W, H, ms, W * (double)H / ms / 1e3);
+        printf("frame %d  u_time %.4f  %s %dx%d  %.3f ms  %.1f Mpix/s\n", f, u.u_time, panorama ? "clouds panorama" : app.c_str(), W, H, ms, W * (double)H / ms / 1e3);
         if (!f32.empty()) {
             if (hipMemcpy(host.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
             FILE* fp = fopen(frame_name(f32, f, frames).c_str(), "wb");
@@ -272,6 +298,7 @@ int main(int argc, char** argv) {
             fclose(fp);
         }
     }
+    if (rays) (void)hipFree(rays);
     if (dev8) (void)hipFree(dev8);
     (void)hipFree(dev);
     if (multi) sbx_multi_destroy(multi);

@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell, SBX_APP_SDF_SCENE with sbx_aux_sdf_scene, sbx_sdf_scene_ramp and sbx_sdf_eval: new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell, SBX_APP_SDF_SCENE with sbx_aux_sdf_scene, sbx_sdf_scene_ramp and sbx_sdf_eval, sbx_clouds_eval: new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -687,6 +687,26 @@ int sbx_atmosphere_eval(sbx_ctx* ctx, const char* fn, const float* rays, const f
  * select the IEEE roots as for the app.  n == 0 returns SBX_OK and touches nothing; SBX_ERR_ARG also for a NULL ctx / scene / xyz /
  * out and n > 2^31. */
 int sbx_sdf_eval(sbx_ctx* ctx, const sbx_aux_sdf_scene* scene, const float* xyz, float* out, size_t n, void* stream);
+/* The volumetric clouds and their sky (src/app_clouds.h, the procedural build as shipped: SKY_SPHERE and USE_NOISE_TEX undefined, both
+ * `#if 0` of illuminate_volume off) as standalone functions over n elements of the caller's: what the reference reaches only through
+ * pixels of the one camera setup_camera fixes at (0, -.5, 0) — sky panoramas and cube faces, the sky a reflective surface of another
+ * scene sees, the density field for the caller's own volume bake.  `aux`: HOST memory, read during the call, NULL = the reference's
+ * defaults; validated as SBX_APP_CLOUDS validates its block (negative march steps: SBX_ERR_ARG, nothing written).  `in`, `out`: device
+ * memory, not overlapping, 4-byte alignment suffices.  Per element:
+ *   "render" (:204-218)            in 6: ray origin xyz, direction xyz.  out 4: the linear RGB render returns (no sRGB), then the alpha
+ *                                  render_clouds returned for this ray — 0 where :212 returned the sky.
+ *   "render_clouds" (:153-202)     in 6: as above.  out 4: the vec4 of :201.
+ *   "render_sky_color" (:36-46)    in 3: eye_dir.  out 3.
+ *   "density_func" (:62-86)        in 3: pos_in (this build does not read `height`).  out 1.
+ *   "illuminate_volume" (:91-123)  in 6: origin xyz, V xyz; L is aux->sun_dir.  out 1.
+ * The ray origin stands where the reference's eye.origin does (:166); u_time enters only through the wind offset (:167); there is no
+ * camera, no u_res and no u_mouse.  Directions are used as given, never normalised; a ray with dir.y <= 0, a zero, NaN or inf component
+ * is data: the result is whatever the reference's arithmetic gives.  Exact for every bit pattern of input.
+ * Asynchronous on `stream` and capturable (inside a capture it allocates nothing, queries nothing and waits for nothing); not counted
+ * in sbx_stats.render_launches; sbx_set_precision does not enter; sbx_set_variant 1 selects the plain statement (same bits).  n == 0
+ * returns SBX_OK and touches nothing; SBX_ERR_ARG for a NULL ctx / fn / in / out, an unknown name, n > 2^31. */
+int sbx_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, float u_time, const float* in, float* out, size_t n,
+                    void* stream);
 /* The size^3 RGBA32F noise volume util/ddsvolgen bakes (ddsvolgen.cpp:101-117): R =
  * fbm_worley_tile((xyz + .5)/size, 2, 1, .5), G = B = A = 0, x fastest.  `rgba`: size^3 * 4 floats. */
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream);

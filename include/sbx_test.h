@@ -35,6 +35,8 @@ extern "C" {
  * SBX_APP_PLANET_CLOSEUP / _CLOUDLESS / _UNLIT: as for APP_PLANET, 1 = the build without its exact skips.
  * sbx_atmosphere_eval: 1 = the plain statement of src/app_atmosphere.h:50-160 lane by lane for every wave (no class test, guarded exp,
  * sqrt_n_, division by the exact reciprocal); 0 runs it only on the waves whose rays are outside the class of csrc/sbx_atmosphere.h.
+ * sbx_clouds_eval: 1 = the statement of k_clouds_perlane lane by lane (hash1 in place, exp_, pow_, the IEEE division in the coverage
+ * smoothstep); 0 takes the lattice hashes from the context's table and the guard-less forms the aux block admits.
  * All variants are specified to produce identical bits (tests/test_gpu_parity.py sweeps them against each other). */
 int sbx_set_variant(sbx_ctx* ctx, int variant);
 
@@ -44,6 +46,14 @@ int sbx_set_variant(sbx_ctx* ctx, int variant);
  * kernel is compared with the plain one (tests/test_gpu_atmosphere_eval.py) and for tools/time_atmosphere_eval.py. */
 int sbx_debug_atmosphere_eval(sbx_ctx* ctx, const char* fn, const float* rays, const float* sun_dir, float* out, size_t n,
                               unsigned* fast_waves_host, void* stream);
+
+/* sbx_clouds_eval (sbx.h) with counts: the same launch (the context's variant and the same choice of hash table included) in a counting
+ * instantiation of the kernel, after which the call waits and stores in counts_host[0] the noise cells (one noise_iq call = one cell,
+ * four per density_func) whose eight lattice hashes came from the context's table and in counts_host[1] the cells whose hashes were
+ * evaluated in place (all of them under variant 1 and where no table is usable).  It allocates and synchronises, so it is not
+ * capturable.  For tests/test_gpu_clouds_eval.py and tools/time_clouds_eval.py. */
+int sbx_debug_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, float u_time, const float* in, float* out, size_t n,
+                          uint64_t counts_host[2], void* stream);
 
 /* Device evaluation of the math spec, elementwise over device arrays (for parity tests):
  * fn in {"sin","cos","tan","exp","pow","acos","atan2","hash","div","div_rd","exp_h13","pow_h","sqrt_n","sqrt_ieee","exp_reg","exp_reg_plain","exp_reg64","exp_reg64_plain","exp_small","exp_small_plain","exp_reg4k","sin_b40","div3","sqrt_rs","divn","srgb_pow","pow_spec"}; b may be NULL

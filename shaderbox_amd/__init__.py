@@ -387,6 +387,9 @@ def load_library(path=None):
     lib.sbx_noise_eval.argtypes = [vp, ctypes.c_char_p, fp, fp, fp, ctypes.c_size_t, vp]
     lib.sbx_atmosphere_eval.argtypes = [vp, ctypes.c_char_p, fp, fp, fp, ctypes.c_size_t, vp]
     lib.sbx_debug_atmosphere_eval.argtypes = [vp, ctypes.c_char_p, fp, fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
+    lib.sbx_clouds_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(AuxClouds), ctypes.c_float, fp, fp, ctypes.c_size_t, vp]
+    lib.sbx_debug_clouds_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(AuxClouds), ctypes.c_float, fp, fp, ctypes.c_size_t,
+                                          ctypes.POINTER(ctypes.c_uint64), vp]
     lib.sbx_worley_volume.argtypes = [vp, ci, fp, vp]
     lib.sbx_render_split_in_place.argtypes = [vp, ci, ctypes.POINTER(Uniforms), vp, ci, ci, ci, ci, ci, fp, vp]
     lib.sbx_multi_create.argtypes = [ci, ctypes.POINTER(ci), ctypes.POINTER(vp)]
@@ -1040,6 +1043,49 @@ class Renderer:
             self._check(self.lib.sbx_atmosphere_eval(*args, self._stream()))
         else:
             self._check(self.lib.sbx_debug_atmosphere_eval(*args, ctypes.byref(waves), self._stream()))
+        return out
+
+    # sbx_clouds_eval: floats per element in / out
+    CLOUDS_EVAL_WIDTHS = {"render": (6, 4), "render_clouds": (6, 4), "render_sky_color": (3, 3), "density_func": (3, 1),
+                          "illuminate_volume": (6, 1)}
+
+    def clouds_eval(self, fn, x, u_time=0.0, aux=None):
+        """APP_CLOUDS' volume and sky over the caller's elements (include/sbx.h sbx_clouds_eval): fn 'render' / 'render_clouds' over rays
+        x[n, 6] (origin xyz, direction xyz) -> [n, 4]; 'render_sky_color' over directions x[n, 3] -> [n, 3]; 'density_func' over points
+        x[n, 3] -> [n, 1]; 'illuminate_volume' over x[n, 6] (origin xyz, V xyz) -> [n, 1].  aux: an AuxClouds, a dict of the fields
+        that differ from the defaults, or None = the defaults.  u_time enters through the wind offset alone."""
+        return self._clouds_eval(fn, x, u_time, aux, None)
+
+    def clouds_eval_counted(self, fn, x, u_time=0.0, aux=None):
+        """include/sbx_test.h sbx_debug_clouds_eval: clouds_eval that waits -> (out, (noise cells whose hashes came from the context's
+        table, cells hashed in place))"""
+        counts = (ctypes.c_uint64 * 2)(0, 0)
+        return self._clouds_eval(fn, x, u_time, aux, counts), (int(counts[0]), int(counts[1]))
+
+    def _clouds_aux(self, aux):
+        if aux is None or isinstance(aux, AuxClouds):
+            return aux
+        a = clouds_defaults(self.lib)
+        for name, v in dict(aux).items():
+            if isinstance(getattr(a, name), ctypes.Array):
+                setattr(a, name, (ctypes.c_float * 3)(*[float(c) for c in v]))
+            else:
+                setattr(a, name, v)
+        return a
+
+    def _clouds_eval(self, fn, x, u_time, aux, counts):
+        if fn not in self.CLOUDS_EVAL_WIDTHS:
+            raise SbxError(SBX_ERR_ARG, "unknown clouds function %r" % (fn,))
+        win, wout = self.CLOUDS_EVAL_WIDTHS[fn]
+        x = x.to(self.tdev, self.torch.float32).contiguous().view(x.numel() // win, win)
+        a = self._clouds_aux(aux)
+        out = self.torch.empty((x.shape[0], wout), dtype=self.torch.float32, device=self.tdev)
+        args = (self.ctx, fn.encode(), None if a is None else ctypes.byref(a), float(u_time), ctypes.c_void_p(x.data_ptr()),
+                ctypes.c_void_p(out.data_ptr()), x.shape[0])
+        if counts is None:
+            self._check(self.lib.sbx_clouds_eval(*args, self._stream()))
+        else:
+            self._check(self.lib.sbx_debug_clouds_eval(*args, counts, self._stream()))
         return out
 
     def sdf_eval(self, scene, xyz):

@@ -13,6 +13,7 @@
 #include "sbx_device.h"
 #include "sbx_noise.h"
 #include "sbx_hashcache.h"
+#include "sbx_clouds.h"
 #include "sbx_exp4k_table.h"
 #include <cmath>
 #include <cstdlib>
@@ -138,33 +139,7 @@ namespace sbx {
 #define CL_EXP_REG(x) exp_tab_<false>((x), etab)
 #endif
 
-__device__ __forceinline__ float clouds_density(const FrameClouds& F, v3 pos_in) {
-    v3 pos = pos_in * F.nf;                                    // cld_noise_factor, :18,20,66 (.001 unless SKY_SPHERE)
-    float shape = fbm<4>(pos * 2.03f, 2.64f, .5f, .5f, [](v3 p) { return noise_iq(p); });   // :72
-    return shape * smoothstep_(F.cov, F.cov_hi, shape);        // :83-84 (per-lane cross-check kernel keeps the IEEE division)
-}
-
-__device__ __forceinline__ float hg_phase(float mu, float g) {  // volumetric.h:27-33, note (4 + PI)
-    return (1.f - g * g) / ((4.f + 3.14159265359f) * pow_(1.f + g * g - 2.f * g * mu, 1.5f));
-}
-
-// illuminate_volume :91-123.  `phase` = henyey_greenstein(clamp(dot(L,V),0,1)) depends only on
-// the pixel's ray, so the caller evaluates it once per pixel (same inputs, same bits).
-// BUILD (CLOUDS_* of sbx_frame.h): CLOUDS_LUMINANCE returns the march's transmittance itself (the `#if 0` of :118 on).
-template <int BUILD>
-__device__ __forceinline__ float clouds_illuminate(const FrameClouds& F, v3 origin, float phase) {
-    const v3 step = F.sun_dir * F.dt;
-    v3 pos = origin + step;
-    float transmittance = 1.f;
-    for (int i = 0; i < F.lsteps; ++i) {
-        float density = clouds_density(F, pos);
-        transmittance *= exp_(-density * F.sigma * F.dt);
-        pos = pos + step;
-    }
-    if (BUILD == CLOUDS_LUMINANCE) return transmittance;
-    return transmittance * F.sun_power * phase;
-}
-
+// (clouds_density, hg_phase and clouds_illuminate — the per-lane statement — are in sbx_clouds.h, shared with kern_clouds_eval.hip)
 // The height-lit build's luminance of main step i (the `#if 0` of :97 on): exp(height) / 2. with height = float(i) / float(cld_march_steps)
 // (:183), the math spec's exp_.  A frame constant per step: k_clouds_lumtab tabulates it, the per-lane kernel and the table-less
 // kernels evaluate it in place — the same operations on the same inputs.
@@ -379,18 +354,7 @@ __device__ __forceinline__ void hc_blend_xy(float4 lo, float4 hi, float fx, floa
 // the frame's index bound (clouds_index_bound) lies within the table's range, every coordinate of a marching lane is bounded by
 // it or is NaN (v_cvt_i32_f32 of NaN is 0), and the lanes that do not march are given the straight-up ray before the march
 // (k_clouds); the table has CLOUDS_HASHTAB_GUARD entries of slack at both ends on top.
-struct GTab { const float* tab; unsigned bias4; };        // bias4 = 4 * bias: the byte offset of lattice index 0
-typedef float gt_f2 __attribute__((ext_vector_type(2), aligned(4)));
-__device__ __forceinline__ unsigned gt_off(float n, unsigned bias4) { return ((unsigned)(int)n << 2) + bias4; }
-__device__ __forceinline__ H8 gt_load(const GTab& g, unsigned off) {
-    const char* p = reinterpret_cast<const char*>(g.tab) + (unsigned long long)off;     // uniform base + 32-bit lane offset + immediates
-    const gt_f2 a = *reinterpret_cast<const gt_f2*>(p), b = *reinterpret_cast<const gt_f2*>(p + 157 * 4);
-    const gt_f2 c = *reinterpret_cast<const gt_f2*>(p + 113 * 4), d = *reinterpret_cast<const gt_f2*>(p + 270 * 4);
-    H8 h;
-    h.lo = make_float4(a.x, a.y, b.x, b.y);              // the cache's corner order: +0, +1, +157, +158, +113, +114, +270, +271
-    h.hi = make_float4(c.x, c.y, d.x, d.y);
-    return h;
-}
+// (GTab, gt_off and gt_load are in sbx_clouds.h, shared with kern_clouds_eval.hip)
 __global__ void __launch_bounds__(256) k_clouds_hashtab(float* __restrict__ tab, int entries, int bias) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < entries) tab[i] = hash1((float)(i - bias));

@@ -228,6 +228,9 @@ Frame2d build_2d(const sbx_uniforms& U);
 
 // ---- sbx_ytab.hip
 int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rgba, hipStream_t s, bool capturing, int build = CLOUDS_DEFAULT);
+// the largest lattice-hash table the context holds, or a new one of CLOUDS_HASHTAB_MIN_RANGE, made ready for stream `s` by the rules of
+// clouds_hash_table — or none (tab == nullptr): inside a capture with no table the host has seen complete, or where the allocation failed
+sbx::CloudsHashTab clouds_hash_table_any(sbx_ctx* ctx, hipStream_t s, bool capturing);
 void release(YTables& Y);
 void release(HashTables& H);
 

@@ -221,6 +221,11 @@ void launch_worley_volume(int size, float* out, hipStream_t s);
 void launch_exp4k_eval(const float* a, float* out, size_t n, hipStream_t s);
 // sbx_atmosphere_eval (kern_atmosphere.hip): fn 0 get_incident_light / 1 get_sun_light; plain = the plain kernel for every wave
 void launch_atmosphere_eval(int fn, bool plain, const float* rays, const float* sun_dir, float* out, size_t n, unsigned* fast_waves, hipStream_t s);
+// sbx_clouds_eval (kern_clouds_eval.hip): fn 0 render / 1 render_clouds / 2 render_sky_color / 3 density_func / 4 illuminate_volume over F =
+// build_clouds of the caller's block; plain = the per-lane statement; ht = a hash table that is ready on `s`, or NULL; counts = NULL or two
+// zeroed 64-bit device words for the counting instantiation
+void launch_clouds_eval(int fn, const FrameClouds& F, bool plain, const CloudsHashTab* ht, const float* in, float* out, size_t n,
+                        unsigned long long* counts, hipStream_t s);
 int launch_math_eval(int fn, const float* a, const float* b, float* out, size_t n, hipStream_t s);
 void launch_cl_exp_eval(const float* a, float* out, size_t n, hipStream_t s, int form);   // exp_reg_ / exp_reg128_ forms (kern_clouds.hip)
 

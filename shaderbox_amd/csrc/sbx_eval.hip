@@ -116,6 +116,74 @@ int sbx_sdf_eval(sbx_ctx* ctx, const sbx_aux_sdf_scene* scene, const float* xyz,
     return launched(ctx, "sdf_eval launch");
 }
 
+// the checks sbx_clouds_eval and its test hook share: SBX_OK with fn_id and the block set, or the failure
+static int clouds_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, const float* in, const float* out, size_t n, int& fn_id,
+                            sbx_aux_clouds& AC) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!fn) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    static const char* names[] = {"render", "render_clouds", "render_sky_color", "density_func", "illuminate_volume"};
+    fn_id = -1;
+    for (int i = 0; i < 5; ++i) if (std::strcmp(fn, names[i]) == 0) fn_id = i;
+    if (fn_id < 0) return fail(ctx, SBX_ERR_ARG, "unknown clouds function");
+    AC = aux_clouds(aux);
+    if (AC.cld_march_steps < 0 || AC.illum_march_steps < 0) return fail(ctx, SBX_ERR_ARG, "negative march steps");
+    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 elements");
+    if (n == 0) return SBX_OK;
+    if (!in || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    return SBX_OK;
+}
+// the frame constants of the caller's block: build_clouds over u_time alone (its camera is not read by the kernel)
+static FrameClouds clouds_eval_frame(const sbx_aux_clouds& AC, float u_time) {
+    const sbx_uniforms U = {{1.f, 1.f}, {0.f, 0.f}, u_time, {0.f, 0.f, 0.f}};
+    return build_clouds(U, AC, false);
+}
+
+int sbx_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, float u_time, const float* in, float* out, size_t n,
+                    void* stream) {
+    int id = -1;
+    sbx_aux_clouds AC;
+    int rc = clouds_eval_args(ctx, fn, aux, in, out, n, id, AC);
+    if (rc != SBX_OK || n == 0) return rc;
+    if ((rc = use_device(ctx)) != SBX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const bool plain = ctx->variant == 1;
+    // the sky reads no hash; the plain form hashes in place.  No usable table (a capture before one was seen complete, a failed
+    // allocation): every cell in place, the same bits
+    CloudsHashTab ht;
+    if (!plain && id != 2) ht = clouds_hash_table_any(ctx, s, stream_is_capturing(s));
+    launch_clouds_eval(id, clouds_eval_frame(AC, u_time), plain, &ht, in, out, n, nullptr, s);
+    return launched(ctx, "clouds_eval launch");
+}
+
+int sbx_debug_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, float u_time, const float* in, float* out, size_t n,
+                          uint64_t counts_host[2], void* stream) {
+    int id = -1;
+    sbx_aux_clouds AC;
+    int rc = clouds_eval_args(ctx, fn, aux, in, out, n, id, AC);
+    if (rc != SBX_OK) return rc;
+    if (!counts_host) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    counts_host[0] = counts_host[1] = 0;
+    if (n == 0) return SBX_OK;
+    if ((rc = use_device(ctx)) != SBX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_is_capturing(s)) return fail(ctx, SBX_ERR_ARG, "the counted launch is not capturable");
+    const bool plain = ctx->variant == 1;
+    unsigned long long* counts = nullptr;
+    hipError_t e = hipMalloc((void**)&counts, 2 * sizeof(unsigned long long));
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
+    if ((e = hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), s)) == hipSuccess) {
+        CloudsHashTab ht;
+        if (!plain && id != 2) ht = clouds_hash_table_any(ctx, s, false);
+        launch_clouds_eval(id, clouds_eval_frame(AC, u_time), plain, &ht, in, out, n, counts, s);
+        unsigned long long h[2] = {0, 0};
+        if ((e = hipGetLastError()) == hipSuccess && (e = hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, s)) == hipSuccess)
+            e = hipStreamSynchronize(s);
+        counts_host[0] = h[0]; counts_host[1] = h[1];
+    }
+    (void)hipFree(counts);
+    return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "clouds_eval (counted)", e);
+}
+
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream) {
     if (!ctx) return SBX_ERR_ARG;
     if (!rgba || size <= 0 || size > 1024) return fail(ctx, SBX_ERR_ARG, "bad volume arguments");

@@ -23,13 +23,14 @@ namespace sbx {
 //   the allocation or the event failed (the error is dropped: the cache kernels render the same frame).
 // A new table is built on `s` in front of the launch.  A table never changes, so its only ordering is "built before read": until the
 // host has once seen `ready` complete (hipEventQuery), every launch waits for it on its own stream.
-static CloudsHashTab clouds_hash_table(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, hipStream_t s, bool capturing, int build) {
+// (the form that takes the wanted range: `need` > 0; largest: the context's largest table whatever its range, a new one of `need` only
+//  where it holds none — sbx_clouds_eval, whose lanes test every index against the table's range themselves)
+static CloudsHashTab clouds_hash_table_range(sbx_ctx* ctx, int need, bool largest, hipStream_t s, bool capturing) {
     CloudsHashTab none;
-    const int need = clouds_hashtab_range(F, M, build);
-    if (need <= 0) return none;
     HashTables& H = ctx->hashtab;
     HashTables::Tab* t = nullptr;
-    for (auto& c : H.tabs) if (c.range >= need) { t = &c; break; }       // ascending: the smallest that covers
+    if (largest) { if (!H.tabs.empty()) t = &H.tabs.back(); }
+    else for (auto& c : H.tabs) if (c.range >= need) { t = &c; break; }       // ascending: the smallest that covers
     if (t && !t->seen_complete) {
         if (capturing) return none;
         if (hipEventQuery(t->ready) == hipSuccess) t->seen_complete = true;
@@ -58,6 +59,14 @@ static CloudsHashTab clouds_hash_table(sbx_ctx* ctx, const FrameClouds& F, const
     CloudsHashTab r;
     r.tab = t->dev; r.entries = t->entries; r.bias = t->bias; r.range = t->range;
     return r;
+}
+static CloudsHashTab clouds_hash_table(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, hipStream_t s, bool capturing, int build) {
+    const int need = clouds_hashtab_range(F, M, build);
+    if (need <= 0) return CloudsHashTab();
+    return clouds_hash_table_range(ctx, need, false, s, capturing);
+}
+CloudsHashTab clouds_hash_table_any(sbx_ctx* ctx, hipStream_t s, bool capturing) {
+    return clouds_hash_table_range(ctx, CLOUDS_HASHTAB_MIN_RANGE, true, s, capturing);
 }
 
 int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rgba, hipStream_t s, bool capturing, int build) {

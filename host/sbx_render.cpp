@@ -13,6 +13,12 @@
 //              "render" (include/sbx.h) with the APP_CLOUDS aux flags and --time / --frames / --dt.  Pixel (x, y) looks along
 //              (cos e sin a, sin e, -cos e cos a) with a = 2 pi (x + .5) / W and e = (pi / 2) (y + .5) / H, evaluated in binary64 and
 //              rounded.  The frame holds what the entry returns: LINEAR rgb and the clouds' alpha.  One GPU, float pixels.
+//     --planet-view W H EX EY EZ LX LY LZ [--fov DEG]: instead of an app's frame, APP_PLANET seen from the caller's camera: the primary
+//              rays of main.h's pipeline (main.h:33-46, util.h:5-20) for a W x H frame with eye (EX, EY, EZ), look_at (LX, LY, LZ) and
+//              FOV = tan(radians(DEG)) (default 30, app_planet.h:369) are computed here, in binary32 in the reference's order of
+//              operations (the tangent: libm's tan of the binary32 angle, evaluated in binary64 and rounded), and go through
+//              sbx_planet_eval "render" (include/sbx.h) with --time / --frames / --dt.  The frame holds what the entry returns:
+//              LINEAR rgb and the cloud shell's alpha.  One GPU, float pixels.
 //     APP_SDF_AO aux block (:484-487):  [--fog-density D] [--fog-falloff F]
 //     app "sdf_ao_shadow" / "sdf_ao_normals": src/app_sdf_ao.h with its `#if 0` at :269 (soft shadows) / :217 (normals view) on; same fog flags
 //     app "egg_straight" / "egg_oval": src/app_egg.h without its `#define BEZIER` (:37, cylinder legs) / with its `#if 1` at :46 off (one scaled sphere)
@@ -120,8 +126,9 @@ int main(int argc, char** argv) {
     sbx_aux_sdf_ao as;
     sbx_aux_clouds_defaults(&ac);
     sbx_aux_sdf_ao_defaults(&as);
-    bool have_ac = false, have_as = false, rgba8_out = false, panorama = false;
+    bool have_ac = false, have_as = false, rgba8_out = false, panorama = false, planet_view = false;
     float eye[3] = {0.f, -.5f, 0.f};
+    float pv_eye[3] = {0.f, 0.f, -2.5f}, pv_look[3] = {0.f, 0.f, 2.f}, pv_fov_deg = 30.f;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -145,6 +152,13 @@ int main(int argc, char** argv) {
         else if (a == "--scene-bin") scene_bin = next();
         else if (a == "--clouds-panorama") { W = atoi(next()); H = atoi(next()); panorama = true; }
         else if (a == "--eye") { for (float& v : eye) v = (float)atof(next()); }
+        else if (a == "--planet-view") {
+            W = atoi(next()); H = atoi(next());
+            for (float& v : pv_eye) v = (float)atof(next());
+            for (float& v : pv_look) v = (float)atof(next());
+            planet_view = true;
+        }
+        else if (a == "--fov") pv_fov_deg = (float)atof(next());
         else if (a == "--wind") { vec3(ac.wind_dir); have_ac = true; }
         else if (a == "--sun") { vec3(ac.sun_dir); have_ac = true; }
         else if (a == "--sun-color") { vec3(ac.sun_color); have_ac = true; }
@@ -166,6 +180,8 @@ int main(int argc, char** argv) {
     if (rgba8_out && !f32.empty()) { fprintf(stderr, "--rgba8 renders 8-bit pixels: there is no float frame for --f32\n"); return 2; }
     if (panorama && (W < 1 || H < 1)) { fprintf(stderr, "--clouds-panorama W H\n"); return 2; }
     if (panorama && (gpus > 1 || rgba8_out)) { fprintf(stderr, "--clouds-panorama renders float pixels on one GPU\n"); return 2; }
+    if (planet_view && (W < 1 || H < 1 || panorama)) { fprintf(stderr, "--planet-view W H EX EY EZ LX LY LZ (not with --clouds-panorama)\n"); return 2; }
+    if (planet_view && (gpus > 1 || rgba8_out)) { fprintf(stderr, "--planet-view renders float pixels on one GPU\n"); return 2; }
     for (const std::string* p : {&ppm, &f32})
         if (!pattern_ok(*p)) { fprintf(stderr, "bad file pattern %s: one %%d / %%0Nd conversion at most, a literal percent as %%%%\n", p->c_str()); return 2; }
     const void* aux = nullptr;
@@ -254,6 +270,29 @@ int main(int argc, char** argv) {
         if (hipMalloc((void**)&rays, hr.size() * sizeof(float)) != hipSuccess ||
             hipMemcpy(rays, hr.data(), hr.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "hipMalloc failed\n"); return 1; }
     }
+    if (planet_view) {
+        // main.h:33-46 and util.h:5-20 in binary32, operation by operation (dot = (x x + y y) + z z, normalize = three divisions by the root)
+        struct V { float x, y, z; };
+        auto dot3 = [](V a, V b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; };
+        auto norm3 = [&](V v) { const float l = sqrtf(dot3(v, v)); return V{v.x / l, v.y / l, v.z / l}; };
+        auto cross3 = [](V a, V b) { return V{a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; };
+        const float fov = (float)tan((double)(pv_fov_deg * 0.017453292519943295f));
+        const float fw = (float)W, fh = (float)H, aspect = fw / fh;
+        const V fwd = norm3(V{pv_look[0] - pv_eye[0], pv_look[1] - pv_eye[1], pv_look[2] - pv_eye[2]});
+        const V right = cross3(V{0.f, 1.f, 0.f}, fwd), up = cross3(fwd, right);
+        std::vector<float> hr(npx * 6);
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x) {
+                const float fx = (float)x + .5f, fy = (float)y + .5f;
+                const float pcx = ((2.f * (fx / fw) - 1.f) * aspect) * fov, pcy = ((2.f * (fy / fh) - 1.f) * 1.f) * fov;
+                const V d = norm3(V{(fwd.x + up.x * pcy) + right.x * pcx, (fwd.y + up.y * pcy) + right.y * pcx, (fwd.z + up.z * pcy) + right.z * pcx});
+                float* r = &hr[((size_t)y * W + x) * 6];
+                r[0] = pv_eye[0]; r[1] = pv_eye[1]; r[2] = pv_eye[2];
+                r[3] = d.x; r[4] = d.y; r[5] = d.z;
+            }
+        if (hipMalloc((void**)&rays, hr.size() * sizeof(float)) != hipSuccess ||
+            hipMemcpy(rays, hr.data(), hr.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "hipMalloc failed\n"); return 1; }
+    }
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     for (int f = 0; f < frames; ++f) {
@@ -261,13 +300,14 @@ int main(int argc, char** argv) {
         u.u_res[0] = (float)W; u.u_res[1] = (float)H; u.u_mouse[0] = mx; u.u_mouse[1] = my; u.u_time = t + f * dt;   // hlsltoy.cpp:502-504
         (void)hipEventRecord(e0, nullptr);
         if (panorama) rc = sbx_clouds_eval(ctx, "render", have_ac ? &ac : nullptr, u.u_time, rays, dev, npx, nullptr);
+        else if (planet_view) rc = sbx_planet_eval(ctx, "render", u.u_time, rays, dev, npx, nullptr);
         else rc = multi ? sbx_multi_render(multi, id, &u, aux, dev, nullptr) : sbx_render_rows(ctx, id, &u, aux, 0, H, dev, nullptr);
         if (rc != SBX_OK) { fprintf(stderr, "render: %s\n", multi ? sbx_multi_last_error(multi) : sbx_last_error(ctx)); return 1; }
         (void)hipEventRecord(e1, nullptr);
         (void)hipEventSynchronize(e1);
         float ms = 0;
         (void)hipEventElapsedTime(&ms, e0, e1);
-        printf("frame %d  u_time %.4f  %s %dx%d  %.3f ms  %.1f Mpix/s\n", f, u.u_time, panorama ? "clouds panorama" : app.c_str(), W, H, ms, W * (double)H / ms / 1e3);
+        printf("frame %d  u_time %.4f  %s %dx%d  %.3f ms  %.1f Mpix/s\n", f, u.u_time, panorama ? "clouds panorama" : planet_view ? "planet view" : app.c_str(), W, H, ms, W * (double)H / ms / 1e3);
         if (!f32.empty()) {
             if (hipMemcpy(host.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
             FILE* fp = fopen(frame_name(f32, f, frames).c_str(), "wb");

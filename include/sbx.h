@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell, SBX_APP_SDF_SCENE with sbx_aux_sdf_scene, sbx_sdf_scene_ramp and sbx_sdf_eval, sbx_clouds_eval: new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell, SBX_APP_SDF_SCENE with sbx_aux_sdf_scene, sbx_sdf_scene_ramp and sbx_sdf_eval, sbx_clouds_eval, sbx_planet_eval: new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -707,6 +707,28 @@ int sbx_sdf_eval(sbx_ctx* ctx, const sbx_aux_sdf_scene* scene, const float* xyz,
  * returns SBX_OK and touches nothing; SBX_ERR_ARG for a NULL ctx / fn / in / out, an unknown name, n > 2^31. */
 int sbx_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, float u_time, const float* in, float* out, size_t n,
                     void* stream);
+/* The planet's terrain, cloud shell and shading (src/app_planet.h as shipped: CLOUDS and LIGHT defined) as standalone functions over n
+ * elements of the caller's: what the reference reaches only through pixels of setup_camera's two views — an orbiting or landing
+ * camera, a cube map of the planet, an equirectangular albedo / height bake, a collision query against the terrain.  There is no
+ * camera, no u_res and no u_mouse.  `in`, `out`: device memory, not overlapping, 4-byte alignment suffices.  Per element:
+ *   "render" (:303-367)                 in 6: ray origin xyz, direction xyz, in the space of `eye` (planet at 0, radius 1).  out 4: the
+ *                                       linear RGB render returns (no sRGB), then cloud.alpha as read at :352 / :365 — 0 where :320
+ *                                       returned the background.
+ *   "terrain_march" (:311-342)          in 6: as above.  out 4: hit.t after intersect_sphere (no_hit's t where it missed), then t,
+ *                                       df.x, df.y as they stand at :344 — the initialisers of :323-324 where :320 returned.
+ *   "sdf_terrain_map" (:175-186)        in 3: pos (planet-local, i.e. after `rot`).  out 2.
+ *   "sdf_terrain_map_detail" (:188-199) in 3: pos.  out 2.
+ *   "sdf_terrain_normal" (:201-212)     in 3: p.  out 3.
+ *   "clouds_density" (:106-114)         in 4: cloud.pos xyz, cloud.height.  out 1: `dens` as handed to integrate_volume.
+ *   "illuminate" (:238-298)             in 4: pos xyz, df.y.  out 3.  local_xform is `rot` of u_time; `eye` is not read.
+ *   "background" (:23-41)               in 3: eye.direction.  out 3.
+ * u_time is read by "render", "terrain_march" and "illuminate" only, through rot / rot_cloud (:307-309).  Directions are used as given,
+ * never normalised.  Every bit pattern is data — a zero, NaN or inf component, an origin inside the shell or inside the planet, the
+ * exact centre where normalize(pos) is 0/0: the result is whatever the reference's arithmetic gives, NaN results included.
+ * Asynchronous on `stream` and capturable (inside a capture it allocates nothing, queries nothing and waits for nothing); not counted
+ * in sbx_stats.render_launches; sbx_set_precision does not enter; sbx_set_variant 1 selects the plain statement (same bits).  n == 0
+ * returns SBX_OK and touches nothing; SBX_ERR_ARG, with nothing written, for a NULL ctx / fn / in / out, an unknown name, n > 2^31. */
+int sbx_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const float* in, float* out, size_t n, void* stream);
 /* The size^3 RGBA32F noise volume util/ddsvolgen bakes (ddsvolgen.cpp:101-117): R =
  * fbm_worley_tile((xyz + .5)/size, 2, 1, .5), G = B = A = 0, x fastest.  `rgba`: size^3 * 4 floats. */
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream);

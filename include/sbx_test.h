@@ -37,6 +37,9 @@ extern "C" {
  * sqrt_n_, division by the exact reciprocal); 0 runs it only on the waves whose rays are outside the class of csrc/sbx_atmosphere.h.
  * sbx_clouds_eval: 1 = the statement of k_clouds_perlane lane by lane (hash1 in place, exp_, pow_, the IEEE division in the coverage
  * smoothstep); 0 takes the lattice hashes from the context's table and the guard-less forms the aux block admits.
+ * sbx_planet_eval: 1 = the SKIP = false statement of k_planet lane by lane for every wave (every fBm octave and cloud sample evaluated,
+ * the IEEE roots and divisions, exp_, lattice indices as the reference forms them); 0 runs it only on the waves whose own operands fail
+ * a guard of csrc/kern_planet_eval.hip, and for any u_time beyond 1e8 in magnitude or NaN.
  * All variants are specified to produce identical bits (tests/test_gpu_parity.py sweeps them against each other). */
 int sbx_set_variant(sbx_ctx* ctx, int variant);
 
@@ -54,6 +57,13 @@ int sbx_debug_atmosphere_eval(sbx_ctx* ctx, const char* fn, const float* rays, c
  * capturable.  For tests/test_gpu_clouds_eval.py and tools/time_clouds_eval.py. */
 int sbx_debug_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, float u_time, const float* in, float* out, size_t n,
                           uint64_t counts_host[2], void* stream);
+
+/* sbx_planet_eval (sbx.h) with counts: the same launch (the context's variant included) followed by a wait, after which counts_host[0]
+ * holds the waves that ran with every guarded short form on and counts_host[1] the waves that took the plain form for at least one
+ * part (all of them under variant 1 or an untame u_time).  It allocates and synchronises, so it is not capturable.  For
+ * tests/test_gpu_planet_eval.py and tools/time_planet_eval.py. */
+int sbx_debug_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const float* in, float* out, size_t n, unsigned counts_host[2],
+                          void* stream);
 
 /* Device evaluation of the math spec, elementwise over device arrays (for parity tests):
  * fn in {"sin","cos","tan","exp","pow","acos","atan2","hash","div","div_rd","exp_h13","pow_h","sqrt_n","sqrt_ieee","exp_reg","exp_reg_plain","exp_reg64","exp_reg64_plain","exp_small","exp_small_plain","exp_reg4k","sin_b40","div3","sqrt_rs","divn","srgb_pow","pow_spec"}; b may be NULL

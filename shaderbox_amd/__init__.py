@@ -390,6 +390,8 @@ def load_library(path=None):
     lib.sbx_clouds_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(AuxClouds), ctypes.c_float, fp, fp, ctypes.c_size_t, vp]
     lib.sbx_debug_clouds_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(AuxClouds), ctypes.c_float, fp, fp, ctypes.c_size_t,
                                           ctypes.POINTER(ctypes.c_uint64), vp]
+    lib.sbx_planet_eval.argtypes = [vp, ctypes.c_char_p, ctypes.c_float, fp, fp, ctypes.c_size_t, vp]
+    lib.sbx_debug_planet_eval.argtypes = [vp, ctypes.c_char_p, ctypes.c_float, fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
     lib.sbx_worley_volume.argtypes = [vp, ci, fp, vp]
     lib.sbx_render_split_in_place.argtypes = [vp, ci, ctypes.POINTER(Uniforms), vp, ci, ci, ci, ci, ci, fp, vp]
     lib.sbx_multi_create.argtypes = [ci, ctypes.POINTER(ci), ctypes.POINTER(vp)]
@@ -1086,6 +1088,37 @@ class Renderer:
             self._check(self.lib.sbx_clouds_eval(*args, self._stream()))
         else:
             self._check(self.lib.sbx_debug_clouds_eval(*args, counts, self._stream()))
+        return out
+
+    # sbx_planet_eval: floats per element in / out
+    PLANET_EVAL_WIDTHS = {"render": (6, 4), "terrain_march": (6, 4), "sdf_terrain_map": (3, 2), "sdf_terrain_map_detail": (3, 2),
+                          "sdf_terrain_normal": (3, 3), "clouds_density": (4, 1), "illuminate": (4, 3), "background": (3, 3)}
+
+    def planet_eval(self, fn, x, u_time=0.0):
+        """APP_PLANET's terrain, cloud shell and shading over the caller's elements (include/sbx.h sbx_planet_eval): fn 'render' /
+        'terrain_march' over rays x[n, 6] (origin xyz, direction xyz; planet at 0, radius 1) -> [n, 4]; 'sdf_terrain_map' /
+        'sdf_terrain_map_detail' over points x[n, 3] -> [n, 2]; 'sdf_terrain_normal' x[n, 3] -> [n, 3]; 'clouds_density' over x[n, 4]
+        (cloud.pos xyz, cloud.height) -> [n, 1]; 'illuminate' over x[n, 4] (pos xyz, df.y) -> [n, 3]; 'background' over directions
+        x[n, 3] -> [n, 3].  u_time enters through rot / rot_cloud alone."""
+        return self._planet_eval(fn, x, u_time, None)
+
+    def planet_eval_counted(self, fn, x, u_time=0.0):
+        """include/sbx_test.h sbx_debug_planet_eval: planet_eval that waits -> (out, (waves with every guarded short form on, waves
+        that took the plain form for at least one part))"""
+        counts = (ctypes.c_uint * 2)(0, 0)
+        return self._planet_eval(fn, x, u_time, counts), (int(counts[0]), int(counts[1]))
+
+    def _planet_eval(self, fn, x, u_time, counts):
+        if fn not in self.PLANET_EVAL_WIDTHS:
+            raise SbxError(SBX_ERR_ARG, "unknown planet function %r" % (fn,))
+        win, wout = self.PLANET_EVAL_WIDTHS[fn]
+        x = x.to(self.tdev, self.torch.float32).contiguous().view(x.numel() // win, win)
+        out = self.torch.empty((x.shape[0], wout), dtype=self.torch.float32, device=self.tdev)
+        args = (self.ctx, fn.encode(), float(u_time), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), x.shape[0])
+        if counts is None:
+            self._check(self.lib.sbx_planet_eval(*args, self._stream()))
+        else:
+            self._check(self.lib.sbx_debug_planet_eval(*args, counts, self._stream()))
         return out
 
     def sdf_eval(self, scene, xyz):

@@ -29,7 +29,8 @@ static int bind_fault_word(int device) {
     }
     unsigned* dev = nullptr;
     if (hipHostGetDevicePointer((void**)&dev, g_fault_word[device], 0) != hipSuccess) return SBX_ERR_HIP;
-    if (bind_fault_clouds(dev) != hipSuccess || bind_fault_clouds_ue4(dev) != hipSuccess || bind_fault_planet(dev) != hipSuccess)
+    if (bind_fault_clouds(dev) != hipSuccess || bind_fault_clouds_ue4(dev) != hipSuccess || bind_fault_planet(dev) != hipSuccess ||
+        bind_fault_planet_eval(dev) != hipSuccess)
         return SBX_ERR_HIP;
     return SBX_OK;
 }

@@ -195,6 +195,7 @@ void launch_assemble_peers(int width, int height, int block_rows, int nranks, in
 hipError_t bind_fault_clouds(unsigned* word);
 hipError_t bind_fault_clouds_ue4(unsigned* word);
 hipError_t bind_fault_planet(unsigned* word);
+hipError_t bind_fault_planet_eval(unsigned* word);
 void launch_raise_fault(unsigned code, hipStream_t s);
 void launch_assemble_spans(int width, int height, int block_rows, const int4* span, const float* peers, size_t stride_pixels,
                            float* frame, hipStream_t s, bool rgba8);
@@ -226,6 +227,10 @@ void launch_atmosphere_eval(int fn, bool plain, const float* rays, const float* 
 // zeroed 64-bit device words for the counting instantiation
 void launch_clouds_eval(int fn, const FrameClouds& F, bool plain, const CloudsHashTab* ht, const float* in, float* out, size_t n,
                         unsigned long long* counts, hipStream_t s);
+// sbx_planet_eval (kern_planet_eval.hip): fn 0 render / 1 terrain_march / 2 sdf_terrain_map / 3 sdf_terrain_map_detail / 4 sdf_terrain_normal /
+// 5 clouds_density / 6 illuminate / 7 background over F = build_planet of u_time (its camera is not read); plain = the SKIP = false
+// statement for every wave; counts = NULL or two zeroed device words (waves with every guarded short form on, waves that fell back)
+void launch_planet_eval(int fn, const FramePlanet& F, bool plain, const float* in, float* out, size_t n, unsigned* counts, hipStream_t s);
 int launch_math_eval(int fn, const float* a, const float* b, float* out, size_t n, hipStream_t s);
 void launch_cl_exp_eval(const float* a, float* out, size_t n, hipStream_t s, int form);   // exp_reg_ / exp_reg128_ forms (kern_clouds.hip)
 

@@ -184,6 +184,62 @@ int sbx_debug_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* au
     return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "clouds_eval (counted)", e);
 }
 
+// the checks sbx_planet_eval and its test hook share: SBX_OK with fn_id set, or the failure
+static int planet_eval_args(sbx_ctx* ctx, const char* fn, const float* in, const float* out, size_t n, int& fn_id) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!fn) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    static const char* names[] = {"render", "terrain_march", "sdf_terrain_map", "sdf_terrain_map_detail", "sdf_terrain_normal",
+                                  "clouds_density", "illuminate", "background"};
+    fn_id = -1;
+    for (int i = 0; i < 8; ++i) if (std::strcmp(fn, names[i]) == 0) fn_id = i;
+    if (fn_id < 0) return fail(ctx, SBX_ERR_ARG, "unknown planet function");
+    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 elements");
+    if (n == 0) return SBX_OK;
+    if (!in || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    return SBX_OK;
+}
+// the frame constants: build_planet over u_time alone (its camera is not read by the kernel)
+static FramePlanet planet_eval_frame(float u_time) {
+    const sbx_uniforms U = {{1.f, 1.f}, {0.f, 0.f}, u_time, {0.f, 0.f, 0.f}};
+    return build_planet(U);
+}
+// the guarded short forms assume rotations of a finite, bounded angle (sbx_capi.hip tame_time, the same bound): beyond it the plain form
+static bool planet_eval_plain(const sbx_ctx* ctx, float u_time) { return ctx->variant == 1 || !(std::fabs(u_time) <= 1e8f); }
+
+int sbx_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const float* in, float* out, size_t n, void* stream) {
+    int id = -1;
+    int rc = planet_eval_args(ctx, fn, in, out, n, id);
+    if (rc != SBX_OK || n == 0) return rc;
+    if ((rc = use_device(ctx)) != SBX_OK) return rc;
+    launch_planet_eval(id, planet_eval_frame(u_time), planet_eval_plain(ctx, u_time), in, out, n, nullptr, (hipStream_t)stream);
+    return launched(ctx, "planet_eval launch");
+}
+
+int sbx_debug_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const float* in, float* out, size_t n, unsigned counts_host[2],
+                          void* stream) {
+    int id = -1;
+    int rc = planet_eval_args(ctx, fn, in, out, n, id);
+    if (rc != SBX_OK) return rc;
+    if (!counts_host) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    counts_host[0] = counts_host[1] = 0;
+    if (n == 0) return SBX_OK;
+    if ((rc = use_device(ctx)) != SBX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_is_capturing(s)) return fail(ctx, SBX_ERR_ARG, "the counted launch is not capturable");
+    unsigned* counts = nullptr;
+    hipError_t e = hipMalloc((void**)&counts, 2 * sizeof(unsigned));
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
+    if ((e = hipMemsetAsync(counts, 0, 2 * sizeof(unsigned), s)) == hipSuccess) {
+        launch_planet_eval(id, planet_eval_frame(u_time), planet_eval_plain(ctx, u_time), in, out, n, counts, s);
+        unsigned h[2] = {0, 0};
+        if ((e = hipGetLastError()) == hipSuccess && (e = hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, s)) == hipSuccess)
+            e = hipStreamSynchronize(s);
+        counts_host[0] = h[0]; counts_host[1] = h[1];
+    }
+    (void)hipFree(counts);
+    return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "planet_eval (counted)", e);
+}
+
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream) {
     if (!ctx) return SBX_ERR_ARG;
     if (!rgba || size <= 0 || size > 1024) return fail(ctx, SBX_ERR_ARG, "bad volume arguments");

@@ -27,7 +27,7 @@ CLOUDS_VARIANTS = [("CL_PARK", 0), ("CL_LIPSKIP", 0), ("CL_LIPSKIP2", 0), ("CL_E
                    ("CL_PRESCALE", 0), ("CL_GTAB", 0), ("CL_GTAB_OCT", 0), ("CL_GTAB_OCT", 3)]
 
 
-# kern_planet.hip / sbx_hashcache.h as k_planet uses it.  Not listed: PL_MIN_WAVES, PL_TW, PL_BATCH* (shapes and sizes).
+# kern_planet.hip / sbx_planet.h / sbx_hashcache.h as k_planet uses it.  Not listed: PL_MIN_WAVES, PL_TW, PL_BATCH* (shapes and sizes).
 PLANET_VARIANTS = [("PL_ATM_FIN", 0), ("PL_PAIRS", 0), ("PL_SPEC", 0), ("PL_TB2", 0), ("SBX_HC_MAGIC_SLOT", 0), ("PL_DIV3", 0), ("PL_MED3", 0), ("PL_EXP4K", 0),
                    ("PL_SQRT_RS", 0), ("PL_SQRT_N", 0), ("PL_PARK", 0), ("PL_TLAST", 0), ("PL_ROLL_DETAIL", 0)]
 
@@ -70,7 +70,7 @@ def main():
             if v is None:
                 continue
             specs.append("v_%s_%s:kern_clouds.hip:-D%s=%s" % (k.lower(), v, k, v))
-        psrc = open(os.path.join(b.CSRC, "kern_planet.hip")).read() + open(os.path.join(b.CSRC, "sbx_hashcache.h")).read()
+        psrc = "".join(open(os.path.join(b.CSRC, f)).read() for f in ("kern_planet.hip", "sbx_planet.h", "sbx_hashcache.h"))
         for k, v in PLANET_VARIANTS:
             if ("#ifndef %s\n" % k) not in psrc and ("#ifndef %s " % k) not in psrc:
                 print("(switch %s no longer exists)" % k)

@@ -19,6 +19,12 @@
 //              operations (the tangent: libm's tan of the binary32 angle, evaluated in binary64 and rounded), and go through
 //              sbx_planet_eval "render" (include/sbx.h) with --time / --frames / --dt.  The frame holds what the entry returns:
 //              LINEAR rgb and the cloud shell's alpha.  One GPU, float pixels.
+//     --egg-view W H EX EY EZ LX LY LZ [--fov F]: instead of an app's frame, APP_EGG seen from the caller's camera: the primary rays of
+//              main.h's pipeline for a W x H frame with eye (EX, EY, EZ), look_at (LX, LY, LZ) and the FOV factor F (default 1,
+//              app_egg.h:253), computed here as for --planet-view, go through sbx_egg_eval "render_scene" (include/sbx.h) under the pose
+//              of --time and the pose flags below; then render's bars and abs (app_egg.h:233-251) in binary32 on the host and
+//              linear_to_srgb by the library's own form of it (sbx_math_eval "srgb_pow", include/sbx_test.h): the frame
+//              SBX_APP_EGG_POSE renders with that camera in its block.  One GPU, float pixels.
 //     APP_SDF_AO aux block (:484-487):  [--fog-density D] [--fog-falloff F]
 //     app "sdf_ao_shadow" / "sdf_ao_normals": src/app_sdf_ao.h with its `#if 0` at :269 (soft shadows) / :217 (normals view) on; same fog flags
 //     app "egg_straight" / "egg_oval": src/app_egg.h without its `#define BEZIER` (:37, cylinder legs) / with its `#if 1` at :46 off (one scaled sphere)
@@ -36,6 +42,10 @@
 //     app "sdf_scene": src/app_sdf_ao.h's renderer over the caller's field (SBX_APP_SDF_SCENE, include/sbx.h):
 //              --scene-bin FILE   the raw 2784 bytes of an sbx_aux_sdf_scene (any other size is refused); without it the ramp block
 //              of --time (sbx_sdf_scene_ramp)
+//     app "egg_pose": src/app_egg.h as shipped with the rider posed by the caller (SBX_APP_EGG_POSE, include/sbx.h).  The block starts as
+//              the pose of --time (sbx_egg_pose_default) and every flag replaces one field of sbx_aux_egg_pose:
+//              [--pose-eye x,y,z] [--pose-look-at x,y,z] [--pose-fov F] [--turn DEG] [--left-foot x,y,z] [--right-foot x,y,z]
+//              [--femur L] [--tibia L]
 //     app "2d" / "2d_tex": src/app_2d.h (its alpha is not 1: the .f32 frames carry it; single GPU only), the USE_TEXTURE build
 //              reading hlsltoy's default 128x128 checkerboard at t0
 //     app "func": src/app_func.h, the tiled Worley fBm of its compiled 2D branch (grey, alpha 1; u_time and --mouse do not enter)
@@ -59,13 +69,14 @@
 #include <vector>
 
 #include "../include/sbx.h"
+#include "../include/sbx_test.h"      // sbx_math_eval "srgb_pow": --egg-view's linear_to_srgb
 
 static int app_from_name(const std::string& s) {
     const char* names[] = {"planet", "clouds", "vinyl", "egg", "raytracer", "atmosphere", "sdf_ao", "clouds_best", "clouds_tex", "clouds_ue4",
                            "clouds_sky", "vinyl_gpu", "planet_atmosphere", "2d", "2d_tex", "func", "atmosphere_ground", "sdf_ao_shadow", "sdf_ao_normals",
                            "egg_straight", "egg_oval", "clouds_height", "clouds_luminance", "raytracer_phong", "raytracer_noshadow", "raytracer_static",
-                           "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow", "planet_closeup", "planet_cloudless", "planet_unlit", "raytracer_scene", "sdf_scene"};
-    const int n = 34;
+                           "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow", "planet_closeup", "planet_cloudless", "planet_unlit", "raytracer_scene", "sdf_scene", "egg_pose"};
+    const int n = 35;
     std::string low;
     for (char c : s) low += (char)tolower(c);
     for (int i = 0; i < n; ++i)
@@ -128,7 +139,10 @@ int main(int argc, char** argv) {
     sbx_aux_sdf_ao_defaults(&as);
     bool have_ac = false, have_as = false, rgba8_out = false, panorama = false, planet_view = false;
     float eye[3] = {0.f, -.5f, 0.f};
-    float pv_eye[3] = {0.f, 0.f, -2.5f}, pv_look[3] = {0.f, 0.f, 2.f}, pv_fov_deg = 30.f;
+    float pv_eye[3] = {0.f, 0.f, -2.5f}, pv_look[3] = {0.f, 0.f, 2.f}, pv_fov = 0.f;      // --fov: degrees for --planet-view (30), the factor for --egg-view (1)
+    bool egg_view = false, have_fov = false;
+    sbx_aux_egg_pose pose_arg{};                     // the fields the pose flags gave, and which
+    bool pose_has[8] = {false, false, false, false, false, false, false, false};      // eye, fov, look_at, turn, left foot, femur, right foot, tibia
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -158,7 +172,21 @@ int main(int argc, char** argv) {
             for (float& v : pv_look) v = (float)atof(next());
             planet_view = true;
         }
-        else if (a == "--fov") pv_fov_deg = (float)atof(next());
+        else if (a == "--egg-view") {
+            W = atoi(next()); H = atoi(next());
+            for (float& v : pv_eye) v = (float)atof(next());
+            for (float& v : pv_look) v = (float)atof(next());
+            egg_view = true;
+        }
+        else if (a == "--fov") { pv_fov = (float)atof(next()); have_fov = true; }
+        else if (a == "--pose-eye") { vec3(pose_arg.eye); pose_has[0] = true; }
+        else if (a == "--pose-fov") { pose_arg.fov = (float)atof(next()); pose_has[1] = true; }
+        else if (a == "--pose-look-at") { vec3(pose_arg.look_at); pose_has[2] = true; }
+        else if (a == "--turn") { pose_arg.turn_deg = (float)atof(next()); pose_has[3] = true; }
+        else if (a == "--left-foot") { vec3(pose_arg.left_foot); pose_has[4] = true; }
+        else if (a == "--femur") { pose_arg.femur = (float)atof(next()); pose_has[5] = true; }
+        else if (a == "--right-foot") { vec3(pose_arg.right_foot); pose_has[6] = true; }
+        else if (a == "--tibia") { pose_arg.tibia = (float)atof(next()); pose_has[7] = true; }
         else if (a == "--wind") { vec3(ac.wind_dir); have_ac = true; }
         else if (a == "--sun") { vec3(ac.sun_dir); have_ac = true; }
         else if (a == "--sun-color") { vec3(ac.sun_color); have_ac = true; }
@@ -182,6 +210,26 @@ int main(int argc, char** argv) {
     if (panorama && (gpus > 1 || rgba8_out)) { fprintf(stderr, "--clouds-panorama renders float pixels on one GPU\n"); return 2; }
     if (planet_view && (W < 1 || H < 1 || panorama)) { fprintf(stderr, "--planet-view W H EX EY EZ LX LY LZ (not with --clouds-panorama)\n"); return 2; }
     if (planet_view && (gpus > 1 || rgba8_out)) { fprintf(stderr, "--planet-view renders float pixels on one GPU\n"); return 2; }
+    if (egg_view && (W < 1 || H < 1 || panorama || planet_view)) { fprintf(stderr, "--egg-view W H EX EY EZ LX LY LZ (not with --clouds-panorama or --planet-view)\n"); return 2; }
+    if (egg_view && (gpus > 1 || rgba8_out)) { fprintf(stderr, "--egg-view renders float pixels on one GPU\n"); return 2; }
+    const bool pose_flags = pose_has[0] || pose_has[1] || pose_has[2] || pose_has[3] || pose_has[4] || pose_has[5] || pose_has[6] || pose_has[7];
+    if (pose_flags && id != SBX_APP_EGG_POSE && !egg_view) { fprintf(stderr, "the pose flags belong to --app egg_pose or --egg-view\n"); return 2; }
+    // the pose of frame time `time`: sbx_egg_pose_default's block with the flags' fields put in
+    auto pose_at = [&](float time) {
+        sbx_uniforms pu{};
+        pu.u_res[0] = (float)W; pu.u_res[1] = (float)H; pu.u_time = time;
+        sbx_aux_egg_pose p;
+        sbx_egg_pose_default(&pu, &p);
+        if (pose_has[0]) memcpy(p.eye, pose_arg.eye, sizeof(p.eye));
+        if (pose_has[1]) p.fov = pose_arg.fov;
+        if (pose_has[2]) memcpy(p.look_at, pose_arg.look_at, sizeof(p.look_at));
+        if (pose_has[3]) p.turn_deg = pose_arg.turn_deg;
+        if (pose_has[4]) memcpy(p.left_foot, pose_arg.left_foot, sizeof(p.left_foot));
+        if (pose_has[5]) p.femur = pose_arg.femur;
+        if (pose_has[6]) memcpy(p.right_foot, pose_arg.right_foot, sizeof(p.right_foot));
+        if (pose_has[7]) p.tibia = pose_arg.tibia;
+        return p;
+    };
     for (const std::string* p : {&ppm, &f32})
         if (!pattern_ok(*p)) { fprintf(stderr, "bad file pattern %s: one %%d / %%0Nd conversion at most, a literal percent as %%%%\n", p->c_str()); return 2; }
     const void* aux = nullptr;
@@ -270,13 +318,19 @@ int main(int argc, char** argv) {
         if (hipMalloc((void**)&rays, hr.size() * sizeof(float)) != hipSuccess ||
             hipMemcpy(rays, hr.data(), hr.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "hipMalloc failed\n"); return 1; }
     }
-    if (planet_view) {
+    std::vector<float> view_pcx;                     // --egg-view: point_cam.x of every pixel, for the bars
+    float *lin = nullptr, *srgb = nullptr;          // --egg-view: the linear colours (3 floats a pixel) and their sRGB form, on the device
+    if (planet_view || egg_view) {
         // main.h:33-46 and util.h:5-20 in binary32, operation by operation (dot = (x x + y y) + z z, normalize = three divisions by the root)
         struct V { float x, y, z; };
         auto dot3 = [](V a, V b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; };
         auto norm3 = [&](V v) { const float l = sqrtf(dot3(v, v)); return V{v.x / l, v.y / l, v.z / l}; };
         auto cross3 = [](V a, V b) { return V{a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; };
-        const float fov = (float)tan((double)(pv_fov_deg * 0.017453292519943295f));
+        const float fov = egg_view ? (have_fov ? pv_fov : 1.f) : (float)tan((double)((have_fov ? pv_fov : 30.f) * 0.017453292519943295f));
+        if (egg_view) {
+            view_pcx.resize(npx);
+            if (hipMalloc((void**)&lin, npx * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&srgb, npx * 3 * sizeof(float)) != hipSuccess) { fprintf(stderr, "hipMalloc failed\n"); return 1; }
+        }
         const float fw = (float)W, fh = (float)H, aspect = fw / fh;
         const V fwd = norm3(V{pv_look[0] - pv_eye[0], pv_look[1] - pv_eye[1], pv_look[2] - pv_eye[2]});
         const V right = cross3(V{0.f, 1.f, 0.f}, fwd), up = cross3(fwd, right);
@@ -289,6 +343,7 @@ int main(int argc, char** argv) {
                 float* r = &hr[((size_t)y * W + x) * 6];
                 r[0] = pv_eye[0]; r[1] = pv_eye[1]; r[2] = pv_eye[2];
                 r[3] = d.x; r[4] = d.y; r[5] = d.z;
+                if (egg_view) view_pcx[(size_t)y * W + x] = pcx;
             }
         if (hipMalloc((void**)&rays, hr.size() * sizeof(float)) != hipSuccess ||
             hipMemcpy(rays, hr.data(), hr.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "hipMalloc failed\n"); return 1; }
@@ -298,16 +353,41 @@ int main(int argc, char** argv) {
     for (int f = 0; f < frames; ++f) {
         sbx_uniforms u{};
         u.u_res[0] = (float)W; u.u_res[1] = (float)H; u.u_mouse[0] = mx; u.u_mouse[1] = my; u.u_time = t + f * dt;   // hlsltoy.cpp:502-504
+        sbx_aux_egg_pose frame_pose;
+        if (id == SBX_APP_EGG_POSE) { frame_pose = pose_at(u.u_time); aux = &frame_pose; }
         (void)hipEventRecord(e0, nullptr);
         if (panorama) rc = sbx_clouds_eval(ctx, "render", have_ac ? &ac : nullptr, u.u_time, rays, dev, npx, nullptr);
         else if (planet_view) rc = sbx_planet_eval(ctx, "render", u.u_time, rays, dev, npx, nullptr);
+        else if (egg_view) {
+            const sbx_aux_egg_pose pose = pose_at(u.u_time);
+            rc = sbx_egg_eval(ctx, "render_scene", &pose, rays, dev, npx, nullptr);
+            // render's bars and abs (app_egg.h:233-251) on what render_scene returned (rgb, depth), in binary32 in the reference's order of
+            // operations (smoothstep: t = clamp((x - e0) / (e1 - e0), 0, 1), t t (3 - 2 t); mix: x (1 - a) + y a; step: x < edge ? 0 : 1)
+            std::vector<float> px(n), l3(npx * 3);
+            if (rc == SBX_OK && hipMemcpy(px.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+            for (size_t i = 0; rc == SBX_OK && i < npx; ++i) {
+                const float x = fabsf(fabsf(view_pcx[i]) - 0.6f) - 0.05f;
+                float ts = (x - 0.0f) / (0.01f - 0.0f);
+                ts = ts < 0.f ? 0.f : ts;                    // m_max(ts, 0) then m_min(., 1): compare-and-select, a NaN stays
+                ts = 1.f < ts ? 1.f : ts;
+                const float bar_factor = 1.0f - (ts * ts) * (3.0f - 2.f * ts);
+                const float depth_factor = 1.f - (px[i * 4 + 3] < 1.f ? 0.f : 1.f);
+                const float a = bar_factor * depth_factor;
+                for (int k = 0; k < 3; ++k) l3[i * 3 + k] = fabsf(px[i * 4 + k] * (1.f - a) + .6f * a);
+            }
+            if (rc == SBX_OK && hipMemcpy(lin, l3.data(), l3.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+            if (rc == SBX_OK) rc = sbx_math_eval(ctx, "srgb_pow", lin, nullptr, srgb, npx * 3, nullptr);
+            if (rc == SBX_OK && hipMemcpy(l3.data(), srgb, l3.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+            for (size_t i = 0; i < npx; ++i) { px[i * 4] = l3[i * 3]; px[i * 4 + 1] = l3[i * 3 + 1]; px[i * 4 + 2] = l3[i * 3 + 2]; px[i * 4 + 3] = 1.f; }      // main.h:52
+            if (rc == SBX_OK && hipMemcpy(dev, px.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        }
         else rc = multi ? sbx_multi_render(multi, id, &u, aux, dev, nullptr) : sbx_render_rows(ctx, id, &u, aux, 0, H, dev, nullptr);
         if (rc != SBX_OK) { fprintf(stderr, "render: %s\n", multi ? sbx_multi_last_error(multi) : sbx_last_error(ctx)); return 1; }
         (void)hipEventRecord(e1, nullptr);
         (void)hipEventSynchronize(e1);
         float ms = 0;
         (void)hipEventElapsedTime(&ms, e0, e1);
-        printf("frame %d  u_time %.4f  %s %dx%d  %.3f ms  %.1f Mpix/s\n", f, u.u_time, panorama ? "clouds panorama" : planet_view ? "planet view" : app.c_str(), W, H, ms, W * (double)H / ms / 1e3);
+        printf("frame %d  u_time %.4f  %s %dx%d  %.3f ms  %.1f Mpix/s\n", f, u.u_time, panorama ? "clouds panorama" : planet_view ? "planet view" : egg_view ? "egg view" : app.c_str(), W, H, ms, W * (double)H / ms / 1e3);
         if (!f32.empty()) {
             if (hipMemcpy(host.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
             FILE* fp = fopen(frame_name(f32, f, frames).c_str(), "wb");
@@ -339,6 +419,8 @@ int main(int argc, char** argv) {
         }
     }
     if (rays) (void)hipFree(rays);
+    if (lin) (void)hipFree(lin);
+    if (srgb) (void)hipFree(srgb);
     if (dev8) (void)hipFree(dev8);
     (void)hipFree(dev);
     if (multi) sbx_multi_destroy(multi);

@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell, SBX_APP_SDF_SCENE with sbx_aux_sdf_scene, sbx_sdf_scene_ramp and sbx_sdf_eval, sbx_clouds_eval, sbx_planet_eval: new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell, SBX_APP_SDF_SCENE with sbx_aux_sdf_scene, sbx_sdf_scene_ramp and sbx_sdf_eval, sbx_clouds_eval, sbx_planet_eval, SBX_APP_EGG_POSE with sbx_aux_egg_pose and sbx_egg_pose_default, sbx_egg_eval: new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -311,7 +311,27 @@ typedef enum sbx_app {
        sbx_set_variant as for SBX_APP_SDF_AO: 1 and 3 select the IEEE roots, 2 forces the witness re-run.
        NOT OFFERED: nested frames (a host composes its offsets itself), scaling, per-object light or AO settings, more than 32
        instructions, and the drop-in header sbx_mainimage.hpp, which has no way to state a scene. */
-    SBX_APP_SDF_SCENE = 33
+    SBX_APP_SDF_SCENE = 33,
+    /* src/app_egg.h as shipped (BEZIER defined, the `#if 1` egg) with the rider POSED BY THE CALLER: what the reference's README lists
+       as its "2D two bone IK solver" (src/IK.h) at work.  The aux block sbx_aux_egg_pose (below) states the camera, the turntable's
+       angle, both feet and both bone lengths — the values app_egg.h derives from u_time or states as literals at :25, :26, :40, :74,
+       :77, :80, :81 and :253; aux == NULL means sbx_egg_pose_default(uni, .), and the frame is then SBX_APP_EGG's in every bit.
+       u_res is read; u_time and u_mouse are not.  Alpha is 1: the output forms are the ones SBX_APP_RAYTRACER_SCENE lists.
+       SEMANTICS (tests/egg_pose_model.py is the definition), all as app_egg.h and IK.h have them:
+         - everything not in the block stays the reference's literal: `side`, both pelvis points, `thick`, the egg, the wheel, the
+           ground, the (0, .5, 3.5) offset, the order of the unions, the 80-step trace, the 20-step shadow march of ground hits, the
+           flat colours, `depth` fresh per pixel, the bars, abs, linear_to_srgb;
+         - the knees are ik_solver(pelvis, foot, femur, tibia) exactly as IK.h:18-41 states it: a foot whose z differs from its
+           pelvis' gives a 3-D `goal` rotated about z, as the arithmetic says;
+         - a goal beyond femur + tibia gives a NaN knee; by op_add's `d1.x < d2.x ? d1 : d2` that leg and that foot then drop out of
+           the union, and the frame holds no NaN;
+         - every float bit pattern is data: nothing is refused beyond what any app refuses.
+       sbx_set_variant 0-3 mean what they mean for SBX_APP_EGG, except that a block from which a non-finite frame constant follows
+       (a NaN knee, toe or bounding sphere, a non-finite angle) always takes the reference form (variant 1's kernel): same bits.
+       SBX_PRECISION_1E4 is ignored.
+       NOT OFFERED: the STRAIGHT / OVAL builds under a pose, other bone counts or a per-leg pelvis, a pose for the wheel or the egg,
+       and the drop-in header sbx_mainimage.hpp, which has no way to state a block. */
+    SBX_APP_EGG_POSE = 34
 } sbx_app;
 
 typedef enum sbx_status {
@@ -423,6 +443,19 @@ typedef struct sbx_aux_sdf_scene {        /* 2784 B */
  * a new one, not SBX_APP_SDF_AO's; that frame's nested rotate_around_y(180) (:134) and its tree of vec2 unions (:108-110, :137,
  * :147-149) are not expressible in this block either. */
 void sbx_sdf_scene_ramp(const sbx_uniforms* uni, sbx_aux_sdf_scene* out);
+
+/* the pose of SBX_APP_EGG_POSE and sbx_egg_eval: plain data, 64 bytes.  (:N names the line of src/app_egg.h whose value the field
+ * replaces.) */
+typedef struct sbx_aux_egg_pose {          /* 64 B */
+    float eye[3];        float fov;        /* :25; :253 (main.h's FOV factor, as given) */
+    float look_at[3];    float turn_deg;   /* :26; the angle handed to rotate_around_y at :40 (the reference: u_time * -100.0) */
+    float left_foot[3];  float femur;      /* left_foot_pos of :74 as a value; :80 */
+    float right_foot[3]; float tibia;      /* right_foot_pos of :77; :81 */
+} sbx_aux_egg_pose;
+/* Host only, no context: what setup_camera and sdf() of app_egg.h make of uni->u_time, the block SBX_APP_EGG_POSE renders when aux is
+ * NULL.  The feet are wheel_pos + mul(rotate_around_z(-u_time * 400.), (0, +-.3, +-.2)) by the math spec, turn_deg is the binary32
+ * product u_time * -100.0f, femur .8, tibia .75, eye (0, .25, 5.25), look_at (0, .25, 0), fov 1. */
+void sbx_egg_pose_default(const sbx_uniforms* uni, sbx_aux_egg_pose* out);
 
 typedef struct sbx_ctx sbx_ctx;
 
@@ -729,6 +762,23 @@ int sbx_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, flo
  * in sbx_stats.render_launches; sbx_set_precision does not enter; sbx_set_variant 1 selects the plain statement (same bits).  n == 0
  * returns SBX_OK and touches nothing; SBX_ERR_ARG, with nothing written, for a NULL ctx / fn / in / out, an unknown name, n > 2^31. */
 int sbx_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const float* in, float* out, size_t n, void* stream);
+/* The two bone IK solver (src/IK.h) and the egg's field, shadow and trace (src/app_egg.h as shipped) as standalone functions over n
+ * elements of the caller's, under the caller's pose: what the reference reaches only through pixels of its one fixed camera — the
+ * solver for a host's own rig, the field for collision queries, the trace for another camera or a reflection.  `pose`: HOST memory,
+ * read during the call; only turn_deg, the feet and the bones are read, the camera is not.  `in`, `out`: device memory, not
+ * overlapping, 4-byte alignment suffices.  Per element:
+ *   "ik_solver" (IK.h:44-52)       in 8: start xyz, goal xyz, L1, L2.  out 3.  `pose` is not read and may be NULL.
+ *   "sdf" (:38-144)                in 3: P (world).  out 2: the distance, the material id as a float.
+ *   "sdf_normal" (:146-157)        in 3: p.  out 3.
+ *   "shadowmarch" (:161-186)       in 6: origin xyz, direction xyz.  out 1.
+ *   "render_scene" (:190-231)      in 6: origin xyz, direction xyz.  out 4: the rgb it returns, then `depth` as it stands after the
+ *                                  call, starting from -max_dist (:188) for every element.
+ * Directions are used as given, never normalised; the ground's shadow ray keeps sh_dir = (0, 1, 1).  Exact for every bit pattern,
+ * NaN results included.  Asynchronous on `stream` and capturable (inside a capture it allocates nothing, queries nothing and waits
+ * for nothing); not counted in sbx_stats.render_launches; sbx_set_variant 1 selects the plain statement (same bits).  n == 0 returns
+ * SBX_OK and touches nothing; SBX_ERR_ARG, with nothing written, for a NULL ctx / fn / in / out, a NULL pose for any name but
+ * "ik_solver", an unknown name, n > 2^31. */
+int sbx_egg_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, const float* in, float* out, size_t n, void* stream);
 /* The size^3 RGBA32F noise volume util/ddsvolgen bakes (ddsvolgen.cpp:101-117): R =
  * fbm_worley_tile((xyz + .5)/size, 2, 1, .5), G = B = A = 0, x fastest.  `rgba`: size^3 * 4 floats. */
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream);

@@ -40,6 +40,10 @@ extern "C" {
  * sbx_planet_eval: 1 = the SKIP = false statement of k_planet lane by lane for every wave (every fBm octave and cloud sample evaluated,
  * the IEEE roots and divisions, exp_, lattice indices as the reference forms them); 0 runs it only on the waves whose own operands fail
  * a guard of csrc/kern_planet_eval.hip, and for any u_time beyond 1e8 in magnitude or NaN.
+ * SBX_APP_EGG_POSE: every value as for APP_EGG; a pose outside the domain of the culls and witnessed roots (a non-finite frame constant, a
+ * value of the block beyond 1e4, 1e10 for the angle) takes 1 whatever is set.  sbx_egg_eval: 1 = CULL = false and the IEEE roots for every
+ * wave; 2 / 3 = the witness's test edge / the IEEE roots; 0 takes the plain form only for such a pose and for the waves whose own inputs
+ * hold a value beyond 1e4 or a NaN (csrc/kern_egg_eval.hip).  "ik_solver" has one form.
  * All variants are specified to produce identical bits (tests/test_gpu_parity.py sweeps them against each other). */
 int sbx_set_variant(sbx_ctx* ctx, int variant);
 
@@ -64,6 +68,14 @@ int sbx_debug_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* au
  * tests/test_gpu_planet_eval.py and tools/time_planet_eval.py. */
 int sbx_debug_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const float* in, float* out, size_t n, unsigned counts_host[2],
                           void* stream);
+
+/* sbx_egg_eval (sbx.h) with counts: the same launch (the context's variant included) followed by a wait, after which counts_host[0]
+ * holds the waves that took the witnessed roots only and counts_host[1] the waves that re-ran with the IEEE roots because a lane
+ * recorded a root outside the witness's interval.  A wave given the plain form (variant 1 or 3, an untame pose, an untame input) and
+ * "ik_solver" are in neither.  It allocates and synchronises, so it is not capturable.  For tests/test_gpu_egg_eval.py and
+ * tools/time_egg_eval.py. */
+int sbx_debug_egg_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, const float* in, float* out, size_t n,
+                       unsigned counts_host[2], void* stream);
 
 /* Device evaluation of the math spec, elementwise over device arrays (for parity tests):
  * fn in {"sin","cos","tan","exp","pow","acos","atan2","hash","div","div_rd","exp_h13","pow_h","sqrt_n","sqrt_ieee","exp_reg","exp_reg_plain","exp_reg64","exp_reg64_plain","exp_small","exp_small_plain","exp_reg4k","sin_b40","div3","sqrt_rs","divn","srgb_pow","pow_spec"}; b may be NULL

@@ -17,7 +17,7 @@ from . import shard  # noqa: F401  (pure-python row-block arithmetic, no GPU nee
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsbx.so")
 
-APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW, APP_PLANET_CLOSEUP, APP_PLANET_CLOUDLESS, APP_PLANET_UNLIT, APP_RAYTRACER_SCENE, APP_SDF_SCENE = range(34)
+APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW, APP_PLANET_CLOSEUP, APP_PLANET_CLOUDLESS, APP_PLANET_UNLIT, APP_RAYTRACER_SCENE, APP_SDF_SCENE, APP_EGG_POSE = range(35)
 APPS = {"APP_PLANET": APP_PLANET, "APP_CLOUDS": APP_CLOUDS, "APP_VINYL": APP_VINYL, "APP_EGG": APP_EGG,
         "APP_RAYTRACER": APP_RAYTRACER, "APP_ATMOSPHERE": APP_ATMOSPHERE, "APP_SDF_AO": APP_SDF_AO,
         "APP_CLOUDS_BEST": APP_CLOUDS_BEST,    # src/app_clouds_best.h (stand-alone shader, not an APP_* define)
@@ -48,6 +48,7 @@ MORE_APPS = {"APP_EGG_STRAIGHT": APP_EGG_STRAIGHT,  # APP_EGG without `#define B
              "APP_PLANET_CLOUDLESS": APP_PLANET_CLOUDLESS,  # APP_PLANET without the `#define CLOUDS` of src/app_planet.h:63: no cloud march, no cloud shadow
              "APP_PLANET_UNLIT": APP_PLANET_UNLIT,          # APP_PLANET without the `#define LIGHT` of src/app_planet.h:249: N = w_normal.y, ocean = water
              "APP_RAYTRACER_SCENE": APP_RAYTRACER_SCENE,    # src/app_raytracer.h's render over the caller's scene: aux = a RaytracerScene (cornell_scene, raytracer_scene)
+             "APP_EGG_POSE": APP_EGG_POSE,                  # src/app_egg.h as shipped with the rider posed by the caller (src/IK.h at work): aux = an EggPose (egg_pose_default, egg_pose)
              "APP_SDF_SCENE": APP_SDF_SCENE}                # src/app_sdf_ao.h's renderer over the caller's field, a program of src/sdf.h's primitives and operators: aux = an SdfScene (sdf_ramp_scene, SdfSceneBuilder)
 ALL_APPS = {**APPS, **MORE_APPS}
 
@@ -124,6 +125,13 @@ class RaytracerScene(ctypes.Structure):     # sbx_aux_raytracer_scene (the aux b
                 ("ambient", ctypes.c_float * 3), ("shadow", ctypes.c_int32),
                 ("n_planes", ctypes.c_int32), ("n_spheres", ctypes.c_int32), ("_pad", ctypes.c_int32 * 2),
                 ("materials", RtMaterial * 8), ("planes", RtPlane * RT_MAX_PLANES), ("spheres", RtSphere * RT_MAX_SPHERES)]
+
+
+class EggPose(ctypes.Structure):            # sbx_aux_egg_pose (the aux block of APP_EGG_POSE and the pose of egg_eval, 64 bytes)
+    _fields_ = [("eye", ctypes.c_float * 3), ("fov", ctypes.c_float),
+                ("look_at", ctypes.c_float * 3), ("turn_deg", ctypes.c_float),
+                ("left_foot", ctypes.c_float * 3), ("femur", ctypes.c_float),
+                ("right_foot", ctypes.c_float * 3), ("tibia", ctypes.c_float)]
 
 
 SDF_MAX_INSTR, SDF_MAX_STACK = 32, 4         # SBX_SDF_MAX_INSTR, SBX_SDF_MAX_STACK
@@ -350,6 +358,10 @@ def load_library(path=None):
     lib.sbx_sdf_scene_ramp.argtypes = [ctypes.POINTER(Uniforms), ctypes.POINTER(SdfScene)]
     lib.sbx_sdf_scene_ramp.restype = None
     lib.sbx_sdf_eval.argtypes = [vp, ctypes.POINTER(SdfScene), fp, fp, ctypes.c_size_t, vp]
+    lib.sbx_egg_pose_default.argtypes = [ctypes.POINTER(Uniforms), ctypes.POINTER(EggPose)]
+    lib.sbx_egg_pose_default.restype = None
+    lib.sbx_egg_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(EggPose), fp, fp, ctypes.c_size_t, vp]
+    lib.sbx_debug_egg_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(EggPose), fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
     lib.sbx_debug_raytracer_scene_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.sbx_create.argtypes = [ci, ctypes.POINTER(vp)]
     lib.sbx_destroy.argtypes = [vp]
@@ -514,6 +526,28 @@ def sdf_ramp_scene(width, height, time, lib=None):
     u = uniforms(width, height, time)
     a = SdfScene()
     lib.sbx_sdf_scene_ramp(ctypes.byref(u), ctypes.byref(a))
+    return a
+
+
+def egg_pose_default(time, lib=None):
+    """sbx_egg_pose_default (host only, no GPU needed): the EggPose that src/app_egg.h's setup_camera and sdf() make of `time` — what
+    APP_EGG_POSE renders when aux is None, the frame of APP_EGG."""
+    lib = lib or load_library()
+    u = uniforms(1, 1, time)
+    a = EggPose()
+    lib.sbx_egg_pose_default(ctypes.byref(u), ctypes.byref(a))
+    return a
+
+
+def egg_pose(left_foot=(0.0, 1.5, 0.2), right_foot=(0.0, 0.9, -0.2), turn_deg=0.0, femur=0.8, tibia=0.75, eye=(0.0, 0.25, 5.25),
+             look_at=(0.0, 0.25, 0.0), fov=1.0):
+    """An EggPose (the aux block of APP_EGG_POSE, the pose of Renderer.egg_eval) from plain Python values, each rounded to binary32.
+    The feet are left_foot_pos / right_foot_pos of src/app_egg.h:74, :77 (the pedals at u_time 0 are the defaults), turn_deg the angle
+    of the turntable (:40), femur and tibia the bone lengths of the IK solver (:80-81), fov the FOV factor of main.h."""
+    a = EggPose()
+    a.eye[:], a.look_at[:] = [float(v) for v in eye], [float(v) for v in look_at]
+    a.left_foot[:], a.right_foot[:] = [float(v) for v in left_foot], [float(v) for v in right_foot]
+    a.fov, a.turn_deg, a.femur, a.tibia = float(fov), float(turn_deg), float(femur), float(tibia)
     return a
 
 
@@ -1119,6 +1153,37 @@ class Renderer:
             self._check(self.lib.sbx_planet_eval(*args, self._stream()))
         else:
             self._check(self.lib.sbx_debug_planet_eval(*args, counts, self._stream()))
+        return out
+
+    # sbx_egg_eval: floats per element in / out
+    EGG_EVAL_WIDTHS = {"ik_solver": (8, 3), "sdf": (3, 2), "sdf_normal": (3, 3), "shadowmarch": (6, 1), "render_scene": (6, 4)}
+
+    def egg_eval(self, fn, x, pose=None):
+        """src/IK.h's solver and APP_EGG's field, normal, shadow march and trace over the caller's elements under an EggPose
+        (include/sbx.h sbx_egg_eval): fn 'ik_solver' over x[n, 8] (start xyz, goal xyz, L1, L2) -> [n, 3], pose not read; 'sdf' over
+        points x[n, 3] -> [n, 2] (distance, material id); 'sdf_normal' x[n, 3] -> [n, 3]; 'shadowmarch' over rays x[n, 6] (origin
+        xyz, direction xyz) -> [n, 1]; 'render_scene' over rays x[n, 6] -> [n, 4] (rgb, depth).  Only the pose's turn_deg, feet and
+        bones are read."""
+        return self._egg_eval(fn, x, pose, None)
+
+    def egg_eval_counted(self, fn, x, pose=None):
+        """include/sbx_test.h sbx_debug_egg_eval: egg_eval that waits -> (out, (waves that took the witnessed roots only, waves that
+        re-ran with the IEEE roots))"""
+        counts = (ctypes.c_uint * 2)(0, 0)
+        return self._egg_eval(fn, x, pose, counts), (int(counts[0]), int(counts[1]))
+
+    def _egg_eval(self, fn, x, pose, counts):
+        if fn not in self.EGG_EVAL_WIDTHS:
+            raise SbxError(SBX_ERR_ARG, "unknown egg function %r" % (fn,))
+        win, wout = self.EGG_EVAL_WIDTHS[fn]
+        x = x.to(self.tdev, self.torch.float32).contiguous().view(x.numel() // win, win)
+        out = self.torch.empty((x.shape[0], wout), dtype=self.torch.float32, device=self.tdev)
+        args = (self.ctx, fn.encode(), None if pose is None else ctypes.byref(pose), ctypes.c_void_p(x.data_ptr()),
+                ctypes.c_void_p(out.data_ptr()), x.shape[0])
+        if counts is None:
+            self._check(self.lib.sbx_egg_eval(*args, self._stream()))
+        else:
+            self._check(self.lib.sbx_debug_egg_eval(*args, counts, self._stream()))
         return out
 
     def sdf_eval(self, scene, xyz):

@@ -210,6 +210,8 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
         SS = aux_sdf_scene(aux, *uni);
         if (const char* why = sdf_scene_check(SS, false)) return fail(ctx, SBX_ERR_ARG, why);
     }
+    sbx_aux_egg_pose EP;
+    if (T.aux == AUX_EGG_POSE) EP = aux_egg_pose(aux, *uni);               // (every bit pattern is data: nothing to refuse)
     if (T.noise_volumes && !ctx->noise.shape) return fail(ctx, SBX_ERR_ARG, "APP_CLOUDS with USE_NOISE_TEX needs sbx_set_noise_volume first");
     const bool capturing = stream_is_capturing(s);
     TimingPair* tp = nullptr;
@@ -247,6 +249,7 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
         auto mix = [&scene](const void* p, size_t n) { for (size_t i = 0; i < n; ++i) scene = (scene ^ ((const unsigned char*)p)[i]) * 1099511628211ull; };
         mix(uni, sizeof(*uni));
         if (T.aux == AUX_CLOUDS) mix(&AC, sizeof(AC));
+        if (T.aux == AUX_EGG_POSE) mix(&EP, sizeof(EP));                   // (the pose IS the scene: a pose that stands still gets its table)
     }
     TileOrder* const ordered = tile_order_begin(ctx->tile_orders, app, M, og, s, capturing, scene, T.scene_policy);
     switch (app) {
@@ -267,6 +270,13 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     case SBX_APP_EGG: launch_egg(build_egg(*uni, EGG_DEFAULT), M, rgba, s, sdf_variant, EGG_DEFAULT); break;
     case SBX_APP_EGG_STRAIGHT: launch_egg(build_egg(*uni, EGG_STRAIGHT), M, rgba, s, sdf_variant, EGG_STRAIGHT); break;
     case SBX_APP_EGG_OVAL: launch_egg(build_egg(*uni, EGG_OVAL), M, rgba, s, sdf_variant, EGG_OVAL); break;
+    // the shipped build over the caller's pose (include/sbx.h): the same kernels over another frame block; a pose outside the domain
+    // of their culls and witnessed roots (sbx_frames.hip egg_pose_tame) takes the reference form
+    case SBX_APP_EGG_POSE: {
+        const FrameEggStraight F = build_egg_pose(*uni, EP, EGG_DEFAULT);
+        launch_egg(F, M, rgba, s, egg_pose_tame(EP, F) ? sdf_variant : 1, EGG_DEFAULT);
+        break;
+    }
     case SBX_APP_RAYTRACER: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots); break;
     // the builds of app_raytracer.h's three switches (include/sbx.h): two kernel builds over the shipped frame, one frame of its own
     case SBX_APP_RAYTRACER_PHONG: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots, RT_PHONG); break;

@@ -211,6 +211,10 @@ int render_rows(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const void* aux,
 // ---- sbx_frames.hip: the frame-constant part of setup_camera()/setup_scene()/sdf() per app
 FrameClouds build_clouds(const sbx_uniforms& U, const sbx_aux_clouds& A, bool sky_sphere = false);
 FrameEggStraight build_egg(const sbx_uniforms& U, int build = EGG_DEFAULT);   // (the other builds read its FrameEgg part)
+// SBX_APP_EGG_POSE / sbx_egg_eval: the frame of the caller's pose (build_egg is this over sbx_egg_pose_default's block), and whether
+// k_egg's culls and witnessed roots stand for it (false: the reference form, sbx_set_variant 1's kernel)
+FrameEggStraight build_egg_pose(const sbx_uniforms& U, const sbx_aux_egg_pose& A, int build = EGG_DEFAULT);
+bool egg_pose_tame(const sbx_aux_egg_pose& A, const FrameEgg& F);
 FrameRaytracer build_raytracer(const sbx_uniforms& U, int build = RT_DEFAULT);   // build: RT_* (sbx_frame.h); RT_STATIC is the scene at rest
 FrameRtScene build_raytracer_scene(const sbx_uniforms& U, const sbx_aux_raytracer_scene& A);   // SBX_APP_RAYTRACER_SCENE: a validated block
 // SBX_APP_SDF_SCENE / sbx_sdf_eval: NULL if the block passes the checks of include/sbx.h, else what is wrong (program_only: n_instr and

@@ -231,6 +231,10 @@ void launch_clouds_eval(int fn, const FrameClouds& F, bool plain, const CloudsHa
 // 5 clouds_density / 6 illuminate / 7 background over F = build_planet of u_time (its camera is not read); plain = the SKIP = false
 // statement for every wave; counts = NULL or two zeroed device words (waves with every guarded short form on, waves that fell back)
 void launch_planet_eval(int fn, const FramePlanet& F, bool plain, const float* in, float* out, size_t n, unsigned* counts, hipStream_t s);
+// sbx_egg_eval (kern_egg_eval.hip): fn 0 sdf / 1 sdf_normal / 2 shadowmarch / 3 render_scene over build_egg_pose's frame; variant as
+// launch_egg's (1 = the reference form); counts: NULL, or two zeroed device words (witnessed waves, re-run waves).  launch_ik_eval: "ik_solver"
+void launch_egg_eval(int fn, const FrameEgg& F, int variant, const float* in, float* out, size_t n, unsigned* counts, hipStream_t s);
+void launch_ik_eval(const float* in, float* out, size_t n, hipStream_t s);
 int launch_math_eval(int fn, const float* a, const float* b, float* out, size_t n, hipStream_t s);
 void launch_cl_exp_eval(const float* a, float* out, size_t n, hipStream_t s, int form);   // exp_reg_ / exp_reg128_ forms (kern_clouds.hip)
 

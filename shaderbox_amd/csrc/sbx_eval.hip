@@ -240,6 +240,67 @@ int sbx_debug_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const floa
     return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "planet_eval (counted)", e);
 }
 
+// the checks sbx_egg_eval and its test hook share: SBX_OK with fn_id set (0 = "ik_solver", else 1 + launch_egg_eval's fn), or the failure
+static int egg_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, const float* in, const float* out, size_t n, int& fn_id) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!fn) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    static const char* names[] = {"ik_solver", "sdf", "sdf_normal", "shadowmarch", "render_scene"};
+    fn_id = -1;
+    for (int i = 0; i < 5; ++i) if (std::strcmp(fn, names[i]) == 0) fn_id = i;
+    if (fn_id < 0) return fail(ctx, SBX_ERR_ARG, "unknown egg function");
+    if (fn_id != 0 && !pose) return fail(ctx, SBX_ERR_ARG, "every egg function but ik_solver needs a pose");
+    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 elements");
+    if (n == 0) return SBX_OK;
+    if (!in || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    return SBX_OK;
+}
+// the launch of either: the frame of the block over a 1 x 1 frame (its camera is not read by the kernel); a pose outside the domain
+// of the culls and witnessed roots (sbx_frames.hip egg_pose_tame, the camera's fields ignored) takes the reference form
+static void egg_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_egg_pose* pose, const float* in, float* out, size_t n, unsigned* counts,
+                            hipStream_t s) {
+    if (id == 0) { launch_ik_eval(in, out, n, s); return; }
+    const sbx_uniforms U = {{1.f, 1.f}, {0.f, 0.f}, 0.f, {0.f, 0.f, 0.f}};
+    sbx_aux_egg_pose A = *pose;
+    A.eye[0] = 0.f; A.eye[1] = .25f; A.eye[2] = 5.25f; A.look_at[0] = 0.f; A.look_at[1] = .25f; A.look_at[2] = 0.f; A.fov = 1.f;
+    const FrameEggStraight F = build_egg_pose(U, A, EGG_DEFAULT);
+    const int variant = ctx->variant == 1 || !egg_pose_tame(A, F) ? 1 : ctx->sdf_roots;
+    launch_egg_eval(id - 1, F, variant, in, out, n, counts, s);
+}
+
+int sbx_egg_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, const float* in, float* out, size_t n, void* stream) {
+    int id = -1;
+    int rc = egg_eval_args(ctx, fn, pose, in, out, n, id);
+    if (rc != SBX_OK || n == 0) return rc;
+    if ((rc = use_device(ctx)) != SBX_OK) return rc;
+    egg_eval_launch(ctx, id, pose, in, out, n, nullptr, (hipStream_t)stream);
+    return launched(ctx, "egg_eval launch");
+}
+
+int sbx_debug_egg_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, const float* in, float* out, size_t n, unsigned counts_host[2],
+                       void* stream) {
+    int id = -1;
+    int rc = egg_eval_args(ctx, fn, pose, in, out, n, id);
+    if (rc != SBX_OK) return rc;
+    if (!counts_host) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    counts_host[0] = counts_host[1] = 0;
+    if (n == 0) return SBX_OK;
+    if ((rc = use_device(ctx)) != SBX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_is_capturing(s)) return fail(ctx, SBX_ERR_ARG, "the counted launch is not capturable");
+    unsigned* counts = nullptr;
+    hipError_t e = hipMalloc((void**)&counts, 2 * sizeof(unsigned));
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
+    if ((e = hipMemsetAsync(counts, 0, 2 * sizeof(unsigned), s)) == hipSuccess) {
+        egg_eval_launch(ctx, id, pose, in, out, n, counts, s);
+        unsigned h[2] = {0, 0};
+        if ((e = hipGetLastError()) == hipSuccess && (e = hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, s)) == hipSuccess)
+            e = hipStreamSynchronize(s);
+        counts_host[0] = h[0]; counts_host[1] = h[1];
+    }
+    (void)hipFree(counts);
+    return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "egg_eval (counted)", e);
+}
+
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream) {
     if (!ctx) return SBX_ERR_ARG;
     if (!rgba || size <= 0 || size > 1024) return fail(ctx, SBX_ERR_ARG, "bad volume arguments");

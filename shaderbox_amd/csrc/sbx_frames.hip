@@ -4,6 +4,7 @@
 // frame on the host with the shared math spec (sbx_math.h) and handed to the kernels as arguments.  Pure host math over the spec: it
 // is compiled with the library's flags, -ffp-contract=off among them, because they are part of that spec.
 #include "sbx_ctx.h"
+#include <cmath>
 #include <cstring>
 
 using namespace sbx;
@@ -70,19 +71,41 @@ static v3 ik_solver(v3 start, v3 goal_abs, float L1, float L2) {       // IK.h:5
     const m3 rot = M3(cos_theta, -sin_theta, 0, sin_theta, cos_theta, 0, 0, 0, 1.f);
     return start + mul(rot, normalize(goal) * L1);
 }
-// build: EGG_DEFAULT (app_egg.h as shipped), EGG_STRAIGHT (without `#define BEZIER`, :37) or EGG_OVAL (`#if 1` at :46 -> `#if 0`)
-FrameEggStraight build_egg(const sbx_uniforms& U, int build) {
-    FrameEggStraight F;
-    F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(.0f, .25f, 5.25f), V3(.0f, .25f, .0f));   // app_egg.h:23-27,253
+// What setup_camera (:23-27) and sdf() (:40, :68-81) of app_egg.h make of u_time, as the block of SBX_APP_EGG_POSE (include/sbx.h): the
+// ONE statement of the shipped pose — build_egg and sbx_egg_pose_default both read it
+static void egg_default_pose(const sbx_uniforms& U, sbx_aux_egg_pose& A) {
+    auto put = [](float* d, v3 v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; };
+    put(A.eye, V3(.0f, .25f, 5.25f));                                  // :25
+    put(A.look_at, V3(.0f, .25f, .0f));                                // :26
+    A.fov = 1.f;                                                       // :253
     const float t = U.u_time;
-    F.rot_y = rotate_around_y(t * -100.0f);                            // :40
+    A.turn_deg = t * -100.0f;                                          // :40
     const v3 wheel_pos = V3(0, 1.2f, 0);
     const float pedal_radius = 0.3f, pedal_speed = 400.f, pedal_off = 0.2f;
     const m3 rot_z = rotate_around_z(-t * pedal_speed);                // :73,76
-    F.left_foot = wheel_pos + mul(rot_z, V3(0.f, pedal_radius, pedal_off));
-    F.right_foot = wheel_pos + mul(rot_z, V3(0.f, -pedal_radius, -pedal_off));
+    put(A.left_foot, wheel_pos + mul(rot_z, V3(0.f, pedal_radius, pedal_off)));
+    put(A.right_foot, wheel_pos + mul(rot_z, V3(0.f, -pedal_radius, -pedal_off)));
+    A.femur = 0.8f; A.tibia = 0.75f;                                   // :80-81
+}
+// build: EGG_DEFAULT (app_egg.h as shipped), EGG_STRAIGHT (without `#define BEZIER`, :37) or EGG_OVAL (`#if 1` at :46 -> `#if 0`)
+FrameEggStraight build_egg(const sbx_uniforms& U, int build) {
+    sbx_aux_egg_pose A;
+    egg_default_pose(U, A);
+    return build_egg_pose(U, A, build);
+}
+// The frame of a pose: everything sdf() computes before it reads its point, from the block's values where app_egg.h has u_time or a
+// literal (include/sbx.h sbx_aux_egg_pose).  Every bound below (the toe midpoints, the Bezier spheres, the bounding sphere) is
+// computed FROM the pose, none is a constant of the shipped one: they hold for any pose whose frame is finite (egg_pose_tame).
+FrameEggStraight build_egg_pose(const sbx_uniforms& U, const sbx_aux_egg_pose& A, int build) {
+    FrameEggStraight F;
+    F.cam = make_camera(U.u_res[0], U.u_res[1], A.fov, V3(A.eye[0], A.eye[1], A.eye[2]), V3(A.look_at[0], A.look_at[1], A.look_at[2]));   // app_egg.h:23-27,253
+    F.rot_y = rotate_around_y(A.turn_deg);                             // :40
+    const v3 wheel_pos = V3(0, 1.2f, 0);
+    const float pedal_off = 0.2f;
+    F.left_foot = V3(A.left_foot[0], A.left_foot[1], A.left_foot[2]);  // :73-77
+    F.right_foot = V3(A.right_foot[0], A.right_foot[1], A.right_foot[2]);
     const v3 side = V3(0, 0, pedal_off);
-    const float femur = 0.8f, tibia = 0.75f, thick = .05f;
+    const float femur = A.femur, tibia = A.tibia, thick = .05f;           // :80-82
     const v3 zero = V3(0.f, 0.f, 0.f);
     const v3 knee_l = ik_solver(zero + side, F.left_foot, femur, tibia);   // :84-85
     const v3 knee_r = ik_solver(zero - side, F.right_foot, femur, tibia);  // :95-96
@@ -143,6 +166,28 @@ FrameEggStraight build_egg(const sbx_uniforms& U, int build) {
     }
     F.ocw = mul(transpose(F.rot_y), F.oc + V3(0, 0.5f, 3.5f));     // p = rot_y P - (0, .5, 3.5)  <=>  P = rot_y^T (p + (0, .5, 3.5))
     return F;
+}
+
+// Do k_egg's culls and witnessed roots stand for this pose?  Their proofs (kern_egg.hip, sbx_sdf.h) take finite frame constants and
+// sample points of the scene's own scale: a NaN knee (a goal beyond femur + tibia), a NaN toe or Bezier frame (collinear or coincident
+// points), a non-finite angle or camera leave comparisons against NaN, and a coordinate near 2^64 overflows the squared lengths the
+// culls compare.  So: every value of the block finite and within 1e4 in magnitude (a ray then stays within 15 + twice that of the
+// origin, the trace's own end), and every derived constant of the frame finite.  Anything else renders with the reference form
+// (CULL = false, IEEE roots: sbx_set_variant 1's kernel), which is the same operations as the reference on whatever the values are.
+bool egg_pose_tame(const sbx_aux_egg_pose& A, const FrameEgg& F) {
+    static_assert(sizeof(sbx_aux_egg_pose) == 16 * sizeof(float), "sbx_aux_egg_pose is 16 floats (include/sbx.h)");
+    float a[16];                                                       // eye, fov, look_at, turn_deg, left_foot, femur, right_foot, tibia
+    std::memcpy(a, &A, sizeof(a));
+    // (turn_deg is an angle: its bound is the one sbx_capi.hip's tame_time puts on u_time * -100, inside which the spec's sin / cos
+    // return a rotation)
+    for (int i = 0; i < 16; ++i) if (!(std::fabs(a[i]) <= (i == 7 ? 1e10f : 1e4f))) return false;
+    auto fin = [](float x) { return std::fabs(x) <= 3.4028234e38f; };  // NaN compares false
+    auto fin3 = [&](v3 v) { return fin(v.x) && fin(v.y) && fin(v.z); };
+    auto finb = [&](const BezierFrame& B) { return fin3(B.b) && fin3(B.u) && fin3(B.v) && fin3(B.w) && fin(B.a2.x) && fin(B.a2.y) && fin(B.c2.x) && fin(B.c2.y) && fin3(B.bc) && fin(B.br); };
+    auto finc = [&](const CylFrame& C) { return fin3(C.dir) && fin(C.len1) && fin(C.len0); };
+    return fin3(F.cam.eye) && fin3(F.cam.fwd) && fin3(F.cam.right) && fin3(F.cam.up) && fin(F.cam.fov) && fin(F.cam.aspect_x) &&
+           fin3(F.rot_y.c0) && fin3(F.rot_y.c1) && fin3(F.rot_y.c2) && finb(F.leg_l) && finb(F.leg_r) && finc(F.foot_l) && finc(F.foot_r) &&
+           fin3(F.foot_ml) && fin3(F.foot_mr) && fin3(F.oc) && fin(F.orad) && fin3(F.ocw);
 }
 
 // The Cornell box of app_raytracer.h as a scene block (include/sbx.h sbx_aux_raytracer_scene): setup_scene :18-36 over setup_cornell_box
@@ -553,6 +598,11 @@ void sbx_checkerboard_texture(int size, int freq, uint32_t* out) {    // hlsltoy
 void sbx_raytracer_scene_cornell(const sbx_uniforms* uni, int at_rest, sbx_aux_raytracer_scene* out) {
     if (!uni || !out) return;
     cornell_block(*uni, at_rest != 0, *out);
+}
+
+void sbx_egg_pose_default(const sbx_uniforms* uni, sbx_aux_egg_pose* out) {
+    if (!uni || !out) return;
+    egg_default_pose(*uni, *out);
 }
 
 void sbx_sdf_scene_ramp(const sbx_uniforms* uni, sbx_aux_sdf_scene* out) {

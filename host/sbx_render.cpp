@@ -25,6 +25,11 @@
 //              of --time and the pose flags below; then render's bars and abs (app_egg.h:233-251) in binary32 on the host and
 //              linear_to_srgb by the library's own form of it (sbx_math_eval "srgb_pow", include/sbx_test.h): the frame
 //              SBX_APP_EGG_POSE renders with that camera in its block.  One GPU, float pixels.
+//     --vinyl-view W H EX EY EZ LX LY LZ [--fov F]: instead of an app's frame, APP_VINYL seen from the caller's camera: the primary rays of
+//              main.h's pipeline, computed here as for --egg-view (F: the FOV factor, default 1, app_vinyl.h:460), go through
+//              sbx_vinyl_eval "render" (include/sbx.h) under the deck of --time and the deck flags below; then linear_to_srgb by the
+//              library's own form of it (sbx_math_eval "srgb_pow"): the frame SBX_APP_VINYL_DECK renders with that camera in its block.
+//              One GPU, float pixels.
 //     APP_SDF_AO aux block (:484-487):  [--fog-density D] [--fog-falloff F]
 //     app "sdf_ao_shadow" / "sdf_ao_normals": src/app_sdf_ao.h with its `#if 0` at :269 (soft shadows) / :217 (normals view) on; same fog flags
 //     app "egg_straight" / "egg_oval": src/app_egg.h without its `#define BEZIER` (:37, cylinder legs) / with its `#if 1` at :46 off (one scaled sphere)
@@ -46,6 +51,12 @@
 //              the pose of --time (sbx_egg_pose_default) and every flag replaces one field of sbx_aux_egg_pose:
 //              [--pose-eye x,y,z] [--pose-look-at x,y,z] [--pose-fov F] [--turn DEG] [--left-foot x,y,z] [--right-foot x,y,z]
 //              [--femur L] [--tibia L]
+//     app "vinyl_deck": src/app_vinyl.h as shipped over the caller's deck (SBX_APP_VINYL_DECK, include/sbx.h).  The block starts as the deck of
+//              --time (sbx_vinyl_deck_default) and every flag replaces one field of sbx_aux_vinyl_deck, so --platter-deg over a frame
+//              sequence is the scratching hand:
+//              [--deck-eye x,y,z] [--deck-look-at x,y,z] [--deck-fov F] [--platter-deg DEG] [--platter-tilt DEG] [--arm-tilt DEG]
+//              [--deck-sun x,y,z] [--groove-color r,g,b] [--dead-wax-color r,g,b] [--label-color r,g,b] [--logo-color r,g,b]
+//              [--shiny-color r,g,b] [--ro-spec V] [--a-x V] [--a-y V] [--shininess V]
 //     app "2d" / "2d_tex": src/app_2d.h (its alpha is not 1: the .f32 frames carry it; single GPU only), the USE_TEXTURE build
 //              reading hlsltoy's default 128x128 checkerboard at t0
 //     app "func": src/app_func.h, the tiled Worley fBm of its compiled 2D branch (grey, alpha 1; u_time and --mouse do not enter)
@@ -75,8 +86,8 @@ static int app_from_name(const std::string& s) {
     const char* names[] = {"planet", "clouds", "vinyl", "egg", "raytracer", "atmosphere", "sdf_ao", "clouds_best", "clouds_tex", "clouds_ue4",
                            "clouds_sky", "vinyl_gpu", "planet_atmosphere", "2d", "2d_tex", "func", "atmosphere_ground", "sdf_ao_shadow", "sdf_ao_normals",
                            "egg_straight", "egg_oval", "clouds_height", "clouds_luminance", "raytracer_phong", "raytracer_noshadow", "raytracer_static",
-                           "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow", "planet_closeup", "planet_cloudless", "planet_unlit", "raytracer_scene", "sdf_scene", "egg_pose"};
-    const int n = 35;
+                           "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow", "planet_closeup", "planet_cloudless", "planet_unlit", "raytracer_scene", "sdf_scene", "egg_pose", "vinyl_deck"};
+    const int n = 36;
     std::string low;
     for (char c : s) low += (char)tolower(c);
     for (int i = 0; i < n; ++i)
@@ -143,6 +154,9 @@ int main(int argc, char** argv) {
     bool egg_view = false, have_fov = false;
     sbx_aux_egg_pose pose_arg{};                     // the fields the pose flags gave, and which
     bool pose_has[8] = {false, false, false, false, false, false, false, false};      // eye, fov, look_at, turn, left foot, femur, right foot, tibia
+    bool vinyl_view = false;
+    sbx_aux_vinyl_deck deck_arg{};                   // the fields the deck flags gave, and which (in the block's order: sbx.h)
+    bool deck_has[16] = {};
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -178,6 +192,28 @@ int main(int argc, char** argv) {
             for (float& v : pv_look) v = (float)atof(next());
             egg_view = true;
         }
+        else if (a == "--vinyl-view") {
+            W = atoi(next()); H = atoi(next());
+            for (float& v : pv_eye) v = (float)atof(next());
+            for (float& v : pv_look) v = (float)atof(next());
+            vinyl_view = true;
+        }
+        else if (a == "--deck-eye") { vec3(deck_arg.eye); deck_has[0] = true; }
+        else if (a == "--deck-fov") { deck_arg.fov = (float)atof(next()); deck_has[1] = true; }
+        else if (a == "--deck-look-at") { vec3(deck_arg.look_at); deck_has[2] = true; }
+        else if (a == "--platter-deg") { deck_arg.platter_deg = (float)atof(next()); deck_has[3] = true; }
+        else if (a == "--deck-sun") { vec3(deck_arg.sun_dir); deck_has[4] = true; }
+        else if (a == "--platter-tilt") { deck_arg.platter_tilt_deg = (float)atof(next()); deck_has[5] = true; }
+        else if (a == "--groove-color") { vec3(deck_arg.groove_color); deck_has[6] = true; }
+        else if (a == "--arm-tilt") { deck_arg.arm_tilt_deg = (float)atof(next()); deck_has[7] = true; }
+        else if (a == "--dead-wax-color") { vec3(deck_arg.dead_wax_color); deck_has[8] = true; }
+        else if (a == "--ro-spec") { deck_arg.ro_spec = (float)atof(next()); deck_has[9] = true; }
+        else if (a == "--label-color") { vec3(deck_arg.label_color); deck_has[10] = true; }
+        else if (a == "--a-x") { deck_arg.a_x = (float)atof(next()); deck_has[11] = true; }
+        else if (a == "--logo-color") { vec3(deck_arg.logo_color); deck_has[12] = true; }
+        else if (a == "--a-y") { deck_arg.a_y = (float)atof(next()); deck_has[13] = true; }
+        else if (a == "--shiny-color") { vec3(deck_arg.shiny_color); deck_has[14] = true; }
+        else if (a == "--shininess") { deck_arg.shininess = (float)atof(next()); deck_has[15] = true; }
         else if (a == "--fov") { pv_fov = (float)atof(next()); have_fov = true; }
         else if (a == "--pose-eye") { vec3(pose_arg.eye); pose_has[0] = true; }
         else if (a == "--pose-fov") { pose_arg.fov = (float)atof(next()); pose_has[1] = true; }
@@ -229,6 +265,26 @@ int main(int argc, char** argv) {
         if (pose_has[6]) memcpy(p.right_foot, pose_arg.right_foot, sizeof(p.right_foot));
         if (pose_has[7]) p.tibia = pose_arg.tibia;
         return p;
+    };
+    if (vinyl_view && (W < 1 || H < 1 || panorama || planet_view || egg_view)) { fprintf(stderr, "--vinyl-view W H EX EY EZ LX LY LZ (not with another view)\n"); return 2; }
+    if (vinyl_view && (gpus > 1 || rgba8_out)) { fprintf(stderr, "--vinyl-view renders float pixels on one GPU\n"); return 2; }
+    bool deck_flags = false;
+    for (bool b : deck_has) deck_flags = deck_flags || b;
+    if (deck_flags && id != SBX_APP_VINYL_DECK && !vinyl_view) { fprintf(stderr, "the deck flags belong to --app vinyl_deck or --vinyl-view\n"); return 2; }
+    // the deck of frame time `time`: sbx_vinyl_deck_default's block with the flags' fields put in (a vec3 and a scalar per row of the block)
+    auto deck_at = [&](float time) {
+        sbx_uniforms du{};
+        du.u_res[0] = (float)W; du.u_res[1] = (float)H; du.u_time = time;
+        sbx_aux_vinyl_deck d;
+        sbx_vinyl_deck_default(&du, &d);
+        float* dst = (float*)&d;
+        const float* src = (const float*)&deck_arg;
+        for (int k = 0; k < 16; ++k) {
+            if (!deck_has[k]) continue;
+            if (k & 1) dst[(k / 2) * 4 + 3] = src[(k / 2) * 4 + 3];
+            else memcpy(dst + (k / 2) * 4, src + (k / 2) * 4, 3 * sizeof(float));
+        }
+        return d;
     };
     for (const std::string* p : {&ppm, &f32})
         if (!pattern_ok(*p)) { fprintf(stderr, "bad file pattern %s: one %%d / %%0Nd conversion at most, a literal percent as %%%%\n", p->c_str()); return 2; }
@@ -320,17 +376,20 @@ int main(int argc, char** argv) {
     }
     std::vector<float> view_pcx;                     // --egg-view: point_cam.x of every pixel, for the bars
     float *lin = nullptr, *srgb = nullptr;          // --egg-view: the linear colours (3 floats a pixel) and their sRGB form, on the device
-    if (planet_view || egg_view) {
+    float* vout = nullptr;                          // --vinyl-view: what "render" returns, 5 floats a pixel
+    if (planet_view || egg_view || vinyl_view) {
         // main.h:33-46 and util.h:5-20 in binary32, operation by operation (dot = (x x + y y) + z z, normalize = three divisions by the root)
         struct V { float x, y, z; };
         auto dot3 = [](V a, V b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; };
         auto norm3 = [&](V v) { const float l = sqrtf(dot3(v, v)); return V{v.x / l, v.y / l, v.z / l}; };
         auto cross3 = [](V a, V b) { return V{a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; };
-        const float fov = egg_view ? (have_fov ? pv_fov : 1.f) : (float)tan((double)((have_fov ? pv_fov : 30.f) * 0.017453292519943295f));
+        const float fov = (egg_view || vinyl_view) ? (have_fov ? pv_fov : 1.f) : (float)tan((double)((have_fov ? pv_fov : 30.f) * 0.017453292519943295f));
         if (egg_view) {
             view_pcx.resize(npx);
             if (hipMalloc((void**)&lin, npx * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&srgb, npx * 3 * sizeof(float)) != hipSuccess) { fprintf(stderr, "hipMalloc failed\n"); return 1; }
         }
+        if (vinyl_view && (hipMalloc((void**)&lin, npx * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&srgb, npx * 3 * sizeof(float)) != hipSuccess ||
+                           hipMalloc((void**)&vout, npx * 5 * sizeof(float)) != hipSuccess)) { fprintf(stderr, "hipMalloc failed\n"); return 1; }
         const float fw = (float)W, fh = (float)H, aspect = fw / fh;
         const V fwd = norm3(V{pv_look[0] - pv_eye[0], pv_look[1] - pv_eye[1], pv_look[2] - pv_eye[2]});
         const V right = cross3(V{0.f, 1.f, 0.f}, fwd), up = cross3(fwd, right);
@@ -355,6 +414,8 @@ int main(int argc, char** argv) {
         u.u_res[0] = (float)W; u.u_res[1] = (float)H; u.u_mouse[0] = mx; u.u_mouse[1] = my; u.u_time = t + f * dt;   // hlsltoy.cpp:502-504
         sbx_aux_egg_pose frame_pose;
         if (id == SBX_APP_EGG_POSE) { frame_pose = pose_at(u.u_time); aux = &frame_pose; }
+        sbx_aux_vinyl_deck frame_deck;
+        if (id == SBX_APP_VINYL_DECK) { frame_deck = deck_at(u.u_time); aux = &frame_deck; }
         (void)hipEventRecord(e0, nullptr);
         if (panorama) rc = sbx_clouds_eval(ctx, "render", have_ac ? &ac : nullptr, u.u_time, rays, dev, npx, nullptr);
         else if (planet_view) rc = sbx_planet_eval(ctx, "render", u.u_time, rays, dev, npx, nullptr);
@@ -381,13 +442,26 @@ int main(int argc, char** argv) {
             for (size_t i = 0; i < npx; ++i) { px[i * 4] = l3[i * 3]; px[i * 4 + 1] = l3[i * 3 + 1]; px[i * 4 + 2] = l3[i * 3 + 2]; px[i * 4 + 3] = 1.f; }      // main.h:52
             if (rc == SBX_OK && hipMemcpy(dev, px.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
         }
+        else if (vinyl_view) {
+            const sbx_aux_vinyl_deck deck = deck_at(u.u_time);
+            rc = sbx_vinyl_eval(ctx, "render", &deck, rays, vout, npx, nullptr);
+            // main.h's linear_to_srgb and alpha 1 on the linear rgb "render" returned (t and the material id are not part of a frame)
+            std::vector<float> v5(npx * 5), l3(npx * 3), px(n);
+            if (rc == SBX_OK && hipMemcpy(v5.data(), vout, v5.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+            for (size_t i = 0; i < npx; ++i) for (int k = 0; k < 3; ++k) l3[i * 3 + k] = v5[i * 5 + k];
+            if (rc == SBX_OK && hipMemcpy(lin, l3.data(), l3.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+            if (rc == SBX_OK) rc = sbx_math_eval(ctx, "srgb_pow", lin, nullptr, srgb, npx * 3, nullptr);
+            if (rc == SBX_OK && hipMemcpy(l3.data(), srgb, l3.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+            for (size_t i = 0; i < npx; ++i) { px[i * 4] = l3[i * 3]; px[i * 4 + 1] = l3[i * 3 + 1]; px[i * 4 + 2] = l3[i * 3 + 2]; px[i * 4 + 3] = 1.f; }      // main.h:52
+            if (rc == SBX_OK && hipMemcpy(dev, px.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        }
         else rc = multi ? sbx_multi_render(multi, id, &u, aux, dev, nullptr) : sbx_render_rows(ctx, id, &u, aux, 0, H, dev, nullptr);
         if (rc != SBX_OK) { fprintf(stderr, "render: %s\n", multi ? sbx_multi_last_error(multi) : sbx_last_error(ctx)); return 1; }
         (void)hipEventRecord(e1, nullptr);
         (void)hipEventSynchronize(e1);
         float ms = 0;
         (void)hipEventElapsedTime(&ms, e0, e1);
-        printf("frame %d  u_time %.4f  %s %dx%d  %.3f ms  %.1f Mpix/s\n", f, u.u_time, panorama ? "clouds panorama" : planet_view ? "planet view" : egg_view ? "egg view" : app.c_str(), W, H, ms, W * (double)H / ms / 1e3);
+        printf("frame %d  u_time %.4f  %s %dx%d  %.3f ms  %.1f Mpix/s\n", f, u.u_time, panorama ? "clouds panorama" : planet_view ? "planet view" : egg_view ? "egg view" : vinyl_view ? "vinyl view" : app.c_str(), W, H, ms, W * (double)H / ms / 1e3);
         if (!f32.empty()) {
             if (hipMemcpy(host.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
             FILE* fp = fopen(frame_name(f32, f, frames).c_str(), "wb");
@@ -419,6 +493,7 @@ int main(int argc, char** argv) {
         }
     }
     if (rays) (void)hipFree(rays);
+    if (vout) (void)hipFree(vout);
     if (lin) (void)hipFree(lin);
     if (srgb) (void)hipFree(srgb);
     if (dev8) (void)hipFree(dev8);

@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell, SBX_APP_SDF_SCENE with sbx_aux_sdf_scene, sbx_sdf_scene_ramp and sbx_sdf_eval, sbx_clouds_eval, sbx_planet_eval, SBX_APP_EGG_POSE with sbx_aux_egg_pose and sbx_egg_pose_default, sbx_egg_eval: new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell, SBX_APP_SDF_SCENE with sbx_aux_sdf_scene, sbx_sdf_scene_ramp and sbx_sdf_eval, sbx_clouds_eval, sbx_planet_eval, SBX_APP_EGG_POSE with sbx_aux_egg_pose and sbx_egg_pose_default, sbx_egg_eval, SBX_APP_VINYL_DECK with sbx_aux_vinyl_deck and sbx_vinyl_deck_default, sbx_vinyl_eval: new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -331,7 +331,26 @@ typedef enum sbx_app {
        SBX_PRECISION_1E4 is ignored.
        NOT OFFERED: the STRAIGHT / OVAL builds under a pose, other bone counts or a per-leg pelvis, a pose for the wheel or the egg,
        and the drop-in header sbx_mainimage.hpp, which has no way to state a block. */
-    SBX_APP_EGG_POSE = 34
+    SBX_APP_EGG_POSE = 34,
+    /* src/app_vinyl.h as shipped (SHADERTOY undefined, the C++ build's 60 march steps) over the CALLER'S DECK: the turntable whose
+       platter angle, tilts, sun, colours and groove BRDF the caller states — among them what the header's "scratching support" branch
+       (:420-425, SHADERTOY only) lets the user's hand do: set the platter's angle.  The aux block sbx_aux_vinyl_deck (below) states the
+       camera, the three angles, the sun, the five base colours, the Ward constants of illuminate and the shininess of its Phong
+       branch; aux == NULL means sbx_vinyl_deck_default(uni, .), and the frame is then SBX_APP_VINYL's in every bit.  u_res is read;
+       u_time and u_mouse are not.  Alpha is 1: the output forms are the ones SBX_APP_VINYL has.
+       SEMANTICS (tests/vinyl_deck_model.py is the definition), all as app_vinyl.h has them:
+         - everything not in the block stays the reference's literal: the geometry of platter, logo, spindle, defects and tonearm,
+           ro_diff, the groove pitch 24, the noise scale and amplitude, the 60 march steps, the 20 shadow steps, mat_debug, the white
+           background, linear_to_srgb;
+         - sun_dir is used as given, never normalised: a sun of another length scales the shadow ray's steps and the dot products;
+         - every float bit pattern is data — a sun below the disc, a zero or NaN sun, a_x = 0, a negative colour, eye == look_at — and
+           the result is what the reference's arithmetic gives, NaN pixels included: nothing is refused beyond what any app refuses.
+       sbx_set_variant 0-3 mean what they mean for SBX_APP_VINYL, except that a block outside the domain of k_vinyl's culls and hardware
+       min / max (a value beyond 1e4, 1e10 for an angle; a non-finite frame constant: csrc/sbx_vinyl.h) always takes the reference
+       form (variant 1's kernel): same bits.  The colours, Ward constants and shininess do not enter that domain.
+       NOT OFFERED: the RIDGES and NOSHADOW builds or the 180 steps of SBX_APP_VINYL_GPU under a deck, a deck for the geometry,
+       u_mouse.z (the caller states platter_deg instead), and the drop-in header sbx_mainimage.hpp, which has no way to state a block. */
+    SBX_APP_VINYL_DECK = 35
 } sbx_app;
 
 typedef enum sbx_status {
@@ -456,6 +475,25 @@ typedef struct sbx_aux_egg_pose {          /* 64 B */
  * NULL.  The feet are wheel_pos + mul(rotate_around_z(-u_time * 400.), (0, +-.3, +-.2)) by the math spec, turn_deg is the binary32
  * product u_time * -100.0f, femur .8, tibia .75, eye (0, .25, 5.25), look_at (0, .25, 0), fov 1. */
 void sbx_egg_pose_default(const sbx_uniforms* uni, sbx_aux_egg_pose* out);
+
+/* the deck of SBX_APP_VINYL_DECK and sbx_vinyl_eval: plain data, 128 bytes.  (:N names the line of src/app_vinyl.h whose value the field
+ * replaces.) */
+typedef struct sbx_aux_vinyl_deck {        /* 128 B */
+    float eye[3];            float fov;               /* :61;  :460 (main.h's FOV factor, as given) */
+    float look_at[3];        float platter_deg;       /* :62;  `rot` as handed to rotate_around_y at :427 (the reference: u_time * 200.; the
+                                                         SHADERTOY build's scratching hand of :422-424 puts u_mouse.y here) */
+    float sun_dir[3];        float platter_tilt_deg;  /* :284-285, used as given, never normalised;  the angle handed to rotate_around_x at :428 */
+    float groove_color[3];   float arm_tilt_deg;      /* :45;  the angle handed to rotate_around_x at :141-142 */
+    float dead_wax_color[3]; float ro_spec;           /* :47;  :327 */
+    float label_color[3];    float a_x;               /* :49;  :328 */
+    float logo_color[3];     float a_y;               /* :51;  :329 */
+    float shiny_color[3];    float shininess;         /* :53;  the 50. of :375 */
+} sbx_aux_vinyl_deck;
+/* Host only, no context: what app_vinyl.h makes of uni->u_time by the math spec, the block SBX_APP_VINYL_DECK renders when aux is NULL.
+ * platter_deg is the binary32 product u_time * 200.f, platter_tilt_deg sin(u_time) * .1f, arm_tilt_deg sin(u_time * 3.6758f) * .1f,
+ * sun_dir the spec's normalize(-1, 4, -3), the colours the literals of :40-54, ro_spec .0725, a_x .025, a_y .5, shininess 50, fov 1,
+ * eye (0, 5.75, 6.75), look_at (0, -2.5, 0). */
+void sbx_vinyl_deck_default(const sbx_uniforms* uni, sbx_aux_vinyl_deck* out);
 
 typedef struct sbx_ctx sbx_ctx;
 
@@ -779,6 +817,24 @@ int sbx_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const float* in,
  * SBX_OK and touches nothing; SBX_ERR_ARG, with nothing written, for a NULL ctx / fn / in / out, a NULL pose for any name but
  * "ik_solver", an unknown name, n > 2^31. */
 int sbx_egg_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, const float* in, float* out, size_t n, void* stream);
+/* The turntable's field, normal, soft shadow, shading and trace (src/app_vinyl.h as shipped) as standalone functions over n elements of
+ * the caller's, under the caller's deck: what the reference reaches only through pixels of two fixed cameras — the field for collision
+ * queries, the anisotropic groove BRDF of illuminate for a host's own surfaces, the trace for another camera or a reflection.  `deck`:
+ * HOST memory, read during the call; the camera fields (eye, fov, look_at) are not read.  `in`, `out`: device memory, not overlapping,
+ * 4-byte alignment suffices.  Per element:
+ *   "sdf" (:251-259)          in 3: pos (world).  out 2: the distance, the material id as a float.
+ *   "sdf_normal" (:261-272)   in 3: p.  out 3.
+ *   "sdf_shadow" (:381-405)   in 6: origin xyz, direction xyz.  out 1.
+ *   "illuminate" (:287-379)   in 7: eye xyz, hit.origin xyz, the material id as a float.  out 3.  int() of the id is taken as :439
+ *                             does — toward zero, saturating at the ends of int, 0 for a NaN; an id outside 1-5 takes the `else`
+ *                             branch, with the white of mat_debug for 0 and the zero colour of an unset slot for any other.
+ *   "render" (:407-458)       in 6: origin xyz, direction xyz.  out 5: the LINEAR rgb it returns (no sRGB), `t` as it stands where
+ *                             render returns, then the hit's material id as a float, or 0 where :457 returned the background.
+ * Directions are used as given, never normalised; the shadow ray of "render" is the block's sun_dir.  Exact for every bit pattern,
+ * NaN results included.  Asynchronous on `stream` and capturable (inside a capture it allocates nothing, queries nothing and waits
+ * for nothing); not counted in sbx_stats.render_launches; sbx_set_variant 1 selects the plain statement (same bits).  n == 0 returns
+ * SBX_OK and touches nothing; SBX_ERR_ARG, with nothing written, for a NULL ctx / fn / deck / in / out, an unknown name, n > 2^31. */
+int sbx_vinyl_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck* deck, const float* in, float* out, size_t n, void* stream);
 /* The size^3 RGBA32F noise volume util/ddsvolgen bakes (ddsvolgen.cpp:101-117): R =
  * fbm_worley_tile((xyz + .5)/size, 2, 1, .5), G = B = A = 0, x fastest.  `rgba`: size^3 * 4 floats. */
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream);

@@ -80,7 +80,7 @@
 #define SBX_SELECTED_APP SBX_APP_ATMOSPHERE
 #elif defined(APP_SDF_AO)
 #define SBX_SELECTED_APP SBX_APP_SDF_AO
-#elif defined(APP_VINYL)
+#elif defined(APP_VINYL)          /* (SBX_APP_VINYL_DECK, the same header over the caller's deck, has no define here: this header has no way to state a block; include/sbx.h) */
 #define SBX_SELECTED_APP SBX_APP_VINYL
 #elif defined(APP_CLOUDS_BEST)   /* src/app_clouds_best.h, the stand-alone shader (no APP_* define in the reference) */
 #define SBX_SELECTED_APP SBX_APP_CLOUDS_BEST

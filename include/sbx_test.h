@@ -44,6 +44,12 @@ extern "C" {
  * value of the block beyond 1e4, 1e10 for the angle) takes 1 whatever is set.  sbx_egg_eval: 1 = CULL = false and the IEEE roots for every
  * wave; 2 / 3 = the witness's test edge / the IEEE roots; 0 takes the plain form only for such a pose and for the waves whose own inputs
  * hold a value beyond 1e4 or a NaN (csrc/kern_egg_eval.hip).  "ik_solver" has one form.
+ * SBX_APP_VINYL_DECK: every value as for APP_VINYL; a deck outside the domain of the culls and the hardware min / max (a value of the
+ * block's first sixteen beyond 1e4, 1e10 for the three angles, a non-finite camera or matrix: csrc/sbx_vinyl.h, sbx_frames.hip
+ * vinyl_deck_tame) takes 1 whatever is set; sbx_debug_vinyl_deck_launches counts such launches.  sbx_vinyl_eval: 1 = CULL = false, the IEEE roots and
+ * compare-and-select unions for every wave; 2 / 3 = the witness's test edge / the IEEE roots; 0 takes the plain form only for such a deck
+ * (the camera's fields ignored) and for the waves whose own points or directions hold a value beyond 1e4 or a NaN
+ * (csrc/kern_vinyl_eval.hip).
  * All variants are specified to produce identical bits (tests/test_gpu_parity.py sweeps them against each other). */
 int sbx_set_variant(sbx_ctx* ctx, int variant);
 
@@ -76,6 +82,16 @@ int sbx_debug_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const floa
  * tools/time_egg_eval.py. */
 int sbx_debug_egg_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, const float* in, float* out, size_t n,
                        unsigned counts_host[2], void* stream);
+
+/* sbx_vinyl_eval (sbx.h) with counts: the same launch (the context's variant included) followed by a wait, after which counts_host[0]
+ * holds the waves that took the witnessed roots only and counts_host[1] the waves that re-ran with the IEEE roots because a lane
+ * recorded a root outside the witness's interval.  A wave given the plain form (variant 1 or 3, an untame deck, an untame input) is in
+ * neither.  It allocates and synchronises, so it is not capturable.  For tests/test_gpu_vinyl_eval.py and tools/time_vinyl_eval.py. */
+int sbx_debug_vinyl_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck* deck, const float* in, float* out, size_t n,
+                         unsigned counts_host[2], void* stream);
+/* SBX_APP_VINYL_DECK launches of this context so far, and how many of them took the reference form because their deck was outside the
+ * domain of the culls (whatever variant was set; a launch under sbx_set_variant 1 with a tame deck is not among the latter). */
+int sbx_debug_vinyl_deck_launches(sbx_ctx* ctx, uint64_t counts[2]);
 
 /* Device evaluation of the math spec, elementwise over device arrays (for parity tests):
  * fn in {"sin","cos","tan","exp","pow","acos","atan2","hash","div","div_rd","exp_h13","pow_h","sqrt_n","sqrt_ieee","exp_reg","exp_reg_plain","exp_reg64","exp_reg64_plain","exp_small","exp_small_plain","exp_reg4k","sin_b40","div3","sqrt_rs","divn","srgb_pow","pow_spec"}; b may be NULL

@@ -17,7 +17,7 @@ from . import shard  # noqa: F401  (pure-python row-block arithmetic, no GPU nee
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsbx.so")
 
-APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW, APP_PLANET_CLOSEUP, APP_PLANET_CLOUDLESS, APP_PLANET_UNLIT, APP_RAYTRACER_SCENE, APP_SDF_SCENE, APP_EGG_POSE = range(35)
+APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW, APP_PLANET_CLOSEUP, APP_PLANET_CLOUDLESS, APP_PLANET_UNLIT, APP_RAYTRACER_SCENE, APP_SDF_SCENE, APP_EGG_POSE, APP_VINYL_DECK = range(36)
 APPS = {"APP_PLANET": APP_PLANET, "APP_CLOUDS": APP_CLOUDS, "APP_VINYL": APP_VINYL, "APP_EGG": APP_EGG,
         "APP_RAYTRACER": APP_RAYTRACER, "APP_ATMOSPHERE": APP_ATMOSPHERE, "APP_SDF_AO": APP_SDF_AO,
         "APP_CLOUDS_BEST": APP_CLOUDS_BEST,    # src/app_clouds_best.h (stand-alone shader, not an APP_* define)
@@ -48,6 +48,7 @@ MORE_APPS = {"APP_EGG_STRAIGHT": APP_EGG_STRAIGHT,  # APP_EGG without `#define B
              "APP_PLANET_CLOUDLESS": APP_PLANET_CLOUDLESS,  # APP_PLANET without the `#define CLOUDS` of src/app_planet.h:63: no cloud march, no cloud shadow
              "APP_PLANET_UNLIT": APP_PLANET_UNLIT,          # APP_PLANET without the `#define LIGHT` of src/app_planet.h:249: N = w_normal.y, ocean = water
              "APP_RAYTRACER_SCENE": APP_RAYTRACER_SCENE,    # src/app_raytracer.h's render over the caller's scene: aux = a RaytracerScene (cornell_scene, raytracer_scene)
+             "APP_VINYL_DECK": APP_VINYL_DECK,              # src/app_vinyl.h as shipped over the caller's deck (platter angle, tilts, sun, colours, groove BRDF): aux = a VinylDeck (vinyl_deck_default, vinyl_deck)
              "APP_EGG_POSE": APP_EGG_POSE,                  # src/app_egg.h as shipped with the rider posed by the caller (src/IK.h at work): aux = an EggPose (egg_pose_default, egg_pose)
              "APP_SDF_SCENE": APP_SDF_SCENE}                # src/app_sdf_ao.h's renderer over the caller's field, a program of src/sdf.h's primitives and operators: aux = an SdfScene (sdf_ramp_scene, SdfSceneBuilder)
 ALL_APPS = {**APPS, **MORE_APPS}
@@ -132,6 +133,17 @@ class EggPose(ctypes.Structure):            # sbx_aux_egg_pose (the aux block of
                 ("look_at", ctypes.c_float * 3), ("turn_deg", ctypes.c_float),
                 ("left_foot", ctypes.c_float * 3), ("femur", ctypes.c_float),
                 ("right_foot", ctypes.c_float * 3), ("tibia", ctypes.c_float)]
+
+
+class VinylDeck(ctypes.Structure):          # sbx_aux_vinyl_deck (the aux block of APP_VINYL_DECK and the deck of vinyl_eval, 128 bytes)
+    _fields_ = [("eye", ctypes.c_float * 3), ("fov", ctypes.c_float),
+                ("look_at", ctypes.c_float * 3), ("platter_deg", ctypes.c_float),
+                ("sun_dir", ctypes.c_float * 3), ("platter_tilt_deg", ctypes.c_float),
+                ("groove_color", ctypes.c_float * 3), ("arm_tilt_deg", ctypes.c_float),
+                ("dead_wax_color", ctypes.c_float * 3), ("ro_spec", ctypes.c_float),
+                ("label_color", ctypes.c_float * 3), ("a_x", ctypes.c_float),
+                ("logo_color", ctypes.c_float * 3), ("a_y", ctypes.c_float),
+                ("shiny_color", ctypes.c_float * 3), ("shininess", ctypes.c_float)]
 
 
 SDF_MAX_INSTR, SDF_MAX_STACK = 32, 4         # SBX_SDF_MAX_INSTR, SBX_SDF_MAX_STACK
@@ -362,6 +374,11 @@ def load_library(path=None):
     lib.sbx_egg_pose_default.restype = None
     lib.sbx_egg_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(EggPose), fp, fp, ctypes.c_size_t, vp]
     lib.sbx_debug_egg_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(EggPose), fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
+    lib.sbx_vinyl_deck_default.argtypes = [ctypes.POINTER(Uniforms), ctypes.POINTER(VinylDeck)]
+    lib.sbx_vinyl_deck_default.restype = None
+    lib.sbx_vinyl_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(VinylDeck), fp, fp, ctypes.c_size_t, vp]
+    lib.sbx_debug_vinyl_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(VinylDeck), fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
+    lib.sbx_debug_vinyl_deck_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.sbx_debug_raytracer_scene_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.sbx_create.argtypes = [ci, ctypes.POINTER(vp)]
     lib.sbx_destroy.argtypes = [vp]
@@ -548,6 +565,30 @@ def egg_pose(left_foot=(0.0, 1.5, 0.2), right_foot=(0.0, 0.9, -0.2), turn_deg=0.
     a.eye[:], a.look_at[:] = [float(v) for v in eye], [float(v) for v in look_at]
     a.left_foot[:], a.right_foot[:] = [float(v) for v in left_foot], [float(v) for v in right_foot]
     a.fov, a.turn_deg, a.femur, a.tibia = float(fov), float(turn_deg), float(femur), float(tibia)
+    return a
+
+
+def vinyl_deck_default(time, lib=None):
+    """sbx_vinyl_deck_default (host only, no GPU needed): the VinylDeck that src/app_vinyl.h makes of `time` — what APP_VINYL_DECK
+    renders when aux is None, the frame of APP_VINYL."""
+    lib = lib or load_library()
+    u = uniforms(1, 1, time)
+    a = VinylDeck()
+    lib.sbx_vinyl_deck_default(ctypes.byref(u), ctypes.byref(a))
+    return a
+
+
+def vinyl_deck(time=0.0, lib=None, **fields):
+    """A VinylDeck (the aux block of APP_VINYL_DECK, the deck of Renderer.vinyl_eval): vinyl_deck_default(time) with the named fields of
+    sbx_aux_vinyl_deck replaced, each value rounded to binary32 — platter_deg=... over a frame sequence is the scratch."""
+    a = vinyl_deck_default(time, lib)
+    for name, value in fields.items():
+        if name not in dict(VinylDeck._fields_):
+            raise SbxError(SBX_ERR_ARG, "sbx_aux_vinyl_deck has no field %r" % (name,))
+        if isinstance(getattr(a, name), float):
+            setattr(a, name, float(value))
+        else:
+            getattr(a, name)[:] = [float(v) for v in value]
     return a
 
 
@@ -1185,6 +1226,43 @@ class Renderer:
         else:
             self._check(self.lib.sbx_debug_egg_eval(*args, counts, self._stream()))
         return out
+
+    # sbx_vinyl_eval: floats per element in / out
+    VINYL_EVAL_WIDTHS = {"sdf": (3, 2), "sdf_normal": (3, 3), "sdf_shadow": (6, 1), "illuminate": (7, 3), "render": (6, 5)}
+
+    def vinyl_eval(self, fn, x, deck):
+        """APP_VINYL's field, normal, soft shadow, shading and trace over the caller's elements under a VinylDeck (include/sbx.h
+        sbx_vinyl_eval): fn 'sdf' over points x[n, 3] -> [n, 2] (distance, material id); 'sdf_normal' x[n, 3] -> [n, 3]; 'sdf_shadow'
+        over rays x[n, 6] (origin xyz, direction xyz) -> [n, 1]; 'illuminate' over x[n, 7] (eye xyz, hit xyz, material id) -> [n, 3];
+        'render' over rays x[n, 6] -> [n, 5] (linear rgb, t, material id or 0).  The deck's camera fields are not read."""
+        return self._vinyl_eval(fn, x, deck, None)
+
+    def vinyl_eval_counted(self, fn, x, deck):
+        """include/sbx_test.h sbx_debug_vinyl_eval: vinyl_eval that waits -> (out, (waves that took the witnessed roots only, waves
+        that re-ran with the IEEE roots))"""
+        counts = (ctypes.c_uint * 2)(0, 0)
+        return self._vinyl_eval(fn, x, deck, counts), (int(counts[0]), int(counts[1]))
+
+    def _vinyl_eval(self, fn, x, deck, counts):
+        if fn not in self.VINYL_EVAL_WIDTHS:
+            raise SbxError(SBX_ERR_ARG, "unknown vinyl function %r" % (fn,))
+        win, wout = self.VINYL_EVAL_WIDTHS[fn]
+        x = x.to(self.tdev, self.torch.float32).contiguous().view(x.numel() // win, win)
+        out = self.torch.empty((x.shape[0], wout), dtype=self.torch.float32, device=self.tdev)
+        args = (self.ctx, fn.encode(), None if deck is None else ctypes.byref(deck), ctypes.c_void_p(x.data_ptr()),
+                ctypes.c_void_p(out.data_ptr()), x.shape[0])
+        if counts is None:
+            self._check(self.lib.sbx_vinyl_eval(*args, self._stream()))
+        else:
+            self._check(self.lib.sbx_debug_vinyl_eval(*args, counts, self._stream()))
+        return out
+
+    def vinyl_deck_launches(self):
+        """include/sbx_test.h sbx_debug_vinyl_deck_launches: (APP_VINYL_DECK launches of this context, those of them an untame deck sent
+        to the reference form)"""
+        c = (ctypes.c_uint64 * 2)(0, 0)
+        self._check(self.lib.sbx_debug_vinyl_deck_launches(self.ctx, c))
+        return int(c[0]), int(c[1])
 
     def sdf_eval(self, scene, xyz):
         """sdf(pos) of an SdfScene's program over points xyz[n, 3] (include/sbx.h sbx_sdf_eval) -> [n, 2]: the distance and the

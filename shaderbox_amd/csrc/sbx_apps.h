@@ -8,7 +8,7 @@
 
 namespace sbx {
 
-constexpr int SBX_APP_COUNT = SBX_APP_EGG_POSE + 1;
+constexpr int SBX_APP_COUNT = SBX_APP_VINYL_DECK + 1;
 // (sbx_debug_tile_order, include/sbx_test.h, answers for every app — the builds after SBX_APP_FUNC that have an order grid below
 // included; an app without one never has a table: 0 tables, 0 launches, nothing to copy)
 
@@ -22,7 +22,7 @@ constexpr int SBX_APP_COUNT = SBX_APP_EGG_POSE + 1;
 //                      the table's key — a scene that stands still gets its table, a moving one never does
 enum { TILE_SCENE_FREE = 0, TILE_SCENE_REFRESH = 1, TILE_SCENE_KEYED = 2 };
 
-enum AuxKind { AUX_NONE, AUX_CLOUDS, AUX_SDF_AO, AUX_CLOUDS_UE4, AUX_RT_SCENE, AUX_SDF_SCENE, AUX_EGG_POSE };   // which block `aux` points to: sbx_aux_clouds, sbx_aux_sdf_ao, sbx_aux_clouds_ue4, sbx_aux_raytracer_scene, sbx_aux_sdf_scene, sbx_aux_egg_pose
+enum AuxKind { AUX_NONE, AUX_CLOUDS, AUX_SDF_AO, AUX_CLOUDS_UE4, AUX_RT_SCENE, AUX_SDF_SCENE, AUX_EGG_POSE, AUX_VINYL_DECK };   // which block `aux` points to: sbx_aux_clouds, sbx_aux_sdf_ao, sbx_aux_clouds_ue4, sbx_aux_raytracer_scene, sbx_aux_sdf_scene, sbx_aux_egg_pose, sbx_aux_vinyl_deck
 
 struct AppTraits {
     AuxKind aux;
@@ -69,6 +69,7 @@ constexpr AppTraits kApps[] = {
     /* SBX_APP_RAYTRACER_SCENE   */ {AUX_RT_SCENE, false, false, nullptr, TILE_SCENE_FREE},
     /* SBX_APP_SDF_SCENE         */ {AUX_SDF_SCENE, false, false, nullptr, TILE_SCENE_FREE},
     /* SBX_APP_EGG_POSE          */ {AUX_EGG_POSE, false, false, egg_grid, TILE_SCENE_KEYED},
+    /* SBX_APP_VINYL_DECK        */ {AUX_VINYL_DECK, false, false, vinyl_grid, TILE_SCENE_KEYED},
 };
 static_assert(sizeof(kApps) / sizeof(kApps[0]) == SBX_APP_COUNT, "every value of enum sbx_app needs its row in kApps");
 
@@ -83,6 +84,7 @@ inline int app_aux_bytes(int app) {
     case AUX_RT_SCENE: return (int)sizeof(sbx_aux_raytracer_scene);
     case AUX_SDF_SCENE: return (int)sizeof(sbx_aux_sdf_scene);
     case AUX_EGG_POSE: return (int)sizeof(sbx_aux_egg_pose);
+    case AUX_VINYL_DECK: return (int)sizeof(sbx_aux_vinyl_deck);
     default: return 0;
     }
 }
@@ -111,6 +113,12 @@ inline sbx_aux_sdf_scene aux_sdf_scene(const void* aux, const sbx_uniforms& uni)
 inline sbx_aux_egg_pose aux_egg_pose(const void* aux, const sbx_uniforms& uni) {
     sbx_aux_egg_pose a;
     if (aux) a = *(const sbx_aux_egg_pose*)aux; else sbx_egg_pose_default(&uni, &a);
+    return a;
+}
+// SBX_APP_VINYL_DECK: the caller's deck, or what app_vinyl.h makes of these uniforms
+inline sbx_aux_vinyl_deck aux_vinyl_deck(const void* aux, const sbx_uniforms& uni) {
+    sbx_aux_vinyl_deck a;
+    if (aux) a = *(const sbx_aux_vinyl_deck*)aux; else sbx_vinyl_deck_default(&uni, &a);
     return a;
 }
 

@@ -212,6 +212,8 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     }
     sbx_aux_egg_pose EP;
     if (T.aux == AUX_EGG_POSE) EP = aux_egg_pose(aux, *uni);               // (every bit pattern is data: nothing to refuse)
+    sbx_aux_vinyl_deck VD;
+    if (T.aux == AUX_VINYL_DECK) VD = aux_vinyl_deck(aux, *uni);           // (likewise)
     if (T.noise_volumes && !ctx->noise.shape) return fail(ctx, SBX_ERR_ARG, "APP_CLOUDS with USE_NOISE_TEX needs sbx_set_noise_volume first");
     const bool capturing = stream_is_capturing(s);
     TimingPair* tp = nullptr;
@@ -250,6 +252,7 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
         mix(uni, sizeof(*uni));
         if (T.aux == AUX_CLOUDS) mix(&AC, sizeof(AC));
         if (T.aux == AUX_EGG_POSE) mix(&EP, sizeof(EP));                   // (the pose IS the scene: a pose that stands still gets its table)
+        if (T.aux == AUX_VINYL_DECK) mix(&VD, sizeof(VD));                 // (and so is the deck: one deck is never served another's table)
     }
     TileOrder* const ordered = tile_order_begin(ctx->tile_orders, app, M, og, s, capturing, scene, T.scene_policy);
     switch (app) {
@@ -308,6 +311,16 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     case SBX_APP_VINYL_CLOSEUP: launch_vinyl(build_vinyl(*uni, 60, VINYL_CLOSEUP), M, rgba, s, sdf_variant, VINYL_CLOSEUP); break;
     case SBX_APP_VINYL_RIDGES: launch_vinyl(build_vinyl(*uni, 60), M, rgba, s, sdf_variant, VINYL_RIDGES); break;
     case SBX_APP_VINYL_NOSHADOW: launch_vinyl(build_vinyl(*uni, 60), M, rgba, s, sdf_variant, VINYL_NOSHADOW); break;
+    // the shipped build over the caller's deck (include/sbx.h): k_vinyl's pixel with illuminate's literals as data (k_vinyl_deck) over
+    // another frame block.  u_time is not read, so its tameness does not enter: the deck's does (sbx_frames.hip vinyl_deck_tame)
+    case SBX_APP_VINYL_DECK: {
+        const FrameVinyl F = build_vinyl_deck(*uni, VD, 60);
+        const bool tame = vinyl_deck_tame(VD, F);
+        ctx->stats.vinyl_deck_launches.fetch_add(1, std::memory_order_relaxed);
+        if (!tame) ctx->stats.vinyl_deck_untame.fetch_add(1, std::memory_order_relaxed);
+        launch_vinyl_deck(F, vinyl_shade_of(VD), M, rgba, s, !tame || ctx->variant == 1 ? 1 : ctx->sdf_roots);
+        break;
+    }
     case SBX_APP_CLOUDS_BEST: launch_clouds_best(build_clouds_best(*uni), M, rgba, s); break;
     case SBX_APP_CLOUDS_UE4: launch_clouds_ue4(build_clouds_ue4(*uni, aux_clouds_ue4(aux)), M, rgba, s); break;
     case SBX_APP_2D: (void)launch_2d(build_2d(*uni), M, rgba, s, false); break;   // (three-channel maps were refused above)
@@ -593,6 +606,13 @@ int sbx_debug_clouds_hashtab_read(sbx_ctx* ctx, size_t first, size_t count, floa
 int sbx_debug_raytracer_scene_launches(sbx_ctx* ctx, uint64_t* launches) {
     if (!ctx || !launches) return SBX_ERR_ARG;
     *launches = ctx->stats.rt_scene_launches.load(std::memory_order_relaxed);
+    return SBX_OK;
+}
+
+int sbx_debug_vinyl_deck_launches(sbx_ctx* ctx, uint64_t counts[2]) {
+    if (!ctx || !counts) return SBX_ERR_ARG;
+    counts[0] = ctx->stats.vinyl_deck_launches.load(std::memory_order_relaxed);
+    counts[1] = ctx->stats.vinyl_deck_untame.load(std::memory_order_relaxed);
     return SBX_OK;
 }
 

@@ -141,6 +141,7 @@ struct Stats {
     Stripe hits[16];
     std::atomic<uint64_t> launches{0}, frames{0}, points{0};
     std::atomic<uint64_t> rt_scene_launches{0};   // k_raytracer_scene launches (sbx_debug_raytracer_scene_launches; never reset)
+    std::atomic<uint64_t> vinyl_deck_launches{0}, vinyl_deck_untame{0};   // SBX_APP_VINYL_DECK launches, and those an untame deck sent to the reference form (sbx_debug_vinyl_deck_launches; never reset)
 };
 
 // sbx_render_rows_host: device staging of a host frame, the stream its strips are copied out on, one event per strip.
@@ -225,6 +226,11 @@ FrameAtmosphere build_atmosphere(const sbx_uniforms& U);
 FrameAtmosphere build_atmosphere_ground(const sbx_uniforms& U);
 FrameSdfAo build_sdf_ao(const sbx_uniforms& U, const sbx_aux_sdf_ao& A);
 FrameVinyl build_vinyl(const sbx_uniforms& U, int steps, int build = VINYL_DEFAULT);   // build: VINYL_* (sbx_frame.h); VINYL_CLOSEUP is the other camera
+// SBX_APP_VINYL_DECK / sbx_vinyl_eval: the frame of the caller's deck (build_vinyl is this over the default block), the shading data
+// of its kernels, and whether k_vinyl's culls and hardware min / max stand for it (false: the reference form, sbx_set_variant 1's kernel)
+FrameVinyl build_vinyl_deck(const sbx_uniforms& U, const sbx_aux_vinyl_deck& A, int steps);
+VinylShade vinyl_shade_of(const sbx_aux_vinyl_deck& A);
+bool vinyl_deck_tame(const sbx_aux_vinyl_deck& A, const FrameVinyl& F);
 FramePlanet build_planet(const sbx_uniforms& U, bool atm_sky = false, int build = PLANET_DEFAULT);   // build: PLANET_* (sbx_frame.h); PLANET_CLOSEUP is the other camera
 FrameCloudsBest build_clouds_best(const sbx_uniforms& U);
 FrameCloudsUe4 build_clouds_ue4(const sbx_uniforms& U, const sbx_aux_clouds_ue4& A);

@@ -210,6 +210,8 @@ dim3 atmosphere_grid(const RowMap& M);
 dim3 planet_grid(const RowMap& M);
 dim3 sdf_ao_grid(const RowMap& M);
 dim3 vinyl_grid(const RowMap& M);
+// SBX_APP_VINYL_DECK (kern_vinyl.hip k_vinyl_deck): the shipped pixel with illuminate's literals read from D; variant as launch_vinyl's
+void launch_vinyl_deck(const FrameVinyl& F, const VinylShade& D, const RowMap& M, float* out, hipStream_t s, int variant);
 dim3 clouds_best_grid(const RowMap& M);
 dim3 clouds_ue4_grid(const RowMap& M);
 bool launch_2d(const Frame2d& F, const RowMap& M, float* out, hipStream_t s, bool tex);   // false: a three-channel map (nothing launched)
@@ -235,6 +237,10 @@ void launch_planet_eval(int fn, const FramePlanet& F, bool plain, const float* i
 // launch_egg's (1 = the reference form); counts: NULL, or two zeroed device words (witnessed waves, re-run waves).  launch_ik_eval: "ik_solver"
 void launch_egg_eval(int fn, const FrameEgg& F, int variant, const float* in, float* out, size_t n, unsigned* counts, hipStream_t s);
 void launch_ik_eval(const float* in, float* out, size_t n, hipStream_t s);
+// sbx_vinyl_eval (kern_vinyl_eval.hip): fn 0 sdf / 1 sdf_normal / 2 sdf_shadow / 3 illuminate / 4 render over build_vinyl_deck's frame
+// and vinyl_shade_of's data; variant as launch_vinyl's (1 = the reference form); counts: NULL, or two zeroed device words
+void launch_vinyl_eval(int fn, const FrameVinyl& F, const VinylShade& D, int variant, const float* in, float* out, size_t n,
+                       unsigned* counts, hipStream_t s);
 int launch_math_eval(int fn, const float* a, const float* b, float* out, size_t n, hipStream_t s);
 void launch_cl_exp_eval(const float* a, float* out, size_t n, hipStream_t s, int form);   // exp_reg_ / exp_reg128_ forms (kern_clouds.hip)
 

@@ -301,6 +301,66 @@ int sbx_debug_egg_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pos
     return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "egg_eval (counted)", e);
 }
 
+// the checks sbx_vinyl_eval and its test hook share: SBX_OK with fn_id set (launch_vinyl_eval's fn), or the failure
+static int vinyl_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck* deck, const float* in, const float* out, size_t n, int& fn_id) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!fn || !deck) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    static const char* names[] = {"sdf", "sdf_normal", "sdf_shadow", "illuminate", "render"};
+    fn_id = -1;
+    for (int i = 0; i < 5; ++i) if (std::strcmp(fn, names[i]) == 0) fn_id = i;
+    if (fn_id < 0) return fail(ctx, SBX_ERR_ARG, "unknown vinyl function");
+    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 elements");
+    if (n == 0) return SBX_OK;
+    if (!in || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    return SBX_OK;
+}
+// the launch of either: the frame of the block over a 1 x 1 frame with the shipped camera in place of the block's (the kernel reads no
+// camera; a deck outside the domain of the culls, sbx_frames.hip vinyl_deck_tame with the camera's fields so ignored, takes the
+// reference form)
+static void vinyl_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_vinyl_deck* deck, const float* in, float* out, size_t n, unsigned* counts,
+                              hipStream_t s) {
+    const sbx_uniforms U = {{1.f, 1.f}, {0.f, 0.f}, 0.f, {0.f, 0.f, 0.f}};
+    sbx_aux_vinyl_deck A = *deck;
+    A.eye[0] = 0.f; A.eye[1] = 5.75f; A.eye[2] = 6.75f; A.look_at[0] = 0.f; A.look_at[1] = -2.5f; A.look_at[2] = 0.f; A.fov = 1.f;
+    const FrameVinyl F = build_vinyl_deck(U, A, 60);
+    const int variant = ctx->variant == 1 || !vinyl_deck_tame(A, F) ? 1 : ctx->sdf_roots;
+    launch_vinyl_eval(id, F, vinyl_shade_of(A), variant, in, out, n, counts, s);
+}
+
+int sbx_vinyl_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck* deck, const float* in, float* out, size_t n, void* stream) {
+    int id = -1;
+    int rc = vinyl_eval_args(ctx, fn, deck, in, out, n, id);
+    if (rc != SBX_OK || n == 0) return rc;
+    if ((rc = use_device(ctx)) != SBX_OK) return rc;
+    vinyl_eval_launch(ctx, id, deck, in, out, n, nullptr, (hipStream_t)stream);
+    return launched(ctx, "vinyl_eval launch");
+}
+
+int sbx_debug_vinyl_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck* deck, const float* in, float* out, size_t n,
+                         unsigned counts_host[2], void* stream) {
+    int id = -1;
+    int rc = vinyl_eval_args(ctx, fn, deck, in, out, n, id);
+    if (rc != SBX_OK) return rc;
+    if (!counts_host) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    counts_host[0] = counts_host[1] = 0;
+    if (n == 0) return SBX_OK;
+    if ((rc = use_device(ctx)) != SBX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_is_capturing(s)) return fail(ctx, SBX_ERR_ARG, "the counted launch is not capturable");
+    unsigned* counts = nullptr;
+    hipError_t e = hipMalloc((void**)&counts, 2 * sizeof(unsigned));
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
+    if ((e = hipMemsetAsync(counts, 0, 2 * sizeof(unsigned), s)) == hipSuccess) {
+        vinyl_eval_launch(ctx, id, deck, in, out, n, counts, s);
+        unsigned h[2] = {0, 0};
+        if ((e = hipGetLastError()) == hipSuccess && (e = hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, s)) == hipSuccess)
+            e = hipStreamSynchronize(s);
+        counts_host[0] = h[0]; counts_host[1] = h[1];
+    }
+    (void)hipFree(counts);
+    return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "vinyl_eval (counted)", e);
+}
+
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream) {
     if (!ctx) return SBX_ERR_ARG;
     if (!rgba || size <= 0 || size > 1024) return fail(ctx, SBX_ERR_ARG, "bad volume arguments");

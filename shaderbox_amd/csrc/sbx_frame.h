@@ -320,7 +320,16 @@ struct FrameVinyl {
 // _VINYL_NOSHADOW (render's `#if 1` at :445 off), _VINYL_CLOSEUP (setup_camera's `#if 1` at :60 off).  RIDGES and NOSHADOW are kernel
 // template parameters (kern_vinyl.hip); CLOSEUP is another camera in the frame block for the shipped kernels (build_vinyl).
 // FrameVinyl is the same type in all four.
-enum { VINYL_DEFAULT = 0, VINYL_RIDGES = 1, VINYL_NOSHADOW = 2, VINYL_CLOSEUP = 3 };
+enum { VINYL_DEFAULT = 0, VINYL_RIDGES = 1, VINYL_NOSHADOW = 2, VINYL_CLOSEUP = 3, VINYL_DECK = 4 };
+// VINYL_DECK (SBX_APP_VINYL_DECK, sbx_vinyl_eval): the shipped hit block with illuminate's literals read from the caller's block.  The
+// choice: an argument of its OWN beside an unchanged FrameVinyl, not new members of FrameVinyl — the frame block is the first kernel
+// argument of all five shipped apps and is copied word by word into LDS (sbx_ldsframe.h), so any member added to it changes their
+// argument list, their LDS size and their device code; these 19 words are read once per hit pixel, after the march, and sit in SGPRs.
+struct VinylShade {
+    v3 color[5];               // materials[mat_groove .. mat_shiny].base_color                app_vinyl.h:45-53
+    float ro_spec, a_x, a_y;   //                                                             :327-329
+    float shininess;           // the exponent of :375
+};
 
 // ---- APP_2D / APP_2D_TEX (src/app_2d.h:70-111; not APP_* defines of the reference) -----------------
 // Everything mainImage decides from the uniforms alone: the phase of t = mod(u_time, 16) (:80-103; 4 = none of the four branches

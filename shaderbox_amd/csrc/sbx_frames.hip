@@ -472,17 +472,71 @@ static Capsule capsule(v3 a, v3 b) {                                   // sdf.h:
     c.rd = recip64(dot(c.ab, c.ab));
     return c;
 }
+// What setup_scene (:40-54), setup_camera (:56-67), render (:419-428), sdf_tonearm (:141-142), illuminate (:327-329, :375) and :284-285 of
+// app_vinyl.h make of u_time or state as literals, as the block of SBX_APP_VINYL_DECK (include/sbx.h): the ONE statement of the shipped
+// deck — build_vinyl and sbx_vinyl_deck_default both read it
+static void vinyl_default_deck(const sbx_uniforms& U, sbx_aux_vinyl_deck& A) {
+    auto put = [](float* d, v3 v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; };
+    put(A.eye, V3(0, 5.75f, 6.75f));                                   // :61
+    put(A.look_at, V3(0, -2.5f, 0));                                   // :62
+    A.fov = 1.f;                                                       // :460
+    const float t = U.u_time;
+    A.platter_deg = t * 200.f;                                         // :419
+    A.platter_tilt_deg = sin_(t) * .1f;                                // :428
+    A.arm_tilt_deg = sin_(t * 3.6758f) * .1f;                          // :141-142
+    put(A.sun_dir, normalize(V3(-1, 4, -3)));                          // :284-285
+    put(A.groove_color, V3(.01f, .01f, .01f));                         // :45
+    put(A.dead_wax_color, V3(.05f, .05f, .05f));                       // :47
+    put(A.label_color, V3(.5f, .5f, .0f));                             // :49
+    put(A.logo_color, V3(0, 0, .7f));                                  // :51
+    put(A.shiny_color, V3(.7f, .7f, .7f));                             // :53
+    A.ro_spec = .0725f; A.a_x = .025f; A.a_y = .5f;                    // :327-329
+    A.shininess = 50.f;                                                // :375
+}
 FrameVinyl build_vinyl(const sbx_uniforms& U, int steps, int build) {
+    sbx_aux_vinyl_deck A;
+    vinyl_default_deck(U, A);
+    if (build == VINYL_CLOSEUP) {                                      // setup_camera's `#else` :64-65
+        A.eye[0] = -2; A.eye[1] = 1.5f; A.eye[2] = 5.5f;
+        A.look_at[0] = -1.5f; A.look_at[1] = 0; A.look_at[2] = 0;
+    }
+    return build_vinyl_deck(U, A, steps);
+}
+VinylShade vinyl_shade_of(const sbx_aux_vinyl_deck& A) {
+    auto get = [](const float* d) { return V3(d[0], d[1], d[2]); };
+    VinylShade D;
+    D.color[0] = get(A.groove_color); D.color[1] = get(A.dead_wax_color); D.color[2] = get(A.label_color);
+    D.color[3] = get(A.logo_color); D.color[4] = get(A.shiny_color);
+    D.ro_spec = A.ro_spec; D.a_x = A.a_x; D.a_y = A.a_y; D.shininess = A.shininess;
+    return D;
+}
+// Do k_vinyl's culls and hardware min / max stand for this deck?  The domain is argued at the top of sbx_vinyl.h: every value of the
+// block's first sixteen (camera, angles, sun) finite and within 1e4 in magnitude — the three angles within 1e10, the bound
+// sbx_capi.hip's tame_time puts on u_time * 200 — and every derived constant of the frame finite.  The colours and shading constants
+// are not part of it.  Anything else renders with the reference form (CULL = false, IEEE roots: sbx_set_variant 1's kernel).
+bool vinyl_deck_tame(const sbx_aux_vinyl_deck& A, const FrameVinyl& F) {
+    static_assert(sizeof(sbx_aux_vinyl_deck) == 32 * sizeof(float), "sbx_aux_vinyl_deck is 32 floats (include/sbx.h)");
+    float a[16];                                                       // eye, fov, look_at, platter_deg, sun_dir, platter_tilt_deg, groove_color, arm_tilt_deg
+    std::memcpy(a, &A, sizeof(a));
+    for (int i = 0; i < 12; ++i) if (!(std::fabs(a[i]) <= ((i & 3) == 3 && i != 3 ? 1e10f : 1e4f))) return false;
+    if (!(std::fabs(a[15]) <= 1e10f)) return false;
+    auto fin = [](float x) { return std::fabs(x) <= 3.4028234e38f; };  // NaN compares false
+    auto fin3 = [&](v3 v) { return fin(v.x) && fin(v.y) && fin(v.z); };
+    auto finm = [&](const m3& m) { return fin3(m.c0) && fin3(m.c1) && fin3(m.c2); };
+    return fin3(F.cam.eye) && fin3(F.cam.fwd) && fin3(F.cam.right) && fin3(F.cam.up) && fin(F.cam.fov) && fin(F.cam.aspect_x) &&
+           finm(F.platter_rot) && finm(F.wobble) && fin3(F.sun_dir);
+}
+// The frame of a deck: everything render and sdf_tonearm compute before they read a point, from the block's values where app_vinyl.h
+// has u_time or a literal (include/sbx.h sbx_aux_vinyl_deck).  The tonearm's frames depend on nothing.
+FrameVinyl build_vinyl_deck(const sbx_uniforms& U, const sbx_aux_vinyl_deck& A, int steps) {
     FrameVinyl F;
     F.steps = steps;                                                   // :411-416
-    const float t = U.u_time;
-    if (build == VINYL_CLOSEUP) F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(-2, 1.5f, 5.5f), V3(-1.5f, 0, 0));   // setup_camera's `#else` :64-65
-    else F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(0, 5.75f, 6.75f), V3(0, -2.5f, 0));   // app_vinyl.h:56-64,459
-    F.platter_rot = mul(rotate_around_y(t * 200.f), rotate_around_x(sin_(t) * .1f));          // :417,424-426
-    F.sun_dir = normalize(V3(-1, 4, -3));
+    F.cam = make_camera(U.u_res[0], U.u_res[1], A.fov, V3(A.eye[0], A.eye[1], A.eye[2]), V3(A.look_at[0], A.look_at[1], A.look_at[2]));   // app_vinyl.h:56-67,460
+    F.platter_rot = mul(rotate_around_y(A.platter_deg), rotate_around_x(A.platter_tilt_deg));          // :419,426-428
+    F.sun_dir = V3(A.sun_dir[0], A.sun_dir[1], A.sun_dir[2]);          // :284-285, as given
     F.ry30 = rotate_around_y(30.f);
     F.rym30 = rotate_around_y(-30.f);
-    F.wobble = rotate_around_x(sin_(t * 3.6758f) * .1f);
+    F.wobble = rotate_around_x(A.arm_tilt_deg);                        // :141-142
     const float R = .1f, H = .8f;
     const v3 base_p = V3(-7, 0, -5);
     const v3 a1 = V3(-6, H, -3), a11 = V3(-4.25f, H, 2), a2 = V3(-4.1f, H, 2.45f), a33 = V3(-3.5f, H, 3), a3 = V3(-2, H, 4);
@@ -598,6 +652,11 @@ void sbx_checkerboard_texture(int size, int freq, uint32_t* out) {    // hlsltoy
 void sbx_raytracer_scene_cornell(const sbx_uniforms* uni, int at_rest, sbx_aux_raytracer_scene* out) {
     if (!uni || !out) return;
     cornell_block(*uni, at_rest != 0, *out);
+}
+
+void sbx_vinyl_deck_default(const sbx_uniforms* uni, sbx_aux_vinyl_deck* out) {
+    if (!uni || !out) return;
+    vinyl_default_deck(*uni, *out);
 }
 
 void sbx_egg_pose_default(const sbx_uniforms* uni, sbx_aux_egg_pose* out) {

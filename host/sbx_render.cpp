@@ -57,6 +57,11 @@
 //              [--deck-eye x,y,z] [--deck-look-at x,y,z] [--deck-fov F] [--platter-deg DEG] [--platter-tilt DEG] [--arm-tilt DEG]
 //              [--deck-sun x,y,z] [--groove-color r,g,b] [--dead-wax-color r,g,b] [--label-color r,g,b] [--logo-color r,g,b]
 //              [--shiny-color r,g,b] [--ro-spec V] [--a-x V] [--a-y V] [--shininess V]
+//     app "atmosphere_air": src/app_atmosphere.h over the caller's air (SBX_APP_ATMOSPHERE_AIR, include/sbx.h).  The block starts as the default
+//              of --time and --air-view (sbx_atmosphere_air_default) and every flag replaces one field of sbx_aux_atmosphere_air:
+//              [--air-view 0|1] [--air-samples N] [--air-samples-light N] [--air-eye x,y,z] [--air-fov F] [--air-look-at x,y,z]
+//              [--air-hg-g G] [--air-sun x,y,z] [--air-sun-power P] [--air-beta-r r,g,b] [--air-h-r H] [--air-beta-m r,g,b] [--air-h-m H]
+//              [--air-earth-radius R] [--air-atmosphere-radius R]
 //     app "2d" / "2d_tex": src/app_2d.h (its alpha is not 1: the .f32 frames carry it; single GPU only), the USE_TEXTURE build
 //              reading hlsltoy's default 128x128 checkerboard at t0
 //     app "func": src/app_func.h, the tiled Worley fBm of its compiled 2D branch (grey, alpha 1; u_time and --mouse do not enter)
@@ -86,8 +91,9 @@ static int app_from_name(const std::string& s) {
     const char* names[] = {"planet", "clouds", "vinyl", "egg", "raytracer", "atmosphere", "sdf_ao", "clouds_best", "clouds_tex", "clouds_ue4",
                            "clouds_sky", "vinyl_gpu", "planet_atmosphere", "2d", "2d_tex", "func", "atmosphere_ground", "sdf_ao_shadow", "sdf_ao_normals",
                            "egg_straight", "egg_oval", "clouds_height", "clouds_luminance", "raytracer_phong", "raytracer_noshadow", "raytracer_static",
-                           "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow", "planet_closeup", "planet_cloudless", "planet_unlit", "raytracer_scene", "sdf_scene", "egg_pose", "vinyl_deck"};
-    const int n = 36;
+                           "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow", "planet_closeup", "planet_cloudless", "planet_unlit", "raytracer_scene", "sdf_scene", "egg_pose", "vinyl_deck",
+                           "atmosphere_air"};
+    const int n = 37;
     std::string low;
     for (char c : s) low += (char)tolower(c);
     for (int i = 0; i < n; ++i)
@@ -157,6 +163,8 @@ int main(int argc, char** argv) {
     bool vinyl_view = false;
     sbx_aux_vinyl_deck deck_arg{};                   // the fields the deck flags gave, and which (in the block's order: sbx.h)
     bool deck_has[16] = {};
+    sbx_aux_atmosphere_air air_arg{};                // the fields the air flags gave, and which (air_has[0-2]: view and the counts; then the
+    bool air_has[15] = {};                           // six rows of a vec3 and a scalar, then the two radii)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -198,6 +206,21 @@ int main(int argc, char** argv) {
             for (float& v : pv_look) v = (float)atof(next());
             vinyl_view = true;
         }
+        else if (a == "--air-view") { air_arg.view = atoi(next()); air_has[0] = true; }
+        else if (a == "--air-samples") { air_arg.num_samples = atoi(next()); air_has[1] = true; }
+        else if (a == "--air-samples-light") { air_arg.num_samples_light = atoi(next()); air_has[2] = true; }
+        else if (a == "--air-eye") { vec3(air_arg.eye); air_has[3] = true; }
+        else if (a == "--air-fov") { air_arg.fov = (float)atof(next()); air_has[4] = true; }
+        else if (a == "--air-look-at") { vec3(air_arg.look_at); air_has[5] = true; }
+        else if (a == "--air-hg-g") { air_arg.hg_g = (float)atof(next()); air_has[6] = true; }
+        else if (a == "--air-sun") { vec3(air_arg.sun_dir); air_has[7] = true; }
+        else if (a == "--air-sun-power") { air_arg.sun_power = (float)atof(next()); air_has[8] = true; }
+        else if (a == "--air-beta-r") { vec3(air_arg.betaR); air_has[9] = true; }
+        else if (a == "--air-h-r") { air_arg.hR = (float)atof(next()); air_has[10] = true; }
+        else if (a == "--air-beta-m") { vec3(air_arg.betaM); air_has[11] = true; }
+        else if (a == "--air-h-m") { air_arg.hM = (float)atof(next()); air_has[12] = true; }
+        else if (a == "--air-earth-radius") { air_arg.earth_radius = (float)atof(next()); air_has[13] = true; }
+        else if (a == "--air-atmosphere-radius") { air_arg.atmosphere_radius = (float)atof(next()); air_has[14] = true; }
         else if (a == "--deck-eye") { vec3(deck_arg.eye); deck_has[0] = true; }
         else if (a == "--deck-fov") { deck_arg.fov = (float)atof(next()); deck_has[1] = true; }
         else if (a == "--deck-look-at") { vec3(deck_arg.look_at); deck_has[2] = true; }
@@ -284,6 +307,28 @@ int main(int argc, char** argv) {
             if (k & 1) dst[(k / 2) * 4 + 3] = src[(k / 2) * 4 + 3];
             else memcpy(dst + (k / 2) * 4, src + (k / 2) * 4, 3 * sizeof(float));
         }
+        return d;
+    };
+    bool air_flags = false;
+    for (bool b : air_has) air_flags = air_flags || b;
+    if (air_flags && id != SBX_APP_ATMOSPHERE_AIR) { fprintf(stderr, "the air flags belong to --app atmosphere_air\n"); return 2; }
+    // the air of frame time `time`: sbx_atmosphere_air_default's block of --air-view with the flags' fields put in
+    auto air_at = [&](float time) {
+        sbx_uniforms du{};
+        du.u_res[0] = (float)W; du.u_res[1] = (float)H; du.u_time = time;
+        sbx_aux_atmosphere_air d;
+        sbx_atmosphere_air_default(&du, air_has[0] ? air_arg.view : 0, &d);
+        if (air_has[1]) d.num_samples = air_arg.num_samples;
+        if (air_has[2]) d.num_samples_light = air_arg.num_samples_light;
+        float* dst = d.eye;                          // the six rows from `eye` on
+        const float* src = air_arg.eye;
+        for (int k = 0; k < 10; ++k) {
+            if (!air_has[3 + k]) continue;
+            if (k & 1) dst[(k / 2) * 4 + 3] = src[(k / 2) * 4 + 3];
+            else memcpy(dst + (k / 2) * 4, src + (k / 2) * 4, 3 * sizeof(float));
+        }
+        if (air_has[13]) d.earth_radius = air_arg.earth_radius;
+        if (air_has[14]) d.atmosphere_radius = air_arg.atmosphere_radius;
         return d;
     };
     for (const std::string* p : {&ppm, &f32})
@@ -416,6 +461,8 @@ int main(int argc, char** argv) {
         if (id == SBX_APP_EGG_POSE) { frame_pose = pose_at(u.u_time); aux = &frame_pose; }
         sbx_aux_vinyl_deck frame_deck;
         if (id == SBX_APP_VINYL_DECK) { frame_deck = deck_at(u.u_time); aux = &frame_deck; }
+        sbx_aux_atmosphere_air frame_air;
+        if (id == SBX_APP_ATMOSPHERE_AIR) { frame_air = air_at(u.u_time); aux = &frame_air; }
         (void)hipEventRecord(e0, nullptr);
         if (panorama) rc = sbx_clouds_eval(ctx, "render", have_ac ? &ac : nullptr, u.u_time, rays, dev, npx, nullptr);
         else if (planet_view) rc = sbx_planet_eval(ctx, "render", u.u_time, rays, dev, npx, nullptr);

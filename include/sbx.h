@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell, SBX_APP_SDF_SCENE with sbx_aux_sdf_scene, sbx_sdf_scene_ramp and sbx_sdf_eval, sbx_clouds_eval, sbx_planet_eval, SBX_APP_EGG_POSE with sbx_aux_egg_pose and sbx_egg_pose_default, sbx_egg_eval, SBX_APP_VINYL_DECK with sbx_aux_vinyl_deck and sbx_vinyl_deck_default, sbx_vinyl_eval: new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell, SBX_APP_SDF_SCENE with sbx_aux_sdf_scene, sbx_sdf_scene_ramp and sbx_sdf_eval, sbx_clouds_eval, sbx_planet_eval, SBX_APP_EGG_POSE with sbx_aux_egg_pose and sbx_egg_pose_default, sbx_egg_eval, SBX_APP_VINYL_DECK with sbx_aux_vinyl_deck and sbx_vinyl_deck_default, sbx_vinyl_eval, SBX_APP_ATMOSPHERE_AIR with sbx_aux_atmosphere_air and sbx_atmosphere_air_default, sbx_atmosphere_air_eval: new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -350,7 +350,28 @@ typedef enum sbx_app {
        form (variant 1's kernel): same bits.  The colours, Ward constants and shininess do not enter that domain.
        NOT OFFERED: the RIDGES and NOSHADOW builds or the 180 steps of SBX_APP_VINYL_GPU under a deck, a deck for the geometry,
        u_mouse.z (the caller states platter_deg instead), and the drop-in header sbx_mainimage.hpp, which has no way to state a block. */
-    SBX_APP_VINYL_DECK = 35
+    SBX_APP_VINYL_DECK = 35,
+    /* src/app_atmosphere.h as shipped over the CALLER'S AIR: the Rayleigh/Mie study with every number the header states taken from
+       the aux block sbx_aux_atmosphere_air (below) — scattering coefficients, scale heights, both radii, the sun and its power, the
+       Henyey-Greenstein g, the two sample counts, the observer and FOV — and with either of the header's two builds chosen by
+       `view`: 0 = the FROM_SPACE build's sky dome (:190-209), 1 = the build without it (:210-225: get_primary_ray, the terrain plane
+       ((0, -1, 0), earth_radius), the grey .33).  aux == NULL means sbx_atmosphere_air_default(uni, 0, .), and the frame is then
+       SBX_APP_ATMOSPHERE's in every bit; the default block of view 1 gives SBX_APP_ATMOSPHERE_GROUND's.  u_res is read; u_time
+       and u_mouse are not when a block is passed.  Alpha is 1.
+       SEMANTICS (tests/atmosphere_air_model.py is the definition), all as app_atmosphere.h has them:
+         - what is not in the block stays the reference's: the 1.1 of :146, rayleigh_phase_func, the Henyey-Greenstein choice of the
+           `#if 1`, the atmosphere sphere centred at 0, linear_to_srgb;
+         - sun_dir is used as given: setup_scene's rotation (:179-180) does not run and nothing is normalised;
+         - earth_radius is the height reference of both marches and, in view 1, the distance of the terrain plane; -height / hR and
+           t1 / float(num_samples) are binary32 divisions by the block's values;
+         - every float bit pattern is data — NaN, inf, a zero or non-unit sun, atmosphere_radius < earth_radius, hR = 0, hg_g = 1,
+           eye == look_at — and the result is what the plain statement of the header computes, NaN pixels included.
+       REFUSED (SBX_ERR_ARG, nothing written): view not 0 or 1, num_samples outside 1 ... 64, num_samples_light outside 1 ... 32, a
+       non-zero reserved word.
+       SBX_PRECISION_1E4 is ignored: the app stays exact.  sbx_set_variant 1 takes the plain statement for every wave (same bits).
+       NOT OFFERED: a caller's value for the 1.1, Schlick's phase function, more suns, ozone or other layers, the tolerance tier,
+       SBX_APP_PLANET_ATMOSPHERE under a block, and the drop-in header sbx_mainimage.hpp, which has no way to state a block. */
+    SBX_APP_ATMOSPHERE_AIR = 36
 } sbx_app;
 
 typedef enum sbx_status {
@@ -494,6 +515,25 @@ typedef struct sbx_aux_vinyl_deck {        /* 128 B */
  * sun_dir the spec's normalize(-1, 4, -3), the colours the literals of :40-54, ro_spec .0725, a_x .025, a_y .5, shininess 50, fov 1,
  * eye (0, 5.75, 6.75), look_at (0, -2.5, 0). */
 void sbx_vinyl_deck_default(const sbx_uniforms* uni, sbx_aux_vinyl_deck* out);
+
+/* the air of SBX_APP_ATMOSPHERE_AIR and sbx_atmosphere_air_eval: plain data, 128 bytes.  (:N names the line of src/app_atmosphere.h
+ * whose value the field replaces.) */
+typedef struct sbx_aux_atmosphere_air {    /* 128 B */
+    int view;                                         /* 0: the FROM_SPACE build's render (:190-209); 1: the build without it (:210-225) */
+    int num_samples, num_samples_light;               /* :47-48; 1 ... 64 and 1 ... 32 */
+    int reserved0;                                    /* must be 0 */
+    float eye[3];            float fov;               /* the ray origin of :205 (view 0), the eye of :172 (view 1);  FOV (:230) */
+    float look_at[3];        float hg_g;              /* :173, read by view 1 only;  :12, as henyey_greenstein_phase_func reads it */
+    float sun_dir[3];        float sun_power;         /* the sun as given (setup_scene's rotation does not run), never normalised;  :41 */
+    float betaR[3];          float hR;                /* :29;  :34 */
+    float betaM[3];          float hM;                /* :30;  :35 */
+    float earth_radius, atmosphere_radius;            /* :37-38: the height reference and (view 1) the terrain plane;  the `atmosphere` sphere */
+    float reserved[6];                                /* must be 0 (as bit patterns) */
+} sbx_aux_atmosphere_air;
+/* Host only, no context: the reference's numbers, with the sun that setup_scene (:177-181) makes of uni->u_time by the math spec — the
+ * block SBX_APP_ATMOSPHERE_AIR renders when aux is NULL (view 0).  eye (0, earth_radius + 1, 0) and look_at (0, earth_radius + 1.5, -1)
+ * in both views, fov 1, counts 16 / 8.  A view other than 0 or 1 is written as given (and refused by the app). */
+void sbx_atmosphere_air_default(const sbx_uniforms* uni, int view, sbx_aux_atmosphere_air* out);
 
 typedef struct sbx_ctx sbx_ctx;
 
@@ -749,6 +789,16 @@ int sbx_noise_eval(sbx_ctx* ctx, const char* fn, const float* xyz, const float* 
  * SBX_ERR_ARG for a NULL ctx / fn / rays / out, a NULL sun_dir with "get_incident_light", an unknown name, n > 2^31. */
 int sbx_atmosphere_eval(sbx_ctx* ctx, const char* fn, const float* rays, const float* sun_dir, float* out,
                         size_t n, void* stream);
+/* sbx_atmosphere_eval under the caller's air: the same two names, element layouts and contract, with every number of the solver —
+ * betaR, betaM, hR, hM, both radii, sun_power, hg_g, the sample counts and the sun — read from `air` (HOST memory, read during the
+ * call).  view, eye, look_at and fov are not read; the counts and the reserved words are checked as SBX_APP_ATMOSPHERE_AIR checks
+ * them.  With the reference's solver numbers (sbx_atmosphere_air_default) the result is sbx_atmosphere_eval's with that sun in every
+ * bit.  Exact for every bit pattern of block and rays.  Asynchronous on `stream` and capturable (no allocation, no wait); not counted
+ * in sbx_stats.render_launches; sbx_set_variant 1 selects the plain statement for every wave (same bits).  n == 0 returns SBX_OK
+ * and touches nothing; SBX_ERR_ARG, with nothing written, for a NULL ctx / fn / air / rays / out, an unknown name, n > 2^31, a count
+ * out of range or a non-zero reserved word. */
+int sbx_atmosphere_air_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_atmosphere_air* air, const float* rays, float* out,
+                            size_t n, void* stream);
 /* The SDF library on its own (src/sdf.h): sdf(pos) of SBX_APP_SDF_SCENE's program over the caller's points — the field's value
  * without a renderer: collision queries, a mesher's samples, another renderer's march.  `scene`: HOST memory, read during the call;
  * ONLY n_instr and program are read, and they are validated as SBX_APP_SDF_SCENE validates them (SBX_ERR_ARG, nothing written).

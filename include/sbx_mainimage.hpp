@@ -76,7 +76,7 @@
 #define SBX_SELECTED_APP SBX_APP_EGG
 #elif defined(APP_RAYTRACER)
 #define SBX_SELECTED_APP SBX_APP_RAYTRACER
-#elif defined(APP_ATMOSPHERE)
+#elif defined(APP_ATMOSPHERE)      /* (SBX_APP_ATMOSPHERE_AIR, the same header over the caller's air, has no define here: this header has no way to state a block; include/sbx.h) */
 #define SBX_SELECTED_APP SBX_APP_ATMOSPHERE
 #elif defined(APP_SDF_AO)
 #define SBX_SELECTED_APP SBX_APP_SDF_AO

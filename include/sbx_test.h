@@ -50,6 +50,8 @@ extern "C" {
  * compare-and-select unions for every wave; 2 / 3 = the witness's test edge / the IEEE roots; 0 takes the plain form only for such a deck
  * (the camera's fields ignored) and for the waves whose own points or directions hold a value beyond 1e4 or a NaN
  * (csrc/kern_vinyl_eval.hip).
+ * SBX_APP_ATMOSPHERE_AIR and sbx_atmosphere_air_eval: 1 = the plain statement for every wave, whatever the block; every other value
+ * leaves the tier to the block (csrc/sbx_frames.hip atmosphere_air_tier).
  * All variants are specified to produce identical bits (tests/test_gpu_parity.py sweeps them against each other). */
 int sbx_set_variant(sbx_ctx* ctx, int variant);
 
@@ -89,6 +91,15 @@ int sbx_debug_egg_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pos
  * neither.  It allocates and synchronises, so it is not capturable.  For tests/test_gpu_vinyl_eval.py and tools/time_vinyl_eval.py. */
 int sbx_debug_vinyl_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck* deck, const float* in, float* out, size_t n,
                          unsigned counts_host[2], void* stream);
+/* sbx_atmosphere_air_eval (sbx.h) with a count: the same launch (the context's variant included) followed by a wait, after which
+ * *fast_waves_host holds the waves that took the fast body (csrc/sbx_atmosphere.h "CALLER'S AIR"): 0 under an untame block or
+ * sbx_set_variant 1.  It allocates and synchronises, so it is not capturable. */
+int sbx_debug_atmosphere_air_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_atmosphere_air* air, const float* rays, float* out, size_t n,
+                                  unsigned* fast_waves_host, void* stream);
+/* SBX_APP_ATMOSPHERE_AIR launches of this context so far: counts[0] all of them, counts[1] those that took the literal tier (the shipped
+ * kernels over the block's sun), counts[2] those that took the plain kernel (sbx_set_variant 1, or a block that is neither literal nor
+ * tame).  The rest took the run-time kernel with its per-wave selection. */
+int sbx_debug_atmosphere_air_launches(sbx_ctx* ctx, uint64_t counts[3]);
 /* SBX_APP_VINYL_DECK launches of this context so far, and how many of them took the reference form because their deck was outside the
  * domain of the culls (whatever variant was set; a launch under sbx_set_variant 1 with a tame deck is not among the latter). */
 int sbx_debug_vinyl_deck_launches(sbx_ctx* ctx, uint64_t counts[2]);

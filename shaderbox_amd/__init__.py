@@ -17,7 +17,7 @@ from . import shard  # noqa: F401  (pure-python row-block arithmetic, no GPU nee
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsbx.so")
 
-APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW, APP_PLANET_CLOSEUP, APP_PLANET_CLOUDLESS, APP_PLANET_UNLIT, APP_RAYTRACER_SCENE, APP_SDF_SCENE, APP_EGG_POSE, APP_VINYL_DECK = range(36)
+APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW, APP_PLANET_CLOSEUP, APP_PLANET_CLOUDLESS, APP_PLANET_UNLIT, APP_RAYTRACER_SCENE, APP_SDF_SCENE, APP_EGG_POSE, APP_VINYL_DECK, APP_ATMOSPHERE_AIR = range(37)
 APPS = {"APP_PLANET": APP_PLANET, "APP_CLOUDS": APP_CLOUDS, "APP_VINYL": APP_VINYL, "APP_EGG": APP_EGG,
         "APP_RAYTRACER": APP_RAYTRACER, "APP_ATMOSPHERE": APP_ATMOSPHERE, "APP_SDF_AO": APP_SDF_AO,
         "APP_CLOUDS_BEST": APP_CLOUDS_BEST,    # src/app_clouds_best.h (stand-alone shader, not an APP_* define)
@@ -48,6 +48,7 @@ MORE_APPS = {"APP_EGG_STRAIGHT": APP_EGG_STRAIGHT,  # APP_EGG without `#define B
              "APP_PLANET_CLOUDLESS": APP_PLANET_CLOUDLESS,  # APP_PLANET without the `#define CLOUDS` of src/app_planet.h:63: no cloud march, no cloud shadow
              "APP_PLANET_UNLIT": APP_PLANET_UNLIT,          # APP_PLANET without the `#define LIGHT` of src/app_planet.h:249: N = w_normal.y, ocean = water
              "APP_RAYTRACER_SCENE": APP_RAYTRACER_SCENE,    # src/app_raytracer.h's render over the caller's scene: aux = a RaytracerScene (cornell_scene, raytracer_scene)
+             "APP_ATMOSPHERE_AIR": APP_ATMOSPHERE_AIR,      # src/app_atmosphere.h over the caller's air (coefficients, scale heights, radii, sun, counts, observer; view 0 = the sky dome, 1 = the ground camera): aux = an AtmosphereAir (atmosphere_air_default, atmosphere_air)
              "APP_VINYL_DECK": APP_VINYL_DECK,              # src/app_vinyl.h as shipped over the caller's deck (platter angle, tilts, sun, colours, groove BRDF): aux = a VinylDeck (vinyl_deck_default, vinyl_deck)
              "APP_EGG_POSE": APP_EGG_POSE,                  # src/app_egg.h as shipped with the rider posed by the caller (src/IK.h at work): aux = an EggPose (egg_pose_default, egg_pose)
              "APP_SDF_SCENE": APP_SDF_SCENE}                # src/app_sdf_ao.h's renderer over the caller's field, a program of src/sdf.h's primitives and operators: aux = an SdfScene (sdf_ramp_scene, SdfSceneBuilder)
@@ -133,6 +134,17 @@ class EggPose(ctypes.Structure):            # sbx_aux_egg_pose (the aux block of
                 ("look_at", ctypes.c_float * 3), ("turn_deg", ctypes.c_float),
                 ("left_foot", ctypes.c_float * 3), ("femur", ctypes.c_float),
                 ("right_foot", ctypes.c_float * 3), ("tibia", ctypes.c_float)]
+
+
+class AtmosphereAir(ctypes.Structure):      # sbx_aux_atmosphere_air (the aux block of APP_ATMOSPHERE_AIR and the air of atmosphere_air_eval, 128 bytes)
+    _fields_ = [("view", ctypes.c_int), ("num_samples", ctypes.c_int), ("num_samples_light", ctypes.c_int), ("reserved0", ctypes.c_int),
+                ("eye", ctypes.c_float * 3), ("fov", ctypes.c_float),
+                ("look_at", ctypes.c_float * 3), ("hg_g", ctypes.c_float),
+                ("sun_dir", ctypes.c_float * 3), ("sun_power", ctypes.c_float),
+                ("betaR", ctypes.c_float * 3), ("hR", ctypes.c_float),
+                ("betaM", ctypes.c_float * 3), ("hM", ctypes.c_float),
+                ("earth_radius", ctypes.c_float), ("atmosphere_radius", ctypes.c_float),
+                ("reserved", ctypes.c_float * 6)]
 
 
 class VinylDeck(ctypes.Structure):          # sbx_aux_vinyl_deck (the aux block of APP_VINYL_DECK and the deck of vinyl_eval, 128 bytes)
@@ -374,6 +386,11 @@ def load_library(path=None):
     lib.sbx_egg_pose_default.restype = None
     lib.sbx_egg_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(EggPose), fp, fp, ctypes.c_size_t, vp]
     lib.sbx_debug_egg_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(EggPose), fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
+    lib.sbx_atmosphere_air_default.argtypes = [ctypes.POINTER(Uniforms), ci, ctypes.POINTER(AtmosphereAir)]
+    lib.sbx_atmosphere_air_default.restype = None
+    lib.sbx_atmosphere_air_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(AtmosphereAir), fp, fp, ctypes.c_size_t, vp]
+    lib.sbx_debug_atmosphere_air_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(AtmosphereAir), fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
+    lib.sbx_debug_atmosphere_air_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.sbx_vinyl_deck_default.argtypes = [ctypes.POINTER(Uniforms), ctypes.POINTER(VinylDeck)]
     lib.sbx_vinyl_deck_default.restype = None
     lib.sbx_vinyl_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(VinylDeck), fp, fp, ctypes.c_size_t, vp]
@@ -565,6 +582,33 @@ def egg_pose(left_foot=(0.0, 1.5, 0.2), right_foot=(0.0, 0.9, -0.2), turn_deg=0.
     a.eye[:], a.look_at[:] = [float(v) for v in eye], [float(v) for v in look_at]
     a.left_foot[:], a.right_foot[:] = [float(v) for v in left_foot], [float(v) for v in right_foot]
     a.fov, a.turn_deg, a.femur, a.tibia = float(fov), float(turn_deg), float(femur), float(tibia)
+    return a
+
+
+def atmosphere_air_default(time, view=0, lib=None):
+    """sbx_atmosphere_air_default (host only, no GPU needed): the AtmosphereAir with the numbers of src/app_atmosphere.h and the sun its
+    setup_scene makes of `time` — what APP_ATMOSPHERE_AIR renders when aux is None (view 0: APP_ATMOSPHERE's frame; view 1:
+    APP_ATMOSPHERE_GROUND's)."""
+    lib = lib or load_library()
+    u = uniforms(1, 1, time)
+    a = AtmosphereAir()
+    lib.sbx_atmosphere_air_default(ctypes.byref(u), int(view), ctypes.byref(a))
+    return a
+
+
+def atmosphere_air(time=0.0, view=0, lib=None, **fields):
+    """An AtmosphereAir: atmosphere_air_default(time, view) with the named fields of sbx_aux_atmosphere_air replaced, each float
+    rounded to binary32."""
+    a = atmosphere_air_default(time, view, lib)
+    for name, value in fields.items():
+        if name not in dict(AtmosphereAir._fields_):
+            raise SbxError(SBX_ERR_ARG, "sbx_aux_atmosphere_air has no field %r" % (name,))
+        if isinstance(getattr(a, name), int):
+            setattr(a, name, int(value))
+        elif isinstance(getattr(a, name), float):
+            setattr(a, name, float(value))
+        else:
+            getattr(a, name)[:] = [float(v) for v in value]
     return a
 
 
@@ -1121,6 +1165,35 @@ class Renderer:
         else:
             self._check(self.lib.sbx_debug_atmosphere_eval(*args, ctypes.byref(waves), self._stream()))
         return out
+
+    def atmosphere_air_eval(self, fn, rays, air):
+        """The Rayleigh/Mie solver over rays[n, 6] under an AtmosphereAir (include/sbx.h sbx_atmosphere_air_eval) -> [n, 3]: fn
+        'get_incident_light' or 'get_sun_light', as atmosphere_eval, with every number of the solver and the sun read from `air`
+        (its view, eye, look_at and fov are not)."""
+        return self._atmosphere_air_eval(fn, rays, air, None)
+
+    def atmosphere_air_eval_counted(self, fn, rays, air):
+        """include/sbx_test.h sbx_debug_atmosphere_air_eval: atmosphere_air_eval that waits -> (out, waves that ran the fast body)"""
+        waves = ctypes.c_uint(0)
+        return self._atmosphere_air_eval(fn, rays, air, waves), waves.value
+
+    def _atmosphere_air_eval(self, fn, rays, air, waves):
+        rays = rays.to(self.tdev, self.torch.float32).contiguous().view(rays.numel() // 6, 6)
+        out = self.torch.empty((rays.shape[0], 3), dtype=self.torch.float32, device=self.tdev)
+        args = (self.ctx, fn.encode(), None if air is None else ctypes.byref(air), ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                rays.shape[0])
+        if waves is None:
+            self._check(self.lib.sbx_atmosphere_air_eval(*args, self._stream()))
+        else:
+            self._check(self.lib.sbx_debug_atmosphere_air_eval(*args, ctypes.byref(waves), self._stream()))
+        return out
+
+    def atmosphere_air_launches(self):
+        """include/sbx_test.h sbx_debug_atmosphere_air_launches: (APP_ATMOSPHERE_AIR launches of this context, those that took the
+        literal tier, those that took the plain kernel)"""
+        c = (ctypes.c_uint64 * 3)(0, 0, 0)
+        self._check(self.lib.sbx_debug_atmosphere_air_launches(self.ctx, c))
+        return int(c[0]), int(c[1]), int(c[2])
 
     # sbx_clouds_eval: floats per element in / out
     CLOUDS_EVAL_WIDTHS = {"render": (6, 4), "render_clouds": (6, 4), "render_sky_color": (3, 3), "density_func": (3, 1),

@@ -200,11 +200,11 @@ void launch_exp4k_eval(const float* a, float* out, size_t n, hipStream_t s) {
 
 dim3 atmosphere_grid(const RowMap& M) { return grid_for<8, ATM_TX>(M); }
 
-void launch_atmosphere(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision) {
+void launch_atmosphere(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision, bool fin_ok) {
     // FIN: camera and sun direction are finite numbers (they are for every finite u_res / u_time)
     const float chk[] = {F.cam.res_x, F.cam.res_y, F.cam.aspect_x, F.cam.fov, F.sun_dir.x, F.sun_dir.y, F.sun_dir.z,
                          F.cam.fwd.x, F.cam.fwd.y, F.cam.fwd.z, F.cam.up.x, F.cam.up.y, F.cam.up.z, F.cam.right.x, F.cam.right.y, F.cam.right.z};
-    bool fin = std::isfinite(F.cam.rres_x) && std::isfinite(F.cam.rres_y);
+    bool fin = std::isfinite(F.cam.rres_x) && std::isfinite(F.cam.rres_y) && fin_ok;
     for (float v : chk) fin = fin && std::isfinite(v);
 #if ATM_NO_FIN
     fin = false;
@@ -214,12 +214,12 @@ void launch_atmosphere(const FrameAtmosphere& F, const RowMap& M, float* out, hi
     else hipLaunchKernelGGL(k_atmosphere<false>, (grid_for<8, ATM_TX>(M)), dim3(64 * ATM_TX), 0, s, F, M, out);
 }
 
-void launch_atmosphere_ground(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision, int variant) {
+void launch_atmosphere_ground(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision, int variant, bool fin_ok) {
     // FIN as in launch_atmosphere, with the eye (a constant of the app) among the checked values; variant 1 is the plain form
     const float chk[] = {F.cam.res_x, F.cam.res_y, F.cam.aspect_x, F.cam.fov, F.sun_dir.x, F.sun_dir.y, F.sun_dir.z,
                          F.cam.fwd.x, F.cam.fwd.y, F.cam.fwd.z, F.cam.up.x, F.cam.up.y, F.cam.up.z, F.cam.right.x, F.cam.right.y, F.cam.right.z,
                          F.cam.eye.x, F.cam.eye.y, F.cam.eye.z};
-    bool fin = std::isfinite(F.cam.rres_x) && std::isfinite(F.cam.rres_y) && variant != 1;
+    bool fin = std::isfinite(F.cam.rres_x) && std::isfinite(F.cam.rres_y) && variant != 1 && fin_ok;
     for (float v : chk) fin = fin && std::isfinite(v);
 #if ATM_NO_FIN
     fin = false;

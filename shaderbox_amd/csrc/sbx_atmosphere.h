@@ -258,4 +258,124 @@ __device__ __forceinline__ v3 atm_incident_light(v3 ro, v3 rd, v3 sun_dir, const
     return col;
 }
 
+// CALLER'S AIR (kern_atmosphere_air.hip: SBX_APP_ATMOSPHERE_AIR, sbx_atmosphere_air_eval — every number above from the caller's block,
+// AtmAir in sbx_frame.h).  Three tiers, chosen on the host (sbx_frames.hip atmosphere_air_tier):
+//   LITERAL   a block whose solver numbers are the literals above bit for bit launches k_atmosphere / k_atmosphere_ground themselves
+//             with the block's sun.  Their FIN forms were argued for the sun setup_scene rotates out of (0, 1, 0); for another sun
+//             they run only where the host finds it finite with |dot(sun, sun) - 1| <= 1e-4 (atm_eval_sun_ok's test), and then:
+//               * every view sample of a ray from (0, Re + 1, 0) lies inside the sphere (dome rays are unit vectors to a few ulp or NaN,
+//                 ground-camera rays unit vectors or (0, 0, 0): above), so fact (a) holds with the view sample as origin and the checked
+//                 sun as direction: no light sample is more than 1.4 km outside the sphere, -height / H >= -51.2; a view sample at
+//                 lambda <= 31/32 of t1 >= 60 km - 1 has |s|^2 <= R^2 - (R^2 - (Re + 1)^2) / 32 = R^2 - 2.4e10, so its light ray's t1 is a number;
+//               * ATM_SQRT_RS on light samples.  k_atmosphere carries the dead-ray exit: a view sample more than 107 km under the ground
+//                 has made optical_depthM +inf (e^88.8 overflows) and its lane runs no sun march, so a light march starts >= 6.25e6 m
+//                 from the centre, its first sample <= 8.03e5 m further, every later one <= 1.61e6 m from one above the ground: never
+//                 within 4.7e6 m of the centre, whatever the sun's direction.  k_atmosphere_ground: no view sample is under the camera's
+//                 height, the same steps (its paragraph above reads "the dome's own" with any such sun);
+//               * ATM_DIV3, the density exp: heights are finite, 0 or >= 1/16 in magnitude, and >= -107 km where a sun march runs;
+//               * the ground camera's direction is a unit vector only while its basis is one: the host also asks |dot(fwd, fwd) - 1| <= 1e-4
+//                 of the block's look_at - eye (a difference whose squared length is subnormal normalises to something else).
+//             A sun that fails the test, or such a basis, takes FIN = false.
+//   RUN-TIME  k_atmosphere_air<VIEW, true> / k_atmosphere_air_eval<FN, true>: both bodies, the fast one (FAST = true below: exp_reg4k_,
+//             div3_, sqrt_rs_, the tau ballot, the dead-ray exit) on a wave whose 64 rays all pass atm_eval_class, and only in a launch
+//             whose block the host finds TAME (sbx_frames.hip atmosphere_air_tame):
+//                 earth_radius, atmosphere_radius, hR, hM equal to ATM_EARTH_R, ATM_ATMOS_R, ATM_HR, ATM_HM bit for bit, the counts
+//                 16 and 8, and a sun that is finite with |dot(sun, sun) - 1| <= 1e-4.
+//             That is the domain of "CALLER'S RAYS" above with Re, R, H_R, H_M read from registers instead of literals: facts (a)-(c)
+//             and the bounds of exp_reg4k_ ([-80, 2^18]), div3_ (dividend 0 or in [2^-100, 2^100], divisor 1200 or 7994) and sqrt_rs_
+//             ([2^-102, inf)) are those paragraphs word for word, with the class test made on the rays the kernel itself builds from the
+//             block's eye (a lane without a march — outside the dome's circle, or a ground pixel — holds the ray (0, Re + 1, 0) + t
+//             (1, 0, 0) of the class and drops the result).  No other radius, scale height or count is in the domain: those proofs have
+//             not been restated, such blocks run plain.  What the block may vary inside the domain enters no proof but two:
+//               * the tau ballot tests its own precondition, here as |tau| <= 80 per component (a NaN or inf tau, from any beta, fails
+//                 it; a negative beta's negative tau stays inside exp_reg4k_'s [-80, 2^18]);
+//               * the DEAD-RAY exit needs tau = +inf in all three components once an optical depth is +inf: betaR (odR + lR) +
+//                 1.1 betaM (odM + lM) with every beta > 0 (a number; 1.1 * the smallest subnormal is still > 0) is a sum of
+//                 non-negative terms one of which is +inf; a zero beta would make 0 * inf, a negative one -inf.  AtmAir.dead_ok states it,
+//                 and the exit is off without it.  sun_power, hg_g and the phase terms multiply the sums after the march; fov and the
+//                 eye only make rays, which the class judges.
+//             t1 / float(n) is the compiler's IEEE division in both bodies (17 per pixel against 336 exp).
+//   PLAIN     FAST = false for every wave (sbx_set_variant 1, every untame block): the plain statement lane by lane — IEEE sqrt (sqrt_:
+//             a block's radii can make arguments below sqrt_n_'s 2^-96), IEEE division by the block's hR and hM, the guarded exp — correct
+//             for every bit pattern of block.
+template <bool FAST>
+__device__ __forceinline__ bool air_isect(v3 ro, v3 rd, float atmos_r, float& t1) {                   // isect_sphere :15-26
+    const v3 rc = V3(0, 0, 0) - ro;
+    const float radius2 = atmos_r * atmos_r;
+    const float tca = dot(rc, rd);
+    const float d2 = dot(rc, rc) - tca * tca;
+    const float thc = FAST ? sqrt_n_(radius2 - d2) : sqrt_(radius2 - d2);   // (FAST: the default radii, as isect_atmosphere)
+    t1 = tca + thc;
+    return d2 < radius2;
+}
+#define AIR_LEN(x) (FAST ? sqrt_rs_(x) : sqrt_(x))
+#define AIR_EXP_H(x) (FAST ? exp_reg4k_((x), kExp2Tab4096) : exp_tab_<true>((x), etab))
+#define AIR_DIV_HR(h) (FAST ? div3_((h), hr_d, hr_r) : (h) / K.hR)
+#define AIR_DIV_HM(h) (FAST ? div3_((h), hm_d, hm_r) : (h) / K.hM)
+// get_sun_light :50-76 with the block's numbers; NL: the literal count of the fast body (the tame domain has one), 0 = K.nl
+template <bool FAST, int NL>
+__device__ __forceinline__ bool air_sun_light(v3 ro, v3 rd, float& odR, float& odM, const double (&etab)[32], const AtmAir& K,
+                                              float hr_d, float hr_r, float hm_d, float hm_r) {
+    float t1;
+    air_isect<FAST>(ro, rd, K.atmos_r, t1);
+    const int nl = NL ? NL : K.nl;
+    float march_pos = 0.f;
+    const float march_step = t1 / (float)nl;
+    for (int i = 0; i < nl; ++i) {
+        const v3 s = ro + rd * __builtin_fmaf(0.5f, march_step, march_pos);
+        const float height = AIR_LEN(dot(s, s)) - K.earth_r;
+        if (height < 0.f) return false;
+        odR += AIR_EXP_H(AIR_DIV_HR(-height)) * march_step;
+        odM += AIR_EXP_H(AIR_DIV_HM(-height)) * march_step;
+        march_pos += march_step;
+    }
+    return true;
+}
+// get_incident_light :78-160 with the block's numbers
+template <bool FAST, int NS, int NL>
+__device__ __forceinline__ v3 air_incident_light(v3 ro, v3 rd, v3 sun_dir, const double (&etab)[32], const AtmAir& K) {
+    v3 col = V3(0.f, 0.f, 0.f);
+    float t1;
+    float hr_d = K.hR, hr_r = K.rhR, hm_d = K.hM, hm_r = K.rhM;
+    if (FAST) asm volatile("" : "+v"(hr_d), "+v"(hr_r), "+v"(hm_d), "+v"(hm_r));      // VGPR operands: full rate
+    if (air_isect<FAST>(ro, rd, K.atmos_r, t1)) {
+        const v3 betaR = K.betaR, betaM = K.betaM;
+        const int ns = NS ? NS : K.ns;
+        const float march_step = t1 / (float)ns;
+        const float mu = dot(rd, sun_dir);
+        const float phaseR = 3.f * (1.f + mu * mu) / (16.f * 3.14159265359f);            // volumetric.h:13-19
+        const float g = K.g;
+        const float phaseM = (1.f - g * g) / ((4.f + 3.14159265359f) * pow_(1.f + g * g - 2.f * g * mu, 1.5f));   // :27-33
+        float odR = 0.f, odM = 0.f, march_pos = 0.f;
+        v3 sumR = V3(0, 0, 0), sumM = V3(0, 0, 0);
+        for (int i = 0; i < ns; ++i) {
+            const v3 s = ro + rd * __builtin_fmaf(0.5f, march_step, march_pos);
+            const float height = AIR_LEN(dot(s, s)) - K.earth_r;
+            const float hr = AIR_EXP_H(AIR_DIV_HR(-height)) * march_step;
+            const float hm = AIR_EXP_H(AIR_DIV_HM(-height)) * march_step;
+            odR += hr;
+            odM += hm;
+            const float inf = u2f(0x7f800000u);
+            const bool dead = FAST && K.dead_ok && (odR == inf || odM == inf);          // DEAD RAYS, above
+            if (FAST && K.dead_ok && __builtin_amdgcn_ballot_w64(!dead) == 0ull) break;   // wave-uniform
+            float lR = 0.f, lM = 0.f;
+            if (!dead && air_sun_light<FAST, NL>(s, sun_dir, lR, lM, etab, K, hr_d, hr_r, hm_d, hm_r)) {
+                const v3 tau = betaR * (odR + lR) + betaM * 1.1f * (odM + lM);
+                v3 att;
+                // (each component by itself and in magnitude: a caller's betas can make ONE tau a NaN, or any of them negative, and
+                // exp_reg4k_'s domain ends at 2^18)
+                if (FAST && __builtin_amdgcn_ballot_w64(!(fabsf(tau.x) <= 80.f && fabsf(tau.y) <= 80.f && fabsf(tau.z) <= 80.f)) == 0ull)
+                    att = V3(exp_reg4k_(-tau.x, kExp2Tab4096), exp_reg4k_(-tau.y, kExp2Tab4096), exp_reg4k_(-tau.z, kExp2Tab4096));
+                else
+                    att = V3(exp_tab_<true>(-tau.x, etab), exp_tab_<true>(-tau.y, etab), exp_tab_<true>(-tau.z, etab));
+                sumR = sumR + hr * att;
+                sumM = sumM + hm * att;
+            }
+            march_pos += march_step;
+        }
+        col = K.sun_power * (sumR * phaseR * betaR + sumM * phaseM * betaM);
+    }
+    return col;
+}
+
 }  // namespace sbx

@@ -214,6 +214,11 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     if (T.aux == AUX_EGG_POSE) EP = aux_egg_pose(aux, *uni);               // (every bit pattern is data: nothing to refuse)
     sbx_aux_vinyl_deck VD;
     if (T.aux == AUX_VINYL_DECK) VD = aux_vinyl_deck(aux, *uni);           // (likewise)
+    sbx_aux_atmosphere_air AA;
+    if (T.aux == AUX_ATM_AIR) {
+        AA = aux_atmosphere_air(aux, *uni);
+        if (const char* why = atmosphere_air_check(AA, true)) return fail(ctx, SBX_ERR_ARG, why);
+    }
     if (T.noise_volumes && !ctx->noise.shape) return fail(ctx, SBX_ERR_ARG, "APP_CLOUDS with USE_NOISE_TEX needs sbx_set_noise_volume first");
     const bool capturing = stream_is_capturing(s);
     TimingPair* tp = nullptr;
@@ -292,6 +297,19 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
         break;
     case SBX_APP_ATMOSPHERE: launch_atmosphere(build_atmosphere(*uni), M, rgba, s, ctx->precision); break;
     case SBX_APP_ATMOSPHERE_GROUND: launch_atmosphere_ground(build_atmosphere_ground(*uni), M, rgba, s, ctx->precision, ctx->variant); break;
+    // app_atmosphere.h over the caller's air (validated above).  sbx_set_precision does not enter.  The tier (sbx_atmosphere.h "CALLER'S
+    // AIR"): the shipped kernels over the block's sun, the run-time kernel with its per-wave selection, or the plain statement
+    case SBX_APP_ATMOSPHERE_AIR: {
+        const FrameAtmosphere F = build_atmosphere_air(*uni, AA);
+        const int tier = atmosphere_air_tier(AA, ctx->variant, true);
+        ctx->stats.atm_air_launches.fetch_add(1, std::memory_order_relaxed);
+        if (tier == ATM_AIR_LITERAL) ctx->stats.atm_air_literal.fetch_add(1, std::memory_order_relaxed);
+        if (tier == ATM_AIR_PLAIN) ctx->stats.atm_air_plain.fetch_add(1, std::memory_order_relaxed);
+        if (tier != ATM_AIR_LITERAL) launch_atmosphere_air(F, atmosphere_air_numbers(AA), AA.view, tier == ATM_AIR_RUNTIME, M, rgba, s);
+        else if (AA.view == 0) launch_atmosphere(F, M, rgba, s, 0, atmosphere_air_literal_fin(AA, F));
+        else launch_atmosphere_ground(F, M, rgba, s, 0, 0, atmosphere_air_literal_fin(AA, F));
+        break;
+    }
     // one scene, three builds of app_sdf_ao.h (include/sbx.h)
     case SBX_APP_SDF_AO: launch_sdf_ao(build_sdf_ao(*uni, aux_sdf_ao(aux)), M, rgba, s, sdf_variant, 0); break;
     case SBX_APP_SDF_AO_SHADOW: launch_sdf_ao(build_sdf_ao(*uni, aux_sdf_ao(aux)), M, rgba, s, sdf_variant, 1); break;
@@ -606,6 +624,14 @@ int sbx_debug_clouds_hashtab_read(sbx_ctx* ctx, size_t first, size_t count, floa
 int sbx_debug_raytracer_scene_launches(sbx_ctx* ctx, uint64_t* launches) {
     if (!ctx || !launches) return SBX_ERR_ARG;
     *launches = ctx->stats.rt_scene_launches.load(std::memory_order_relaxed);
+    return SBX_OK;
+}
+
+int sbx_debug_atmosphere_air_launches(sbx_ctx* ctx, uint64_t counts[3]) {
+    if (!ctx || !counts) return SBX_ERR_ARG;
+    counts[0] = ctx->stats.atm_air_launches.load(std::memory_order_relaxed);
+    counts[1] = ctx->stats.atm_air_literal.load(std::memory_order_relaxed);
+    counts[2] = ctx->stats.atm_air_plain.load(std::memory_order_relaxed);
     return SBX_OK;
 }
 

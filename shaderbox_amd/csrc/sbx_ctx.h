@@ -141,6 +141,7 @@ struct Stats {
     Stripe hits[16];
     std::atomic<uint64_t> launches{0}, frames{0}, points{0};
     std::atomic<uint64_t> rt_scene_launches{0};   // k_raytracer_scene launches (sbx_debug_raytracer_scene_launches; never reset)
+    std::atomic<uint64_t> atm_air_launches{0}, atm_air_literal{0}, atm_air_plain{0};   // SBX_APP_ATMOSPHERE_AIR launches, those of the literal tier, those of the plain kernel (sbx_debug_atmosphere_air_launches; never reset)
     std::atomic<uint64_t> vinyl_deck_launches{0}, vinyl_deck_untame{0};   // SBX_APP_VINYL_DECK launches, and those an untame deck sent to the reference form (sbx_debug_vinyl_deck_launches; never reset)
 };
 
@@ -224,6 +225,16 @@ const char* sdf_scene_check(const sbx_aux_sdf_scene& A, bool program_only);
 FrameSdfScene build_sdf_scene(const sbx_uniforms& U, const sbx_aux_sdf_scene& A);
 FrameAtmosphere build_atmosphere(const sbx_uniforms& U);
 FrameAtmosphere build_atmosphere_ground(const sbx_uniforms& U);
+// SBX_APP_ATMOSPHERE_AIR / sbx_atmosphere_air_eval (sbx_frames.hip): why a block is refused (nullptr: it is not; `app` false: the
+// solver entry, which does not read `view`), the frame of a valid block (the default blocks give build_atmosphere's and
+// build_atmosphere_ground's bit for bit), the solver's numbers, and the tier a launch takes (sbx_atmosphere.h "CALLER'S AIR")
+enum { ATM_AIR_LITERAL = 0, ATM_AIR_RUNTIME = 1, ATM_AIR_PLAIN = 2 };
+const char* atmosphere_air_check(const sbx_aux_atmosphere_air& A, bool app);
+FrameAtmosphere build_atmosphere_air(const sbx_uniforms& U, const sbx_aux_atmosphere_air& A);
+AtmAir atmosphere_air_numbers(const sbx_aux_atmosphere_air& A);
+bool atmosphere_air_tame(const sbx_aux_atmosphere_air& A);
+int atmosphere_air_tier(const sbx_aux_atmosphere_air& A, int variant, bool app);   // app false: never ATM_AIR_LITERAL
+bool atmosphere_air_literal_fin(const sbx_aux_atmosphere_air& A, const FrameAtmosphere& F);   // the literal tier's fin_ok
 FrameSdfAo build_sdf_ao(const sbx_uniforms& U, const sbx_aux_sdf_ao& A);
 FrameVinyl build_vinyl(const sbx_uniforms& U, int steps, int build = VINYL_DEFAULT);   // build: VINYL_* (sbx_frame.h); VINYL_CLOSEUP is the other camera
 // SBX_APP_VINYL_DECK / sbx_vinyl_eval: the frame of the caller's deck (build_vinyl is this over the default block), the shading data

@@ -179,8 +179,13 @@ void launch_tex3d_eval(int size, const float* rgba, const float* xyz, float* out
 void launch_egg(const FrameEggStraight& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = EGG_DEFAULT);   // build: EGG_* (sbx_frame.h), the one F was built for
 void launch_raytracer(const FrameRaytracer& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = RT_DEFAULT);   // build: RT_* (sbx_frame.h)
 void launch_raytracer_scene(const FrameRtScene& F, const RowMap& M, float* out, hipStream_t s, int variant);   // SBX_APP_RAYTRACER_SCENE (kern_raytracer.hip)
-void launch_atmosphere(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision = 0);
-void launch_atmosphere_ground(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision, int variant);   // kern_atmosphere.hip
+// fin_ok = false: the caller has found the frame outside the domain of the FIN forms (SBX_APP_ATMOSPHERE_AIR's literal tier: a sun the
+// written arguments do not admit, sbx_atmosphere.h "CALLER'S AIR"); the plain kernel then runs whatever else holds
+void launch_atmosphere(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision = 0, bool fin_ok = true);
+void launch_atmosphere_ground(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision, int variant, bool fin_ok = true);   // kern_atmosphere.hip
+// SBX_APP_ATMOSPHERE_AIR (kern_atmosphere_air.hip k_atmosphere_air): the run-time tier (fast = true: tame blocks, the fast body on the
+// waves whose rays are of the class) and the plain tier (false)
+void launch_atmosphere_air(const FrameAtmosphere& F, const AtmAir& K, int view, bool fast, const RowMap& M, float* out, hipStream_t s);
 void launch_sdf_ao(const FrameSdfAo& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = 0);   // build: 1 / 2 = the shadow / normals builds (kern_sdf_ao.hip)
 void launch_sdf_scene(const FrameSdfScene& F, const RowMap& M, float* out, hipStream_t s, int variant);   // SBX_APP_SDF_SCENE (kern_sdf_scene.hip)
 void launch_sdf_scene_eval(const FrameSdfScene& F, const float* xyz, float* out, size_t n, hipStream_t s, int variant);   // sbx_sdf_eval
@@ -224,6 +229,9 @@ void launch_worley_volume(int size, float* out, hipStream_t s);
 void launch_exp4k_eval(const float* a, float* out, size_t n, hipStream_t s);
 // sbx_atmosphere_eval (kern_atmosphere.hip): fn 0 get_incident_light / 1 get_sun_light; plain = the plain kernel for every wave
 void launch_atmosphere_eval(int fn, bool plain, const float* rays, const float* sun_dir, float* out, size_t n, unsigned* fast_waves, hipStream_t s);
+// sbx_atmosphere_air_eval (kern_atmosphere_air.hip): the same under the caller's air; fast as launch_atmosphere_air's
+void launch_atmosphere_air_eval(int fn, bool fast, const float* rays, const float* sun_dir, const AtmAir& K, float* out, size_t n, unsigned* fast_waves,
+                                hipStream_t s);
 // sbx_clouds_eval (kern_clouds_eval.hip): fn 0 render / 1 render_clouds / 2 render_sky_color / 3 density_func / 4 illuminate_volume over F =
 // build_clouds of the caller's block; plain = the per-lane statement; ht = a hash table that is ready on `s`, or NULL; counts = NULL or two
 // zeroed 64-bit device words for the counting instantiation

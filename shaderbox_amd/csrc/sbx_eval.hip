@@ -97,6 +97,56 @@ int sbx_debug_atmosphere_eval(sbx_ctx* ctx, const char* fn, const float* rays, c
     return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "atmosphere_eval (counted)", e);
 }
 
+// the checks sbx_atmosphere_air_eval and its test hook share
+static int atmosphere_air_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_atmosphere_air* air, const float* rays, const float* out, size_t n, int& fn_id) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!fn || !air) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    fn_id = std::strcmp(fn, "get_incident_light") == 0 ? 0 : std::strcmp(fn, "get_sun_light") == 0 ? 1 : -1;
+    if (fn_id < 0) return fail(ctx, SBX_ERR_ARG, "unknown atmosphere function");
+    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 rays");
+    if (const char* why = atmosphere_air_check(*air, false)) return fail(ctx, SBX_ERR_ARG, why);
+    if (n == 0) return SBX_OK;
+    if (!rays || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    return SBX_OK;
+}
+// the block is read here, on the host, during the call: the kernel gets its numbers as arguments
+static void atmosphere_air_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_atmosphere_air& A, const float* rays, float* out, size_t n,
+                                       unsigned* fast_waves, hipStream_t s) {
+    launch_atmosphere_air_eval(id, atmosphere_air_tier(A, ctx->variant, false) == ATM_AIR_RUNTIME, rays, A.sun_dir, atmosphere_air_numbers(A), out, n,
+                               fast_waves, s);
+}
+
+int sbx_atmosphere_air_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_atmosphere_air* air, const float* rays, float* out, size_t n, void* stream) {
+    int id = -1;
+    int rc = atmosphere_air_eval_args(ctx, fn, air, rays, out, n, id);
+    if (rc != SBX_OK || n == 0) return rc;
+    if ((rc = use_device(ctx)) != SBX_OK) return rc;
+    atmosphere_air_eval_launch(ctx, id, *air, rays, out, n, nullptr, (hipStream_t)stream);
+    return launched(ctx, "atmosphere_air_eval launch");
+}
+
+int sbx_debug_atmosphere_air_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_atmosphere_air* air, const float* rays, float* out, size_t n,
+                                  unsigned* fast_waves_host, void* stream) {
+    int id = -1;
+    int rc = atmosphere_air_eval_args(ctx, fn, air, rays, out, n, id);
+    if (rc != SBX_OK) return rc;
+    if (!fast_waves_host) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    *fast_waves_host = 0;
+    if (n == 0) return SBX_OK;
+    if ((rc = use_device(ctx)) != SBX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned* counter = nullptr;
+    hipError_t e = hipMalloc((void**)&counter, sizeof(unsigned));
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
+    if ((e = hipMemsetAsync(counter, 0, sizeof(unsigned), s)) == hipSuccess) {
+        atmosphere_air_eval_launch(ctx, id, *air, rays, out, n, counter, s);
+        if ((e = hipGetLastError()) == hipSuccess && (e = hipMemcpyAsync(fast_waves_host, counter, sizeof(unsigned), hipMemcpyDeviceToHost, s)) == hipSuccess)
+            e = hipStreamSynchronize(s);
+    }
+    (void)hipFree(counter);
+    return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "atmosphere_air_eval (counted)", e);
+}
+
 int sbx_sdf_eval(sbx_ctx* ctx, const sbx_aux_sdf_scene* scene, const float* xyz, float* out, size_t n, void* stream) {
     if (!ctx) return SBX_ERR_ARG;
     if (!scene) return fail(ctx, SBX_ERR_ARG, "NULL argument");

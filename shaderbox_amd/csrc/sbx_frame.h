@@ -216,6 +216,16 @@ struct FrameAtmosphere {
     Camera cam;
     v3 sun_dir;           // (0,1,0) * rotate_around_x(-|sin(t/2)|*90)  app_atmosphere.h:177-181
 };
+// SBX_APP_ATMOSPHERE_AIR / sbx_atmosphere_air_eval: the solver's numbers from the caller's block (include/sbx.h sbx_aux_atmosphere_air),
+// the second argument of k_atmosphere_air and k_atmosphere_air_eval.  The sun and (for the app) the eye travel in FrameAtmosphere.
+struct AtmAir {
+    v3 betaR, betaM;                  // :29-30
+    float hR, rhR, hM, rhM;           // :34-35 and RN(1 / h): div3_'s pair (read by the fast forms only)
+    float earth_r, atmos_r;           // :37-38
+    float sun_power, g;               // :41, :12
+    int ns, nl;                       // :47-48
+    int dead_ok;                      // the dead-ray exit may run: all six betas are positive numbers (sbx_atmosphere.h "CALLER'S AIR")
+};
 
 // ---- APP_SDF_AO (src/app_sdf_ao.h) ----------------------------------------------------------
 struct FrameSdfAo {

@@ -298,6 +298,91 @@ FrameAtmosphere build_atmosphere_ground(const sbx_uniforms& U) {
     return F;
 }
 
+// ---- SBX_APP_ATMOSPHERE_AIR (include/sbx.h sbx_aux_atmosphere_air; the tiers: sbx_atmosphere.h "CALLER'S AIR") ----------------------
+// the reference's numbers (app_atmosphere.h:12,29-41,47-48,172-173,230; the literals of sbx_atmosphere.h) with the sun of build_atmosphere
+static void atmosphere_default_air(const sbx_uniforms& U, int view, sbx_aux_atmosphere_air& A) {
+    auto put = [](float* d, v3 v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; };
+    std::memset(&A, 0, sizeof(A));
+    const float earth_radius = 6360e3f;
+    A.view = view;
+    A.num_samples = 16; A.num_samples_light = 8;
+    put(A.eye, V3(0, earth_radius + 1.f, 0)); A.fov = 1.f;
+    put(A.look_at, V3(0, earth_radius + 1.5f, -1)); A.hg_g = .76f;
+    put(A.sun_dir, build_atmosphere(U).sun_dir); A.sun_power = 20.0f;
+    put(A.betaR, V3(5.5e-6f, 13.0e-6f, 22.4e-6f)); A.hR = 7994.0f;
+    put(A.betaM, V3(21e-6f, 21e-6f, 21e-6f)); A.hM = 1200.0f;
+    A.earth_radius = earth_radius; A.atmosphere_radius = 6420e3f;
+}
+const char* atmosphere_air_check(const sbx_aux_atmosphere_air& A, bool app) {
+    static_assert(sizeof(sbx_aux_atmosphere_air) == 128, "sbx_aux_atmosphere_air is 128 bytes (include/sbx.h)");
+    if (app && A.view != 0 && A.view != 1) return "atmosphere air: view must be 0 (the sky dome) or 1 (the ground camera)";
+    if (A.num_samples < 1 || A.num_samples > 64) return "atmosphere air: num_samples must lie in 1..64";
+    if (A.num_samples_light < 1 || A.num_samples_light > 32) return "atmosphere air: num_samples_light must lie in 1..32";
+    uint32_t r[6];
+    std::memcpy(r, A.reserved, sizeof(r));
+    if (A.reserved0 != 0 || (r[0] | r[1] | r[2] | r[3] | r[4] | r[5]) != 0u) return "atmosphere air: the reserved words must be 0";
+    return nullptr;
+}
+// view 0: main.h's camera of the FROM_SPACE build (:169-170; only point_cam reads it) with the block's FOV, and the block's eye as the
+// dome's ray origin (:205); view 1: the camera of :172-173 from the block
+FrameAtmosphere build_atmosphere_air(const sbx_uniforms& U, const sbx_aux_atmosphere_air& A) {
+    FrameAtmosphere F;
+    const v3 eye = V3(A.eye[0], A.eye[1], A.eye[2]);
+    if (A.view == 0) {
+        F.cam = make_camera(U.u_res[0], U.u_res[1], A.fov, V3(0, 0, 0), V3(0, 1, 0));
+        F.cam.eye = eye;
+    } else {
+        F.cam = make_camera(U.u_res[0], U.u_res[1], A.fov, eye, V3(A.look_at[0], A.look_at[1], A.look_at[2]));
+    }
+    F.sun_dir = V3(A.sun_dir[0], A.sun_dir[1], A.sun_dir[2]);
+    return F;
+}
+static bool positive_number(float v) { return v > 0.f && std::isfinite(v); }
+AtmAir atmosphere_air_numbers(const sbx_aux_atmosphere_air& A) {
+    AtmAir K;
+    K.betaR = V3(A.betaR[0], A.betaR[1], A.betaR[2]);
+    K.betaM = V3(A.betaM[0], A.betaM[1], A.betaM[2]);
+    K.hR = A.hR; K.rhR = 1.0f / A.hR;
+    K.hM = A.hM; K.rhM = 1.0f / A.hM;
+    K.earth_r = A.earth_radius; K.atmos_r = A.atmosphere_radius;
+    K.sun_power = A.sun_power; K.g = A.hg_g;
+    K.ns = A.num_samples; K.nl = A.num_samples_light;
+    K.dead_ok = 1;
+    for (int k = 0; k < 3; ++k) if (!positive_number(A.betaR[k]) || !positive_number(A.betaM[k])) K.dead_ok = 0;
+    return K;
+}
+// the host's part of the class (kern_atmosphere.hip atm_eval_sun_ok): a sun that is finite and a unit vector to 1e-4
+static bool air_sun_ok(const float* s) {
+    const float ss = (s[0] * s[0] + s[1] * s[1]) + s[2] * s[2];
+    return std::isfinite(s[0]) && std::isfinite(s[1]) && std::isfinite(s[2]) && std::fabs(ss - 1.0f) <= 1e-4f;
+}
+static bool same_floats(const float* a, const float* b, int n) { return std::memcmp(a, b, n * sizeof(float)) == 0; }
+// radii, scale heights and counts are the reference's bit for bit: the domain in which sbx_atmosphere.h's proofs are written
+static bool air_default_geometry(const sbx_aux_atmosphere_air& A, const sbx_aux_atmosphere_air& D) {
+    return same_floats(&A.earth_radius, &D.earth_radius, 1) && same_floats(&A.atmosphere_radius, &D.atmosphere_radius, 1) &&
+           same_floats(&A.hR, &D.hR, 1) && same_floats(&A.hM, &D.hM, 1) && A.num_samples == 16 && A.num_samples_light == 8;
+}
+bool atmosphere_air_tame(const sbx_aux_atmosphere_air& A) {
+    sbx_aux_atmosphere_air D;
+    atmosphere_default_air(sbx_uniforms{}, 0, D);
+    return air_default_geometry(A, D) && air_sun_ok(A.sun_dir);
+}
+int atmosphere_air_tier(const sbx_aux_atmosphere_air& A, int variant, bool app) {
+    if (variant == 1) return ATM_AIR_PLAIN;
+    sbx_aux_atmosphere_air D;
+    atmosphere_default_air(sbx_uniforms{}, 0, D);
+    const bool solver = air_default_geometry(A, D) && same_floats(A.betaR, D.betaR, 3) && same_floats(A.betaM, D.betaM, 3) &&
+                        same_floats(&A.sun_power, &D.sun_power, 1) && same_floats(&A.hg_g, &D.hg_g, 1);
+    if (app && solver && same_floats(A.eye, D.eye, 3) && (A.view == 1 || same_floats(&A.fov, &D.fov, 1))) return ATM_AIR_LITERAL;
+    return atmosphere_air_tame(A) ? ATM_AIR_RUNTIME : ATM_AIR_PLAIN;
+}
+bool atmosphere_air_literal_fin(const sbx_aux_atmosphere_air& A, const FrameAtmosphere& F) {
+    if (!air_sun_ok(A.sun_dir)) return false;
+    if (A.view == 0) return true;
+    const float ff = (F.cam.fwd.x * F.cam.fwd.x + F.cam.fwd.y * F.cam.fwd.y) + F.cam.fwd.z * F.cam.fwd.z;
+    return std::fabs(ff - 1.0f) <= 1e-4f;                          // (a NaN compares false)
+}
+
 FrameSdfAo build_sdf_ao(const sbx_uniforms& U, const sbx_aux_sdf_ao& A) {
     FrameSdfAo F;
     const m3 rot = rotate_around_y(U.u_time * 50.f);                   // app_sdf_ao.h:45-50
@@ -652,6 +737,11 @@ void sbx_checkerboard_texture(int size, int freq, uint32_t* out) {    // hlsltoy
 void sbx_raytracer_scene_cornell(const sbx_uniforms* uni, int at_rest, sbx_aux_raytracer_scene* out) {
     if (!uni || !out) return;
     cornell_block(*uni, at_rest != 0, *out);
+}
+
+void sbx_atmosphere_air_default(const sbx_uniforms* uni, int view, sbx_aux_atmosphere_air* out) {
+    if (!uni || !out) return;
+    atmosphere_default_air(*uni, view, *out);
 }
 
 void sbx_vinyl_deck_default(const sbx_uniforms* uni, sbx_aux_vinyl_deck* out) {

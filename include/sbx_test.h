@@ -41,7 +41,7 @@ extern "C" {
  * the IEEE roots and divisions, exp_, lattice indices as the reference forms them); 0 runs it only on the waves whose own operands fail
  * a guard of csrc/kern_planet_eval.hip, and for any u_time beyond 1e8 in magnitude or NaN.
  * SBX_APP_EGG_POSE: every value as for APP_EGG; a pose outside the domain of the culls and witnessed roots (a non-finite frame constant, a
- * value of the block beyond 1e4, 1e10 for the angle) takes 1 whatever is set.  sbx_egg_eval: 1 = CULL = false and the IEEE roots for every
+ * value of the block beyond 1e4, 1e10 for the angle) takes 1 whatever is set; sbx_debug_egg_pose_launches counts such launches.  sbx_egg_eval: 1 = CULL = false and the IEEE roots for every
  * wave; 2 / 3 = the witness's test edge / the IEEE roots; 0 takes the plain form only for such a pose and for the waves whose own inputs
  * hold a value beyond 1e4 or a NaN (csrc/kern_egg_eval.hip).  "ik_solver" has one form.
  * SBX_APP_VINYL_DECK: every value as for APP_VINYL; a deck outside the domain of the culls and the hardware min / max (a value of the
@@ -103,6 +103,12 @@ int sbx_debug_atmosphere_air_launches(sbx_ctx* ctx, uint64_t counts[3]);
 /* SBX_APP_VINYL_DECK launches of this context so far, and how many of them took the reference form because their deck was outside the
  * domain of the culls (whatever variant was set; a launch under sbx_set_variant 1 with a tame deck is not among the latter). */
 int sbx_debug_vinyl_deck_launches(sbx_ctx* ctx, uint64_t counts[2]);
+/* The same record for SBX_APP_EGG_POSE: counts[0] its launches of this context so far, counts[1] those of them that took the reference
+ * form because their pose was outside the domain of the culls and witnessed roots (csrc/sbx_frames.hip egg_pose_tame), whatever variant
+ * was set; a launch under sbx_set_variant 1 with a tame pose is not among the latter.  Host bookkeeping: one launch adds one to
+ * counts[0] whatever rows or points it renders.  For the tests that a pose compared with the plain kernel did not take it itself
+ * (tests/test_gpu_caller_sweeps.py). */
+int sbx_debug_egg_pose_launches(sbx_ctx* ctx, uint64_t counts[2]);
 
 /* Device evaluation of the math spec, elementwise over device arrays (for parity tests):
  * fn in {"sin","cos","tan","exp","pow","acos","atan2","hash","div","div_rd","exp_h13","pow_h","sqrt_n","sqrt_ieee","exp_reg","exp_reg_plain","exp_reg64","exp_reg64_plain","exp_small","exp_small_plain","exp_reg4k","sin_b40","div3","sqrt_rs","divn","srgb_pow","pow_spec"}; b may be NULL

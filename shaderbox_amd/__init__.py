@@ -396,6 +396,7 @@ def load_library(path=None):
     lib.sbx_vinyl_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(VinylDeck), fp, fp, ctypes.c_size_t, vp]
     lib.sbx_debug_vinyl_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(VinylDeck), fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
     lib.sbx_debug_vinyl_deck_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    lib.sbx_debug_egg_pose_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.sbx_debug_raytracer_scene_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.sbx_create.argtypes = [ci, ctypes.POINTER(vp)]
     lib.sbx_destroy.argtypes = [vp]
@@ -1335,6 +1336,13 @@ class Renderer:
         to the reference form)"""
         c = (ctypes.c_uint64 * 2)(0, 0)
         self._check(self.lib.sbx_debug_vinyl_deck_launches(self.ctx, c))
+        return int(c[0]), int(c[1])
+
+    def egg_pose_launches(self):
+        """include/sbx_test.h sbx_debug_egg_pose_launches: (APP_EGG_POSE launches of this context, those of them an untame pose sent
+        to the reference form)"""
+        c = (ctypes.c_uint64 * 2)(0, 0)
+        self._check(self.lib.sbx_debug_egg_pose_launches(self.ctx, c))
         return int(c[0]), int(c[1])
 
     def sdf_eval(self, scene, xyz):

@@ -282,7 +282,10 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     // of their culls and witnessed roots (sbx_frames.hip egg_pose_tame) takes the reference form
     case SBX_APP_EGG_POSE: {
         const FrameEggStraight F = build_egg_pose(*uni, EP, EGG_DEFAULT);
-        launch_egg(F, M, rgba, s, egg_pose_tame(EP, F) ? sdf_variant : 1, EGG_DEFAULT);
+        const bool tame = egg_pose_tame(EP, F);
+        ctx->stats.egg_pose_launches.fetch_add(1, std::memory_order_relaxed);
+        if (!tame) ctx->stats.egg_pose_untame.fetch_add(1, std::memory_order_relaxed);
+        launch_egg(F, M, rgba, s, tame ? sdf_variant : 1, EGG_DEFAULT);
         break;
     }
     case SBX_APP_RAYTRACER: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots); break;
@@ -639,6 +642,13 @@ int sbx_debug_vinyl_deck_launches(sbx_ctx* ctx, uint64_t counts[2]) {
     if (!ctx || !counts) return SBX_ERR_ARG;
     counts[0] = ctx->stats.vinyl_deck_launches.load(std::memory_order_relaxed);
     counts[1] = ctx->stats.vinyl_deck_untame.load(std::memory_order_relaxed);
+    return SBX_OK;
+}
+
+int sbx_debug_egg_pose_launches(sbx_ctx* ctx, uint64_t counts[2]) {
+    if (!ctx || !counts) return SBX_ERR_ARG;
+    counts[0] = ctx->stats.egg_pose_launches.load(std::memory_order_relaxed);
+    counts[1] = ctx->stats.egg_pose_untame.load(std::memory_order_relaxed);
     return SBX_OK;
 }
 

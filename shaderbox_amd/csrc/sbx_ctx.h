@@ -143,6 +143,7 @@ struct Stats {
     std::atomic<uint64_t> rt_scene_launches{0};   // k_raytracer_scene launches (sbx_debug_raytracer_scene_launches; never reset)
     std::atomic<uint64_t> atm_air_launches{0}, atm_air_literal{0}, atm_air_plain{0};   // SBX_APP_ATMOSPHERE_AIR launches, those of the literal tier, those of the plain kernel (sbx_debug_atmosphere_air_launches; never reset)
     std::atomic<uint64_t> vinyl_deck_launches{0}, vinyl_deck_untame{0};   // SBX_APP_VINYL_DECK launches, and those an untame deck sent to the reference form (sbx_debug_vinyl_deck_launches; never reset)
+    std::atomic<uint64_t> egg_pose_launches{0}, egg_pose_untame{0};       // SBX_APP_EGG_POSE launches, and those an untame pose sent to the reference form (sbx_debug_egg_pose_launches; never reset)
 };
 
 // sbx_render_rows_host: device staging of a host frame, the stream its strips are copied out on, one event per strip.

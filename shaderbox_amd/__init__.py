@@ -1144,50 +1144,128 @@ class Renderer:
                                             xyz.shape[0], self._stream()))
         return out
 
+    # The eval entries (include/sbx.h sbx_<family>_eval): per family, function name -> floats per element (in, out).  A new entry adds
+    # its row here and a public method that calls _eval.
+    EVAL_WIDTHS = {
+        "atmosphere": {"get_incident_light": (6, 3), "get_sun_light": (6, 3)},
+        "atmosphere_air": {"get_incident_light": (6, 3), "get_sun_light": (6, 3)},
+        "clouds": {"render": (6, 4), "render_clouds": (6, 4), "render_sky_color": (3, 3), "density_func": (3, 1), "illuminate_volume": (6, 1)},
+        "planet": {"render": (6, 4), "terrain_march": (6, 4), "sdf_terrain_map": (3, 2), "sdf_terrain_map_detail": (3, 2),
+                   "sdf_terrain_normal": (3, 3), "clouds_density": (4, 1), "illuminate": (4, 3), "background": (3, 3)},
+        "egg": {"ik_solver": (8, 3), "sdf": (3, 2), "sdf_normal": (3, 3), "shadowmarch": (6, 1), "render_scene": (6, 4)},
+        "vinyl": {"sdf": (3, 2), "sdf_normal": (3, 3), "sdf_shadow": (6, 1), "illuminate": (7, 3), "render": (6, 5)},
+        "sdf": {"sdf": (3, 2)},
+    }
+    CLOUDS_EVAL_WIDTHS, PLANET_EVAL_WIDTHS = EVAL_WIDTHS["clouds"], EVAL_WIDTHS["planet"]
+    EGG_EVAL_WIDTHS, VINYL_EVAL_WIDTHS = EVAL_WIDTHS["egg"], EVAL_WIDTHS["vinyl"]
+
+    def _eval(self, family, fn, x, lead, counts=None, mid=(), named=True):
+        """sbx_<family>_eval or, with `counts` (what the twin writes its counters to), sbx_debug_<family>_eval of include/sbx_test.h
+        over x -> [n, floats out].  The call is (ctx, fn, *lead, in, *mid, out, n[, counts], stream): `lead` the family's own arguments
+        (its block by reference or None, u_time), `mid` what its prototype puts between in and out; named=False: the entry takes no fn."""
+        widths = self.EVAL_WIDTHS[family]
+        if fn not in widths:
+            raise SbxError(SBX_ERR_ARG, "unknown %s function %r" % (family.replace("_", " "), fn))
+        win, wout = widths[fn]
+        x = x.to(self.tdev, self.torch.float32).contiguous().view(x.numel() // win, win)
+        out = self.torch.empty((x.shape[0], wout), dtype=self.torch.float32, device=self.tdev)
+        args = (self.ctx,) + ((fn.encode(),) if named else ()) + tuple(lead) + (ctypes.c_void_p(x.data_ptr()),) + tuple(mid) + \
+               (ctypes.c_void_p(out.data_ptr()), x.shape[0])
+        if counts is None:
+            self._check(getattr(self.lib, "sbx_%s_eval" % family)(*args, self._stream()))
+        else:
+            self._check(getattr(self.lib, "sbx_debug_%s_eval" % family)(*args, counts, self._stream()))
+        return out
+
+    @staticmethod
+    def _by_ref(block):
+        return None if block is None else ctypes.byref(block)
+
+    @staticmethod
+    def _sun_mid(sun_dir):
+        """sbx_atmosphere_eval's sun_dir, which sits between in and out"""
+        return (None if sun_dir is None else ctypes.cast((ctypes.c_float * 3)(*[float(v) for v in sun_dir]), ctypes.c_void_p),)
+
     def atmosphere_eval(self, fn, rays, sun_dir=(0.0, 1.0, 0.0)):
         """The Rayleigh/Mie solver over rays[n, 6] (origin xyz, direction xyz; include/sbx.h sbx_atmosphere_eval) -> [n, 3]:
         fn 'get_incident_light' = linear RGB for the sun direction `sun_dir` (used as given), 'get_sun_light' = (overground,
         optical_depthR, optical_depthM) along the ray (sun_dir may be None)."""
-        return self._atmosphere_eval(fn, rays, sun_dir, None)
+        return self._eval("atmosphere", fn, rays, (), mid=self._sun_mid(sun_dir))
 
     def atmosphere_eval_counted(self, fn, rays, sun_dir=(0.0, 1.0, 0.0)):
         """include/sbx_test.h sbx_debug_atmosphere_eval: atmosphere_eval that waits -> (out, waves that ran the fast forms)"""
         waves = ctypes.c_uint(0)
-        return self._atmosphere_eval(fn, rays, sun_dir, waves), waves.value
-
-    def _atmosphere_eval(self, fn, rays, sun_dir, waves):
-        rays = rays.to(self.tdev, self.torch.float32).contiguous().view(rays.numel() // 6, 6)
-        sun = None if sun_dir is None else (ctypes.c_float * 3)(*[float(v) for v in sun_dir])
-        sun_p = None if sun is None else ctypes.cast(sun, ctypes.c_void_p)
-        out = self.torch.empty((rays.shape[0], 3), dtype=self.torch.float32, device=self.tdev)
-        args = (self.ctx, fn.encode(), ctypes.c_void_p(rays.data_ptr()), sun_p, ctypes.c_void_p(out.data_ptr()), rays.shape[0])
-        if waves is None:
-            self._check(self.lib.sbx_atmosphere_eval(*args, self._stream()))
-        else:
-            self._check(self.lib.sbx_debug_atmosphere_eval(*args, ctypes.byref(waves), self._stream()))
-        return out
+        return self._eval("atmosphere", fn, rays, (), ctypes.byref(waves), mid=self._sun_mid(sun_dir)), waves.value
 
     def atmosphere_air_eval(self, fn, rays, air):
         """The Rayleigh/Mie solver over rays[n, 6] under an AtmosphereAir (include/sbx.h sbx_atmosphere_air_eval) -> [n, 3]: fn
         'get_incident_light' or 'get_sun_light', as atmosphere_eval, with every number of the solver and the sun read from `air`
         (its view, eye, look_at and fov are not)."""
-        return self._atmosphere_air_eval(fn, rays, air, None)
+        return self._eval("atmosphere_air", fn, rays, (self._by_ref(air),))
 
     def atmosphere_air_eval_counted(self, fn, rays, air):
         """include/sbx_test.h sbx_debug_atmosphere_air_eval: atmosphere_air_eval that waits -> (out, waves that ran the fast body)"""
         waves = ctypes.c_uint(0)
-        return self._atmosphere_air_eval(fn, rays, air, waves), waves.value
+        return self._eval("atmosphere_air", fn, rays, (self._by_ref(air),), ctypes.byref(waves)), waves.value
 
-    def _atmosphere_air_eval(self, fn, rays, air, waves):
-        rays = rays.to(self.tdev, self.torch.float32).contiguous().view(rays.numel() // 6, 6)
-        out = self.torch.empty((rays.shape[0], 3), dtype=self.torch.float32, device=self.tdev)
-        args = (self.ctx, fn.encode(), None if air is None else ctypes.byref(air), ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                rays.shape[0])
-        if waves is None:
-            self._check(self.lib.sbx_atmosphere_air_eval(*args, self._stream()))
-        else:
-            self._check(self.lib.sbx_debug_atmosphere_air_eval(*args, ctypes.byref(waves), self._stream()))
-        return out
+    def clouds_eval(self, fn, x, u_time=0.0, aux=None):
+        """APP_CLOUDS' volume and sky over the caller's elements (include/sbx.h sbx_clouds_eval): fn 'render' / 'render_clouds' over rays
+        x[n, 6] (origin xyz, direction xyz) -> [n, 4]; 'render_sky_color' over directions x[n, 3] -> [n, 3]; 'density_func' over points
+        x[n, 3] -> [n, 1]; 'illuminate_volume' over x[n, 6] (origin xyz, V xyz) -> [n, 1].  aux: an AuxClouds, a dict of the fields
+        that differ from the defaults, or None = the defaults.  u_time enters through the wind offset alone."""
+        return self._eval("clouds", fn, x, (self._by_ref(self._clouds_aux(aux)), float(u_time)))
+
+    def clouds_eval_counted(self, fn, x, u_time=0.0, aux=None):
+        """include/sbx_test.h sbx_debug_clouds_eval: clouds_eval that waits -> (out, (noise cells whose hashes came from the context's
+        table, cells hashed in place))"""
+        counts = (ctypes.c_uint64 * 2)(0, 0)
+        return self._eval("clouds", fn, x, (self._by_ref(self._clouds_aux(aux)), float(u_time)), counts), (int(counts[0]), int(counts[1]))
+
+    def planet_eval(self, fn, x, u_time=0.0):
+        """APP_PLANET's terrain, cloud shell and shading over the caller's elements (include/sbx.h sbx_planet_eval): fn 'render' /
+        'terrain_march' over rays x[n, 6] (origin xyz, direction xyz; planet at 0, radius 1) -> [n, 4]; 'sdf_terrain_map' /
+        'sdf_terrain_map_detail' over points x[n, 3] -> [n, 2]; 'sdf_terrain_normal' x[n, 3] -> [n, 3]; 'clouds_density' over x[n, 4]
+        (cloud.pos xyz, cloud.height) -> [n, 1]; 'illuminate' over x[n, 4] (pos xyz, df.y) -> [n, 3]; 'background' over directions
+        x[n, 3] -> [n, 3].  u_time enters through rot / rot_cloud alone."""
+        return self._eval("planet", fn, x, (float(u_time),))
+
+    def planet_eval_counted(self, fn, x, u_time=0.0):
+        """include/sbx_test.h sbx_debug_planet_eval: planet_eval that waits -> (out, (waves with every guarded short form on, waves
+        that took the plain form for at least one part))"""
+        counts = (ctypes.c_uint * 2)(0, 0)
+        return self._eval("planet", fn, x, (float(u_time),), counts), (int(counts[0]), int(counts[1]))
+
+    def egg_eval(self, fn, x, pose=None):
+        """src/IK.h's solver and APP_EGG's field, normal, shadow march and trace over the caller's elements under an EggPose
+        (include/sbx.h sbx_egg_eval): fn 'ik_solver' over x[n, 8] (start xyz, goal xyz, L1, L2) -> [n, 3], pose not read; 'sdf' over
+        points x[n, 3] -> [n, 2] (distance, material id); 'sdf_normal' x[n, 3] -> [n, 3]; 'shadowmarch' over rays x[n, 6] (origin
+        xyz, direction xyz) -> [n, 1]; 'render_scene' over rays x[n, 6] -> [n, 4] (rgb, depth).  Only the pose's turn_deg, feet and
+        bones are read."""
+        return self._eval("egg", fn, x, (self._by_ref(pose),))
+
+    def egg_eval_counted(self, fn, x, pose=None):
+        """include/sbx_test.h sbx_debug_egg_eval: egg_eval that waits -> (out, (waves that took the witnessed roots only, waves that
+        re-ran with the IEEE roots))"""
+        counts = (ctypes.c_uint * 2)(0, 0)
+        return self._eval("egg", fn, x, (self._by_ref(pose),), counts), (int(counts[0]), int(counts[1]))
+
+    def vinyl_eval(self, fn, x, deck):
+        """APP_VINYL's field, normal, soft shadow, shading and trace over the caller's elements under a VinylDeck (include/sbx.h
+        sbx_vinyl_eval): fn 'sdf' over points x[n, 3] -> [n, 2] (distance, material id); 'sdf_normal' x[n, 3] -> [n, 3]; 'sdf_shadow'
+        over rays x[n, 6] (origin xyz, direction xyz) -> [n, 1]; 'illuminate' over x[n, 7] (eye xyz, hit xyz, material id) -> [n, 3];
+        'render' over rays x[n, 6] -> [n, 5] (linear rgb, t, material id or 0).  The deck's camera fields are not read."""
+        return self._eval("vinyl", fn, x, (self._by_ref(deck),))
+
+    def vinyl_eval_counted(self, fn, x, deck):
+        """include/sbx_test.h sbx_debug_vinyl_eval: vinyl_eval that waits -> (out, (waves that took the witnessed roots only, waves
+        that re-ran with the IEEE roots))"""
+        counts = (ctypes.c_uint * 2)(0, 0)
+        return self._eval("vinyl", fn, x, (self._by_ref(deck),), counts), (int(counts[0]), int(counts[1]))
+
+    def sdf_eval(self, scene, xyz):
+        """sdf(pos) of an SdfScene's program over points xyz[n, 3] (include/sbx.h sbx_sdf_eval) -> [n, 2]: the distance and the
+        nearest object's material id as a float.  Only the program of `scene` is read."""
+        return self._eval("sdf", "sdf", xyz, (ctypes.byref(scene),), named=False)
 
     def atmosphere_air_launches(self):
         """include/sbx_test.h sbx_debug_atmosphere_air_launches: (APP_ATMOSPHERE_AIR launches of this context, those that took the
@@ -1195,23 +1273,6 @@ class Renderer:
         c = (ctypes.c_uint64 * 3)(0, 0, 0)
         self._check(self.lib.sbx_debug_atmosphere_air_launches(self.ctx, c))
         return int(c[0]), int(c[1]), int(c[2])
-
-    # sbx_clouds_eval: floats per element in / out
-    CLOUDS_EVAL_WIDTHS = {"render": (6, 4), "render_clouds": (6, 4), "render_sky_color": (3, 3), "density_func": (3, 1),
-                          "illuminate_volume": (6, 1)}
-
-    def clouds_eval(self, fn, x, u_time=0.0, aux=None):
-        """APP_CLOUDS' volume and sky over the caller's elements (include/sbx.h sbx_clouds_eval): fn 'render' / 'render_clouds' over rays
-        x[n, 6] (origin xyz, direction xyz) -> [n, 4]; 'render_sky_color' over directions x[n, 3] -> [n, 3]; 'density_func' over points
-        x[n, 3] -> [n, 1]; 'illuminate_volume' over x[n, 6] (origin xyz, V xyz) -> [n, 1].  aux: an AuxClouds, a dict of the fields
-        that differ from the defaults, or None = the defaults.  u_time enters through the wind offset alone."""
-        return self._clouds_eval(fn, x, u_time, aux, None)
-
-    def clouds_eval_counted(self, fn, x, u_time=0.0, aux=None):
-        """include/sbx_test.h sbx_debug_clouds_eval: clouds_eval that waits -> (out, (noise cells whose hashes came from the context's
-        table, cells hashed in place))"""
-        counts = (ctypes.c_uint64 * 2)(0, 0)
-        return self._clouds_eval(fn, x, u_time, aux, counts), (int(counts[0]), int(counts[1]))
 
     def _clouds_aux(self, aux):
         if aux is None or isinstance(aux, AuxClouds):
@@ -1223,113 +1284,6 @@ class Renderer:
             else:
                 setattr(a, name, v)
         return a
-
-    def _clouds_eval(self, fn, x, u_time, aux, counts):
-        if fn not in self.CLOUDS_EVAL_WIDTHS:
-            raise SbxError(SBX_ERR_ARG, "unknown clouds function %r" % (fn,))
-        win, wout = self.CLOUDS_EVAL_WIDTHS[fn]
-        x = x.to(self.tdev, self.torch.float32).contiguous().view(x.numel() // win, win)
-        a = self._clouds_aux(aux)
-        out = self.torch.empty((x.shape[0], wout), dtype=self.torch.float32, device=self.tdev)
-        args = (self.ctx, fn.encode(), None if a is None else ctypes.byref(a), float(u_time), ctypes.c_void_p(x.data_ptr()),
-                ctypes.c_void_p(out.data_ptr()), x.shape[0])
-        if counts is None:
-            self._check(self.lib.sbx_clouds_eval(*args, self._stream()))
-        else:
-            self._check(self.lib.sbx_debug_clouds_eval(*args, counts, self._stream()))
-        return out
-
-    # sbx_planet_eval: floats per element in / out
-    PLANET_EVAL_WIDTHS = {"render": (6, 4), "terrain_march": (6, 4), "sdf_terrain_map": (3, 2), "sdf_terrain_map_detail": (3, 2),
-                          "sdf_terrain_normal": (3, 3), "clouds_density": (4, 1), "illuminate": (4, 3), "background": (3, 3)}
-
-    def planet_eval(self, fn, x, u_time=0.0):
-        """APP_PLANET's terrain, cloud shell and shading over the caller's elements (include/sbx.h sbx_planet_eval): fn 'render' /
-        'terrain_march' over rays x[n, 6] (origin xyz, direction xyz; planet at 0, radius 1) -> [n, 4]; 'sdf_terrain_map' /
-        'sdf_terrain_map_detail' over points x[n, 3] -> [n, 2]; 'sdf_terrain_normal' x[n, 3] -> [n, 3]; 'clouds_density' over x[n, 4]
-        (cloud.pos xyz, cloud.height) -> [n, 1]; 'illuminate' over x[n, 4] (pos xyz, df.y) -> [n, 3]; 'background' over directions
-        x[n, 3] -> [n, 3].  u_time enters through rot / rot_cloud alone."""
-        return self._planet_eval(fn, x, u_time, None)
-
-    def planet_eval_counted(self, fn, x, u_time=0.0):
-        """include/sbx_test.h sbx_debug_planet_eval: planet_eval that waits -> (out, (waves with every guarded short form on, waves
-        that took the plain form for at least one part))"""
-        counts = (ctypes.c_uint * 2)(0, 0)
-        return self._planet_eval(fn, x, u_time, counts), (int(counts[0]), int(counts[1]))
-
-    def _planet_eval(self, fn, x, u_time, counts):
-        if fn not in self.PLANET_EVAL_WIDTHS:
-            raise SbxError(SBX_ERR_ARG, "unknown planet function %r" % (fn,))
-        win, wout = self.PLANET_EVAL_WIDTHS[fn]
-        x = x.to(self.tdev, self.torch.float32).contiguous().view(x.numel() // win, win)
-        out = self.torch.empty((x.shape[0], wout), dtype=self.torch.float32, device=self.tdev)
-        args = (self.ctx, fn.encode(), float(u_time), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), x.shape[0])
-        if counts is None:
-            self._check(self.lib.sbx_planet_eval(*args, self._stream()))
-        else:
-            self._check(self.lib.sbx_debug_planet_eval(*args, counts, self._stream()))
-        return out
-
-    # sbx_egg_eval: floats per element in / out
-    EGG_EVAL_WIDTHS = {"ik_solver": (8, 3), "sdf": (3, 2), "sdf_normal": (3, 3), "shadowmarch": (6, 1), "render_scene": (6, 4)}
-
-    def egg_eval(self, fn, x, pose=None):
-        """src/IK.h's solver and APP_EGG's field, normal, shadow march and trace over the caller's elements under an EggPose
-        (include/sbx.h sbx_egg_eval): fn 'ik_solver' over x[n, 8] (start xyz, goal xyz, L1, L2) -> [n, 3], pose not read; 'sdf' over
-        points x[n, 3] -> [n, 2] (distance, material id); 'sdf_normal' x[n, 3] -> [n, 3]; 'shadowmarch' over rays x[n, 6] (origin
-        xyz, direction xyz) -> [n, 1]; 'render_scene' over rays x[n, 6] -> [n, 4] (rgb, depth).  Only the pose's turn_deg, feet and
-        bones are read."""
-        return self._egg_eval(fn, x, pose, None)
-
-    def egg_eval_counted(self, fn, x, pose=None):
-        """include/sbx_test.h sbx_debug_egg_eval: egg_eval that waits -> (out, (waves that took the witnessed roots only, waves that
-        re-ran with the IEEE roots))"""
-        counts = (ctypes.c_uint * 2)(0, 0)
-        return self._egg_eval(fn, x, pose, counts), (int(counts[0]), int(counts[1]))
-
-    def _egg_eval(self, fn, x, pose, counts):
-        if fn not in self.EGG_EVAL_WIDTHS:
-            raise SbxError(SBX_ERR_ARG, "unknown egg function %r" % (fn,))
-        win, wout = self.EGG_EVAL_WIDTHS[fn]
-        x = x.to(self.tdev, self.torch.float32).contiguous().view(x.numel() // win, win)
-        out = self.torch.empty((x.shape[0], wout), dtype=self.torch.float32, device=self.tdev)
-        args = (self.ctx, fn.encode(), None if pose is None else ctypes.byref(pose), ctypes.c_void_p(x.data_ptr()),
-                ctypes.c_void_p(out.data_ptr()), x.shape[0])
-        if counts is None:
-            self._check(self.lib.sbx_egg_eval(*args, self._stream()))
-        else:
-            self._check(self.lib.sbx_debug_egg_eval(*args, counts, self._stream()))
-        return out
-
-    # sbx_vinyl_eval: floats per element in / out
-    VINYL_EVAL_WIDTHS = {"sdf": (3, 2), "sdf_normal": (3, 3), "sdf_shadow": (6, 1), "illuminate": (7, 3), "render": (6, 5)}
-
-    def vinyl_eval(self, fn, x, deck):
-        """APP_VINYL's field, normal, soft shadow, shading and trace over the caller's elements under a VinylDeck (include/sbx.h
-        sbx_vinyl_eval): fn 'sdf' over points x[n, 3] -> [n, 2] (distance, material id); 'sdf_normal' x[n, 3] -> [n, 3]; 'sdf_shadow'
-        over rays x[n, 6] (origin xyz, direction xyz) -> [n, 1]; 'illuminate' over x[n, 7] (eye xyz, hit xyz, material id) -> [n, 3];
-        'render' over rays x[n, 6] -> [n, 5] (linear rgb, t, material id or 0).  The deck's camera fields are not read."""
-        return self._vinyl_eval(fn, x, deck, None)
-
-    def vinyl_eval_counted(self, fn, x, deck):
-        """include/sbx_test.h sbx_debug_vinyl_eval: vinyl_eval that waits -> (out, (waves that took the witnessed roots only, waves
-        that re-ran with the IEEE roots))"""
-        counts = (ctypes.c_uint * 2)(0, 0)
-        return self._vinyl_eval(fn, x, deck, counts), (int(counts[0]), int(counts[1]))
-
-    def _vinyl_eval(self, fn, x, deck, counts):
-        if fn not in self.VINYL_EVAL_WIDTHS:
-            raise SbxError(SBX_ERR_ARG, "unknown vinyl function %r" % (fn,))
-        win, wout = self.VINYL_EVAL_WIDTHS[fn]
-        x = x.to(self.tdev, self.torch.float32).contiguous().view(x.numel() // win, win)
-        out = self.torch.empty((x.shape[0], wout), dtype=self.torch.float32, device=self.tdev)
-        args = (self.ctx, fn.encode(), None if deck is None else ctypes.byref(deck), ctypes.c_void_p(x.data_ptr()),
-                ctypes.c_void_p(out.data_ptr()), x.shape[0])
-        if counts is None:
-            self._check(self.lib.sbx_vinyl_eval(*args, self._stream()))
-        else:
-            self._check(self.lib.sbx_debug_vinyl_eval(*args, counts, self._stream()))
-        return out
 
     def vinyl_deck_launches(self):
         """include/sbx_test.h sbx_debug_vinyl_deck_launches: (APP_VINYL_DECK launches of this context, those of them an untame deck sent
@@ -1344,15 +1298,6 @@ class Renderer:
         c = (ctypes.c_uint64 * 2)(0, 0)
         self._check(self.lib.sbx_debug_egg_pose_launches(self.ctx, c))
         return int(c[0]), int(c[1])
-
-    def sdf_eval(self, scene, xyz):
-        """sdf(pos) of an SdfScene's program over points xyz[n, 3] (include/sbx.h sbx_sdf_eval) -> [n, 2]: the distance and the
-        nearest object's material id as a float.  Only the program of `scene` is read."""
-        xyz = xyz.to(self.tdev, self.torch.float32).contiguous().view(xyz.numel() // 3, 3)
-        out = self.torch.empty((xyz.shape[0], 2), dtype=self.torch.float32, device=self.tdev)
-        self._check(self.lib.sbx_sdf_eval(self.ctx, ctypes.byref(scene), ctypes.c_void_p(xyz.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                          xyz.shape[0], self._stream()))
-        return out
 
     def worley_volume(self, size=128):
         """The ddsvolgen noise volume: float32 [size, size, size, 4] (z, y, x, rgba)."""

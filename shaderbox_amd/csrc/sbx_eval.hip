@@ -1,9 +1,181 @@
 // shaderbox_amd/csrc/sbx_eval.hip — the hooks that evaluate one piece of the math spec or of a kernel on the device for the tests
-// (include/sbx_test.h), and the binding of what the textured apps sample: t0 of APP_2D_TEX, the noise volumes of APP_CLOUDS_TEX.
+// (include/sbx_test.h), the eval entries ("a function of an app over the caller's elements": sbx_atmosphere_eval, sbx_atmosphere_air_eval,
+// sbx_sdf_eval, sbx_clouds_eval, sbx_planet_eval, sbx_egg_eval, sbx_vinyl_eval of include/sbx.h, six of them with a counted twin in
+// include/sbx_test.h), and the binding of what the textured apps sample: t0 of APP_2D_TEX, the noise volumes of APP_CLOUDS_TEX.
+// The eval entries share one argument check (eval_args), one plain launch and one counted launch; a new one brings its name list, its
+// `*_eval_args` with whatever check is its own, and its `*_eval_launch` closure, all in the section below.
 #include "sbx_ctx.h"
 #include <cstring>
 
 using namespace sbx;
+
+namespace {
+
+// ---- what the eval entries share
+
+// the index of fn among names, or -1 (a NULL fn too)
+template <size_t N>
+int name_id(const char* fn, const char* const (&names)[N]) {
+    for (size_t i = 0; fn && i < N; ++i) if (std::strcmp(fn, names[i]) == 0) return (int)i;
+    return -1;
+}
+
+// The checks of every eval entry: SBX_OK, or the failure.  `id` is name_id's answer for fn, `unknown` the family's words for a miss,
+// `own` the entry's complaint about its own arguments (NULL: none), which holds at n == 0 too; n == 0 is SBX_OK with `in` and `out`
+// not looked at, so the caller returns before its launch.
+int eval_args(sbx_ctx* ctx, const char* fn, int id, const char* unknown, const char* own, const char* too_many, const void* in, const void* out,
+              size_t n) {
+    if (!ctx) return SBX_ERR_ARG;
+    if (!fn) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    if (id < 0) return fail(ctx, SBX_ERR_ARG, unknown);
+    if (own) return fail(ctx, SBX_ERR_ARG, own);
+    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, too_many);
+    if (n == 0) return SBX_OK;
+    if (!in || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    return SBX_OK;
+}
+
+// the entry itself: one kernel launch and nothing else (capturable).  launch(counters, stream) with no counters.
+template <class Launch>
+int plain_launch(sbx_ctx* ctx, const char* what, void* stream, Launch launch) {
+    const int rc = use_device(ctx);
+    if (rc != SBX_OK) return rc;
+    launch(nullptr, (hipStream_t)stream);
+    return launched(ctx, what);
+}
+
+// The counted twin: the same launch with K device words of type W zeroed before it and read back into host[0..K) after it.  It
+// allocates and waits, so it is not capturable: a capturing stream is refused with the capture intact.
+template <class W, int K, class H, class Launch>
+int counted_launch(sbx_ctx* ctx, const char* what, size_t n, H* host, void* stream, Launch launch) {
+    if (!host) return fail(ctx, SBX_ERR_ARG, "NULL argument");
+    for (int k = 0; k < K; ++k) host[k] = 0;
+    if (n == 0) return SBX_OK;
+    const int rc = use_device(ctx);
+    if (rc != SBX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_is_capturing(s)) return fail(ctx, SBX_ERR_ARG, "the counted launch is not capturable");
+    W* counts = nullptr;
+    hipError_t e = hipMalloc((void**)&counts, K * sizeof(W));
+    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
+    if ((e = hipMemsetAsync(counts, 0, K * sizeof(W), s)) == hipSuccess) {
+        launch(counts, s);
+        W h[K] = {};
+        if ((e = hipGetLastError()) == hipSuccess && (e = hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, s)) == hipSuccess)
+            e = hipStreamSynchronize(s);
+        for (int k = 0; k < K; ++k) host[k] = h[k];
+    }
+    (void)hipFree(counts);
+    return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, what, e);
+}
+
+// a 1 x 1 frame at u_time: what the build_* of an app need to give the frame constants of a block (its camera is not read by the kernels)
+sbx_uniforms frame_1x1(float u_time) { return {{1.f, 1.f}, {0.f, 0.f}, u_time, {0.f, 0.f, 0.f}}; }
+
+// ---- each family: its names, the checks that are its own, its launch
+
+const char* const ATMOSPHERE_FNS[] = {"get_incident_light", "get_sun_light"};
+
+// get_incident_light needs sun_dir, and only where it has rays
+int atmosphere_eval_args(sbx_ctx* ctx, const char* fn, const float* rays, const float* sun_dir, const float* out, size_t n, int& id) {
+    id = name_id(fn, ATMOSPHERE_FNS);
+    const int rc = eval_args(ctx, fn, id, "unknown atmosphere function", nullptr, "more than 2^31 rays", rays, out, n);
+    if (rc == SBX_OK && n > 0 && id == 0 && !sun_dir) return fail(ctx, SBX_ERR_ARG, "get_incident_light needs sun_dir");
+    return rc;
+}
+auto atmosphere_eval_launch(const sbx_ctx* ctx, int id, const float* rays, const float* sun_dir, float* out, size_t n) {
+    return [=](unsigned* fast_waves, hipStream_t s) { launch_atmosphere_eval(id, ctx->variant == 1, rays, sun_dir, out, n, fast_waves, s); };
+}
+
+// the block is required and checked whatever n is
+int atmosphere_air_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_atmosphere_air* air, const float* rays, const float* out, size_t n, int& id) {
+    id = name_id(fn, ATMOSPHERE_FNS);
+    return eval_args(ctx, fn, id, "unknown atmosphere function", !air ? "NULL argument" : atmosphere_air_check(*air, false), "more than 2^31 rays", rays,
+                     out, n);
+}
+// the block is read here, on the host, during the call: the kernel gets its numbers as arguments
+auto atmosphere_air_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_atmosphere_air* air, const float* rays, float* out, size_t n) {
+    return [=](unsigned* fast_waves, hipStream_t s) {
+        const sbx_aux_atmosphere_air& A = *air;
+        launch_atmosphere_air_eval(id, atmosphere_air_tier(A, ctx->variant, false) == ATM_AIR_RUNTIME, rays, A.sun_dir, atmosphere_air_numbers(A), out, n,
+                                   fast_waves, s);
+    };
+}
+
+// a NULL aux is the defaults; AC is the block either way.  Negative march steps are refused whatever n is.
+int clouds_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, const float* in, const float* out, size_t n, int& id, sbx_aux_clouds& AC) {
+    static const char* const names[] = {"render", "render_clouds", "render_sky_color", "density_func", "illuminate_volume"};
+    id = name_id(fn, names);
+    AC = aux_clouds(aux);
+    const bool negative = AC.cld_march_steps < 0 || AC.illum_march_steps < 0;
+    return eval_args(ctx, fn, id, "unknown clouds function", negative ? "negative march steps" : nullptr, "more than 2^31 elements", in, out, n);
+}
+// The frame constants of the block: build_clouds over u_time alone.  The sky reads no hash; the plain form hashes in place.  No usable
+// table (a capture before one was seen complete, which only the entry itself can meet: may_capture; a failed allocation): every cell
+// in place, the same bits
+auto clouds_eval_launch(sbx_ctx* ctx, int id, const sbx_aux_clouds& AC, float u_time, const float* in, float* out, size_t n, bool may_capture) {
+    return [=](unsigned long long* counts, hipStream_t s) {
+        const bool plain = ctx->variant == 1;
+        CloudsHashTab ht;
+        if (!plain && id != 2) ht = clouds_hash_table_any(ctx, s, may_capture && stream_is_capturing(s));
+        launch_clouds_eval(id, build_clouds(frame_1x1(u_time), AC, false), plain, &ht, in, out, n, counts, s);
+    };
+}
+
+int planet_eval_args(sbx_ctx* ctx, const char* fn, const float* in, const float* out, size_t n, int& id) {
+    static const char* const names[] = {"render", "terrain_march", "sdf_terrain_map", "sdf_terrain_map_detail", "sdf_terrain_normal",
+                                        "clouds_density", "illuminate", "background"};
+    id = name_id(fn, names);
+    return eval_args(ctx, fn, id, "unknown planet function", nullptr, "more than 2^31 elements", in, out, n);
+}
+// The frame constants: build_planet over u_time alone.  The guarded short forms assume rotations of a finite, bounded angle
+// (sbx_capi.hip tame_time, the same bound): beyond it the plain form
+auto planet_eval_launch(const sbx_ctx* ctx, int id, float u_time, const float* in, float* out, size_t n) {
+    return [=](unsigned* counts, hipStream_t s) {
+        const bool plain = ctx->variant == 1 || !(std::fabs(u_time) <= 1e8f);
+        launch_planet_eval(id, build_planet(frame_1x1(u_time)), plain, in, out, n, counts, s);
+    };
+}
+
+// id 0 = "ik_solver", else 1 + launch_egg_eval's fn; every function but ik_solver needs a pose, whatever n is
+int egg_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, const float* in, const float* out, size_t n, int& id) {
+    static const char* const names[] = {"ik_solver", "sdf", "sdf_normal", "shadowmarch", "render_scene"};
+    id = name_id(fn, names);
+    return eval_args(ctx, fn, id, "unknown egg function", id > 0 && !pose ? "every egg function but ik_solver needs a pose" : nullptr,
+                     "more than 2^31 elements", in, out, n);
+}
+// the frame of the block with the shipped camera in place of the block's; a pose outside the domain of the culls and witnessed roots
+// (sbx_frames.hip egg_pose_tame, the camera's fields so ignored) takes the reference form
+auto egg_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_egg_pose* pose, const float* in, float* out, size_t n) {
+    return [=](unsigned* counts, hipStream_t s) {
+        if (id == 0) { launch_ik_eval(in, out, n, s); return; }
+        sbx_aux_egg_pose A = *pose;
+        A.eye[0] = 0.f; A.eye[1] = .25f; A.eye[2] = 5.25f; A.look_at[0] = 0.f; A.look_at[1] = .25f; A.look_at[2] = 0.f; A.fov = 1.f;
+        const FrameEggStraight F = build_egg_pose(frame_1x1(0.f), A, EGG_DEFAULT);
+        const int variant = ctx->variant == 1 || !egg_pose_tame(A, F) ? 1 : ctx->sdf_roots;
+        launch_egg_eval(id - 1, F, variant, in, out, n, counts, s);
+    };
+}
+
+// id = launch_vinyl_eval's fn; the deck is required whatever n is
+int vinyl_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck* deck, const float* in, const float* out, size_t n, int& id) {
+    static const char* const names[] = {"sdf", "sdf_normal", "sdf_shadow", "illuminate", "render"};
+    id = name_id(fn, names);
+    return eval_args(ctx, fn, id, "unknown vinyl function", !deck ? "NULL argument" : nullptr, "more than 2^31 elements", in, out, n);
+}
+// the frame of the block with the shipped camera in place of the block's (the kernel reads no camera; a deck outside the domain of the
+// culls, sbx_frames.hip vinyl_deck_tame with the camera's fields so ignored, takes the reference form)
+auto vinyl_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_vinyl_deck* deck, const float* in, float* out, size_t n) {
+    return [=](unsigned* counts, hipStream_t s) {
+        sbx_aux_vinyl_deck A = *deck;
+        A.eye[0] = 0.f; A.eye[1] = 5.75f; A.eye[2] = 6.75f; A.look_at[0] = 0.f; A.look_at[1] = -2.5f; A.look_at[2] = 0.f; A.fov = 1.f;
+        const FrameVinyl F = build_vinyl_deck(frame_1x1(0.f), A, 60);
+        const int variant = ctx->variant == 1 || !vinyl_deck_tame(A, F) ? 1 : ctx->sdf_roots;
+        launch_vinyl_eval(id, F, vinyl_shade_of(A), variant, in, out, n, counts, s);
+    };
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -20,9 +192,8 @@ int sbx_pack_unorm8(sbx_ctx* ctx, int width, int rows, const float* rgba, unsign
 int sbx_math_eval(sbx_ctx* ctx, const char* fn, const float* a, const float* b, float* out, size_t n, void* stream) {
     if (!ctx) return SBX_ERR_ARG;
     if (!fn || !a || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    static const char* names[] = {"sin", "cos", "tan", "exp", "pow", "acos", "atan2", "hash", "div", "div_rd", "exp_h13", "pow_h", "sqrt_n", "sqrt_ieee", "exp_reg", "exp_reg_plain", "exp_reg64", "exp_reg64_plain", "exp_small", "exp_small_plain", "exp_reg4k", "sin_b40", "div3", "sqrt_rs", "divn", "srgb_pow", "pow_spec"};
-    int id = -1;
-    for (int i = 0; i < 27; ++i) if (std::strcmp(fn, names[i]) == 0) id = i;
+    static const char* const names[] = {"sin", "cos", "tan", "exp", "pow", "acos", "atan2", "hash", "div", "div_rd", "exp_h13", "pow_h", "sqrt_n", "sqrt_ieee", "exp_reg", "exp_reg_plain", "exp_reg64", "exp_reg64_plain", "exp_small", "exp_small_plain", "exp_reg4k", "sin_b40", "div3", "sqrt_rs", "divn", "srgb_pow", "pow_spec"};
+    const int id = name_id(fn, names);
     if (id < 0) return fail(ctx, SBX_ERR_ARG, "unknown math function");
     if ((id == 4 || id == 6 || id == 8 || id == 9 || id == 11 || id == 22 || id == 24 || id == 26) && !b) return fail(ctx, SBX_ERR_ARG, "binary function needs b");
     if (n == 0) return SBX_OK;
@@ -39,10 +210,9 @@ int sbx_noise_eval(sbx_ctx* ctx, const char* fn, const float* xyz, const float* 
                    void* stream) {
     if (!ctx) return SBX_ERR_ARG;
     if (!fn || !xyz || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    static const char* names[] = {"noise_iq", "hash_w", "noise_w", "fbm_worley_tile", "normalize", "wit_normalize", "wit_record",
-                                  "worley_fbm"};
-    int id = -1;
-    for (int i = 0; i < 8; ++i) if (std::strcmp(fn, names[i]) == 0) id = i;
+    static const char* const names[] = {"noise_iq", "hash_w", "noise_w", "fbm_worley_tile", "normalize", "wit_normalize", "wit_record",
+                                        "worley_fbm"};
+    const int id = name_id(fn, names);
     if (id < 0) return fail(ctx, SBX_ERR_ARG, "unknown noise function");
     const float zero[3] = {0.f, 0.f, 0.f};
     if ((id == 2 || id == 3) && !params) return fail(ctx, SBX_ERR_ARG, "noise_w / fbm_worley_tile need params");
@@ -53,362 +223,115 @@ int sbx_noise_eval(sbx_ctx* ctx, const char* fn, const float* xyz, const float* 
     return launched(ctx, "noise_eval launch");
 }
 
-// the checks sbx_atmosphere_eval and its test hook share: SBX_OK with fn_id set, or the failure
-static int atmosphere_eval_args(sbx_ctx* ctx, const char* fn, const float* rays, const float* sun_dir, const float* out, size_t n, int& fn_id) {
-    if (!ctx) return SBX_ERR_ARG;
-    if (!fn) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    fn_id = std::strcmp(fn, "get_incident_light") == 0 ? 0 : std::strcmp(fn, "get_sun_light") == 0 ? 1 : -1;
-    if (fn_id < 0) return fail(ctx, SBX_ERR_ARG, "unknown atmosphere function");
-    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 rays");
-    if (n == 0) return SBX_OK;
-    if (!rays || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    if (fn_id == 0 && !sun_dir) return fail(ctx, SBX_ERR_ARG, "get_incident_light needs sun_dir");
-    return SBX_OK;
-}
+// ---- the eval entries.  Each checks its arguments (`*_eval_args`: eval_args around what is the family's own), states its launch once
+// (`*_eval_launch`: a closure over the counter pointer and the stream) and hands that to plain_launch, its counted twin to counted_launch.
 
 int sbx_atmosphere_eval(sbx_ctx* ctx, const char* fn, const float* rays, const float* sun_dir, float* out, size_t n, void* stream) {
     int id = -1;
-    int rc = atmosphere_eval_args(ctx, fn, rays, sun_dir, out, n, id);
+    const int rc = atmosphere_eval_args(ctx, fn, rays, sun_dir, out, n, id);
     if (rc != SBX_OK || n == 0) return rc;
-    if ((rc = use_device(ctx)) != SBX_OK) return rc;
-    launch_atmosphere_eval(id, ctx->variant == 1, rays, sun_dir, out, n, nullptr, (hipStream_t)stream);
-    return launched(ctx, "atmosphere_eval launch");
+    return plain_launch(ctx, "atmosphere_eval launch", stream, atmosphere_eval_launch(ctx, id, rays, sun_dir, out, n));
 }
 
 int sbx_debug_atmosphere_eval(sbx_ctx* ctx, const char* fn, const float* rays, const float* sun_dir, float* out, size_t n,
                               unsigned* fast_waves_host, void* stream) {
     int id = -1;
-    int rc = atmosphere_eval_args(ctx, fn, rays, sun_dir, out, n, id);
+    const int rc = atmosphere_eval_args(ctx, fn, rays, sun_dir, out, n, id);
     if (rc != SBX_OK) return rc;
-    if (!fast_waves_host) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    *fast_waves_host = 0;
-    if (n == 0) return SBX_OK;
-    if ((rc = use_device(ctx)) != SBX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned* counter = nullptr;
-    hipError_t e = hipMalloc((void**)&counter, sizeof(unsigned));
-    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
-    if ((e = hipMemsetAsync(counter, 0, sizeof(unsigned), s)) == hipSuccess) {
-        launch_atmosphere_eval(id, ctx->variant == 1, rays, sun_dir, out, n, counter, s);
-        if ((e = hipGetLastError()) == hipSuccess && (e = hipMemcpyAsync(fast_waves_host, counter, sizeof(unsigned), hipMemcpyDeviceToHost, s)) == hipSuccess)
-            e = hipStreamSynchronize(s);
-    }
-    (void)hipFree(counter);
-    return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "atmosphere_eval (counted)", e);
-}
-
-// the checks sbx_atmosphere_air_eval and its test hook share
-static int atmosphere_air_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_atmosphere_air* air, const float* rays, const float* out, size_t n, int& fn_id) {
-    if (!ctx) return SBX_ERR_ARG;
-    if (!fn || !air) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    fn_id = std::strcmp(fn, "get_incident_light") == 0 ? 0 : std::strcmp(fn, "get_sun_light") == 0 ? 1 : -1;
-    if (fn_id < 0) return fail(ctx, SBX_ERR_ARG, "unknown atmosphere function");
-    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 rays");
-    if (const char* why = atmosphere_air_check(*air, false)) return fail(ctx, SBX_ERR_ARG, why);
-    if (n == 0) return SBX_OK;
-    if (!rays || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    return SBX_OK;
-}
-// the block is read here, on the host, during the call: the kernel gets its numbers as arguments
-static void atmosphere_air_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_atmosphere_air& A, const float* rays, float* out, size_t n,
-                                       unsigned* fast_waves, hipStream_t s) {
-    launch_atmosphere_air_eval(id, atmosphere_air_tier(A, ctx->variant, false) == ATM_AIR_RUNTIME, rays, A.sun_dir, atmosphere_air_numbers(A), out, n,
-                               fast_waves, s);
+    return counted_launch<unsigned, 1>(ctx, "atmosphere_eval (counted)", n, fast_waves_host, stream, atmosphere_eval_launch(ctx, id, rays, sun_dir, out, n));
 }
 
 int sbx_atmosphere_air_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_atmosphere_air* air, const float* rays, float* out, size_t n, void* stream) {
     int id = -1;
-    int rc = atmosphere_air_eval_args(ctx, fn, air, rays, out, n, id);
+    const int rc = atmosphere_air_eval_args(ctx, fn, air, rays, out, n, id);
     if (rc != SBX_OK || n == 0) return rc;
-    if ((rc = use_device(ctx)) != SBX_OK) return rc;
-    atmosphere_air_eval_launch(ctx, id, *air, rays, out, n, nullptr, (hipStream_t)stream);
-    return launched(ctx, "atmosphere_air_eval launch");
+    return plain_launch(ctx, "atmosphere_air_eval launch", stream, atmosphere_air_eval_launch(ctx, id, air, rays, out, n));
 }
 
 int sbx_debug_atmosphere_air_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_atmosphere_air* air, const float* rays, float* out, size_t n,
                                   unsigned* fast_waves_host, void* stream) {
     int id = -1;
-    int rc = atmosphere_air_eval_args(ctx, fn, air, rays, out, n, id);
+    const int rc = atmosphere_air_eval_args(ctx, fn, air, rays, out, n, id);
     if (rc != SBX_OK) return rc;
-    if (!fast_waves_host) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    *fast_waves_host = 0;
-    if (n == 0) return SBX_OK;
-    if ((rc = use_device(ctx)) != SBX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned* counter = nullptr;
-    hipError_t e = hipMalloc((void**)&counter, sizeof(unsigned));
-    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
-    if ((e = hipMemsetAsync(counter, 0, sizeof(unsigned), s)) == hipSuccess) {
-        atmosphere_air_eval_launch(ctx, id, *air, rays, out, n, counter, s);
-        if ((e = hipGetLastError()) == hipSuccess && (e = hipMemcpyAsync(fast_waves_host, counter, sizeof(unsigned), hipMemcpyDeviceToHost, s)) == hipSuccess)
-            e = hipStreamSynchronize(s);
-    }
-    (void)hipFree(counter);
-    return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "atmosphere_air_eval (counted)", e);
+    return counted_launch<unsigned, 1>(ctx, "atmosphere_air_eval (counted)", n, fast_waves_host, stream, atmosphere_air_eval_launch(ctx, id, air, rays, out, n));
 }
 
 int sbx_sdf_eval(sbx_ctx* ctx, const sbx_aux_sdf_scene* scene, const float* xyz, float* out, size_t n, void* stream) {
-    if (!ctx) return SBX_ERR_ARG;
-    if (!scene) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    if (const char* why = sdf_scene_check(*scene, true)) return fail(ctx, SBX_ERR_ARG, why);
-    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 points");
-    if (n == 0) return SBX_OK;
-    if (!xyz || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    const int rc = use_device(ctx);
-    if (rc != SBX_OK) return rc;
-    // only the program of the block is read: the renderer's settings are taken from the ramp block, whatever the caller's hold
-    sbx_aux_sdf_scene A;
-    const sbx_uniforms U = {{1.f, 1.f}, {0.f, 0.f}, 0.f, {0.f, 0.f, 0.f}};
-    sbx_sdf_scene_ramp(&U, &A);
-    A.n_instr = scene->n_instr;
-    std::memcpy(A.program, scene->program, sizeof(A.program));
-    launch_sdf_scene_eval(build_sdf_scene(U, A), xyz, out, n, (hipStream_t)stream, ctx->variant == 1 ? 1 : ctx->sdf_roots);
-    return launched(ctx, "sdf_eval launch");
-}
-
-// the checks sbx_clouds_eval and its test hook share: SBX_OK with fn_id and the block set, or the failure
-static int clouds_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, const float* in, const float* out, size_t n, int& fn_id,
-                            sbx_aux_clouds& AC) {
-    if (!ctx) return SBX_ERR_ARG;
-    if (!fn) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    static const char* names[] = {"render", "render_clouds", "render_sky_color", "density_func", "illuminate_volume"};
-    fn_id = -1;
-    for (int i = 0; i < 5; ++i) if (std::strcmp(fn, names[i]) == 0) fn_id = i;
-    if (fn_id < 0) return fail(ctx, SBX_ERR_ARG, "unknown clouds function");
-    AC = aux_clouds(aux);
-    if (AC.cld_march_steps < 0 || AC.illum_march_steps < 0) return fail(ctx, SBX_ERR_ARG, "negative march steps");
-    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 elements");
-    if (n == 0) return SBX_OK;
-    if (!in || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    return SBX_OK;
-}
-// the frame constants of the caller's block: build_clouds over u_time alone (its camera is not read by the kernel)
-static FrameClouds clouds_eval_frame(const sbx_aux_clouds& AC, float u_time) {
-    const sbx_uniforms U = {{1.f, 1.f}, {0.f, 0.f}, u_time, {0.f, 0.f, 0.f}};
-    return build_clouds(U, AC, false);
+    // one function, so no name: the scene's complaint stands where a family's own does, before the sizes
+    const int rc = eval_args(ctx, "", 0, nullptr, !scene ? "NULL argument" : sdf_scene_check(*scene, true), "more than 2^31 points", xyz, out, n);
+    if (rc != SBX_OK || n == 0) return rc;
+    return plain_launch(ctx, "sdf_eval launch", stream, [=](unsigned*, hipStream_t s) {
+        // only the program of the block is read: the renderer's settings are taken from the ramp block, whatever the caller's hold
+        sbx_aux_sdf_scene A;
+        const sbx_uniforms U = frame_1x1(0.f);
+        sbx_sdf_scene_ramp(&U, &A);
+        A.n_instr = scene->n_instr;
+        std::memcpy(A.program, scene->program, sizeof(A.program));
+        launch_sdf_scene_eval(build_sdf_scene(U, A), xyz, out, n, s, ctx->variant == 1 ? 1 : ctx->sdf_roots);
+    });
 }
 
 int sbx_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, float u_time, const float* in, float* out, size_t n,
                     void* stream) {
     int id = -1;
     sbx_aux_clouds AC;
-    int rc = clouds_eval_args(ctx, fn, aux, in, out, n, id, AC);
+    const int rc = clouds_eval_args(ctx, fn, aux, in, out, n, id, AC);
     if (rc != SBX_OK || n == 0) return rc;
-    if ((rc = use_device(ctx)) != SBX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const bool plain = ctx->variant == 1;
-    // the sky reads no hash; the plain form hashes in place.  No usable table (a capture before one was seen complete, a failed
-    // allocation): every cell in place, the same bits
-    CloudsHashTab ht;
-    if (!plain && id != 2) ht = clouds_hash_table_any(ctx, s, stream_is_capturing(s));
-    launch_clouds_eval(id, clouds_eval_frame(AC, u_time), plain, &ht, in, out, n, nullptr, s);
-    return launched(ctx, "clouds_eval launch");
+    return plain_launch(ctx, "clouds_eval launch", stream, clouds_eval_launch(ctx, id, AC, u_time, in, out, n, true));
 }
 
 int sbx_debug_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, float u_time, const float* in, float* out, size_t n,
                           uint64_t counts_host[2], void* stream) {
     int id = -1;
     sbx_aux_clouds AC;
-    int rc = clouds_eval_args(ctx, fn, aux, in, out, n, id, AC);
+    const int rc = clouds_eval_args(ctx, fn, aux, in, out, n, id, AC);
     if (rc != SBX_OK) return rc;
-    if (!counts_host) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    counts_host[0] = counts_host[1] = 0;
-    if (n == 0) return SBX_OK;
-    if ((rc = use_device(ctx)) != SBX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (stream_is_capturing(s)) return fail(ctx, SBX_ERR_ARG, "the counted launch is not capturable");
-    const bool plain = ctx->variant == 1;
-    unsigned long long* counts = nullptr;
-    hipError_t e = hipMalloc((void**)&counts, 2 * sizeof(unsigned long long));
-    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
-    if ((e = hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), s)) == hipSuccess) {
-        CloudsHashTab ht;
-        if (!plain && id != 2) ht = clouds_hash_table_any(ctx, s, false);
-        launch_clouds_eval(id, clouds_eval_frame(AC, u_time), plain, &ht, in, out, n, counts, s);
-        unsigned long long h[2] = {0, 0};
-        if ((e = hipGetLastError()) == hipSuccess && (e = hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, s)) == hipSuccess)
-            e = hipStreamSynchronize(s);
-        counts_host[0] = h[0]; counts_host[1] = h[1];
-    }
-    (void)hipFree(counts);
-    return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "clouds_eval (counted)", e);
+    return counted_launch<unsigned long long, 2>(ctx, "clouds_eval (counted)", n, counts_host, stream, clouds_eval_launch(ctx, id, AC, u_time, in, out, n, false));
 }
-
-// the checks sbx_planet_eval and its test hook share: SBX_OK with fn_id set, or the failure
-static int planet_eval_args(sbx_ctx* ctx, const char* fn, const float* in, const float* out, size_t n, int& fn_id) {
-    if (!ctx) return SBX_ERR_ARG;
-    if (!fn) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    static const char* names[] = {"render", "terrain_march", "sdf_terrain_map", "sdf_terrain_map_detail", "sdf_terrain_normal",
-                                  "clouds_density", "illuminate", "background"};
-    fn_id = -1;
-    for (int i = 0; i < 8; ++i) if (std::strcmp(fn, names[i]) == 0) fn_id = i;
-    if (fn_id < 0) return fail(ctx, SBX_ERR_ARG, "unknown planet function");
-    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 elements");
-    if (n == 0) return SBX_OK;
-    if (!in || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    return SBX_OK;
-}
-// the frame constants: build_planet over u_time alone (its camera is not read by the kernel)
-static FramePlanet planet_eval_frame(float u_time) {
-    const sbx_uniforms U = {{1.f, 1.f}, {0.f, 0.f}, u_time, {0.f, 0.f, 0.f}};
-    return build_planet(U);
-}
-// the guarded short forms assume rotations of a finite, bounded angle (sbx_capi.hip tame_time, the same bound): beyond it the plain form
-static bool planet_eval_plain(const sbx_ctx* ctx, float u_time) { return ctx->variant == 1 || !(std::fabs(u_time) <= 1e8f); }
 
 int sbx_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const float* in, float* out, size_t n, void* stream) {
     int id = -1;
-    int rc = planet_eval_args(ctx, fn, in, out, n, id);
+    const int rc = planet_eval_args(ctx, fn, in, out, n, id);
     if (rc != SBX_OK || n == 0) return rc;
-    if ((rc = use_device(ctx)) != SBX_OK) return rc;
-    launch_planet_eval(id, planet_eval_frame(u_time), planet_eval_plain(ctx, u_time), in, out, n, nullptr, (hipStream_t)stream);
-    return launched(ctx, "planet_eval launch");
+    return plain_launch(ctx, "planet_eval launch", stream, planet_eval_launch(ctx, id, u_time, in, out, n));
 }
 
 int sbx_debug_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const float* in, float* out, size_t n, unsigned counts_host[2],
                           void* stream) {
     int id = -1;
-    int rc = planet_eval_args(ctx, fn, in, out, n, id);
+    const int rc = planet_eval_args(ctx, fn, in, out, n, id);
     if (rc != SBX_OK) return rc;
-    if (!counts_host) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    counts_host[0] = counts_host[1] = 0;
-    if (n == 0) return SBX_OK;
-    if ((rc = use_device(ctx)) != SBX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (stream_is_capturing(s)) return fail(ctx, SBX_ERR_ARG, "the counted launch is not capturable");
-    unsigned* counts = nullptr;
-    hipError_t e = hipMalloc((void**)&counts, 2 * sizeof(unsigned));
-    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
-    if ((e = hipMemsetAsync(counts, 0, 2 * sizeof(unsigned), s)) == hipSuccess) {
-        launch_planet_eval(id, planet_eval_frame(u_time), planet_eval_plain(ctx, u_time), in, out, n, counts, s);
-        unsigned h[2] = {0, 0};
-        if ((e = hipGetLastError()) == hipSuccess && (e = hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, s)) == hipSuccess)
-            e = hipStreamSynchronize(s);
-        counts_host[0] = h[0]; counts_host[1] = h[1];
-    }
-    (void)hipFree(counts);
-    return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "planet_eval (counted)", e);
-}
-
-// the checks sbx_egg_eval and its test hook share: SBX_OK with fn_id set (0 = "ik_solver", else 1 + launch_egg_eval's fn), or the failure
-static int egg_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, const float* in, const float* out, size_t n, int& fn_id) {
-    if (!ctx) return SBX_ERR_ARG;
-    if (!fn) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    static const char* names[] = {"ik_solver", "sdf", "sdf_normal", "shadowmarch", "render_scene"};
-    fn_id = -1;
-    for (int i = 0; i < 5; ++i) if (std::strcmp(fn, names[i]) == 0) fn_id = i;
-    if (fn_id < 0) return fail(ctx, SBX_ERR_ARG, "unknown egg function");
-    if (fn_id != 0 && !pose) return fail(ctx, SBX_ERR_ARG, "every egg function but ik_solver needs a pose");
-    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 elements");
-    if (n == 0) return SBX_OK;
-    if (!in || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    return SBX_OK;
-}
-// the launch of either: the frame of the block over a 1 x 1 frame (its camera is not read by the kernel); a pose outside the domain
-// of the culls and witnessed roots (sbx_frames.hip egg_pose_tame, the camera's fields ignored) takes the reference form
-static void egg_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_egg_pose* pose, const float* in, float* out, size_t n, unsigned* counts,
-                            hipStream_t s) {
-    if (id == 0) { launch_ik_eval(in, out, n, s); return; }
-    const sbx_uniforms U = {{1.f, 1.f}, {0.f, 0.f}, 0.f, {0.f, 0.f, 0.f}};
-    sbx_aux_egg_pose A = *pose;
-    A.eye[0] = 0.f; A.eye[1] = .25f; A.eye[2] = 5.25f; A.look_at[0] = 0.f; A.look_at[1] = .25f; A.look_at[2] = 0.f; A.fov = 1.f;
-    const FrameEggStraight F = build_egg_pose(U, A, EGG_DEFAULT);
-    const int variant = ctx->variant == 1 || !egg_pose_tame(A, F) ? 1 : ctx->sdf_roots;
-    launch_egg_eval(id - 1, F, variant, in, out, n, counts, s);
+    return counted_launch<unsigned, 2>(ctx, "planet_eval (counted)", n, counts_host, stream, planet_eval_launch(ctx, id, u_time, in, out, n));
 }
 
 int sbx_egg_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, const float* in, float* out, size_t n, void* stream) {
     int id = -1;
-    int rc = egg_eval_args(ctx, fn, pose, in, out, n, id);
+    const int rc = egg_eval_args(ctx, fn, pose, in, out, n, id);
     if (rc != SBX_OK || n == 0) return rc;
-    if ((rc = use_device(ctx)) != SBX_OK) return rc;
-    egg_eval_launch(ctx, id, pose, in, out, n, nullptr, (hipStream_t)stream);
-    return launched(ctx, "egg_eval launch");
+    return plain_launch(ctx, "egg_eval launch", stream, egg_eval_launch(ctx, id, pose, in, out, n));
 }
 
 int sbx_debug_egg_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, const float* in, float* out, size_t n, unsigned counts_host[2],
                        void* stream) {
     int id = -1;
-    int rc = egg_eval_args(ctx, fn, pose, in, out, n, id);
+    const int rc = egg_eval_args(ctx, fn, pose, in, out, n, id);
     if (rc != SBX_OK) return rc;
-    if (!counts_host) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    counts_host[0] = counts_host[1] = 0;
-    if (n == 0) return SBX_OK;
-    if ((rc = use_device(ctx)) != SBX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (stream_is_capturing(s)) return fail(ctx, SBX_ERR_ARG, "the counted launch is not capturable");
-    unsigned* counts = nullptr;
-    hipError_t e = hipMalloc((void**)&counts, 2 * sizeof(unsigned));
-    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
-    if ((e = hipMemsetAsync(counts, 0, 2 * sizeof(unsigned), s)) == hipSuccess) {
-        egg_eval_launch(ctx, id, pose, in, out, n, counts, s);
-        unsigned h[2] = {0, 0};
-        if ((e = hipGetLastError()) == hipSuccess && (e = hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, s)) == hipSuccess)
-            e = hipStreamSynchronize(s);
-        counts_host[0] = h[0]; counts_host[1] = h[1];
-    }
-    (void)hipFree(counts);
-    return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "egg_eval (counted)", e);
-}
-
-// the checks sbx_vinyl_eval and its test hook share: SBX_OK with fn_id set (launch_vinyl_eval's fn), or the failure
-static int vinyl_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck* deck, const float* in, const float* out, size_t n, int& fn_id) {
-    if (!ctx) return SBX_ERR_ARG;
-    if (!fn || !deck) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    static const char* names[] = {"sdf", "sdf_normal", "sdf_shadow", "illuminate", "render"};
-    fn_id = -1;
-    for (int i = 0; i < 5; ++i) if (std::strcmp(fn, names[i]) == 0) fn_id = i;
-    if (fn_id < 0) return fail(ctx, SBX_ERR_ARG, "unknown vinyl function");
-    if (n > ((size_t)1 << 31)) return fail(ctx, SBX_ERR_ARG, "more than 2^31 elements");
-    if (n == 0) return SBX_OK;
-    if (!in || !out) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    return SBX_OK;
-}
-// the launch of either: the frame of the block over a 1 x 1 frame with the shipped camera in place of the block's (the kernel reads no
-// camera; a deck outside the domain of the culls, sbx_frames.hip vinyl_deck_tame with the camera's fields so ignored, takes the
-// reference form)
-static void vinyl_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_vinyl_deck* deck, const float* in, float* out, size_t n, unsigned* counts,
-                              hipStream_t s) {
-    const sbx_uniforms U = {{1.f, 1.f}, {0.f, 0.f}, 0.f, {0.f, 0.f, 0.f}};
-    sbx_aux_vinyl_deck A = *deck;
-    A.eye[0] = 0.f; A.eye[1] = 5.75f; A.eye[2] = 6.75f; A.look_at[0] = 0.f; A.look_at[1] = -2.5f; A.look_at[2] = 0.f; A.fov = 1.f;
-    const FrameVinyl F = build_vinyl_deck(U, A, 60);
-    const int variant = ctx->variant == 1 || !vinyl_deck_tame(A, F) ? 1 : ctx->sdf_roots;
-    launch_vinyl_eval(id, F, vinyl_shade_of(A), variant, in, out, n, counts, s);
+    return counted_launch<unsigned, 2>(ctx, "egg_eval (counted)", n, counts_host, stream, egg_eval_launch(ctx, id, pose, in, out, n));
 }
 
 int sbx_vinyl_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck* deck, const float* in, float* out, size_t n, void* stream) {
     int id = -1;
-    int rc = vinyl_eval_args(ctx, fn, deck, in, out, n, id);
+    const int rc = vinyl_eval_args(ctx, fn, deck, in, out, n, id);
     if (rc != SBX_OK || n == 0) return rc;
-    if ((rc = use_device(ctx)) != SBX_OK) return rc;
-    vinyl_eval_launch(ctx, id, deck, in, out, n, nullptr, (hipStream_t)stream);
-    return launched(ctx, "vinyl_eval launch");
+    return plain_launch(ctx, "vinyl_eval launch", stream, vinyl_eval_launch(ctx, id, deck, in, out, n));
 }
 
 int sbx_debug_vinyl_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck* deck, const float* in, float* out, size_t n,
                          unsigned counts_host[2], void* stream) {
     int id = -1;
-    int rc = vinyl_eval_args(ctx, fn, deck, in, out, n, id);
+    const int rc = vinyl_eval_args(ctx, fn, deck, in, out, n, id);
     if (rc != SBX_OK) return rc;
-    if (!counts_host) return fail(ctx, SBX_ERR_ARG, "NULL argument");
-    counts_host[0] = counts_host[1] = 0;
-    if (n == 0) return SBX_OK;
-    if ((rc = use_device(ctx)) != SBX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (stream_is_capturing(s)) return fail(ctx, SBX_ERR_ARG, "the counted launch is not capturable");
-    unsigned* counts = nullptr;
-    hipError_t e = hipMalloc((void**)&counts, 2 * sizeof(unsigned));
-    if (e != hipSuccess) return fail(ctx, SBX_ERR_HIP, "hipMalloc", e);
-    if ((e = hipMemsetAsync(counts, 0, 2 * sizeof(unsigned), s)) == hipSuccess) {
-        vinyl_eval_launch(ctx, id, deck, in, out, n, counts, s);
-        unsigned h[2] = {0, 0};
-        if ((e = hipGetLastError()) == hipSuccess && (e = hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, s)) == hipSuccess)
-            e = hipStreamSynchronize(s);
-        counts_host[0] = h[0]; counts_host[1] = h[1];
-    }
-    (void)hipFree(counts);
-    return e == hipSuccess ? SBX_OK : fail(ctx, SBX_ERR_HIP, "vinyl_eval (counted)", e);
+    return counted_launch<unsigned, 2>(ctx, "vinyl_eval (counted)", n, counts_host, stream, vinyl_eval_launch(ctx, id, deck, in, out, n));
 }
 
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream) {

@@ -114,7 +114,8 @@ def test_entry_point_is_declared_bound_and_exported():
     lib = shaderbox_amd.load_library()
     assert len(lib.sbx_clouds_eval.argtypes) == 8 and len(lib.sbx_debug_clouds_eval.argtypes) == 9
     assert callable(shaderbox_amd.Renderer.clouds_eval) and callable(shaderbox_amd.Renderer.clouds_eval_counted)
-    assert set(shaderbox_amd.Renderer.CLOUDS_EVAL_WIDTHS.items()) == set(M.WIDTHS.items())
+    R = shaderbox_amd.Renderer
+    assert R.EVAL_WIDTHS["clouds"] == M.WIDTHS and R.CLOUDS_EVAL_WIDTHS is R.EVAL_WIDTHS["clouds"]      # one table, stated once
     # without a context every call is refused before it looks at anything else
     assert lib.sbx_clouds_eval(None, b"render", None, 0.0, None, None, 0, None) == -1
     assert lib.sbx_debug_clouds_eval(None, b"render", None, 0.0, None, None, 0, None, None) == -1

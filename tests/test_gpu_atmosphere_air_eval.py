@@ -4,6 +4,7 @@ numbers, against sbx_atmosphere_eval; the default kernel (the fast body on the w
 block: csrc/sbx_atmosphere.h "CALLER'S AIR"; the count of such waves is asserted wherever it is compared) against the plain one; wave
 composition, ragged sizes, bounds, alignment, a stream capture, the argument checks."""
 import ctypes
+from functools import partial
 
 import numpy as np
 import pytest
@@ -12,7 +13,7 @@ from tests import atmosphere_air_model as M
 from tests import atmosphere_eval_model as E
 from tests.app_checks import frame_cache
 from tests.app_checks import renderer, variant_restored  # noqa: F401 (fixtures)
-from tests.model_common import F, same_bits
+from tests.eval_checks import check_capture_replay, check_ragged, check_refusals, differing, raw_call, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -35,24 +36,14 @@ def reference(fn, key):
     return (M.get_incident_light if fn == FNS[0] else M.get_sun_light)(BLOCKS[key], RAYS)
 
 
-def differing(got, want):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else got
-    return int((~same_bits(got, want).all(axis=-1)).sum())
-
-
-def _dev(rays):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(rays, dtype=F))
-
-
 def counted(r, fn, rays, key):
-    return r.atmosphere_air_eval_counted(fn, _dev(rays), M.as_aux(BLOCKS[key]))
+    return r.atmosphere_air_eval_counted(fn, to_dev(rays), M.as_aux(BLOCKS[key]))
 
 
 def check_default(r, fn, key):
     """the entry and its counted twin over RAYS against the model; the first wave ran the fast body iff the block is tame"""
     want = reference(fn, key)
-    assert differing(r.atmosphere_air_eval(fn, _dev(RAYS), M.as_aux(BLOCKS[key])), want) == 0, (fn, key)
+    assert differing(r.atmosphere_air_eval(fn, to_dev(RAYS), M.as_aux(BLOCKS[key])), want) == 0, (fn, key)
     out, waves = counted(r, fn, RAYS, key)
     assert waves == (1 if M.tame(BLOCKS[key]) else 0), (fn, key, waves)
     assert differing(out, want) == 0, (fn, key)
@@ -77,8 +68,8 @@ def test_default_solver_numbers_are_sbx_atmosphere_eval(renderer):
     for sun in E.SUNS + (M.sun(2., 40.),):
         A = M.air(0., sun_dir=sun, view=1, eye=(1., 2., 3.), fov=7., look_at=(0., 0., 0.))
         for fn in FNS:
-            want = renderer.atmosphere_eval(fn, _dev(RAYS), tuple(float(c) for c in A["sun_dir"])).cpu().numpy()
-            got, waves = renderer.atmosphere_air_eval_counted(fn, _dev(RAYS), M.as_aux(A))
+            want = renderer.atmosphere_eval(fn, to_dev(RAYS), tuple(float(c) for c in A["sun_dir"])).cpu().numpy()
+            got, waves = renderer.atmosphere_air_eval_counted(fn, to_dev(RAYS), M.as_aux(A))
             assert differing(got, want) == 0, (fn, sun)
             assert waves == (1 if M.sun_ok(sun) else 0), (fn, sun, waves)
 
@@ -104,53 +95,19 @@ def test_wave_composition_does_not_matter(renderer):
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
 def test_ragged_sizes_bounds_and_alignment(renderer, n):
     """out inside a poisoned buffer with guard words either side; rays and out 4 bytes off their allocation's alignment"""
-    import torch
-    rays = np.resize(RAYS, (n, 6))
-    guard, poison = 64, -7.25
     for key in ("brighter", "coarse"):
         a = M.as_aux(BLOCKS[key])
-        for fn in FNS:
-            want = np.resize(reference(fn, key), (n, 3))
-            rbuf = torch.zeros(1 + 6 * n, dtype=torch.float32, device=renderer.tdev)
-            rbuf[1:] = torch.from_numpy(rays.ravel()).to(renderer.tdev)
-            obuf = torch.full((1 + 2 * guard + 3 * n,), poison, dtype=torch.float32, device=renderer.tdev)
-            r_ptr, o_ptr = rbuf.data_ptr() + 4, obuf.data_ptr() + 4 * (1 + guard)
-            assert r_ptr % 8 == 4 and o_ptr % 8 == 4
-            renderer._check(renderer.lib.sbx_atmosphere_air_eval(renderer.ctx, fn.encode(), ctypes.byref(a), ctypes.c_void_p(r_ptr), ctypes.c_void_p(o_ptr), n,
-                                                                 renderer._stream()))
-            o = obuf.cpu().numpy()
-            assert (o[:1 + guard] == poison).all() and (o[1 + guard + 3 * n:] == poison).all(), (fn, n)
-            assert differing(o[1 + guard:1 + guard + 3 * n].reshape(n, 3), want) == 0, (fn, n, key)
-            assert np.array_equal(rbuf[1:].cpu().numpy().view(np.uint32), rays.ravel().view(np.uint32))
+        cases = [(fn, (6, 3), np.resize(RAYS, (n, 6)), np.resize(reference(fn, key), (n, 3))) for fn in FNS]
+        check_ragged(renderer, raw_call(renderer, "atmosphere_air", lead=(ctypes.byref(a),)), cases, n)
 
 
 def test_inside_a_stream_capture(renderer):
-    """the call is one kernel launch and nothing else: recorded into a graph, it is replayed over other rays in the same buffers"""
-    import torch
-    n = len(RAYS)
-    want = reference(FNS[0], "brighter")
-    a = M.as_aux(BLOCKS["brighter"])
-    rays = torch.from_numpy(RAYS).to(renderer.tdev)
-    out = torch.zeros((n, 3), dtype=torch.float32, device=renderer.tdev)
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        torch.zeros(1, device=renderer.tdev)                            # the stream exists before the capture
-    s.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        renderer._check(renderer.lib.sbx_atmosphere_air_eval(renderer.ctx, b"get_incident_light", ctypes.byref(a), ctypes.c_void_p(rays.data_ptr()),
-                                                             ctypes.c_void_p(out.data_ptr()), n, renderer._stream()))
-    torch.cuda.synchronize()
-    assert bool((out == 0).all()), "a capture runs nothing"
-    g.replay()
-    torch.cuda.synchronize()
-    assert differing(out, want) == 0
-    rays.copy_(torch.from_numpy(RAYS[::-1].copy()))
-    out.zero_()
-    torch.cuda.synchronize()
-    g.replay()
-    torch.cuda.synchronize()
-    assert differing(out, want[::-1]) == 0
+    """the call is one kernel launch and nothing else: recorded into a graph, it is replayed over other rays in the same buffers; the
+    counted twin refuses the capturing stream"""
+    a = ctypes.byref(M.as_aux(BLOCKS["brighter"]))
+    twin = raw_call(renderer, "atmosphere_air", lead=(a,), counts=ctypes.byref(ctypes.c_uint(7)))
+    check_capture_replay(renderer, partial(raw_call(renderer, "atmosphere_air", lead=(a,)), FNS[0]), RAYS, reference(FNS[0], "brighter"), 3,
+                         refused_twin=partial(twin, FNS[1]))
 
 
 def test_arguments(renderer):
@@ -164,10 +121,9 @@ def test_arguments(renderer):
     a = ctypes.byref(good)
     il, sl = b"get_incident_light", b"get_sun_light"
     assert lib.sbx_atmosphere_air_eval(None, il, a, rp, op, 4, s) == -1
-    for args in [(ctx, None, a, rp, op, 4, s), (ctx, il, None, rp, op, 4, s), (ctx, il, a, None, op, 4, s), (ctx, il, a, rp, None, 4, s),
-                 (ctx, b"get_light", a, rp, op, 4, s), (ctx, b"", a, rp, op, 4, s), (ctx, il, a, rp, op, (1 << 31) + 1, s)]:
-        assert lib.sbx_atmosphere_air_eval(*args) == -1, args
-        assert lib.sbx_last_error(ctx)
+    bad_args = [(ctx, None, a, rp, op, 4, s), (ctx, il, None, rp, op, 4, s), (ctx, il, a, None, op, 4, s), (ctx, il, a, rp, None, 4, s),
+                (ctx, b"get_light", a, rp, op, 4, s), (ctx, b"", a, rp, op, 4, s), (ctx, il, a, rp, op, (1 << 31) + 1, s)]
+    check_refusals(renderer, lib.sbx_atmosphere_air_eval, None, bad_args, out)
     for bad in (M.air(num_samples=0), M.air(num_samples=65), M.air(num_samples_light=0), M.air(num_samples_light=33), M.air(reserved0=1),
                 M.air(reserved=(0., 0., 1., 0., 0., 0.))):
         assert M.refused(bad, app=False) is not None

@@ -3,6 +3,7 @@
 the default kernel (fast forms on the waves whose rays qualify, csrc/sbx_atmosphere.h "CALLER'S RAYS"; the count of such waves is
 asserted wherever it is compared) against the plain one; wave composition, ragged sizes, bounds, alignment, the ground app's sky, the argument checks."""
 import ctypes
+from functools import partial
 
 import numpy as np
 import pytest
@@ -11,7 +12,8 @@ from tests import atmosphere_eval_model as M
 from tests import atmosphere_ground_model as GM
 from tests.app_checks import assert_same, frame_cache
 from tests.app_checks import renderer, variant_restored  # noqa: F401 (fixtures)
-from tests.model_common import F, same_bits
+from tests.eval_checks import check_capture_replay, check_ragged, check_refusals, differing, raw_call, to_dev
+from tests.model_common import F
 
 pytestmark = pytest.mark.gpu
 
@@ -38,11 +40,6 @@ def model_reference(sun):
     return M.get_incident_light(RAYS, sun)
 
 
-def differing(got, want):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else got
-    return int((~same_bits(got, want).all(axis=-1)).sum())
-
-
 def sun_accepted(sun):
     """the host's part of the class (csrc/kern_atmosphere.hip atm_eval_sun_ok), in binary32"""
     s = np.asarray(sun, dtype=F)
@@ -50,18 +47,13 @@ def sun_accepted(sun):
         return bool(np.isfinite(s).all() and np.abs((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2] - F(1)) <= F(1e-4))
 
 
-def _dev(rays):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(rays, dtype=F))
-
-
 def ev(r, fn, rays, sun=(0.0, 1.0, 0.0)):
-    return r.atmosphere_eval(fn, _dev(rays), sun)
+    return r.atmosphere_eval(fn, to_dev(rays), sun)
 
 
 def counted(r, fn, rays, sun=(0.0, 1.0, 0.0)):
     """(out, waves that ran the fast forms): the same launch through include/sbx_test.h sbx_debug_atmosphere_eval"""
-    return r.atmosphere_eval_counted(fn, _dev(rays), sun)
+    return r.atmosphere_eval_counted(fn, to_dev(rays), sun)
 
 
 def check_default(r, fn, sun, want, what):
@@ -141,24 +133,9 @@ def test_wave_composition_does_not_matter(renderer):
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
 def test_ragged_sizes_bounds_and_alignment(renderer, n):
     """out inside a poisoned buffer with guard words either side; rays and out 4 bytes off their allocation's alignment"""
-    import torch
-    rays = np.resize(RAYS, (n, 6))
-    sun = tuple(GM.sun_dir(.37))
-    sunp = (ctypes.c_float * 3)(*sun)
-    guard, poison = 64, -7.25
-    for fn in FNS:
-        want = np.resize(hook_reference(fn, .37), (n, 3))
-        rbuf = torch.zeros(1 + 6 * n, dtype=torch.float32, device=renderer.tdev)
-        rbuf[1:] = torch.from_numpy(rays.ravel()).to(renderer.tdev)
-        obuf = torch.full((1 + 2 * guard + 3 * n,), poison, dtype=torch.float32, device=renderer.tdev)
-        r_ptr, o_ptr = rbuf.data_ptr() + 4, obuf.data_ptr() + 4 * (1 + guard)
-        assert r_ptr % 8 == 4 and o_ptr % 8 == 4
-        renderer._check(renderer.lib.sbx_atmosphere_eval(renderer.ctx, fn.encode(), ctypes.c_void_p(r_ptr), ctypes.cast(sunp, ctypes.c_void_p),
-                                                         ctypes.c_void_p(o_ptr), n, renderer._stream()))
-        o = obuf.cpu().numpy()
-        assert (o[:1 + guard] == poison).all() and (o[1 + guard + 3 * n:] == poison).all(), (fn, n)
-        assert differing(o[1 + guard:1 + guard + 3 * n].reshape(n, 3), want) == 0, (fn, n)
-        assert np.array_equal(rbuf[1:].cpu().numpy().view(np.uint32), rays.ravel().view(np.uint32))
+    sun = ctypes.cast((ctypes.c_float * 3)(*GM.sun_dir(.37)), ctypes.c_void_p)
+    cases = [(fn, (6, 3), np.resize(RAYS, (n, 6)), np.resize(hook_reference(fn, .37), (n, 3))) for fn in FNS]
+    check_ragged(renderer, raw_call(renderer, "atmosphere", mid=(sun,)), cases, n)
 
 
 def test_same_solver_as_the_ground_app(renderer):
@@ -178,32 +155,12 @@ def test_same_solver_as_the_ground_app(renderer):
 
 
 def test_inside_a_stream_capture(renderer):
-    """the call is one kernel launch and nothing else: recorded into a graph, it is replayed over other rays in the same buffers"""
-    import torch
-    n = len(RAYS)
-    want = hook_reference("get_incident_light", .37)
-    rays = torch.from_numpy(RAYS).to(renderer.tdev)
-    out = torch.zeros((n, 3), dtype=torch.float32, device=renderer.tdev)
-    sunp = (ctypes.c_float * 3)(*GM.sun_dir(.37))
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        torch.zeros(1, device=renderer.tdev)                            # the stream exists before the capture
-    s.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        renderer._check(renderer.lib.sbx_atmosphere_eval(renderer.ctx, b"get_incident_light", ctypes.c_void_p(rays.data_ptr()),
-                                                         ctypes.cast(sunp, ctypes.c_void_p), ctypes.c_void_p(out.data_ptr()), n, renderer._stream()))
-    torch.cuda.synchronize()
-    assert bool((out == 0).all()), "a capture runs nothing"
-    g.replay()
-    torch.cuda.synchronize()
-    assert differing(out, want) == 0
-    rays.copy_(torch.from_numpy(RAYS[::-1].copy()))
-    out.zero_()
-    torch.cuda.synchronize()
-    g.replay()
-    torch.cuda.synchronize()
-    assert differing(out, want[::-1]) == 0
+    """the call is one kernel launch and nothing else: recorded into a graph, it is replayed over other rays in the same buffers; the
+    counted twin refuses the capturing stream"""
+    sun = ctypes.cast((ctypes.c_float * 3)(*GM.sun_dir(.37)), ctypes.c_void_p)
+    twin = raw_call(renderer, "atmosphere", mid=(sun,), counts=ctypes.byref(ctypes.c_uint(7)))
+    check_capture_replay(renderer, partial(raw_call(renderer, "atmosphere", mid=(sun,)), FNS[0]), RAYS, hook_reference(FNS[0], .37), 3,
+                         refused_twin=partial(twin, FNS[1]))
 
 
 def test_arguments(renderer):
@@ -216,12 +173,9 @@ def test_arguments(renderer):
     sun = ctypes.cast((ctypes.c_float * 3)(0.0, 1.0, 0.0), ctypes.c_void_p)
     il, sl = b"get_incident_light", b"get_sun_light"
     assert lib.sbx_atmosphere_eval(None, il, rp, sun, op, 4, s) == -1
-    for args in [(ctx, None, rp, sun, op, 4, s), (ctx, il, None, sun, op, 4, s), (ctx, il, rp, sun, None, 4, s), (ctx, il, rp, None, op, 4, s),
-                 (ctx, b"get_light", rp, sun, op, 4, s), (ctx, b"", rp, sun, op, 4, s), (ctx, il, rp, sun, op, (1 << 31) + 1, s)]:
-        assert lib.sbx_atmosphere_eval(*args) == -1, args
-        assert lib.sbx_last_error(ctx)
-    torch.cuda.synchronize()
-    assert bool((out == -1.0).all()), "a refused call writes nothing"
+    bad_args = [(ctx, None, rp, sun, op, 4, s), (ctx, il, None, sun, op, 4, s), (ctx, il, rp, sun, None, 4, s), (ctx, il, rp, None, op, 4, s),
+                (ctx, b"get_light", rp, sun, op, 4, s), (ctx, b"", rp, sun, op, 4, s), (ctx, il, rp, sun, op, (1 << 31) + 1, s)]
+    check_refusals(renderer, lib.sbx_atmosphere_eval, None, bad_args, out)
     assert lib.sbx_atmosphere_eval(ctx, il, None, None, None, 0, s) == 0      # n == 0 touches nothing
     assert lib.sbx_atmosphere_eval(ctx, sl, None, None, None, 0, s) == 0
     assert lib.sbx_atmosphere_eval(ctx, sl, rp, None, op, 4, s) == 0          # get_sun_light reads no sun

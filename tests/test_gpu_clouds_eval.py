@@ -4,6 +4,7 @@ the four aux sets and both times, through the entry and through its counted twin
 form (hashes from the context's table, asserted through the counts) against the plain one; wave composition, ragged sizes, bounds and
 alignment, a stream capture, the argument checks, and host/sbx_render's panorama."""
 import ctypes
+from functools import partial
 import ctypes.util
 
 import numpy as np
@@ -12,7 +13,8 @@ import pytest
 from tests import clouds_eval_model as M
 from tests.app_checks import assert_same, frame_cache, run_sbx_render
 from tests.app_checks import renderer, variant_restored  # noqa: F401 (fixtures)
-from tests.model_common import F, same_bits
+from tests.eval_checks import check_capture_replay, check_ragged, check_refusals, differing, raw_call, to_dev
+from tests.model_common import F
 
 pytestmark = pytest.mark.gpu
 
@@ -29,24 +31,13 @@ def cases():
     return [(fn, aux, t) for fn in M.FNS for aux in M.AUX for t in (M.TIMES if fn in RAY_FNS else (0.0,))]
 
 
-def differing(got, want):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else got
-    assert got.shape == want.shape, (got.shape, want.shape)
-    return int((~same_bits(got, want).reshape(len(want), -1).all(axis=-1)).sum())
-
-
-def _dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=F))
-
-
 def ev(r, fn, x, t=0.0, aux="default"):
-    return r.clouds_eval(fn, _dev(x), t, M.AUX[aux])
+    return r.clouds_eval(fn, to_dev(x), t, M.AUX[aux])
 
 
 def counted(r, fn, x, t=0.0, aux="default"):
     """(out, (cells from the table, cells hashed in place)): the same launch through include/sbx_test.h sbx_debug_clouds_eval"""
-    return r.clouds_eval_counted(fn, _dev(x), t, M.AUX[aux])
+    return r.clouds_eval_counted(fn, to_dev(x), t, M.AUX[aux])
 
 
 @pytest.mark.parametrize("aux", list(M.AUX))
@@ -133,52 +124,20 @@ def test_wave_composition_does_not_matter(renderer):
 def test_ragged_sizes_bounds_and_alignment(renderer, n):
     """out inside a poisoned buffer with guard words either side; in and out 4 bytes off their allocation's alignment; the 4-, 3- and
     1-float output widths"""
-    import torch
-    guard, poison = 64, -7.25
+    cases = []
     for fn in ("render", "render_sky_color", "density_func"):
-        win, wout = M.WIDTHS[fn]
         pick = np.resize(np.arange(len(M.inputs(fn)))[::-1], n)                # from the specials backwards
-        x, want = M.inputs(fn)[pick], reference(fn, "default", 0.0)[pick]
-        ibuf = torch.zeros(1 + win * n, dtype=torch.float32, device=renderer.tdev)
-        ibuf[1:] = torch.from_numpy(x.ravel()).to(renderer.tdev)
-        obuf = torch.full((1 + 2 * guard + wout * n,), poison, dtype=torch.float32, device=renderer.tdev)
-        i_ptr, o_ptr = ibuf.data_ptr() + 4, obuf.data_ptr() + 4 * (1 + guard)
-        assert i_ptr % 8 == 4 and o_ptr % 8 == 4
-        renderer._check(renderer.lib.sbx_clouds_eval(renderer.ctx, fn.encode(), None, 0.0, ctypes.c_void_p(i_ptr), ctypes.c_void_p(o_ptr), n,
-                                                     renderer._stream()))
-        o = obuf.cpu().numpy()
-        assert (o[:1 + guard] == poison).all() and (o[1 + guard + wout * n:] == poison).all(), (fn, n)
-        assert differing(o[1 + guard:1 + guard + wout * n].reshape(n, wout), want) == 0, (fn, n)
-        assert np.array_equal(ibuf[1:].cpu().numpy().view(np.uint32), x.ravel().view(np.uint32)), (fn, n)
+        cases.append((fn, M.WIDTHS[fn], M.inputs(fn)[pick], reference(fn, "default", 0.0)[pick]))
+    check_ragged(renderer, raw_call(renderer, "clouds", lead=(None, ctypes.c_float(0.0))), cases, n)
 
 
 def test_inside_a_stream_capture(renderer):
-    """one capture, replayed over other rays in the same buffers; only the bits are asserted, whichever hash path the capture took"""
-    import torch
-    rays = M.rays()
-    n = len(rays)
-    want = reference("render", "default", 1.5)
-    dev = torch.from_numpy(rays).to(renderer.tdev)
-    out = torch.zeros((n, 4), dtype=torch.float32, device=renderer.tdev)
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        torch.zeros(1, device=renderer.tdev)                            # the stream exists before the capture
-    s.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        renderer._check(renderer.lib.sbx_clouds_eval(renderer.ctx, b"render", None, 1.5, ctypes.c_void_p(dev.data_ptr()),
-                                                     ctypes.c_void_p(out.data_ptr()), n, renderer._stream()))
-    torch.cuda.synchronize()
-    assert bool((out == 0).all()), "a capture runs nothing"
-    g.replay()
-    torch.cuda.synchronize()
-    assert differing(out, want) == 0
-    dev.copy_(torch.from_numpy(rays[::-1].copy()))
-    out.zero_()
-    torch.cuda.synchronize()
-    g.replay()
-    torch.cuda.synchronize()
-    assert differing(out, want[::-1]) == 0
+    """one capture, replayed over other rays in the same buffers; only the bits are asserted, whichever hash path the capture took;
+    the counted twin refuses the capturing stream"""
+    lead = (None, ctypes.c_float(1.5))
+    twin = raw_call(renderer, "clouds", lead=lead, counts=(ctypes.c_uint64 * 2)(7, 7))
+    check_capture_replay(renderer, partial(raw_call(renderer, "clouds", lead=lead), "render"), M.rays(), reference("render", "default", 1.5), 4,
+                         refused_twin=partial(twin, "density_func"))
 
 
 def test_arguments(renderer):
@@ -190,16 +149,11 @@ def test_arguments(renderer):
     rp, op = ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(out.data_ptr())
     neg_main, neg_light = renderer._clouds_aux({"cld_march_steps": -1}), renderer._clouds_aux({"illum_march_steps": -3})
     assert lib.sbx_clouds_eval(None, b"render", None, 0.0, rp, op, 4, s) == -1
-    for args in [(ctx, None, None, 0.0, rp, op, 4, s), (ctx, b"render", None, 0.0, None, op, 4, s), (ctx, b"render", None, 0.0, rp, None, 4, s),
-                 (ctx, b"get_sun_light", None, 0.0, rp, op, 4, s), (ctx, b"", None, 0.0, rp, op, 4, s), (ctx, b"Render", None, 0.0, rp, op, 4, s),
-                 (ctx, b"render", None, 0.0, rp, op, (1 << 31) + 1, s), (ctx, b"render", ctypes.byref(neg_main), 0.0, rp, op, 4, s),
-                 (ctx, b"density_func", ctypes.byref(neg_light), 0.0, rp, op, 4, s)]:
-        assert lib.sbx_clouds_eval(*args) == -1, args
-        assert lib.sbx_last_error(ctx)
-        counts = (ctypes.c_uint64 * 2)(7, 7)
-        assert lib.sbx_debug_clouds_eval(*args[:7], counts, s) == -1, args
-    torch.cuda.synchronize()
-    assert bool((out == -1.0).all()), "a refused call writes nothing"
+    bad_args = [(ctx, None, None, 0.0, rp, op, 4, s), (ctx, b"render", None, 0.0, None, op, 4, s), (ctx, b"render", None, 0.0, rp, None, 4, s),
+                (ctx, b"get_sun_light", None, 0.0, rp, op, 4, s), (ctx, b"", None, 0.0, rp, op, 4, s), (ctx, b"Render", None, 0.0, rp, op, 4, s),
+                (ctx, b"render", None, 0.0, rp, op, (1 << 31) + 1, s), (ctx, b"render", ctypes.byref(neg_main), 0.0, rp, op, 4, s),
+                (ctx, b"density_func", ctypes.byref(neg_light), 0.0, rp, op, 4, s)]
+    check_refusals(renderer, lib.sbx_clouds_eval, lambda args: lib.sbx_debug_clouds_eval(*args[:-1], (ctypes.c_uint64 * 2)(7, 7), s), bad_args, out)
     for fn in M.FNS:
         assert lib.sbx_clouds_eval(ctx, fn.encode(), None, 0.0, None, None, 0, s) == 0      # n == 0 touches nothing
         assert renderer.clouds_eval(fn, torch.zeros((0, M.WIDTHS[fn][0]))).shape == (0, M.WIDTHS[fn][1])
@@ -229,6 +183,6 @@ def test_panorama_of_sbx_render(renderer, tmp_path):
             rays[y, x, 3:] = (libm.cos(el) * libm.sin(az), libm.sin(el), -libm.cos(el) * libm.cos(az))
     assert rays[0, :, 4].max() < .05 < rays[1, :, 4].min() and rays[-1, 0, 4] > .99        # from under the horizon cut to the zenith
     got = run_sbx_render(tmp_path, "clouds", w, h, t, flags=("--clouds-panorama", str(w), str(h), "--eye", "10", "20", "-30", "--coverage", ".6"))
-    want = renderer.clouds_eval("render", _dev(rays.reshape(-1, 6)), t, {"cld_coverage": float(F(.6))}).cpu().numpy()
+    want = renderer.clouds_eval("render", to_dev(rays.reshape(-1, 6)), t, {"cld_coverage": float(F(.6))}).cpu().numpy()
     assert_same(got.reshape(w * h, 4), want, "panorama")
     assert 0 < int((want[:, 3] > 0).sum()) < w * h

@@ -4,18 +4,21 @@ seeded points and rays in a box, points on the members' axes (where the witness 
 are counted), a family of NaN / inf / zero / huge values, an untame pose, ragged sizes with guard words, variant 1, a stream capture,
 the refusals, "render_scene" tied to SBX_APP_EGG_POSE's frame, and host/sbx_render's --egg-view."""
 import ctypes
+from functools import partial
 
 import numpy as np
 import pytest
 
+from shaderbox_amd import Renderer
 from tests import egg_pose_model as M
 from tests.app_checks import assert_same, frame_cache, run_sbx_render
 from tests.app_checks import renderer, variant_restored  # noqa: F401 (fixtures)
-from tests.model_common import F, same_bits
+from tests.eval_checks import check_capture_replay, check_ragged, check_refusals, differing, raw_call, to_dev
+from tests.model_common import F
 
 pytestmark = pytest.mark.gpu
 W, H = M.SIZE
-WIDTHS = {"ik_solver": (8, 3), "sdf": (3, 2), "sdf_normal": (3, 3), "shadowmarch": (6, 1), "render_scene": (6, 4)}
+WIDTHS = Renderer.EVAL_WIDTHS["egg"]
 FNS = ("sdf", "sdf_normal", "shadowmarch", "render_scene")
 
 
@@ -81,25 +84,14 @@ def model(fn, P, x):
 reference = frame_cache(lambda fn, name: model(fn, M.POSES[POSE_OF[name]], family(name, WIDTHS[fn][0])))
 
 
-def differing(got, want):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else got
-    assert got.shape == want.shape, (got.shape, want.shape)
-    return int((~same_bits(got, want).reshape(len(want), -1).all(axis=-1)).sum())
-
-
-def _dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=F))
-
-
 @pytest.mark.parametrize("fn", FNS)
 @pytest.mark.parametrize("name", ["frame", "box", "axes", "specials"])
 def test_against_the_model(renderer, fn, name):
     x, a = family(name, WIDTHS[fn][0]), M.as_aux(M.POSES[POSE_OF[name]])
     want = reference(fn, name)
     assert want.shape == (len(x), WIDTHS[fn][1])
-    assert differing(renderer.egg_eval(fn, _dev(x), a), want) == 0, (fn, name)
-    out, (witnessed, rerun) = renderer.egg_eval_counted(fn, _dev(x), a)
+    assert differing(renderer.egg_eval(fn, to_dev(x), a), want) == 0, (fn, name)
+    out, (witnessed, rerun) = renderer.egg_eval_counted(fn, to_dev(x), a)
     assert differing(out, want) == 0, (fn, name, "counted")
     waves = (len(x) + 63) // 64
     print(fn, name, "waves", waves, "witnessed", witnessed, "re-run", rerun)
@@ -115,7 +107,7 @@ def test_both_kinds_of_wave_in_one_launch(renderer):
     """64 seeded points, then the 64 on the axes: one wave of each kind, the same bits as apart"""
     P = M.POSES["bones"]
     x = np.concatenate([family("box", 3)[:64], family("axes", 3)], axis=0)
-    out, counts = renderer.egg_eval_counted("sdf", _dev(x), M.as_aux(P))
+    out, counts = renderer.egg_eval_counted("sdf", to_dev(x), M.as_aux(P))
     assert counts == (1, 1), counts
     assert differing(out, model("sdf", P, x)) == 0
 
@@ -126,7 +118,7 @@ def test_an_untame_pose_takes_the_plain_form(renderer):
     for P in (M.POSES["reach"], M.pose((np.inf, 1.3, .2), (-.3, 1.1, -.2)), M.pose((.3, 1.3, .2), (-.3, 1.1, -.2), femur=np.nan)):
         for fn in ("sdf", "render_scene"):
             xi = x[:, :WIDTHS[fn][0]].copy()
-            out, counts = renderer.egg_eval_counted(fn, _dev(xi), M.as_aux(P))
+            out, counts = renderer.egg_eval_counted(fn, to_dev(xi), M.as_aux(P))
             assert counts == (0, 0), (fn, counts)
             assert differing(out, model(fn, P, xi)) == 0, fn
 
@@ -134,9 +126,9 @@ def test_an_untame_pose_takes_the_plain_form(renderer):
 def test_the_camera_of_the_pose_is_not_read(renderer):
     x = family("box", 6)[:128]
     P = dict(M.POSES["stride"])
-    want = renderer.egg_eval("render_scene", _dev(x), M.as_aux(P)).cpu().numpy()
+    want = renderer.egg_eval("render_scene", to_dev(x), M.as_aux(P)).cpu().numpy()
     P.update(eye=(F(np.nan),) * 3, look_at=(F(np.inf),) * 3, fov=F(-3e38))
-    out, counts = renderer.egg_eval_counted("render_scene", _dev(x), M.as_aux(P))
+    out, counts = renderer.egg_eval_counted("render_scene", to_dev(x), M.as_aux(P))
     assert differing(out, want) == 0 and counts[0] + counts[1] == 2
 
 
@@ -146,7 +138,7 @@ def test_variant_1_same_bits(renderer, variant_restored):
             x, a = family(name, WIDTHS[fn][0]), M.as_aux(M.POSES[POSE_OF[name]])
             for variant in (1, 2, 3):
                 renderer.set_variant(variant)
-                out, counts = renderer.egg_eval_counted(fn, _dev(x), a)
+                out, counts = renderer.egg_eval_counted(fn, to_dev(x), a)
                 assert differing(out, reference(fn, name)) == 0, (fn, name, variant)
                 if variant != 2:
                     assert counts == (0, 0), (fn, name, variant, counts)
@@ -156,62 +148,24 @@ def test_variant_1_same_bits(renderer, variant_restored):
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 4097])
 def test_ragged_sizes_bounds_and_alignment(renderer, n):
     """out inside a poisoned buffer with guard words either side; in and out 4 bytes off a 16-byte boundary; every output width"""
-    import torch
-    guard, poison = 64, -7.25
     a = M.as_aux(M.POSES["stride"])
+    cases = []
     for fn in FNS + ("ik_solver",):
-        win, wout = WIDTHS[fn]
-        base = ik_inputs() if fn == "ik_solver" else family("frame", win)
+        base = ik_inputs() if fn == "ik_solver" else family("frame", WIDTHS[fn][0])
         full = ik_reference() if fn == "ik_solver" else reference(fn, "frame")
         pick = np.resize(np.arange(len(base)), n)
-        x, want = base[pick], full[pick]
-        ibuf = torch.zeros(1 + win * n, dtype=torch.float32, device=renderer.tdev)
-        ibuf[1:] = torch.from_numpy(x.ravel()).to(renderer.tdev)
-        obuf = torch.full((1 + 2 * guard + wout * n,), poison, dtype=torch.float32, device=renderer.tdev)
-        i_ptr, o_ptr = ibuf.data_ptr() + 4, obuf.data_ptr() + 4 * (1 + guard)
-        assert i_ptr % 16 == 4 and o_ptr % 16 == 4
-        renderer._check(renderer.lib.sbx_egg_eval(renderer.ctx, fn.encode(), ctypes.byref(a), ctypes.c_void_p(i_ptr), ctypes.c_void_p(o_ptr), n,
-                                                  renderer._stream()))
-        o = obuf.cpu().numpy()
-        assert (o[:1 + guard] == poison).all() and (o[1 + guard + wout * n:] == poison).all(), (fn, n)
-        assert differing(o[1 + guard:1 + guard + wout * n].reshape(n, wout), want) == 0, (fn, n)
-        assert np.array_equal(ibuf[1:].cpu().numpy().view(np.uint32), x.ravel().view(np.uint32)), (fn, n)
+        cases.append((fn, WIDTHS[fn], base[pick], full[pick]))
+    check_ragged(renderer, raw_call(renderer, "egg", lead=(ctypes.byref(a),)), cases, n)
 
 
 def test_inside_a_stream_capture(renderer):
-    """one capture, replayed twice, the second time over other rays in the same buffers"""
-    import torch
-    rays, a = family("frame", 6)[:1024], M.as_aux(M.POSES["stride"])
-    want = reference("render_scene", "frame")[:1024]
-    n = len(rays)
-    dev = torch.from_numpy(rays).to(renderer.tdev)
-    out = torch.zeros((n, 4), dtype=torch.float32, device=renderer.tdev)
-    ik_in = torch.from_numpy(ik_inputs()[:256]).to(renderer.tdev)
-    ik_out = torch.zeros((256, 3), dtype=torch.float32, device=renderer.tdev)
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        torch.zeros(1, device=renderer.tdev)                            # the stream exists before the capture
-    s.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        renderer._check(renderer.lib.sbx_egg_eval(renderer.ctx, b"render_scene", ctypes.byref(a), ctypes.c_void_p(dev.data_ptr()),
-                                                  ctypes.c_void_p(out.data_ptr()), n, renderer._stream()))
-        renderer._check(renderer.lib.sbx_egg_eval(renderer.ctx, b"ik_solver", None, ctypes.c_void_p(ik_in.data_ptr()),
-                                                  ctypes.c_void_p(ik_out.data_ptr()), 256, renderer._stream()))
-        counts = (ctypes.c_uint * 2)(7, 7)                               # the counted twin refuses a capture
-        assert renderer.lib.sbx_debug_egg_eval(renderer.ctx, b"sdf", ctypes.byref(a), ctypes.c_void_p(dev.data_ptr()),
-                                               ctypes.c_void_p(out.data_ptr()), 4, counts, renderer._stream()) == -1
-    torch.cuda.synchronize()
-    assert bool((out == 0).all()) and bool((ik_out == 0).all()), "a capture runs nothing"
-    g.replay()
-    torch.cuda.synchronize()
-    assert differing(out, want) == 0 and differing(ik_out, ik_reference()[:256]) == 0
-    dev.copy_(torch.from_numpy(rays[::-1].copy()))
-    out.zero_()
-    torch.cuda.synchronize()
-    g.replay()
-    torch.cuda.synchronize()
-    assert differing(out, want[::-1]) == 0
+    """one capture of "render_scene" and of "ik_solver" without a pose, replayed twice, the second time over other elements in the same
+    buffers; the counted twin refuses the capturing stream"""
+    a = ctypes.byref(M.as_aux(M.POSES["stride"]))
+    twin = raw_call(renderer, "egg", lead=(a,), counts=(ctypes.c_uint * 2)(7, 7))
+    check_capture_replay(renderer, partial(raw_call(renderer, "egg", lead=(a,)), "render_scene"), family("frame", 6)[:1024],
+                         reference("render_scene", "frame")[:1024], 4, refused_twin=partial(twin, "sdf"),
+                         also=[(partial(raw_call(renderer, "egg", lead=(None,)), "ik_solver"), ik_inputs()[:256], ik_reference()[:256], 3)])
 
 
 def test_arguments(renderer):
@@ -223,17 +177,12 @@ def test_arguments(renderer):
     out = torch.full((4, 4), -1.0, dtype=torch.float32, device=renderer.tdev)
     rp, op, ap = ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(out.data_ptr()), ctypes.byref(a)
     assert lib.sbx_egg_eval(None, b"render_scene", ap, rp, op, 4, s) == -1
-    for args in [(ctx, None, ap, rp, op, 4, s), (ctx, b"render_scene", ap, None, op, 4, s), (ctx, b"render_scene", ap, rp, None, 4, s),
-                 (ctx, b"render_scene", None, rp, op, 4, s), (ctx, b"sdf", None, rp, op, 4, s), (ctx, b"sdf_normal", None, rp, op, 4, s),
-                 (ctx, b"shadowmarch", None, rp, op, 4, s), (ctx, b"render", ap, rp, op, 4, s), (ctx, b"", ap, rp, op, 4, s),
-                 (ctx, b"Sdf", ap, rp, op, 4, s), (ctx, b"ik_solver", None, None, op, 1, s), (ctx, b"ik_solver", None, rp, None, 1, s),
-                 (ctx, b"render_scene", ap, rp, op, (1 << 31) + 1, s), (ctx, b"ik_solver", None, rp, op, (1 << 31) + 1, s)]:
-        assert lib.sbx_egg_eval(*args) == -1, args
-        assert lib.sbx_last_error(ctx)
-        counts = (ctypes.c_uint * 2)(7, 7)
-        assert lib.sbx_debug_egg_eval(*args[:6], counts, s) == -1, args
-    torch.cuda.synchronize()
-    assert bool((out == -1.0).all()), "a refused call writes nothing"
+    bad_args = [(ctx, None, ap, rp, op, 4, s), (ctx, b"render_scene", ap, None, op, 4, s), (ctx, b"render_scene", ap, rp, None, 4, s),
+                (ctx, b"render_scene", None, rp, op, 4, s), (ctx, b"sdf", None, rp, op, 4, s), (ctx, b"sdf_normal", None, rp, op, 4, s),
+                (ctx, b"shadowmarch", None, rp, op, 4, s), (ctx, b"render", ap, rp, op, 4, s), (ctx, b"", ap, rp, op, 4, s),
+                (ctx, b"Sdf", ap, rp, op, 4, s), (ctx, b"ik_solver", None, None, op, 1, s), (ctx, b"ik_solver", None, rp, None, 1, s),
+                (ctx, b"render_scene", ap, rp, op, (1 << 31) + 1, s), (ctx, b"ik_solver", None, rp, op, (1 << 31) + 1, s)]
+    check_refusals(renderer, lib.sbx_egg_eval, lambda args: lib.sbx_debug_egg_eval(*args[:-1], (ctypes.c_uint * 2)(7, 7), s), bad_args, out)
     for fn, (win, wout) in WIDTHS.items():
         assert lib.sbx_egg_eval(ctx, fn.encode(), ap, None, None, 0, s) == 0            # n == 0 touches nothing
         assert renderer.egg_eval(fn, torch.zeros((0, win)), a).shape == (0, wout)
@@ -252,7 +201,7 @@ def test_render_scene_over_the_primary_rays_is_the_apps_frame(renderer, name):
     """"render_scene" over a frame's primary rays, then render's bars, abs and sRGB from the model: SBX_APP_EGG_POSE's frame"""
     P = M.POSES[name]
     pcx, rays = frame_rays(P, W, H)
-    out = renderer.egg_eval("render_scene", _dev(rays), M.as_aux(P)).cpu().numpy()
+    out = renderer.egg_eval("render_scene", to_dev(rays), M.as_aux(P)).cpu().numpy()
     frame = renderer.render("egg_pose", W, H, 0.0, aux=M.as_aux(P)).cpu().numpy()
     assert_same(M.finish(out[:, :3], out[:, 3], pcx).reshape(H, W, 4), frame, name)
     assert_same(frame, M.fixture(name)["frame"], (name, "fixture"))
@@ -293,8 +242,8 @@ def test_ik_solver_seeded_goals(renderer):
     reach = np.linalg.norm(x[:, 3:6].astype(np.float64) - x[:, :3], axis=1)
     assert (reach > x[:, 6] + x[:, 7]).sum() > 500 and (reach < np.abs(x[:, 6] - x[:, 7])).sum() > 100, "unreachable and folded goals are there"
     assert 500 < int(np.isnan(want).any(axis=1).sum()) < 3000
-    assert differing(renderer.egg_eval("ik_solver", _dev(x)), want) == 0
-    assert differing(renderer.egg_eval("ik_solver", _dev(x), M.as_aux(M.POSES["reach"])), want) == 0       # a pose changes nothing
+    assert differing(renderer.egg_eval("ik_solver", to_dev(x)), want) == 0
+    assert differing(renderer.egg_eval("ik_solver", to_dev(x), M.as_aux(M.POSES["reach"])), want) == 0       # a pose changes nothing
 
 
 def test_ik_solver_gives_the_knees_of_the_default_pose(renderer):
@@ -306,7 +255,7 @@ def test_ik_solver_gives_the_knees_of_the_default_pose(renderer):
                       list(S["pelvis_r"]) + list(P["right_foot"]) + [P["femur"], P["tibia"]]], dtype=F)
         want = np.array([S["knee_l"], S["knee_r"]], dtype=F)
         assert np.isfinite(want).all()
-        assert differing(renderer.egg_eval("ik_solver", _dev(x)), want) == 0, t
+        assert differing(renderer.egg_eval("ik_solver", to_dev(x)), want) == 0, t
 
 
 def test_egg_view_of_sbx_render(renderer, tmp_path):

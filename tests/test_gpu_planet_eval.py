@@ -5,6 +5,7 @@ through its counted twin; against the SBX_APP_PLANET and SBX_APP_PLANET_CLOSEUP 
 wave counts (A never falls back, D and E and variant 1 never run the guarded forms); wave composition, ragged sizes, bounds and
 alignment, a stream capture, the argument checks, and host/sbx_render's --planet-view."""
 import ctypes
+from functools import partial
 
 import numpy as np
 import pytest
@@ -12,7 +13,8 @@ import pytest
 from tests import planet_eval_model as M
 from tests.app_checks import assert_same, frame_cache, run_sbx_render
 from tests.app_checks import renderer, variant_restored  # noqa: F401 (fixtures)
-from tests.model_common import F, same_bits
+from tests.eval_checks import check_capture_replay, check_ragged, check_refusals, differing, raw_call, to_dev
+from tests.model_common import F
 
 pytestmark = pytest.mark.gpu
 
@@ -27,24 +29,13 @@ def times(fn):
     return M.TIMES if fn in M.TIME_FNS else (0.0,)
 
 
-def differing(got, want):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else got
-    assert got.shape == want.shape, (got.shape, want.shape)
-    return int((~same_bits(got, want).reshape(len(want), -1).all(axis=-1)).sum())
-
-
-def _dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=F))
-
-
 def ev(r, fn, x, t=0.0):
-    return r.planet_eval(fn, _dev(x), t)
+    return r.planet_eval(fn, to_dev(x), t)
 
 
 def counted(r, fn, x, t=0.0):
     """(out, (waves with every guarded form on, waves that fell back)): the same launch through include/sbx_test.h sbx_debug_planet_eval"""
-    return r.planet_eval_counted(fn, _dev(x), t)
+    return r.planet_eval_counted(fn, to_dev(x), t)
 
 
 @pytest.mark.parametrize("fn", M.FNS)
@@ -166,53 +157,19 @@ def test_wave_composition_does_not_matter(renderer):
 def test_ragged_sizes_bounds_and_alignment(renderer, n):
     """out inside a poisoned buffer with guard words either side; in 4 bytes off a 16-byte boundary, out 4 bytes off too; the 4-, 3-,
     2- and 1-float output widths"""
-    import torch
-    guard, poison = 64, -7.25
+    cases = []
     for fn in ("render", "sdf_terrain_normal", "sdf_terrain_map", "clouds_density"):
-        win, wout = M.WIDTHS[fn]
         pick = np.resize(np.arange(len(M.inputs(fn)))[::-1], n)                # from the specials backwards
-        x, want = M.inputs(fn)[pick], reference(fn, 0.0)[pick]
-        ibuf = torch.zeros(1 + win * n, dtype=torch.float32, device=renderer.tdev)
-        ibuf[1:] = torch.from_numpy(x.ravel()).to(renderer.tdev)
-        obuf = torch.full((1 + 2 * guard + wout * n,), poison, dtype=torch.float32, device=renderer.tdev)
-        assert ibuf.data_ptr() % 16 == 0 and obuf.data_ptr() % 16 == 0
-        i_ptr, o_ptr = ibuf.data_ptr() + 4, obuf.data_ptr() + 4 * (1 + guard)
-        assert i_ptr % 16 == 4 and o_ptr % 16 == 4
-        renderer._check(renderer.lib.sbx_planet_eval(renderer.ctx, fn.encode(), 0.0, ctypes.c_void_p(i_ptr), ctypes.c_void_p(o_ptr), n,
-                                                     renderer._stream()))
-        o = obuf.cpu().numpy()
-        assert (o[:1 + guard] == poison).all() and (o[1 + guard + wout * n:] == poison).all(), (fn, n)
-        assert differing(o[1 + guard:1 + guard + wout * n].reshape(n, wout), want) == 0, (fn, n)
-        assert np.array_equal(ibuf[1:].cpu().numpy().view(np.uint32), x.ravel().view(np.uint32)), (fn, n)
+        cases.append((fn, M.WIDTHS[fn], M.inputs(fn)[pick], reference(fn, 0.0)[pick]))
+    check_ragged(renderer, raw_call(renderer, "planet", lead=(ctypes.c_float(0.0),)), cases, n)
 
 
 def test_inside_a_stream_capture(renderer):
-    """one capture, replayed over other rays in the same buffers"""
-    import torch
-    rays = M.rays()
-    n = len(rays)
-    want = reference("render", .37)
-    dev = torch.from_numpy(rays).to(renderer.tdev)
-    out = torch.zeros((n, 4), dtype=torch.float32, device=renderer.tdev)
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        torch.zeros(1, device=renderer.tdev)                            # the stream exists before the capture
-    s.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        renderer._check(renderer.lib.sbx_planet_eval(renderer.ctx, b"render", .37, ctypes.c_void_p(dev.data_ptr()),
-                                                     ctypes.c_void_p(out.data_ptr()), n, renderer._stream()))
-    torch.cuda.synchronize()
-    assert bool((out == 0).all()), "a capture runs nothing"
-    g.replay()
-    torch.cuda.synchronize()
-    assert differing(out, want) == 0
-    dev.copy_(torch.from_numpy(rays[::-1].copy()))
-    out.zero_()
-    torch.cuda.synchronize()
-    g.replay()
-    torch.cuda.synchronize()
-    assert differing(out, want[::-1]) == 0
+    """one capture, replayed over other rays in the same buffers; the counted twin refuses the capturing stream"""
+    lead = (ctypes.c_float(.37),)
+    twin = raw_call(renderer, "planet", lead=lead, counts=(ctypes.c_uint * 2)(7, 7))
+    check_capture_replay(renderer, partial(raw_call(renderer, "planet", lead=lead), "render"), M.rays(), reference("render", .37), 4,
+                         refused_twin=partial(twin, "background"))
 
 
 def test_arguments(renderer):
@@ -223,15 +180,10 @@ def test_arguments(renderer):
     out = torch.full((4, 4), -1.0, dtype=torch.float32, device=renderer.tdev)
     rp, op = ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(out.data_ptr())
     assert lib.sbx_planet_eval(None, b"render", 0.0, rp, op, 4, s) == -1
-    for args in [(ctx, None, 0.0, rp, op, 4, s), (ctx, b"render", 0.0, None, op, 4, s), (ctx, b"render", 0.0, rp, None, 4, s),
-                 (ctx, b"density_func", 0.0, rp, op, 4, s), (ctx, b"", 0.0, rp, op, 4, s), (ctx, b"Render", 0.0, rp, op, 4, s),
-                 (ctx, b"render", 0.0, rp, op, (1 << 31) + 1, s)]:
-        assert lib.sbx_planet_eval(*args) == -1, args
-        assert lib.sbx_last_error(ctx)
-        counts = (ctypes.c_uint * 2)(7, 7)
-        assert lib.sbx_debug_planet_eval(*args[:6], counts, s) == -1, args
-    torch.cuda.synchronize()
-    assert bool((out == -1.0).all()), "a refused call writes nothing"
+    bad_args = [(ctx, None, 0.0, rp, op, 4, s), (ctx, b"render", 0.0, None, op, 4, s), (ctx, b"render", 0.0, rp, None, 4, s),
+                (ctx, b"density_func", 0.0, rp, op, 4, s), (ctx, b"", 0.0, rp, op, 4, s), (ctx, b"Render", 0.0, rp, op, 4, s),
+                (ctx, b"render", 0.0, rp, op, (1 << 31) + 1, s)]
+    check_refusals(renderer, lib.sbx_planet_eval, lambda args: lib.sbx_debug_planet_eval(*args[:-1], (ctypes.c_uint * 2)(7, 7), s), bad_args, out)
     for fn in M.FNS:
         assert lib.sbx_planet_eval(ctx, fn.encode(), 0.0, None, None, 0, s) == 0       # n == 0 touches nothing
         assert renderer.planet_eval(fn, torch.zeros((0, M.WIDTHS[fn][0]))).shape == (0, M.WIDTHS[fn][1])

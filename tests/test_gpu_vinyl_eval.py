@@ -5,18 +5,21 @@ points on the spindle's axis where the witness records), a family of NaN / inf /
 0 / 0, launches that mix tame and untame waves, an untame deck, ragged sizes with guard words, variants 1-3, a stream capture, the
 refusals, "render" tied to SBX_APP_VINYL_DECK's frame, and host/sbx_render's --vinyl-view."""
 import ctypes
+from functools import partial
 
 import numpy as np
 import pytest
 
+from shaderbox_amd import Renderer
 from tests import vinyl_deck_model as M
 from tests.app_checks import assert_same, frame_cache, run_sbx_render
 from tests.app_checks import renderer, variant_restored  # noqa: F401 (fixtures)
-from tests.model_common import F, same_bits
+from tests.eval_checks import check_capture_replay, check_ragged, check_refusals, differing, raw_call, to_dev
+from tests.model_common import F
 
 pytestmark = pytest.mark.gpu
 W, H = M.SIZE
-WIDTHS = {"sdf": (3, 2), "sdf_normal": (3, 3), "sdf_shadow": (6, 1), "illuminate": (7, 3), "render": (6, 5)}
+WIDTHS = Renderer.EVAL_WIDTHS["vinyl"]
 FNS = tuple(WIDTHS)
 # the deck of the axis-aligned family: no rotation at all, so that the platter's faces are the planes y = +-.05 of the world
 FLAT = M.deck(0., platter_deg=0., platter_tilt_deg=0., arm_tilt_deg=0., sun_dir=(0., 1., 0.))
@@ -106,25 +109,14 @@ def model(fn, D, x):
 reference = frame_cache(lambda fn, name: model(fn, DECK_OF[name], family(name, WIDTHS[fn][0])))
 
 
-def differing(got, want):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else got
-    assert got.shape == want.shape, (got.shape, want.shape)
-    return int((~same_bits(got, want).reshape(len(want), -1).all(axis=-1)).sum())
-
-
-def _dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=F))
-
-
 @pytest.mark.parametrize("fn", FNS)
 @pytest.mark.parametrize("name", ["frame", "box", "axes", "specials"])
 def test_against_the_model(renderer, fn, name):
     x, a = family(name, WIDTHS[fn][0]), M.as_aux(DECK_OF[name])
     want = reference(fn, name)
     assert want.shape == (len(x), WIDTHS[fn][1])
-    assert differing(renderer.vinyl_eval(fn, _dev(x), a), want) == 0, (fn, name)
-    out, (witnessed, rerun) = renderer.vinyl_eval_counted(fn, _dev(x), a)
+    assert differing(renderer.vinyl_eval(fn, to_dev(x), a), want) == 0, (fn, name)
+    out, (witnessed, rerun) = renderer.vinyl_eval_counted(fn, to_dev(x), a)
     assert differing(out, want) == 0, (fn, name, "counted")
     waves = (len(x) + 63) // 64
     print(fn, name, "waves", waves, "witnessed", witnessed, "re-run", rerun, "NaN rows", int(np.isnan(want).any(axis=1).sum()))
@@ -148,7 +140,7 @@ def test_tame_and_untame_waves_in_one_launch(renderer):
         box = family("box", win)
         x = np.concatenate([box[:64], box[64:128], box[128:192], box[192:197] * F(3e4)], axis=0)
         x[64 + 17, 1] = np.nan
-        out, counts = renderer.vinyl_eval_counted(fn, _dev(x), M.as_aux(D))
+        out, counts = renderer.vinyl_eval_counted(fn, to_dev(x), M.as_aux(D))
         assert counts[0] + counts[1] == 2, (fn, counts)
         assert differing(out, model(fn, D, x)) == 0, fn
 
@@ -159,7 +151,7 @@ def test_an_untame_deck_takes_the_plain_form(renderer):
     for D in (M.deck(.37, sun_dir=(np.nan, 1., 0.)), M.deck(.37, platter_deg=np.inf), M.deck(.37, sun_dir=(0., 2e4, 0.))):
         for fn in ("sdf", "sdf_shadow", "render"):
             xi = np.ascontiguousarray(x[:, :WIDTHS[fn][0]])
-            out, counts = renderer.vinyl_eval_counted(fn, _dev(xi), M.as_aux(D))
+            out, counts = renderer.vinyl_eval_counted(fn, to_dev(xi), M.as_aux(D))
             assert counts == (0, 0), (fn, counts)
             assert differing(out, model(fn, D, xi)) == 0, fn
 
@@ -167,9 +159,9 @@ def test_an_untame_deck_takes_the_plain_form(renderer):
 def test_the_camera_of_the_deck_is_not_read(renderer):
     x = family("box", 6)[:128]
     D = dict(M.DECKS["coloured"])
-    want = renderer.vinyl_eval("render", _dev(x), M.as_aux(D)).cpu().numpy()
+    want = renderer.vinyl_eval("render", to_dev(x), M.as_aux(D)).cpu().numpy()
     D.update(eye=(F(np.nan),) * 3, look_at=(F(np.inf),) * 3, fov=F(-3e38))
-    out, counts = renderer.vinyl_eval_counted("render", _dev(x), M.as_aux(D))
+    out, counts = renderer.vinyl_eval_counted("render", to_dev(x), M.as_aux(D))
     assert differing(out, want) == 0 and counts[0] + counts[1] == 2
 
 
@@ -179,7 +171,7 @@ def test_variants_same_bits(renderer, variant_restored):
             x, a = family(name, WIDTHS[fn][0]), M.as_aux(DECK_OF[name])
             for variant in (1, 2, 3):
                 renderer.set_variant(variant)
-                out, counts = renderer.vinyl_eval_counted(fn, _dev(x), a)
+                out, counts = renderer.vinyl_eval_counted(fn, to_dev(x), a)
                 assert differing(out, reference(fn, name)) == 0, (fn, name, variant)
                 if variant != 2:
                     assert counts == (0, 0), (fn, name, variant, counts)
@@ -190,57 +182,18 @@ def test_variants_same_bits(renderer, variant_restored):
 def test_ragged_sizes_bounds_and_alignment(renderer, n):
     """out inside a poisoned buffer with guard words either side; in and out at an odd dword offset (4 bytes off a 16-byte boundary);
     every output width"""
-    import torch
-    guard, poison = 64, -7.25
     a = M.as_aux(DECK_OF["frame"])
-    for fn in FNS:
-        win, wout = WIDTHS[fn]
-        base, full = family("frame", win), reference(fn, "frame")
-        pick = np.resize(np.arange(len(base)), n)
-        x, want = base[pick], full[pick]
-        ibuf = torch.zeros(1 + win * n, dtype=torch.float32, device=renderer.tdev)
-        ibuf[1:] = torch.from_numpy(x.ravel()).to(renderer.tdev)
-        obuf = torch.full((1 + 2 * guard + wout * n,), poison, dtype=torch.float32, device=renderer.tdev)
-        i_ptr, o_ptr = ibuf.data_ptr() + 4, obuf.data_ptr() + 4 * (1 + guard)
-        assert i_ptr % 16 == 4 and o_ptr % 16 == 4
-        renderer._check(renderer.lib.sbx_vinyl_eval(renderer.ctx, fn.encode(), ctypes.byref(a), ctypes.c_void_p(i_ptr), ctypes.c_void_p(o_ptr), n,
-                                                    renderer._stream()))
-        o = obuf.cpu().numpy()
-        assert (o[:1 + guard] == poison).all() and (o[1 + guard + wout * n:] == poison).all(), (fn, n)
-        assert differing(o[1 + guard:1 + guard + wout * n].reshape(n, wout), want) == 0, (fn, n)
-        assert np.array_equal(ibuf[1:].cpu().numpy().view(np.uint32), x.ravel().view(np.uint32)), (fn, n)
+    pick = np.resize(np.arange(len(family("frame", 6))), n)
+    cases = [(fn, WIDTHS[fn], family("frame", WIDTHS[fn][0])[pick], reference(fn, "frame")[pick]) for fn in FNS]
+    check_ragged(renderer, raw_call(renderer, "vinyl", lead=(ctypes.byref(a),)), cases, n)
 
 
 def test_inside_a_stream_capture(renderer):
-    """one capture, replayed twice, the second time over other rays in the same buffers"""
-    import torch
-    rays, a = family("frame", 6)[:1024], M.as_aux(DECK_OF["frame"])
-    want = reference("render", "frame")[:1024]
-    n = len(rays)
-    dev = torch.from_numpy(rays).to(renderer.tdev)
-    out = torch.zeros((n, 5), dtype=torch.float32, device=renderer.tdev)
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        torch.zeros(1, device=renderer.tdev)                            # the stream exists before the capture
-    s.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        renderer._check(renderer.lib.sbx_vinyl_eval(renderer.ctx, b"render", ctypes.byref(a), ctypes.c_void_p(dev.data_ptr()),
-                                                    ctypes.c_void_p(out.data_ptr()), n, renderer._stream()))
-        counts = (ctypes.c_uint * 2)(7, 7)                               # the counted twin refuses a capture
-        assert renderer.lib.sbx_debug_vinyl_eval(renderer.ctx, b"sdf", ctypes.byref(a), ctypes.c_void_p(dev.data_ptr()),
-                                                 ctypes.c_void_p(out.data_ptr()), 4, counts, renderer._stream()) == -1
-    torch.cuda.synchronize()
-    assert bool((out == 0).all()), "a capture runs nothing"
-    g.replay()
-    torch.cuda.synchronize()
-    assert differing(out, want) == 0
-    dev.copy_(torch.from_numpy(rays[::-1].copy()))
-    out.zero_()
-    torch.cuda.synchronize()
-    g.replay()
-    torch.cuda.synchronize()
-    assert differing(out, want[::-1]) == 0
+    """one capture, replayed twice, the second time over other rays in the same buffers; the counted twin refuses the capturing stream"""
+    a = ctypes.byref(M.as_aux(DECK_OF["frame"]))
+    twin = raw_call(renderer, "vinyl", lead=(a,), counts=(ctypes.c_uint * 2)(7, 7))
+    check_capture_replay(renderer, partial(raw_call(renderer, "vinyl", lead=(a,)), "render"), family("frame", 6)[:1024],
+                         reference("render", "frame")[:1024], 5, refused_twin=partial(twin, "sdf"))
 
 
 def test_arguments(renderer):
@@ -252,16 +205,11 @@ def test_arguments(renderer):
     out = torch.full((4, 5), -1.0, dtype=torch.float32, device=renderer.tdev)
     rp, op, ap = ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(out.data_ptr()), ctypes.byref(a)
     assert lib.sbx_vinyl_eval(None, b"render", ap, rp, op, 4, s) == -1
-    for args in [(ctx, None, ap, rp, op, 4, s), (ctx, b"render", ap, None, op, 4, s), (ctx, b"render", ap, rp, None, 4, s),
-                 (ctx, b"render", None, rp, op, 4, s), (ctx, b"sdf", None, rp, op, 4, s), (ctx, b"illuminate", None, rp, op, 0, s),
-                 (ctx, b"render_scene", ap, rp, op, 4, s), (ctx, b"", ap, rp, op, 4, s), (ctx, b"Sdf", ap, rp, op, 4, s),
-                 (ctx, b"shadowmarch", ap, rp, op, 4, s), (ctx, b"render", ap, rp, op, (1 << 31) + 1, s)]:
-        assert lib.sbx_vinyl_eval(*args) == -1, args
-        assert lib.sbx_last_error(ctx)
-        counts = (ctypes.c_uint * 2)(7, 7)
-        assert lib.sbx_debug_vinyl_eval(*args[:6], counts, s) == -1, args
-    torch.cuda.synchronize()
-    assert bool((out == -1.0).all()), "a refused call writes nothing"
+    bad_args = [(ctx, None, ap, rp, op, 4, s), (ctx, b"render", ap, None, op, 4, s), (ctx, b"render", ap, rp, None, 4, s),
+                (ctx, b"render", None, rp, op, 4, s), (ctx, b"sdf", None, rp, op, 4, s), (ctx, b"illuminate", None, rp, op, 0, s),
+                (ctx, b"render_scene", ap, rp, op, 4, s), (ctx, b"", ap, rp, op, 4, s), (ctx, b"Sdf", ap, rp, op, 4, s),
+                (ctx, b"shadowmarch", ap, rp, op, 4, s), (ctx, b"render", ap, rp, op, (1 << 31) + 1, s)]
+    check_refusals(renderer, lib.sbx_vinyl_eval, lambda args: lib.sbx_debug_vinyl_eval(*args[:-1], (ctypes.c_uint * 2)(7, 7), s), bad_args, out)
     for fn, (win, wout) in WIDTHS.items():
         assert lib.sbx_vinyl_eval(ctx, fn.encode(), ap, None, None, 0, s) == 0            # n == 0 touches nothing
         assert renderer.vinyl_eval(fn, torch.zeros((0, win)), a).shape == (0, wout)
@@ -279,7 +227,7 @@ def test_arguments(renderer):
 def test_render_over_the_primary_rays_is_the_apps_frame(renderer, name):
     """"render" over a frame's primary rays, then linear_to_srgb from the model: SBX_APP_VINYL_DECK's frame"""
     D = M.DECKS[name]
-    out = renderer.vinyl_eval("render", _dev(frame_rays(D, W, H)), M.as_aux(D)).cpu().numpy()
+    out = renderer.vinyl_eval("render", to_dev(frame_rays(D, W, H)), M.as_aux(D)).cpu().numpy()
     frame = renderer.render("vinyl_deck", W, H, 0.0, aux=M.as_aux(D)).cpu().numpy()
     assert_same(M.finish(out[:, :3]).reshape(H, W, 4), frame, name)
     assert_same(frame, M.fixture(name)["frame"], (name, "fixture"))

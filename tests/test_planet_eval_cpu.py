@@ -118,7 +118,8 @@ def test_entry_point_is_declared_bound_and_exported():
     lib = shaderbox_amd.load_library()
     assert len(lib.sbx_planet_eval.argtypes) == 7 and len(lib.sbx_debug_planet_eval.argtypes) == 8
     assert callable(shaderbox_amd.Renderer.planet_eval) and callable(shaderbox_amd.Renderer.planet_eval_counted)
-    assert set(shaderbox_amd.Renderer.PLANET_EVAL_WIDTHS.items()) == set(M.WIDTHS.items())
+    R = shaderbox_amd.Renderer
+    assert R.EVAL_WIDTHS["planet"] == M.WIDTHS and R.PLANET_EVAL_WIDTHS is R.EVAL_WIDTHS["planet"]      # one table, stated once
     # without a context every call is refused before it looks at anything else
     assert lib.sbx_planet_eval(None, b"render", 0.0, None, None, 0, None) == -1
     assert lib.sbx_debug_planet_eval(None, b"render", 0.0, None, None, 0, None, None) == -1

@@ -3,7 +3,8 @@ shipped with every number it states read from the block sbx_aux_atmosphere_air â
 tests/model_common.py, in the operation order of tests/atmosphere_eval_model.py (whose helpers, ray families and class test it
 imports) and tests/atmosphere_ground_model.py (whose plane test it calls with the block's eye and radius); exp, pow, sin, cos, acos
 and atan2 are the oracle's.  A block is a dict of the struct's fields; tier_of restates the host's choice of kernel
-(csrc/sbx_frames.hip atmosphere_air_tier).  tests/test_atmosphere_air_cpu.py pins the module to the oracle, to the ground model and to
+(csrc/sbx_frames.hip atmosphere_air_tier); _incident_light's optional `witness` says which paths a ray takes through the march and
+tile_bodies which body each wave of a run-time launch takes, for the sweep of tests/caller_sweeps.py.  tests/test_atmosphere_air_cpu.py pins the module to the oracle, to the ground model and to
 what the reference's own header renders with four blocks written into it (tools/make_golden_atmosphere_airs.py)."""
 import os
 
@@ -182,8 +183,18 @@ def get_sun_light(A, rays):
     return np.stack([np.where(ok, ONE, ZERO), odr, odm], axis=-1).astype(F)
 
 
-def _incident_light(A, ro, rd):
-    """ro, rd: three float32 arrays [n] each -> float32 [n, 3], the linear RGB of :78-160"""
+WITNESS = ("tau_in", "tau_out", "od_inf", "under")
+
+
+def _incident_light(A, ro, rd, witness=None):
+    """ro, rd: three float32 arrays [n] each -> float32 [n, 3], the linear RGB of :78-160.  witness: None, or a dict that receives
+    one bool [n] per name of WITNESS, the paths the ray takes through the march (all False for a ray that misses the sphere):
+      tau_in   a lit sample (its light march did not return) has all three |tau| <= 80: the guard-less exp's side of the fast body's ballot
+      tau_out  a lit sample has not (a NaN tau included)
+      od_inf   optical_depthR or optical_depthM reaches +inf
+      under    a light march returned under the ground
+    tau_in, tau_out and under count the samples at which neither optical depth is +inf yet: the ones the fast body's dead-ray exit
+    never skips, so that what they say holds of that body whether the exit is on or off."""
     n = len(rd[0])
     ro = tuple(np.broadcast_to(_f(c), (n,)) for c in ro)
     sun_dir = tuple(np.full(n, v, dtype=F) for v in A["sun_dir"])
@@ -200,6 +211,7 @@ def _incident_light(A, ro, rd):
         sum_r = [np.zeros(n, dtype=F) for _ in range(3)]
         sum_m = [np.zeros(n, dtype=F) for _ in range(3)]
         march_pos = np.zeros(n, dtype=F)
+        seen = {k: np.zeros(n, dtype=bool) for k in WITNESS}
         for _ in range(A["num_samples"]):
             s = _sample(ro, rd, march_pos + F(.5) * march_step)
             height = np.sqrt(dot(s, s)) - A["earth_radius"]
@@ -208,12 +220,21 @@ def _incident_light(A, ro, rd):
             odr = odr + hr
             odm = odm + hm
             over, lr, lm = _sun_light(A, s, sun_dir)
+            small = np.ones(n, dtype=bool)
             for k in range(3):
                 tau = A["betaR"][k] * (odr + lr) + (A["betaM"][k] * F(1.1)) * (odm + lm)
+                small = small & (np.abs(tau) <= F(80))
                 att = _exp(-tau)
                 sum_r[k] = np.where(over, sum_r[k] + hr * att, sum_r[k])
                 sum_m[k] = np.where(over, sum_m[k] + hm * att, sum_m[k])
+            seen["od_inf"] |= hit & ((odr == np.inf) | (odm == np.inf))
+            live = hit & ~seen["od_inf"]
+            seen["tau_in"] |= live & over & small
+            seen["tau_out"] |= live & over & ~small
+            seen["under"] |= live & ~over
             march_pos = march_pos + march_step
+        if witness is not None:
+            witness.update(seen)
         col = [A["sun_power"] * ((sum_r[k] * phase_r) * A["betaR"][k] + (sum_m[k] * phase_m) * A["betaM"][k]) for k in range(3)]
         return np.stack([np.where(hit, c, ZERO) for c in col], axis=-1).astype(F)
 
@@ -249,6 +270,56 @@ def parts(A, width, height, fx, fy):
     if sky.any():
         col[sky] = _incident_light(A, A["eye"], tuple(c[sky] for c in rd))
     return col, ~sky
+
+
+# ---- which body a wave of the run-time tier takes -------------------------------------------------------------------------------------
+
+SKIPPED, FAST, PLAIN_BODY = 0, 1, 2
+CLASS_RAY = (ZERO, E.EARTH_RADIUS + ONE, ZERO, ONE, ZERO, ZERO)      # kern_atmosphere_air.hip air_class_ray
+
+
+def held_rays(A, width, height):
+    """-> (rays float32 [height, width, 6], march bool [height, width]): the ray each pixel's lane holds when its wave votes on the
+    class in k_atmosphere_air<VIEW, true> â€” its own where it marches (view 0: inside the dome's circle, z2 > 2 false; view 1: no plane
+    hit), CLASS_RAY where it does not"""
+    fx, fy = np.broadcast_arrays(*frame_coords(width, height))
+    pcx, pcy = point_cam(width, height, fx.ravel(), fy.ravel(), A["fov"])
+    with np.errstate(all="ignore"):
+        if A["view"] == 0:
+            march = ~(pcx * pcx + pcy * pcy > F(2))
+            rd = dome_dirs(pcx, pcy)
+        else:
+            rd = get_primary_ray(pcx, pcy, A["eye"], A["look_at"])
+            march = G.intersect_plane_t(rd, origin=A["eye"], distance=A["earth_radius"]) > G.MAX_DIST
+    rays = np.empty((pcx.size, 6), dtype=F)
+    rays[:] = np.array(CLASS_RAY, dtype=F)
+    for k in range(3):
+        rays[march, k] = F(A["eye"][k])
+        rays[march, 3 + k] = rd[k][march]
+    return rays.reshape(height, width, 6), march.reshape(height, width)
+
+
+def tiles_of(a, fill):
+    """[height, width, ...] -> [tiles_y, tiles_x, 64, ...]: the 8x8 pixel tiles of pixel_of<8, 1> (csrc/sbx_device.h: lane = 8 * row + column
+    within the tile, tile rows from row 0), the lanes past a ragged edge holding `fill`"""
+    h, w = a.shape[:2]
+    th, tw = (h + 7) // 8, (w + 7) // 8
+    full = np.full((th * 8, tw * 8) + a.shape[2:], fill, dtype=a.dtype)
+    full[:h, :w] = a
+    full = full.reshape((th, 8, tw, 8) + a.shape[2:])
+    return np.moveaxis(full, 2, 1).reshape((th, tw, 64) + a.shape[2:])
+
+
+def tile_bodies(A, width, height):
+    """-> int [tiles_y, tiles_x]: what each wave of a tame block's launch does.  A wave is an 8x8 pixel tile; the lanes past a ragged
+    edge return before any ballot and have no vote.  SKIPPED: no lane marches (view 0: the whole tile outside the circle; view 1:
+    under the horizon) and the wave leaves; FAST: every valid lane's held ray passes E.in_class; PLAIN_BODY otherwise."""
+    rays, march = held_rays(A, width, height)
+    valid = tiles_of(np.ones((height, width), dtype=bool), False)
+    in_class = tiles_of(E.in_class(rays.reshape(-1, 6)).reshape(height, width), False)
+    marches = (tiles_of(march, False) & valid).any(axis=-1)
+    fast = (in_class | ~valid).all(axis=-1)
+    return np.where(~marches, SKIPPED, np.where(fast, FAST, PLAIN_BODY))
 
 
 def finish(rgb):

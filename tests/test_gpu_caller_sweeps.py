@@ -5,6 +5,7 @@ hardware min / max are derived from data no fixture has — bent knees, bones of
 any side of the deck, tilts up to 90 degrees, an un-normalised sun.  The launch records (sbx_debug_egg_pose_launches,
 sbx_debug_vinyl_deck_launches) show that the host judged every block tame, so that no comparison is the plain kernel with itself;
 tests/test_caller_sweeps_cpu.py shows that the frames are not empty.  Then the edge of the tame domain, and ten launches of one block.
+(The airs of SBX_APP_ATMOSPHERE_AIR that tests/caller_sweeps.py also generates: tests/test_gpu_caller_sweeps_air.py.)
 
 A seed that fails is a finding about csrc/: its block goes into FINDINGS below, by name, and stays there."""
 import numpy as np
@@ -20,7 +21,7 @@ from tests.model_common import F, same_bits
 pytestmark = pytest.mark.gpu
 MODEL = {"egg_pose": E, "vinyl_deck": D}
 MAKE = {"egg_pose": C.egg_pose, "vinyl_deck": C.vinyl_deck}
-CLASSES = [(app, cls) for app in C.CASES for cls in C.CASES[app]]
+CLASSES = [(app, cls) for app in MODEL for cls in C.CASES[app]]      # (SBX_APP_ATMOSPHERE_AIR's classes: tests/test_gpu_caller_sweeps_air.py)
 SIZE = (128, 72)                                     # the frame compared with the model
 DENSE = (333, 187)                                   # legs and tonearm several pixels wide, tiles ragged both ways: device only
 EDGE = (67, 35)

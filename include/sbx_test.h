@@ -19,8 +19,10 @@ extern "C" {
  * lane hashing its own lattice corners (no cache, no staging, no tables); APP_EGG / APP_SDF_AO / APP_VINYL with every
  * member of the SDF union evaluated everywhere (no culling); APP_PLANET without its exact skips.
  * 2 / 3 = the default kernels, except APP_EGG / APP_SDF_AO / APP_VINYL(_GPU): 2 = their square-root witness with the recording
- * edge raised to 1.0, so that the re-run path (csrc/sbx_sdf.h, Wit) executes on ordinary frames; 3 = the culled kernels with the
- * IEEE roots only.  APP_FUNC: 1 = hash_w in place for every cell (no hash table; worley_fbm as src/app_func.h writes it).
+ * edge raised to 1.0, so that the re-run path (csrc/sbx_witness.h `witnessed`) executes on ordinary frames; 3 = the culled
+ * kernels with the IEEE roots only.  For every app and eval entry below that has a witness, the one table from 1 / 2 / 3 to the
+ * kernel's CULL and WIT is witness_dispatch's in that header; a kernel with nothing to cull folds 1 and 3 together.
+ * APP_FUNC: 1 = hash_w in place for every cell (no hash table; worley_fbm as src/app_func.h writes it).
  * SBX_APP_ATMOSPHERE_GROUND: 1 = the plain statement of src/app_atmosphere.h:211-224 lane by lane (no wave-level exit, guarded exp,
  * sqrt_n_, division by the exact reciprocal; exact, whatever sbx_set_precision says).  SBX_APP_ATMOSPHERE ignores the knob.
  * SBX_APP_SDF_AO_SHADOW / SBX_APP_SDF_AO_NORMALS: every value as for APP_SDF_AO, the shadow march included — 1 = no culling, the spec's

@@ -105,8 +105,7 @@ __device__ __forceinline__ v3 egg_bars(v3 color, float pcx, float depth) {
     return abs3(mix3(color, V3(.6f, .6f, .6f), bar_factor * depth_factor));
 }
 
-// WIT: 0 = IEEE roots; 1 = witnessed roots (the shipped form); 2 = the same with the witness's lower edge at 1.0, so that waves
-// near any primitive's axis DO record and re-run (sbx_set_variant 2: the test of the re-run path — same frame required)
+// WIT: sbx_witness.h `witnessed` (0 = IEEE roots; 1 = witnessed roots, the shipped form; 2 = the witness's test edge)
 template <int BUILD> struct EggFrame { using type = FrameEgg; };
 template <> struct EggFrame<EGG_STRAIGHT> { using type = FrameEggStraight; };      // FrameEgg and the four cylinders (sbx_frame.h)
 template <bool CULL, int WIT, int BUILD = EGG_DEFAULT>
@@ -134,18 +133,7 @@ __global__ void __launch_bounds__(64 * EGG_TX) k_egg(typename EggFrame<BUILD>::t
     const v2 pc = point_cam(F.cam, px.fx, px.fy);
     float depth;
     v3 color;
-    if (WIT != 0) {
-        Wit<true> w;
-        if (WIT == 2) w.lo = 0x3F800000u;
-        egg_pixel<CULL, BUILD>(F, pc, w, color, depth, st_trace, st_shadow);
-        if (__builtin_amdgcn_ballot_w64(w.bad) != 0ull) {      // some lane took a root outside the proved interval: the IEEE forms
-            Wit<false> w0;
-            egg_pixel<CULL, BUILD>(F, pc, w0, color, depth, st_trace, st_shadow);
-        }
-    } else {
-        Wit<false> w0;
-        egg_pixel<CULL, BUILD>(F, pc, w0, color, depth, st_trace, st_shadow);
-    }
+    witnessed<WIT>(true, [&](auto& w) { egg_pixel<CULL, BUILD>(F, pc, w, color, depth, st_trace, st_shadow); });
     tile_cost_store_at(M, tl_t0, bx, by);                  // (bx, by: after the hot-first mapping)
     color = egg_bars(color, pc.x, depth);
 #ifdef SBX_EGG_STATS
@@ -220,10 +208,7 @@ static void launch_egg_t(const FrameEggStraight& F, const RowMap& M, float* out,
 }
 template <int BUILD>
 static void launch_egg_b(const FrameEggStraight& F, const RowMap& M, float* out, hipStream_t s, int variant, dim3 grid, HotRect hot, size_t pad) {
-    if (variant == 1) launch_egg_t<false, 0, BUILD>(F, M, out, s, grid, hot, pad);
-    else if (variant == 2) launch_egg_t<true, 2, BUILD>(F, M, out, s, grid, hot, pad);
-    else if (variant == 3) launch_egg_t<true, 0, BUILD>(F, M, out, s, grid, hot, pad);
-    else launch_egg_t<true, EGG_WITNESS, BUILD>(F, M, out, s, grid, hot, pad);
+    witness_dispatch<EGG_WITNESS>(variant, [&](auto cull, auto wit) { launch_egg_t<cull.value, wit.value, BUILD>(F, M, out, s, grid, hot, pad); });
 }
 
 dim3 egg_grid(const RowMap& M) { return grid_for<EGG_TW, EGG_TX>(M); }

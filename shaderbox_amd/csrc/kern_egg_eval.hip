@@ -2,21 +2,15 @@
 // :38-144, sdf_normal :146-157, shadowmarch :161-186, render_scene :190-231 with `depth` of :188) over the caller's points and rays
 // under the caller's pose, and the two bone IK solver (src/IK.h:5-52) over the caller's goals (include/sbx.h).  No camera, no u_res.
 //
-// k_egg_eval: one lane per element, one 64-lane wave per workgroup, a ragged last wave; a lane past n loads nothing, evaluates element
-// zeros harmlessly and stores nothing.  Everything runs on k_egg's device functions (sbx_egg.h) over the FrameEgg that
-// build_egg_pose (sbx_frames.hip) makes of the block.  The decisions:
-//   THE FORM OF A WAVE.  k_egg's culls and witnessed roots are proved for finite frame constants and sample points of the scene's scale
-//     (sbx_egg.h, sbx_sdf.h; sbx_frames.hip egg_pose_tame).  The frame is the host's to judge: a pose that is not tame gets the PLAIN
-//     kernel (CULL = false, IEEE roots — the reference's operations on whatever the values are), as does sbx_set_variant 1.  The
-//     elements are the wave's to judge: a cull CLAIMS "the union is the ground plane", which is false where the full evaluation would
-//     return a NaN member last (a NaN or inf coordinate of P: 0 * inf in the turntable product), and a coordinate near 2^64 overflows
-//     the squared lengths the culls compare.  So a wave takes the culled form only if every committing lane's inputs are within 1e4
-//     per coordinate, NaN failing (`ee_within`); then a march stays within |P| <= 1e4 + 1.8e4 * (15 + |d|) < 2^33 — t leaves the
-//     loops beyond 15 and 10, and one step adds at most the ground's distance — whose squares are far inside binary32.  Any other
-//     wave takes the plain form for all of its lanes.  Per wave, not per lane: one predicate, one branch, no divergent copies.
-//   THE WITNESS RE-RUN is decided per wave by ballot, as in k_egg: the witness's record accumulates per lane, and a wave in which any
-//     lane took a root outside the proved interval evaluates again with the IEEE roots (still culled: the cull does not depend on
-//     the roots).  Off-axis points never record; a point on a primitive's axis or centre does, which sbx_debug_egg_eval counts.
+// k_egg_eval: the element wave of sbx_witness.h (witnessed_elements: the form of a wave, the witness re-run, loads and stores) over
+// k_egg's device functions (sbx_egg.h) and the FrameEgg that build_egg_pose (sbx_frames.hip) makes of the block.  What is its own:
+//   THE BOUND'S REASONS.  k_egg's culls and witnessed roots are proved for finite frame constants and sample points of the scene's
+//     scale (sbx_egg.h, sbx_sdf.h; sbx_frames.hip egg_pose_tame decides PLAIN).  A cull CLAIMS "the union is the ground plane", which
+//     is false where the full evaluation would return a NaN member last (a NaN or inf coordinate of P: 0 * inf in the turntable
+//     product), and a coordinate near 2^64 overflows the squared lengths the culls compare.  Within 1e4 per coordinate a march stays
+//     within |P| <= 1e4 + 1.8e4 * (15 + |d|) < 2^33 — t leaves the loops beyond 15 and 10, and one step adds at most the ground's
+//     distance — whose squares are far inside binary32.  Off-axis points never record; a point on a primitive's axis or centre does,
+//     which sbx_debug_egg_eval counts.
 //   VGPR CONSTANTS.  As k_egg (EGG_VCONST = 1): the turntable matrix and the cull sphere, read first by every sdf() call, are forced
 //     into VGPRs — a VALU instruction with an SGPR source issues at half rate on gfx950 (profiles/r02_ubench_issue.txt).  The toe
 //     midpoints stay scalar (k_egg's EGG_VCONST > 1 lost there, and the register budget here is the same code's).
@@ -24,10 +18,6 @@
 //     point, and one shared test on p with a margin of .05 would be a new bound to prove for nothing measurable.
 //     Its final normalize is the IEEE one in every form: over flat ground two of the three differences are exactly 0, which the
 //     witnessed normalize records (a component whose square is not normal), and a wave must not re-run six fields for that.
-//   LOADS AND STORES.  `in` and `out` need only 4-byte alignment, so an element is read and written as dwords: lane i reads
-//     in[W i + k], k < W.  A wave's W loads together cover 64 W contiguous floats — every cache line fetched is fully used — and
-//     at 12-40 B per element against an 80-step march the traffic is noise beside the arithmetic (profiles/egg_eval_timing.txt).
-//     A staged, vectorised copy through LDS would need the alignment the contract does not give.
 // k_ik_eval: "ik_solver", a kernel of its own — 44 B per element and some thirty operations: bandwidth-bound, so the spec's division,
 //     square root and normalisation as they stand (no witness, no short form), and the zero terms of mul(rot, v) kept as
 //     sbx_frames.hip's host version keeps them (0 * inf is a NaN, (-0) + 0 is +0).  256 lanes per workgroup.
@@ -37,14 +27,12 @@ namespace sbx {
 
 enum { EE_SDF = 0, EE_NORMAL = 1, EE_SHADOW = 2, EE_RENDER = 3 };
 
-__device__ __forceinline__ bool ee_within(float x) { return abs_(x) <= 1e4f; }     // a NaN compares false
-
 constexpr int ee_in_width(int fn) { return fn <= EE_NORMAL ? 3 : 6; }
 constexpr int ee_out_width(int fn) { return fn == EE_SDF ? 2 : fn == EE_NORMAL ? 3 : fn == EE_SHADOW ? 1 : 4; }
 
 // one element of FN with sdf()'s CULL and the roots of witness `w`; q = its inputs, r = its outputs
 template <int FN, bool CULL, class W>
-__device__ __forceinline__ void ee_element(const FrameEgg& F, const float (&q)[6], W& w, float (&r)[4]) {
+__device__ __forceinline__ void ee_element(const FrameEgg& F, const float (&q)[ELEM_WORDS], W& w, float (&r)[ELEM_WORDS]) {
     const v3 a = V3(q[0], q[1], q[2]), b = V3(q[3], q[4], q[5]);
     if (FN == EE_SDF) {
         const D2 d = egg_sdf<CULL, EGG_DEFAULT>(F, a, w);
@@ -82,61 +70,27 @@ __device__ __forceinline__ void ee_element(const FrameEgg& F, const float (&q)[6
     }
 }
 
-// PLAIN: the reference form for every wave (an untame pose, sbx_set_variant 1).  WIT as k_egg: 0 IEEE roots, 1 witnessed roots, 2 the
-// witness's lower edge at 1.0 (sbx_set_variant 2: waves near any primitive DO record and re-run).  counts: NULL or two zeroed words.
+// PLAIN, WIT, counts: sbx_witness.h witnessed_elements
 template <int FN, bool PLAIN, int WIT>
 __global__ void __launch_bounds__(64) k_egg_eval(FrameEgg F, const float* __restrict__ in, float* __restrict__ out, size_t n,
                                                  unsigned* __restrict__ counts) {
-    constexpr int WIN = ee_in_width(FN), WOUT = ee_out_width(FN);
     asm volatile("" : "+v"(F.rot_y.c0.x), "+v"(F.rot_y.c0.y), "+v"(F.rot_y.c0.z), "+v"(F.rot_y.c1.x), "+v"(F.rot_y.c1.y),
                       "+v"(F.rot_y.c1.z), "+v"(F.rot_y.c2.x), "+v"(F.rot_y.c2.y), "+v"(F.rot_y.c2.z));
     asm volatile("" : "+v"(F.ocw.x), "+v"(F.ocw.y), "+v"(F.ocw.z), "+v"(F.orad));
-    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
-    const bool on = i < n;
-    float q[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (on) {
-#pragma unroll
-        for (int k = 0; k < WIN; ++k) q[k] = in[(size_t)WIN * i + k];
-    }
-    float r[4] = {0.f, 0.f, 0.f, 0.f};
-    bool tame = true;
-#pragma unroll
-    for (int k = 0; k < WIN; ++k) tame = tame && ee_within(q[k]);
-    const bool culled = !PLAIN && __builtin_amdgcn_ballot_w64(on && !tame) == 0ull;      // wave-uniform
-    bool rerun = false;
-    if (culled) {
-        if (WIT != 0) {
-            Wit<true> w;
-            if (WIT == 2) w.lo = 0x3F800000u;
-            ee_element<FN, true>(F, q, w, r);
-            rerun = __builtin_amdgcn_ballot_w64(on && w.bad) != 0ull;
-        }
-        if (WIT == 0 || rerun) {
-            Wit<false> w0;
-            ee_element<FN, true>(F, q, w0, r);
-        }
-    } else {
-        Wit<false> w0;
-        ee_element<FN, false>(F, q, w0, r);
-    }
-    if (on) {
-#pragma unroll
-        for (int k = 0; k < WOUT; ++k) out[(size_t)WOUT * i + k] = r[k];
-    }
-    if (counts && (threadIdx.x & 63) == 0 && culled && WIT != 0) atomicAdd(counts + (rerun ? 1 : 0), 1u);
+    witnessed_elements<ee_in_width(FN), ee_in_width(FN), ee_out_width(FN), PLAIN, WIT>(in, out, n, counts,
+        [&](auto cull, const auto& q, auto& w, auto& r) { ee_element<FN, cull.value>(F, q, w, r); });
 }
 
 template <int FN>
 static void ee_launch(const FrameEgg& F, int variant, const float* in, float* out, size_t n, unsigned* counts, hipStream_t s) {
     const dim3 grid((unsigned)((n + 63) / 64));
-    if (variant == 1) hipLaunchKernelGGL((k_egg_eval<FN, true, 0>), grid, dim3(64), 0, s, F, in, out, n, counts);
-    else if (variant == 2) hipLaunchKernelGGL((k_egg_eval<FN, false, 2>), grid, dim3(64), 0, s, F, in, out, n, counts);
-    else if (variant == 3) hipLaunchKernelGGL((k_egg_eval<FN, false, 0>), grid, dim3(64), 0, s, F, in, out, n, counts);
-    else hipLaunchKernelGGL((k_egg_eval<FN, false, 1>), grid, dim3(64), 0, s, F, in, out, n, counts);
+    witness_dispatch<1>(variant, [&](auto cull, auto wit) {
+        hipLaunchKernelGGL((k_egg_eval<FN, !cull.value, wit.value>), grid, dim3(64), 0, s, F, in, out, n, counts);
+    });
 }
 
 // fn: EE_* in the order of sbx_eval.hip's names after "ik_solver".  F: build_egg_pose of the caller's block (its camera is not read).
-// variant: 0 default, 1 plain, 2 the witness's test edge, 3 IEEE roots (as launch_egg).  n in 1 ... 2^31.
+// variant: witness_dispatch's.  n in 1 ... 2^31.
 void launch_egg_eval(int fn, const FrameEgg& F, int variant, const float* in, float* out, size_t n, unsigned* counts, hipStream_t s) {
     switch (fn) {
     case EE_SDF: ee_launch<EE_SDF>(F, variant, in, out, n, counts, s); break;

@@ -255,18 +255,11 @@ __global__ void __launch_bounds__(WG_THREADS) k_raytracer(FrameRaytracer F, RowM
     if (!px.valid) return;
     const v2 pc = point_cam(F.cam, px.fx, px.fy);
     v3 color;
-    if (WIT != 0) {
-        Wit<true> w;
-        if (WIT == 2) w.lo = 0x3F800000u;
-        color = rt_pixel<WALLS, BUILD>(F, RT_F, pc, w);
-        if (__builtin_amdgcn_ballot_w64(w.bad) != 0ull) {      // some lane left the fast forms' proved domain: the IEEE forms
-            Wit<false> w0;
-            color = rt_pixel<false, BUILD>(F, RT_F, pc, w0);
-        }
-    } else {
-        Wit<false> w0;
-        color = rt_pixel<false, BUILD>(F, RT_F, pc, w0);
-    }
+    // (hit_walls is the fast pass's alone: the IEEE pass takes the six-plane loop)
+    witnessed<WIT>(true, [&](auto& w) {
+        using W = std::remove_reference_t<decltype(w)>;
+        color = rt_pixel<WALLS && W::fast, BUILD>(F, RT_F, pc, w);
+    });
     tile_cost_store(M, tl_t0);
     store_rgba(M, out, px.idx, to_srgb(color));
 }
@@ -275,11 +268,13 @@ dim3 raytracer_grid(const RowMap& M) { return grid_for(M); }
 
 template <int BUILD>
 static void launch_build(const FrameRaytracer& F, const RowMap& M, float* out, hipStream_t s, int variant, bool walls) {
-    if (variant == 2 && walls) hipLaunchKernelGGL((k_raytracer<2, true, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);     // (the witness's test build
-    else if (variant == 2) hipLaunchKernelGGL((k_raytracer<2, false, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);         //  keeps hit_walls' domain too)
-    else if (variant == 1 || variant == 3) hipLaunchKernelGGL((k_raytracer<0, false, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else if (!walls) hipLaunchKernelGGL((k_raytracer<RT_WITNESS, false, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else hipLaunchKernelGGL((k_raytracer<RT_WITNESS, true, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    // hit_walls belongs to the fast forms (the witness's test build keeps its domain too); the IEEE kernel has no use for it
+    witness_dispatch<RT_WITNESS>(variant, [&](auto, auto wit) {
+        if constexpr (wit.value != 0) {
+            if (walls) { hipLaunchKernelGGL((k_raytracer<wit.value, true, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out); return; }
+        }
+        hipLaunchKernelGGL((k_raytracer<wit.value, false, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    });
 }
 
 void launch_raytracer(const FrameRaytracer& F, const RowMap& M, float* out, hipStream_t s, int variant, int build) {
@@ -444,26 +439,15 @@ __global__ void __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu
     if (!px.valid) return;
     const v2 pc = point_cam(F.cam, px.fx, px.fy);
     v3 color;
-    if (WIT != 0) {
-        Wit<true> w;
-        if (WIT == 2) w.lo = 0x3F800000u;
-        color = scene_pixel(F, Fs, pc, w);
-        if (__builtin_amdgcn_ballot_w64(w.bad) != 0ull) {      // some lane left the fast forms' proved domain: the IEEE forms
-            Wit<false> w0;
-            color = scene_pixel(F, Fs, pc, w0);
-        }
-    } else {
-        Wit<false> w0;
-        color = scene_pixel(F, Fs, pc, w0);
-    }
+    witnessed<WIT>(true, [&](auto& w) { color = scene_pixel(F, Fs, pc, w); });
     tile_cost_store(M, tl_t0);
     store_rgba(M, out, px.idx, to_srgb(color));
 }
 
 void launch_raytracer_scene(const FrameRtScene& F, const RowMap& M, float* out, hipStream_t s, int variant) {
-    if (variant == 2) hipLaunchKernelGGL((k_raytracer_scene<2>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else if (variant == 1 || variant == 3) hipLaunchKernelGGL((k_raytracer_scene<0>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else hipLaunchKernelGGL((k_raytracer_scene<RT_WITNESS>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    witness_dispatch<RT_WITNESS>(variant, [&](auto, auto wit) {
+        hipLaunchKernelGGL((k_raytracer_scene<wit.value>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    });
 }
 
 }  // namespace sbx

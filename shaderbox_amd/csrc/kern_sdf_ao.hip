@@ -188,7 +188,7 @@ __device__ __forceinline__ void ao_pixel(const FrameSdfAo& F, v3 ro, v2 pc, W& w
     }
 }
 
-template <bool CULL, int WIT, int BUILD = AO_DEFAULT>   // WIT: 0 IEEE roots, 1 witnessed roots, 2 the witness's test edge (sbx_set_variant 2), as k_egg
+template <bool CULL, int WIT, int BUILD = AO_DEFAULT>   // WIT: sbx_witness.h `witnessed`
 __global__ void __launch_bounds__(WG_THREADS, AO_MIN_WAVES) k_sdf_ao(FrameSdfAo F, RowMap M, float* __restrict__ out) {
     const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();      // (the dispatch order's cost table, RowMap.cost)
     const Pixel px = pixel_of_thread(M);
@@ -197,18 +197,7 @@ __global__ void __launch_bounds__(WG_THREADS, AO_MIN_WAVES) k_sdf_ao(FrameSdfAo 
     const v3 ro = F.cam.eye;
     v3 rgb, rd;
     float t;
-    if (WIT != 0) {
-        Wit<true> w;
-        if (WIT == 2) w.lo = 0x3F800000u;
-        ao_pixel<CULL, BUILD>(F, ro, pc, w, rgb, t, rd);
-        if (__builtin_amdgcn_ballot_w64(w.bad) != 0ull) {
-            Wit<false> w0;
-            ao_pixel<CULL, BUILD>(F, ro, pc, w0, rgb, t, rd);
-        }
-    } else {
-        Wit<false> w0;
-        ao_pixel<CULL, BUILD>(F, ro, pc, w0, rgb, t, rd);
-    }
+    witnessed<WIT>(true, [&](auto& w) { ao_pixel<CULL, BUILD>(F, ro, pc, w, rgb, t, rd); });
     // fog :287-311 (t is the march length at exit)
     const float fog_factor = F.fog_density * exp_(-ro.y * F.fog_falloff)
                            * (1.f - exp_(-t * rd.y * F.fog_falloff))
@@ -222,10 +211,9 @@ dim3 sdf_ao_grid(const RowMap& M) { return grid_for(M); }
 
 template <int BUILD>
 static void launch_sdf_ao_build(const FrameSdfAo& F, const RowMap& M, float* out, hipStream_t s, int variant) {
-    if (variant == 1) hipLaunchKernelGGL((k_sdf_ao<false, 0, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else if (variant == 2) hipLaunchKernelGGL((k_sdf_ao<true, 2, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else if (variant == 3) hipLaunchKernelGGL((k_sdf_ao<true, 0, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else hipLaunchKernelGGL((k_sdf_ao<true, AO_WITNESS, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    witness_dispatch<AO_WITNESS>(variant, [&](auto cull, auto wit) {
+        hipLaunchKernelGGL((k_sdf_ao<cull.value, wit.value, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    });
 }
 
 // build: 0 SBX_APP_SDF_AO, 1 SBX_APP_SDF_AO_SHADOW, 2 SBX_APP_SDF_AO_NORMALS

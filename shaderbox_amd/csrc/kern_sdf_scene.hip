@@ -217,7 +217,7 @@ __device__ __forceinline__ void scene_pixel(const FrameSdfScene& F, const SdfRd&
     rgb = accum * mat_c;
 }
 
-template <int WIT>   // 0 IEEE roots, 1 witnessed roots, 2 the witness's test edge (sbx_set_variant 2), as k_sdf_ao
+template <int WIT>   // sbx_witness.h `witnessed`
 __global__ void __launch_bounds__(WG_THREADS, SDF_SCENE_MIN_WAVES) k_sdf_scene(FrameSdfScene F, RowMap M, float* __restrict__ out) {
     const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();
     __shared__ FrameSdfScene Fs;
@@ -230,18 +230,7 @@ __global__ void __launch_bounds__(WG_THREADS, SDF_SCENE_MIN_WAVES) k_sdf_scene(F
     const v3 rd = normalize_ieee(F.cam.fwd + F.cam.up * pc.y + F.cam.right * pc.x);   // util.h:17
     v3 rgb;
     float t;
-    if (WIT != 0) {
-        Wit<true> w;
-        if (WIT == 2) w.lo = 0x3F800000u;
-        scene_pixel(F, R, ro, rd, w, rgb, t);
-        if (__builtin_amdgcn_ballot_w64(w.bad) != 0ull) {        // some lane left the fast root's compared domain: the IEEE roots
-            Wit<false> w0;
-            scene_pixel(F, R, ro, rd, w0, rgb, t);
-        }
-    } else {
-        Wit<false> w0;
-        scene_pixel(F, R, ro, rd, w0, rgb, t);
-    }
+    witnessed<WIT>(true, [&](auto& w) { scene_pixel(F, R, ro, rd, w, rgb, t); });
     // fog :287-311 (t is the march length at exit)
     const float fog_factor = F.fog_density * exp_(-ro.y * F.fog_falloff)
                            * (1.f - exp_(-t * rd.y * F.fog_falloff))
@@ -261,34 +250,23 @@ __global__ void __launch_bounds__(WG_THREADS) k_sdf_scene_eval(FrameSdfScene F, 
     if (i >= npoints) return;
     const v3 pos = V3(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
     D2 d;
-    if (WIT != 0) {
-        Wit<true> w;
-        if (WIT == 2) w.lo = 0x3F800000u;
-        d = scene_sdf(F, R, F.n_instr, pos, w);
-        if (__builtin_amdgcn_ballot_w64(w.bad) != 0ull) {
-            Wit<false> w0;
-            d = scene_sdf(F, R, F.n_instr, pos, w0);
-        }
-    } else {
-        Wit<false> w0;
-        d = scene_sdf(F, R, F.n_instr, pos, w0);
-    }
+    witnessed<WIT>(true, [&](auto& w) { d = scene_sdf(F, R, F.n_instr, pos, w); });
     out[2 * i] = d.d;
     out[2 * i + 1] = d.m;
 }
 
-// variant: 1 / 3 the IEEE roots, 2 the witness's test edge, else the witnessed roots (as launch_sdf_ao; there is nothing to cull)
+// variant: witness_dispatch's (there is nothing to cull: 1 and 3 are both the IEEE roots)
 void launch_sdf_scene(const FrameSdfScene& F, const RowMap& M, float* out, hipStream_t s, int variant) {
-    if (variant == 2) hipLaunchKernelGGL((k_sdf_scene<2>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else if (variant == 1 || variant == 3) hipLaunchKernelGGL((k_sdf_scene<0>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else hipLaunchKernelGGL((k_sdf_scene<SDF_SCENE_WITNESS>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    witness_dispatch<SDF_SCENE_WITNESS>(variant, [&](auto, auto wit) {
+        hipLaunchKernelGGL((k_sdf_scene<wit.value>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    });
 }
 
 void launch_sdf_scene_eval(const FrameSdfScene& F, const float* xyz, float* out, size_t n, hipStream_t s, int variant) {
     const dim3 grid((unsigned)((n + WG_THREADS - 1) / WG_THREADS));
-    if (variant == 2) hipLaunchKernelGGL((k_sdf_scene_eval<2>), grid, dim3(WG_THREADS), 0, s, F, xyz, out, n);
-    else if (variant == 1 || variant == 3) hipLaunchKernelGGL((k_sdf_scene_eval<0>), grid, dim3(WG_THREADS), 0, s, F, xyz, out, n);
-    else hipLaunchKernelGGL((k_sdf_scene_eval<SDF_SCENE_WITNESS>), grid, dim3(WG_THREADS), 0, s, F, xyz, out, n);
+    witness_dispatch<SDF_SCENE_WITNESS>(variant, [&](auto, auto wit) {
+        hipLaunchKernelGGL((k_sdf_scene_eval<wit.value>), grid, dim3(WG_THREADS), 0, s, F, xyz, out, n);
+    });
 }
 
 }  // namespace sbx

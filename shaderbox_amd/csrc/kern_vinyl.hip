@@ -18,7 +18,7 @@ namespace sbx {
 // spill nothing.
 constexpr int vinyl_min_waves(bool cull, int build) { return (!cull && build != VINYL_DEFAULT) ? 2 : VI_MIN_WAVES; }
 
-template <bool CULL, int WIT, int BUILD>      // WIT: 0 IEEE roots, 1 witnessed roots, 2 the witness's test edge (sbx_set_variant 2), as k_egg
+template <bool CULL, int WIT, int BUILD>      // WIT: sbx_witness.h `witnessed`
 __global__ void __launch_bounds__(WG_THREADS, vinyl_min_waves(CULL, BUILD)) k_vinyl(FrameVinyl F, RowMap M, float* __restrict__ out) {
     const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();      // (the dispatch order's cost table, RowMap.cost)
 #if VI_LDS_FRAME
@@ -33,18 +33,7 @@ __global__ void __launch_bounds__(WG_THREADS, vinyl_min_waves(CULL, BUILD)) k_vi
     if (!px.valid) return;
     const v2 pc = point_cam(F.cam, px.fx, px.fy);
     v3 color;
-    if (WIT != 0) {
-        Wit<true> w;
-        if (WIT == 2) w.lo = 0x3F800000u;
-        vinyl_pixel<CULL, BUILD>(F, VI_FS, ShadeLit{}, pc, w, color);
-        if (__builtin_amdgcn_ballot_w64(w.bad) != 0ull) {
-            Wit<false> w0;
-            vinyl_pixel<CULL, BUILD>(F, VI_FS, ShadeLit{}, pc, w0, color);
-        }
-    } else {
-        Wit<false> w0;
-        vinyl_pixel<CULL, BUILD>(F, VI_FS, ShadeLit{}, pc, w0, color);
-    }
+    witnessed<WIT>(true, [&](auto& w) { vinyl_pixel<CULL, BUILD>(F, VI_FS, ShadeLit{}, pc, w, color); });
     tile_cost_store(M, tl_t0);
     store_rgba(M, out, px.idx, to_srgb(color));
 }
@@ -53,10 +42,9 @@ dim3 vinyl_grid(const RowMap& M) { return grid_for(M); }
 
 template <int BUILD>
 static void launch_vinyl_build(const FrameVinyl& F, const RowMap& M, float* out, hipStream_t s, int variant) {
-    if (variant == 1) hipLaunchKernelGGL((k_vinyl<false, 0, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else if (variant == 2) hipLaunchKernelGGL((k_vinyl<true, 2, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else if (variant == 3) hipLaunchKernelGGL((k_vinyl<true, 0, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
-    else hipLaunchKernelGGL((k_vinyl<true, VI_WITNESS, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    witness_dispatch<VI_WITNESS>(variant, [&](auto cull, auto wit) {
+        hipLaunchKernelGGL((k_vinyl<cull.value, wit.value, BUILD>), grid_for(M), dim3(WG_THREADS), 0, s, F, M, out);
+    });
 }
 // build: VINYL_* (sbx_frame.h).  VINYL_CLOSEUP is a frame block (build_vinyl), not a kernel: the shipped instantiations run over it.
 void launch_vinyl(const FrameVinyl& F, const RowMap& M, float* out, hipStream_t s, int variant, int build) {
@@ -83,28 +71,16 @@ __global__ void __launch_bounds__(WG_THREADS, vinyl_min_waves(CULL, VINYL_DECK))
     const v2 pc = point_cam(F.cam, px.fx, px.fy);
     const ShadeDeck S{D};
     v3 color;
-    if (WIT != 0) {
-        Wit<true> w;
-        if (WIT == 2) w.lo = 0x3F800000u;
-        vinyl_pixel<CULL, VINYL_DECK>(F, VI_FS, S, pc, w, color);
-        if (__builtin_amdgcn_ballot_w64(w.bad) != 0ull) {
-            Wit<false> w0;
-            vinyl_pixel<CULL, VINYL_DECK>(F, VI_FS, S, pc, w0, color);
-        }
-    } else {
-        Wit<false> w0;
-        vinyl_pixel<CULL, VINYL_DECK>(F, VI_FS, S, pc, w0, color);
-    }
+    witnessed<WIT>(true, [&](auto& w) { vinyl_pixel<CULL, VINYL_DECK>(F, VI_FS, S, pc, w, color); });
     tile_cost_store(M, tl_t0);
     store_rgba(M, out, px.idx, to_srgb(color));
 }
 
 // variant as launch_vinyl's; the caller has already turned an untame deck into 1 (sbx_frames.hip vinyl_deck_tame)
 void launch_vinyl_deck(const FrameVinyl& F, const VinylShade& D, const RowMap& M, float* out, hipStream_t s, int variant) {
-    if (variant == 1) hipLaunchKernelGGL((k_vinyl_deck<false, 0>), grid_for(M), dim3(WG_THREADS), 0, s, F, D, M, out);
-    else if (variant == 2) hipLaunchKernelGGL((k_vinyl_deck<true, 2>), grid_for(M), dim3(WG_THREADS), 0, s, F, D, M, out);
-    else if (variant == 3) hipLaunchKernelGGL((k_vinyl_deck<true, 0>), grid_for(M), dim3(WG_THREADS), 0, s, F, D, M, out);
-    else hipLaunchKernelGGL((k_vinyl_deck<true, VI_WITNESS>), grid_for(M), dim3(WG_THREADS), 0, s, F, D, M, out);
+    witness_dispatch<VI_WITNESS>(variant, [&](auto cull, auto wit) {
+        hipLaunchKernelGGL((k_vinyl_deck<cull.value, wit.value>), grid_for(M), dim3(WG_THREADS), 0, s, F, D, M, out);
+    });
 }
 
 }  // namespace sbx

@@ -2,23 +2,18 @@
 // :251-259, sdf_normal :261-272, sdf_shadow :381-405, illuminate :287-379, render :407-458) over the caller's points and rays under the
 // caller's deck (include/sbx.h sbx_aux_vinyl_deck).  No camera, no u_res, no sRGB.
 //
-// k_vinyl_eval: one lane per element, one 64-lane wave per workgroup, a ragged last wave; a lane past n loads nothing, evaluates
-// element zeros harmlessly and stores nothing.  Everything runs on k_vinyl's device functions (sbx_vinyl.h) over the FrameVinyl that
-// build_vinyl_deck (sbx_frames.hip) makes of the block, and the VinylShade beside it.  The decisions:
-//   THE FORM OF A WAVE.  k_vinyl's culls and hardware min / max are proved for finite frame constants and finite points of bounded
-//     scale (sbx_vinyl.h, at the top).  The frame is the host's to judge: a deck that is not tame (vinyl_deck_tame, the camera's fields
-//     ignored) gets the PLAIN kernel (CULL = false, IEEE roots, compare-and-select unions: the reference's operations on whatever the
-//     values are), as does sbx_set_variant 1.  The elements are the wave's to judge: a NaN or inf coordinate makes primitives NaN as
-//     FIRST operands of the unions, where v_min_f32 and the spec's select differ, and makes a cull's comparison false where the member
-//     it skips would have been the union's NaN.  So a wave takes the culled form only if every committing lane's points and
-//     directions are within 1e4 per coordinate, NaN failing (`ve_within`): then a march point stays within 1e4 + 1e4 (40 + 4.1e5)
-//     < 4.2e9 and a shadow point of "render" within 4.2e9 + 1e4 (5 + 4.3e9) < 4.4e13 — t leaves the loops beyond 40 and 5, and one step
-//     adds at most the field's value, which is at most |point| + 10 — whose squares (2e27) are inside binary32.  Any other wave takes
-//     the plain form for all of its lanes.  Per wave, not per lane: one predicate, one branch, no divergent copies.
-//     The material id of "illuminate" is not a coordinate and is not tested: it only selects a branch and a colour.
-//   THE WITNESS RE-RUN is decided per wave by ballot, as in k_vinyl: a wave in which any lane took a root outside the proved interval
-//     evaluates again with the IEEE roots (still culled: the culls do not depend on the roots).  A point on a cylinder's axis or a
-//     sphere's centre records; sbx_debug_vinyl_eval counts both kinds of wave.
+// k_vinyl_eval: the element wave of sbx_witness.h (witnessed_elements: the form of a wave, the witness re-run, loads and stores) over
+// k_vinyl's device functions (sbx_vinyl.h), the FrameVinyl that build_vinyl_deck (sbx_frames.hip) makes of the block, and the
+// VinylShade beside it.  What is its own:
+//   THE BOUND'S REASONS.  k_vinyl's culls and hardware min / max are proved for finite frame constants and finite points of bounded
+//     scale (sbx_vinyl.h, at the top; vinyl_deck_tame, the camera's fields ignored, decides PLAIN, whose unions are compare-and-select).
+//     A NaN or inf coordinate makes primitives NaN as FIRST operands of the unions, where v_min_f32 and the spec's select differ, and
+//     makes a cull's comparison false where the member it skips would have been the union's NaN.  Within 1e4 per coordinate of points
+//     and directions a march point stays within 1e4 + 1e4 (40 + 4.1e5) < 4.2e9 and a shadow point of "render" within
+//     4.2e9 + 1e4 (5 + 4.3e9) < 4.4e13 — t leaves the loops beyond 40 and 5, and one step adds at most the field's value, which is at
+//     most |point| + 10 — whose squares (2e27) are inside binary32.  The material id of "illuminate" is not a coordinate and is not
+//     tested: it only selects a branch and a colour.  A point on a cylinder's axis or a sphere's centre records; sbx_debug_vinyl_eval
+//     counts both kinds of wave.
 //   THE FRAME BLOCK IN LDS, as k_vinyl (sbx_ldsframe.h): ~220 floats do not fit the SGPR file, an SGPR operand halves the VALU's issue
 //     rate on gfx950, and the volatile per-use loads keep nothing alive across the march.  The block is the kernel's first argument;
 //     the 19 words of the shading data are the second and stay scalar (read once per element, after the march).
@@ -28,9 +23,6 @@
 //   int() OF THE MATERIAL ID ("illuminate", as :439 does): toward zero, saturating, a NaN gives 0 (include/sbx.h) — what
 //     v_cvt_i32_f32 does, stated in C++ (`ve_int`) because the language leaves an out-of-range conversion undefined.
 //   THE WAVE BOUND: ve_min_waves below, chosen so that no default instantiation spills (tools/kernel_resources.py).
-//   LOADS AND STORES.  `in` and `out` need only 4-byte alignment, so an element is read and written as dwords: lane i reads
-//     in[W i + k], k < W.  A wave's W loads together cover 64 W contiguous floats — every cache line fetched is fully used — and at
-//     12-28 B per element against a 60-step march of a ~400-instruction field the traffic is noise.
 #include "sbx_vinyl.h"
 
 #ifndef VE_MIN_WAVES
@@ -40,8 +32,6 @@
 namespace sbx {
 
 enum { VE_SDF = 0, VE_NORMAL = 1, VE_SHADOW = 2, VE_ILLUMINATE = 3, VE_RENDER = 4 };
-
-__device__ __forceinline__ bool ve_within(float x) { return abs_(x) <= 1e4f; }     // a NaN compares false
 
 __device__ __forceinline__ int ve_int(float x) {
     if (x != x) return 0;
@@ -62,8 +52,8 @@ constexpr int ve_out_width(int fn) { return fn == VE_SDF ? 2 : fn == VE_SHADOW ?
 
 // one element of FN with sdf()'s CULL and the roots of witness `w`; q = its inputs, r = its outputs
 template <int FN, bool CULL, class W>
-__device__ __forceinline__ void ve_element(const FrameVinyl& F, const FrameVinyl& Fs, const VinylShade& D, const float (&q)[7], W& w,
-                                           float (&r)[5]) {
+__device__ __forceinline__ void ve_element(const FrameVinyl& F, const FrameVinyl& Fs, const VinylShade& D, const float (&q)[ELEM_WORDS],
+                                           W& w, float (&r)[ELEM_WORDS]) {
     const v3 a = V3(q[0], q[1], q[2]), b = V3(q[3], q[4], q[5]);
     const ShadeDeck S{D};
     if (FN == VE_SDF) {
@@ -92,62 +82,29 @@ __device__ __forceinline__ void ve_element(const FrameVinyl& F, const FrameVinyl
     }
 }
 
-// PLAIN: the reference form for every wave (an untame deck, sbx_set_variant 1).  WIT as k_vinyl: 0 IEEE roots, 1 witnessed roots, 2 the
-// witness's lower edge at 1.0 (sbx_set_variant 2).  counts: NULL or two zeroed words.
+// PLAIN, WIT, counts: sbx_witness.h witnessed_elements
 template <int FN, bool PLAIN, int WIT>
 __global__ void __launch_bounds__(64, ve_min_waves(FN, PLAIN)) k_vinyl_eval(FrameVinyl F, VinylShade D, const float* __restrict__ in,
                                                                           float* __restrict__ out, size_t n, unsigned* __restrict__ counts) {
-    constexpr int WIN = ve_in_width(FN), WOUT = ve_out_width(FN);
+    constexpr int WIN = ve_in_width(FN);
     constexpr int WPOS = FN == VE_ILLUMINATE ? 6 : WIN;            // the inputs that are coordinates
     __shared__ FrameVinyl Fs;
     lds_frame_fill<FrameVinyl, 64>(Fs);
-    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
-    const bool on = i < n;
-    float q[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (on) {
-#pragma unroll
-        for (int k = 0; k < WIN; ++k) q[k] = in[(size_t)WIN * i + k];
-    }
-    float r[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    bool tame = true;
-#pragma unroll
-    for (int k = 0; k < WPOS; ++k) tame = tame && ve_within(q[k]);
-    const bool culled = !PLAIN && __builtin_amdgcn_ballot_w64(on && !tame) == 0ull;      // wave-uniform
-    bool rerun = false;
-    if (culled) {
-        if (WIT != 0) {
-            Wit<true> w;
-            if (WIT == 2) w.lo = 0x3F800000u;
-            ve_element<FN, true>(F, Fs, D, q, w, r);
-            rerun = __builtin_amdgcn_ballot_w64(on && w.bad) != 0ull;
-        }
-        if (WIT == 0 || rerun) {
-            Wit<false> w0;
-            ve_element<FN, true>(F, Fs, D, q, w0, r);
-        }
-    } else {
-        Wit<false> w0;
-        ve_element<FN, false>(F, Fs, D, q, w0, r);
-    }
-    if (on) {
-#pragma unroll
-        for (int k = 0; k < WOUT; ++k) out[(size_t)WOUT * i + k] = r[k];
-    }
-    if (counts && (threadIdx.x & 63) == 0 && culled && WIT != 0) atomicAdd(counts + (rerun ? 1 : 0), 1u);
+    witnessed_elements<WIN, WPOS, ve_out_width(FN), PLAIN, WIT>(in, out, n, counts,
+        [&](auto cull, const auto& q, auto& w, auto& r) { ve_element<FN, cull.value>(F, Fs, D, q, w, r); });
 }
 
 template <int FN>
 static void ve_launch(const FrameVinyl& F, const VinylShade& D, int variant, const float* in, float* out, size_t n, unsigned* counts,
                       hipStream_t s) {
     const dim3 grid((unsigned)((n + 63) / 64));
-    if (variant == 1) hipLaunchKernelGGL((k_vinyl_eval<FN, true, 0>), grid, dim3(64), 0, s, F, D, in, out, n, counts);
-    else if (variant == 2) hipLaunchKernelGGL((k_vinyl_eval<FN, false, 2>), grid, dim3(64), 0, s, F, D, in, out, n, counts);
-    else if (variant == 3) hipLaunchKernelGGL((k_vinyl_eval<FN, false, 0>), grid, dim3(64), 0, s, F, D, in, out, n, counts);
-    else hipLaunchKernelGGL((k_vinyl_eval<FN, false, 1>), grid, dim3(64), 0, s, F, D, in, out, n, counts);
+    witness_dispatch<1>(variant, [&](auto cull, auto wit) {
+        hipLaunchKernelGGL((k_vinyl_eval<FN, !cull.value, wit.value>), grid, dim3(64), 0, s, F, D, in, out, n, counts);
+    });
 }
 
 // fn: VE_* in the order of sbx_eval.hip's names.  F, D: build_vinyl_deck / vinyl_shade_of the caller's block (F's camera is not read).
-// variant: 0 default, 1 plain, 2 the witness's test edge, 3 IEEE roots (as launch_vinyl).  n in 1 ... 2^31.
+// variant: witness_dispatch's.  n in 1 ... 2^31.
 void launch_vinyl_eval(int fn, const FrameVinyl& F, const VinylShade& D, int variant, const float* in, float* out, size_t n,
                        unsigned* counts, hipStream_t s) {
     switch (fn) {

@@ -240,7 +240,7 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     int rc = SBX_OK;
     ctx->stats.launches.fetch_add(1, std::memory_order_relaxed);
     const int cull_variant = tame_time(uni->u_time) ? ctx->variant : 1;
-    const int sdf_variant = cull_variant == 1 ? 1 : ctx->sdf_roots;      // EGG / SDF_AO / VINYL: 2 / 3 = the witness's test build / IEEE roots
+    const int sdf_variant = witness_variant(ctx, tame_time(uni->u_time));   // EGG / SDF_AO / VINYL and their builds
     // The dispatch order of this launch (TileOrder): the tiles by the cost earlier frames of this app and shape measured, longest
     // first.  For the kernels it was measured to help (profiles/r06_tile_order.txt: CLOUDS 4K 2.41 -> 2.23 ms, CLOUDS_SKY 5.14 ->
     // 4.91, VINYL 1.25 -> 1.19, VINYL_GPU 1.24 -> 1.14, and APP_EGG 1920x1080 0.205 -> 0.134 ms back to back — its launch drags a tail
@@ -285,17 +285,17 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
         const bool tame = egg_pose_tame(EP, F);
         ctx->stats.egg_pose_launches.fetch_add(1, std::memory_order_relaxed);
         if (!tame) ctx->stats.egg_pose_untame.fetch_add(1, std::memory_order_relaxed);
-        launch_egg(F, M, rgba, s, tame ? sdf_variant : 1, EGG_DEFAULT);
+        launch_egg(F, M, rgba, s, witness_variant(ctx, tame && tame_time(uni->u_time)), EGG_DEFAULT);   // (u_time as for APP_EGG)
         break;
     }
-    case SBX_APP_RAYTRACER: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots); break;
+    case SBX_APP_RAYTRACER: launch_raytracer(build_raytracer(*uni), M, rgba, s, witness_variant(ctx)); break;
     // the builds of app_raytracer.h's three switches (include/sbx.h): two kernel builds over the shipped frame, one frame of its own
-    case SBX_APP_RAYTRACER_PHONG: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots, RT_PHONG); break;
-    case SBX_APP_RAYTRACER_NOSHADOW: launch_raytracer(build_raytracer(*uni), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots, RT_NOSHADOW); break;
-    case SBX_APP_RAYTRACER_STATIC: launch_raytracer(build_raytracer(*uni, RT_STATIC), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots, RT_STATIC); break;
+    case SBX_APP_RAYTRACER_PHONG: launch_raytracer(build_raytracer(*uni), M, rgba, s, witness_variant(ctx), RT_PHONG); break;
+    case SBX_APP_RAYTRACER_NOSHADOW: launch_raytracer(build_raytracer(*uni), M, rgba, s, witness_variant(ctx), RT_NOSHADOW); break;
+    case SBX_APP_RAYTRACER_STATIC: launch_raytracer(build_raytracer(*uni, RT_STATIC), M, rgba, s, witness_variant(ctx), RT_STATIC); break;
     // the caller's scene (validated above), always through its own kernel: a block equal to the Cornell box is no special case
     case SBX_APP_RAYTRACER_SCENE:
-        launch_raytracer_scene(build_raytracer_scene(*uni, RS), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots);
+        launch_raytracer_scene(build_raytracer_scene(*uni, RS), M, rgba, s, witness_variant(ctx));
         ctx->stats.rt_scene_launches.fetch_add(1, std::memory_order_relaxed);
         break;
     case SBX_APP_ATMOSPHERE: launch_atmosphere(build_atmosphere(*uni), M, rgba, s, ctx->precision); break;
@@ -318,7 +318,7 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     case SBX_APP_SDF_AO_SHADOW: launch_sdf_ao(build_sdf_ao(*uni, aux_sdf_ao(aux)), M, rgba, s, sdf_variant, 1); break;
     case SBX_APP_SDF_AO_NORMALS: launch_sdf_ao(build_sdf_ao(*uni, aux_sdf_ao(aux)), M, rgba, s, sdf_variant, 2); break;
     // the caller's field (validated above) through app_sdf_ao.h's renderer
-    case SBX_APP_SDF_SCENE: launch_sdf_scene(build_sdf_scene(*uni, SS), M, rgba, s, ctx->variant == 1 ? 1 : ctx->sdf_roots); break;
+    case SBX_APP_SDF_SCENE: launch_sdf_scene(build_sdf_scene(*uni, SS), M, rgba, s, witness_variant(ctx)); break;
     case SBX_APP_PLANET: launch_planet(build_planet(*uni), M, rgba, s, cull_variant); break;
     case SBX_APP_PLANET_ATMOSPHERE: launch_planet(build_planet(*uni, true), M, rgba, s, cull_variant); break;
     // the builds of app_planet.h's three switches (include/sbx.h): kernel builds over the shipped frame, CLOSEUP over a frame of its own
@@ -339,7 +339,7 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
         const bool tame = vinyl_deck_tame(VD, F);
         ctx->stats.vinyl_deck_launches.fetch_add(1, std::memory_order_relaxed);
         if (!tame) ctx->stats.vinyl_deck_untame.fetch_add(1, std::memory_order_relaxed);
-        launch_vinyl_deck(F, vinyl_shade_of(VD), M, rgba, s, !tame || ctx->variant == 1 ? 1 : ctx->sdf_roots);
+        launch_vinyl_deck(F, vinyl_shade_of(VD), M, rgba, s, witness_variant(ctx, tame));
         break;
     }
     case SBX_APP_CLOUDS_BEST: launch_clouds_best(build_clouds_best(*uni), M, rgba, s); break;

@@ -193,6 +193,11 @@ struct sbx_ctx {
 
 namespace sbx {
 
+// The variant an SDF or raytracer launch takes (sbx_witness.h witness_dispatch has the table): 1, the reference form, if
+// sbx_set_variant chose it or the caller found the frame outside the domain of the kernel's culls (`tame` false: u_time, a pose,
+// a deck); else sbx_set_variant's 2 / 3, else 0.  A launch with nothing to judge passes no `tame`.
+inline int witness_variant(const sbx_ctx* ctx, bool tame = true) { return ctx->variant == 1 || !tame ? 1 : ctx->sdf_roots; }
+
 // exported since the store exchange (sbx_shared.hip) was a translation unit of its own
 unsigned* fault_word_device(int device);   // the device's sticky fault word, as a device pointer (sbx_capi.hip)
 int ctx_device(const sbx_ctx* ctx);

@@ -152,7 +152,7 @@ auto egg_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_egg_pose* pose, c
         sbx_aux_egg_pose A = *pose;
         A.eye[0] = 0.f; A.eye[1] = .25f; A.eye[2] = 5.25f; A.look_at[0] = 0.f; A.look_at[1] = .25f; A.look_at[2] = 0.f; A.fov = 1.f;
         const FrameEggStraight F = build_egg_pose(frame_1x1(0.f), A, EGG_DEFAULT);
-        const int variant = ctx->variant == 1 || !egg_pose_tame(A, F) ? 1 : ctx->sdf_roots;
+        const int variant = witness_variant(ctx, egg_pose_tame(A, F));
         launch_egg_eval(id - 1, F, variant, in, out, n, counts, s);
     };
 }
@@ -170,7 +170,7 @@ auto vinyl_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_vinyl_deck* dec
         sbx_aux_vinyl_deck A = *deck;
         A.eye[0] = 0.f; A.eye[1] = 5.75f; A.eye[2] = 6.75f; A.look_at[0] = 0.f; A.look_at[1] = -2.5f; A.look_at[2] = 0.f; A.fov = 1.f;
         const FrameVinyl F = build_vinyl_deck(frame_1x1(0.f), A, 60);
-        const int variant = ctx->variant == 1 || !vinyl_deck_tame(A, F) ? 1 : ctx->sdf_roots;
+        const int variant = witness_variant(ctx, vinyl_deck_tame(A, F));
         launch_vinyl_eval(id, F, vinyl_shade_of(A), variant, in, out, n, counts, s);
     };
 }
@@ -267,7 +267,7 @@ int sbx_sdf_eval(sbx_ctx* ctx, const sbx_aux_sdf_scene* scene, const float* xyz,
         sbx_sdf_scene_ramp(&U, &A);
         A.n_instr = scene->n_instr;
         std::memcpy(A.program, scene->program, sizeof(A.program));
-        launch_sdf_scene_eval(build_sdf_scene(U, A), xyz, out, n, s, ctx->variant == 1 ? 1 : ctx->sdf_roots);
+        launch_sdf_scene_eval(build_sdf_scene(U, A), xyz, out, n, s, witness_variant(ctx));
     });
 }
 

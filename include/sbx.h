@@ -35,7 +35,7 @@ extern "C" {
 
 /* Bumped whenever an entry point, enum value or struct layout of this header changes (2 = round 5: the store exchange
  * sbx_shared_*, sbx_stats, sbx_abi_version itself; the test hooks moved to sbx_test.h).  Not bumped for SBX_APP_2D / SBX_APP_2D_TEX,
- * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell, SBX_APP_SDF_SCENE with sbx_aux_sdf_scene, sbx_sdf_scene_ramp and sbx_sdf_eval, sbx_clouds_eval, sbx_planet_eval, SBX_APP_EGG_POSE with sbx_aux_egg_pose and sbx_egg_pose_default, sbx_egg_eval, SBX_APP_VINYL_DECK with sbx_aux_vinyl_deck and sbx_vinyl_deck_default, sbx_vinyl_eval, SBX_APP_ATMOSPHERE_AIR with sbx_aux_atmosphere_air and sbx_atmosphere_air_default, sbx_atmosphere_air_eval: new enum values after the old ones,
+ * sbx_set_texture2d, sbx_checkerboard_texture, SBX_APP_FUNC, SBX_APP_ATMOSPHERE_GROUND, SBX_APP_SDF_AO_SHADOW, SBX_APP_SDF_AO_NORMALS, SBX_APP_EGG_STRAIGHT, SBX_APP_EGG_OVAL, SBX_APP_CLOUDS_HEIGHT, SBX_APP_CLOUDS_LUMINANCE, SBX_APP_RAYTRACER_PHONG, SBX_APP_RAYTRACER_NOSHADOW, SBX_APP_RAYTRACER_STATIC, SBX_APP_VINYL_CLOSEUP, SBX_APP_VINYL_RIDGES, SBX_APP_VINYL_NOSHADOW, SBX_APP_PLANET_CLOSEUP, SBX_APP_PLANET_CLOUDLESS, SBX_APP_PLANET_UNLIT, sbx_noise_eval's "worley_fbm", sbx_atmosphere_eval, SBX_APP_RAYTRACER_SCENE with sbx_aux_raytracer_scene and sbx_raytracer_scene_cornell, SBX_APP_SDF_SCENE with sbx_aux_sdf_scene, sbx_sdf_scene_ramp and sbx_sdf_eval, sbx_clouds_eval, sbx_planet_eval, SBX_APP_EGG_POSE with sbx_aux_egg_pose and sbx_egg_pose_default, sbx_egg_eval, SBX_APP_VINYL_DECK with sbx_aux_vinyl_deck and sbx_vinyl_deck_default, sbx_vinyl_eval, SBX_APP_ATMOSPHERE_AIR with sbx_aux_atmosphere_air and sbx_atmosphere_air_default, sbx_atmosphere_air_eval, sbx_raytracer_eval: new enum values after the old ones,
  * new entry points and names only, no value renumbered and no layout changed, so a host built against version 2 without them works unchanged.  A host checks
  * sbx_abi_version() == SBX_ABI_VERSION after loading the library: include/sbx_mainimage.hpp and shaderbox_amd.load_library do. */
 #define SBX_ABI_VERSION 2
@@ -885,6 +885,33 @@ int sbx_egg_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, con
  * for nothing); not counted in sbx_stats.render_launches; sbx_set_variant 1 selects the plain statement (same bits).  n == 0 returns
  * SBX_OK and touches nothing; SBX_ERR_ARG, with nothing written, for a NULL ctx / fn / deck / in / out, an unknown name, n > 2^31. */
 int sbx_vinyl_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck* deck, const float* in, float* out, size_t n, void* stream);
+/* The raytracer's trace, shading, shadow test and render (src/app_raytracer.h over src/intersect.h, src/light.h, src/util_optics.h) as
+ * standalone functions over n elements of the caller's, under the caller's scene: what SBX_APP_RAYTRACER_SCENE reaches only through
+ * its pinhole camera and into sRGB pixels — for rays of another lens, a probe grid, the secondary rays of a host's own integrator, a
+ * picking ray.  `scene`: HOST memory, read during the call, required and range-checked as the app checks it (counts 0..16, bounces 1..8,
+ * light_type 1 | 2, lighting 0 | 1, shadow 0 | 1) whatever n is; its eye, look_at and fov are not read.  `in`, `out`: device memory, not
+ * overlapping, 4-byte alignment suffices.  Per element:
+ *   "raytrace_iteration" (:70-86)  in 7: origin xyz, direction xyz, mat_to_ignore as a float (-1: none).  out 8: hit.t, the hit's
+ *                                  material id as a float, hit.origin xyz, hit.normal xyz; a miss is no_hit of def.h: t =
+ *                                  (float)(1e8 + 1e1), material -1, zeros.  Planes are taken in array order and never skipped; a
+ *                                  sphere whose material equals mat_to_ignore is.
+ *   "illuminate" (:46-68)          in 10: eye xyz, hit.origin xyz, hit.normal xyz, the material id as a float.  out 3: the colour
+ *                                  under the block's lighting model, light type and ambient colour; material 0 gives the flat
+ *                                  mat_debug colour, an id outside 0..7 the zero material.
+ *   "shadow" (:109-116)            in 3: hit.origin.  out 2: shadow_hit.t of the ray from hit.origin + shadow_dir * BIAS with
+ *                                  mat_debug ignored, then length(shadow_line); shadow_line = lights[0].L - hit.origin also under
+ *                                  LIGHT_DIR, as in the reference.  It runs whatever the block's `shadow` says (the switch is
+ *                                  "render"'s); render darkens the pixel where out[0] < out[1].
+ *   "render" (:88-136)             in 6: origin xyz, direction xyz.  out 4: the LINEAR rgb (no sRGB) over the block's bounce count,
+ *                                  shadow switch and lighting, the ray's own origin being the primary origin of :105; then the
+ *                                  depth, the number of bounce-loop traces that found a hit, as a float (0: the background).
+ * intersect_plane and intersect_sphere on their own are "raytrace_iteration" over a block with one primitive: they have no entry.
+ * int() of a material id or mat_to_ignore is taken as for sbx_vinyl_eval — toward zero, saturating at the ends of int, 0 for a NaN.
+ * Directions are used as given, never normalised.  Exact for every bit pattern, NaN results included.  Asynchronous on `stream` and
+ * capturable (one kernel launch and nothing else); not counted in sbx_stats.render_launches; sbx_set_variant 1 selects the IEEE roots
+ * (same bits).  n == 0 returns SBX_OK with `in` and `out` not looked at; SBX_ERR_ARG, with nothing written, for a NULL ctx / fn /
+ * scene / in / out, a scene outside the ranges above (the app's texts), an unknown name, n > 2^31. */
+int sbx_raytracer_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_raytracer_scene* scene, const float* in, float* out, size_t n, void* stream);
 /* The size^3 RGBA32F noise volume util/ddsvolgen bakes (ddsvolgen.cpp:101-117): R =
  * fbm_worley_tile((xyz + .5)/size, 2, 1, .5), G = B = A = 0, x fastest.  `rgba`: size^3 * 4 floats. */
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream);

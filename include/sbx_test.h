@@ -52,6 +52,8 @@ extern "C" {
  * compare-and-select unions for every wave; 2 / 3 = the witness's test edge / the IEEE roots; 0 takes the plain form only for such a deck
  * (the camera's fields ignored) and for the waves whose own points or directions hold a value beyond 1e4 or a NaN
  * (csrc/kern_vinyl_eval.hip).
+ * sbx_raytracer_eval: 1 and 3 = the IEEE roots for every wave, 2 = the witness's test edge, 0 the witnessed roots; no block and no
+ * element changes a wave's form (csrc/kern_raytracer_eval.hip).
  * SBX_APP_ATMOSPHERE_AIR and sbx_atmosphere_air_eval: 1 = the plain statement for every wave, whatever the block; every other value
  * leaves the tier to the block (csrc/sbx_frames.hip atmosphere_air_tier).
  * All variants are specified to produce identical bits (tests/test_gpu_parity.py sweeps them against each other). */
@@ -93,6 +95,13 @@ int sbx_debug_egg_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pos
  * neither.  It allocates and synchronises, so it is not capturable.  For tests/test_gpu_vinyl_eval.py and tools/time_vinyl_eval.py. */
 int sbx_debug_vinyl_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck* deck, const float* in, float* out, size_t n,
                          unsigned counts_host[2], void* stream);
+/* sbx_raytracer_eval (sbx.h) with counts: the same launch (the context's variant included) followed by a wait, after which
+ * counts_host[0] holds the waves that took the witnessed roots only and counts_host[1] the waves that re-ran with the IEEE roots because
+ * a lane recorded an argument outside the witness's interval.  No wave's form depends on its elements or on the block, so under
+ * variants 0 and 2 the two add up to the waves of the launch; under 1 and 3 (the IEEE roots) both are 0.  It allocates and synchronises,
+ * so it is not capturable.  For tests/test_gpu_raytracer_eval.py and tools/time_raytracer_eval.py. */
+int sbx_debug_raytracer_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_raytracer_scene* scene, const float* in, float* out, size_t n,
+                             unsigned counts_host[2], void* stream);
 /* sbx_atmosphere_air_eval (sbx.h) with a count: the same launch (the context's variant included) followed by a wait, after which
  * *fast_waves_host holds the waves that took the fast body (csrc/sbx_atmosphere.h "CALLER'S AIR"): 0 under an untame block or
  * sbx_set_variant 1.  It allocates and synchronises, so it is not capturable. */

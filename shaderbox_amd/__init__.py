@@ -396,6 +396,8 @@ def load_library(path=None):
     lib.sbx_vinyl_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(VinylDeck), fp, fp, ctypes.c_size_t, vp]
     lib.sbx_debug_vinyl_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(VinylDeck), fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
     lib.sbx_debug_vinyl_deck_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    lib.sbx_raytracer_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(RaytracerScene), fp, fp, ctypes.c_size_t, vp]
+    lib.sbx_debug_raytracer_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(RaytracerScene), fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
     lib.sbx_debug_egg_pose_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.sbx_debug_raytracer_scene_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.sbx_create.argtypes = [ci, ctypes.POINTER(vp)]
@@ -1155,6 +1157,7 @@ class Renderer:
         "egg": {"ik_solver": (8, 3), "sdf": (3, 2), "sdf_normal": (3, 3), "shadowmarch": (6, 1), "render_scene": (6, 4)},
         "vinyl": {"sdf": (3, 2), "sdf_normal": (3, 3), "sdf_shadow": (6, 1), "illuminate": (7, 3), "render": (6, 5)},
         "sdf": {"sdf": (3, 2)},
+        "raytracer": {"raytrace_iteration": (7, 8), "illuminate": (10, 3), "shadow": (3, 2), "render": (6, 4)},
     }
     CLOUDS_EVAL_WIDTHS, PLANET_EVAL_WIDTHS = EVAL_WIDTHS["clouds"], EVAL_WIDTHS["planet"]
     EGG_EVAL_WIDTHS, VINYL_EVAL_WIDTHS = EVAL_WIDTHS["egg"], EVAL_WIDTHS["vinyl"]
@@ -1261,6 +1264,20 @@ class Renderer:
         that re-ran with the IEEE roots))"""
         counts = (ctypes.c_uint * 2)(0, 0)
         return self._eval("vinyl", fn, x, (self._by_ref(deck),), counts), (int(counts[0]), int(counts[1]))
+
+    def raytracer_eval(self, fn, x, scene):
+        """src/app_raytracer.h's trace, shading, shadow test and render over the caller's elements under a RaytracerScene (include/sbx.h
+        sbx_raytracer_eval): fn 'raytrace_iteration' over x[n, 7] (origin xyz, direction xyz, mat_to_ignore) -> [n, 8] (hit.t, material
+        id, hit.origin xyz, hit.normal xyz); 'illuminate' over x[n, 10] (eye xyz, hit.origin xyz, hit.normal xyz, material id) ->
+        [n, 3]; 'shadow' over hit origins x[n, 3] -> [n, 2] (shadow_hit.t, length(shadow_line)); 'render' over rays x[n, 6] -> [n, 4]
+        (linear rgb, depth).  The scene's eye, look_at and fov are not read."""
+        return self._eval("raytracer", fn, x, (self._by_ref(scene),))
+
+    def raytracer_eval_counted(self, fn, x, scene):
+        """include/sbx_test.h sbx_debug_raytracer_eval: raytracer_eval that waits -> (out, (waves that took the witnessed roots only,
+        waves that re-ran with the IEEE roots))"""
+        counts = (ctypes.c_uint * 2)(0, 0)
+        return self._eval("raytracer", fn, x, (self._by_ref(scene),), counts), (int(counts[0]), int(counts[1]))
 
     def sdf_eval(self, scene, xyz):
         """sdf(pos) of an SdfScene's program over points xyz[n, 3] (include/sbx.h sbx_sdf_eval) -> [n, 2]: the distance and the

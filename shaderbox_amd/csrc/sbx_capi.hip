@@ -198,12 +198,7 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     sbx_aux_raytracer_scene RS;
     if (T.aux == AUX_RT_SCENE) {
         RS = aux_raytracer_scene(aux, *uni);
-        if (RS.n_planes < 0 || RS.n_planes > SBX_RT_MAX_PLANES || RS.n_spheres < 0 || RS.n_spheres > SBX_RT_MAX_SPHERES)
-            return fail(ctx, SBX_ERR_ARG, "raytracer scene: n_planes and n_spheres must lie in 0..16");
-        if (RS.bounces < 1 || RS.bounces > 8) return fail(ctx, SBX_ERR_ARG, "raytracer scene: bounces must lie in 1..8");
-        if (RS.light_type != 1 && RS.light_type != 2) return fail(ctx, SBX_ERR_ARG, "raytracer scene: light_type must be 1 (LIGHT_POINT) or 2 (LIGHT_DIR)");
-        if (RS.lighting != 0 && RS.lighting != 1) return fail(ctx, SBX_ERR_ARG, "raytracer scene: lighting must be 0 (Cook-Torrance) or 1 (Phong)");
-        if (RS.shadow != 0 && RS.shadow != 1) return fail(ctx, SBX_ERR_ARG, "raytracer scene: shadow must be 0 or 1");
+        if (const char* why = raytracer_scene_check(RS)) return fail(ctx, SBX_ERR_ARG, why);
     }
     sbx_aux_sdf_scene SS;
     if (T.aux == AUX_SDF_SCENE) {

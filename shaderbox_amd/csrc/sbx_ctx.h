@@ -224,7 +224,10 @@ FrameEggStraight build_egg(const sbx_uniforms& U, int build = EGG_DEFAULT);   //
 FrameEggStraight build_egg_pose(const sbx_uniforms& U, const sbx_aux_egg_pose& A, int build = EGG_DEFAULT);
 bool egg_pose_tame(const sbx_aux_egg_pose& A, const FrameEgg& F);
 FrameRaytracer build_raytracer(const sbx_uniforms& U, int build = RT_DEFAULT);   // build: RT_* (sbx_frame.h); RT_STATIC is the scene at rest
-FrameRtScene build_raytracer_scene(const sbx_uniforms& U, const sbx_aux_raytracer_scene& A);   // SBX_APP_RAYTRACER_SCENE: a validated block
+// SBX_APP_RAYTRACER_SCENE / sbx_raytracer_eval: NULL if the block passes the range checks of include/sbx.h, else what is wrong;
+// build_raytracer_scene takes a block that passed
+const char* raytracer_scene_check(const sbx_aux_raytracer_scene& A);
+FrameRtScene build_raytracer_scene(const sbx_uniforms& U, const sbx_aux_raytracer_scene& A);
 // SBX_APP_SDF_SCENE / sbx_sdf_eval: NULL if the block passes the checks of include/sbx.h, else what is wrong (program_only: n_instr and
 // the program alone, what sbx_sdf_eval reads); build_sdf_scene takes a block that passed
 const char* sdf_scene_check(const sbx_aux_sdf_scene& A, bool program_only);

@@ -179,6 +179,9 @@ void launch_tex3d_eval(int size, const float* rgba, const float* xyz, float* out
 void launch_egg(const FrameEggStraight& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = EGG_DEFAULT);   // build: EGG_* (sbx_frame.h), the one F was built for
 void launch_raytracer(const FrameRaytracer& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = RT_DEFAULT);   // build: RT_* (sbx_frame.h)
 void launch_raytracer_scene(const FrameRtScene& F, const RowMap& M, float* out, hipStream_t s, int variant);   // SBX_APP_RAYTRACER_SCENE (kern_raytracer.hip)
+// sbx_raytracer_eval (kern_raytracer_eval.hip k_raytracer_eval): fn 0 raytrace_iteration, 1 illuminate, 2 shadow, 3 render; variant:
+// witness_dispatch's; counts: NULL, or two zeroed words (waves that took the witnessed roots only, waves that re-ran)
+void launch_raytracer_eval(int fn, const FrameRtScene& F, int variant, const float* in, float* out, size_t n, unsigned* counts, hipStream_t s);
 // fin_ok = false: the caller has found the frame outside the domain of the FIN forms (SBX_APP_ATMOSPHERE_AIR's literal tier: a sun the
 // written arguments do not admit, sbx_atmosphere.h "CALLER'S AIR"); the plain kernel then runs whatever else holds
 void launch_atmosphere(const FrameAtmosphere& F, const RowMap& M, float* out, hipStream_t s, int precision = 0, bool fin_ok = true);

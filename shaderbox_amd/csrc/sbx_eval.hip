@@ -1,6 +1,6 @@
 // shaderbox_amd/csrc/sbx_eval.hip — the hooks that evaluate one piece of the math spec or of a kernel on the device for the tests
 // (include/sbx_test.h), the eval entries ("a function of an app over the caller's elements": sbx_atmosphere_eval, sbx_atmosphere_air_eval,
-// sbx_sdf_eval, sbx_clouds_eval, sbx_planet_eval, sbx_egg_eval, sbx_vinyl_eval of include/sbx.h, six of them with a counted twin in
+// sbx_sdf_eval, sbx_clouds_eval, sbx_planet_eval, sbx_egg_eval, sbx_vinyl_eval, sbx_raytracer_eval of include/sbx.h, seven of them with a counted twin in
 // include/sbx_test.h), and the binding of what the textured apps sample: t0 of APP_2D_TEX, the noise volumes of APP_CLOUDS_TEX.
 // The eval entries share one argument check (eval_args), one plain launch and one counted launch; a new one brings its name list, its
 // `*_eval_args` with whatever check is its own, and its `*_eval_launch` closure, all in the section below.
@@ -175,6 +175,23 @@ auto vinyl_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_vinyl_deck* dec
     };
 }
 
+// id = launch_raytracer_eval's fn; the scene is required and range-checked (the app's checks, the app's texts) whatever n is
+int raytracer_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_raytracer_scene* scene, const float* in, const float* out, size_t n, int& id) {
+    static const char* const names[] = {"raytrace_iteration", "illuminate", "shadow", "render"};
+    id = name_id(fn, names);
+    return eval_args(ctx, fn, id, "unknown raytracer function", !scene ? "NULL argument" : raytracer_scene_check(*scene), "more than 2^31 elements", in,
+                     out, n);
+}
+// the frame of the block with the shipped camera in place of the block's (the kernel reads no camera).  No host judgement of the block:
+// no shortcut of the kernel has a domain (kern_raytracer_eval.hip, at the top), so the variant is the context's own
+auto raytracer_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_raytracer_scene* scene, const float* in, float* out, size_t n) {
+    return [=](unsigned* counts, hipStream_t s) {
+        sbx_aux_raytracer_scene A = *scene;
+        A.eye[0] = 0.f; A.eye[1] = 2.f; A.eye[2] = 4.666f; A.look_at[0] = 0.f; A.look_at[1] = 2.f; A.look_at[2] = 0.f; A.fov = 1.f;
+        launch_raytracer_eval(id, build_raytracer_scene(frame_1x1(0.f), A), witness_variant(ctx), in, out, n, counts, s);
+    };
+}
+
 }  // namespace
 
 extern "C" {
@@ -332,6 +349,21 @@ int sbx_debug_vinyl_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck*
     const int rc = vinyl_eval_args(ctx, fn, deck, in, out, n, id);
     if (rc != SBX_OK) return rc;
     return counted_launch<unsigned, 2>(ctx, "vinyl_eval (counted)", n, counts_host, stream, vinyl_eval_launch(ctx, id, deck, in, out, n));
+}
+
+int sbx_raytracer_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_raytracer_scene* scene, const float* in, float* out, size_t n, void* stream) {
+    int id = -1;
+    const int rc = raytracer_eval_args(ctx, fn, scene, in, out, n, id);
+    if (rc != SBX_OK || n == 0) return rc;
+    return plain_launch(ctx, "raytracer_eval launch", stream, raytracer_eval_launch(ctx, id, scene, in, out, n));
+}
+
+int sbx_debug_raytracer_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_raytracer_scene* scene, const float* in, float* out, size_t n,
+                             unsigned counts_host[2], void* stream) {
+    int id = -1;
+    const int rc = raytracer_eval_args(ctx, fn, scene, in, out, n, id);
+    if (rc != SBX_OK) return rc;
+    return counted_launch<unsigned, 2>(ctx, "raytracer_eval (counted)", n, counts_host, stream, raytracer_eval_launch(ctx, id, scene, in, out, n));
 }
 
 int sbx_worley_volume(sbx_ctx* ctx, int size, float* rgba, void* stream) {

@@ -267,8 +267,19 @@ FrameRaytracer build_raytracer(const sbx_uniforms& U, int build) {
     return F;
 }
 
-// SBX_APP_RAYTRACER_SCENE: the caller's block (validated by render_mapped: the counts are within the arrays) as the kernel reads it.
-// The slots past the counts are copied as they are; the kernel never reads them.
+// the range checks of a caller's scene, the app's and sbx_raytracer_eval's: the counts are within the arrays, the switches are switches
+const char* raytracer_scene_check(const sbx_aux_raytracer_scene& A) {
+    if (A.n_planes < 0 || A.n_planes > SBX_RT_MAX_PLANES || A.n_spheres < 0 || A.n_spheres > SBX_RT_MAX_SPHERES)
+        return "raytracer scene: n_planes and n_spheres must lie in 0..16";
+    if (A.bounces < 1 || A.bounces > 8) return "raytracer scene: bounces must lie in 1..8";
+    if (A.light_type != 1 && A.light_type != 2) return "raytracer scene: light_type must be 1 (LIGHT_POINT) or 2 (LIGHT_DIR)";
+    if (A.lighting != 0 && A.lighting != 1) return "raytracer scene: lighting must be 0 (Cook-Torrance) or 1 (Phong)";
+    if (A.shadow != 0 && A.shadow != 1) return "raytracer scene: shadow must be 0 or 1";
+    return nullptr;
+}
+
+// SBX_APP_RAYTRACER_SCENE / sbx_raytracer_eval: the caller's block (one that passed raytracer_scene_check) as the kernels read it.
+// The slots past the counts are copied as they are; the kernels never read them.
 FrameRtScene build_raytracer_scene(const sbx_uniforms& U, const sbx_aux_raytracer_scene& A) {
     FrameRtScene F;
     F.cam = make_camera(U.u_res[0], U.u_res[1], A.fov, v3_of(A.eye), v3_of(A.look_at));

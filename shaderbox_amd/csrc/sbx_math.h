@@ -70,7 +70,7 @@ SBX_HD float radians_(float deg) { return deg * 0.017453292519943295f; }
 // rounding points are multiples of 2^-149, their midpoints have few bits, and a quotient can BE one: 5 * 2^-149 / 10 = 2^-150 exactly,
 // which IEEE division rounds to even, 0, while RN64(1 / 10) > 1 / 10 puts the product above the tie and the conversion gives 2^-149.
 // So a caller must show |n / d| >= 2^-126 (or n == 0, or d a power of two) or treat a result of magnitude <= 2^-126 as unproved, as
-// k_raytracer_scene does (kern_raytracer.hip "CALLER'S NUMBERS").  The callers older than that kernel — point_cam's fragCoord / u_res,
+// k_raytracer_scene does (sbx_raytracer.h "CALLER'S NUMBERS").  The callers older than that kernel — point_cam's fragCoord / u_res,
 // k_raytracer's hit_sphere, the smoothstep_rd forms — were written under the stronger sentence and have not been re-examined for
 // dividends that small (a fragCoord below 2^-126 * u_res given to sbx_render_points is one): DESIGN.md §6 keeps that as an open item.
 SBX_HD double recip64(float d) { return 1.0 / (double)d; }

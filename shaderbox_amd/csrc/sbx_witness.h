@@ -82,7 +82,7 @@ __device__ __forceinline__ bool witnessed(bool on, Body&& body) {
     return rerun;
 }
 
-// THE ELEMENT WAVE of the witnessed eval kernels (k_egg_eval, k_vinyl_eval), between a kernel's own prologue and its end: one lane
+// THE ELEMENT WAVE of the witnessed eval kernels (k_egg_eval, k_vinyl_eval, k_raytracer_eval), between a kernel's own prologue and its end: one lane
 // per element, one 64-lane wave per workgroup, a ragged last wave; a lane past n loads nothing, evaluates element zeros harmlessly
 // and stores nothing.  element(cull, q, w, r) is one element — std::true_type / std::false_type for the field's CULL, q its WIN
 // inputs, w the witness, r its WOUT outputs.
@@ -98,19 +98,20 @@ __device__ __forceinline__ bool witnessed(bool on, Body&& body) {
 //     used — and at 12-40 B per element against a march of tens of steps the traffic is noise beside the arithmetic
 //     (profiles/egg_eval_timing.txt).  A staged, vectorised copy through LDS would need the alignment the contract does not give.
 //   counts: NULL, or two zeroed words that receive the culled waves that did not / did re-run.
-constexpr int ELEM_WORDS = 8;                                    // the capacity of q and r
-template <int WIN, int WPOS, int WOUT, bool PLAIN, int WIT, class Element>
+//   CAP: the capacity of q and r in dwords, ELEM_WORDS unless a kernel's widest element needs more (k_raytracer_eval's "illuminate": 10).
+constexpr int ELEM_WORDS = 8;                                    // the default capacity of q and r
+template <int WIN, int WPOS, int WOUT, bool PLAIN, int WIT, int CAP = ELEM_WORDS, class Element>
 __device__ __forceinline__ void witnessed_elements(const float* __restrict__ in, float* __restrict__ out, size_t n,
                                                    unsigned* __restrict__ counts, Element&& element) {
-    static_assert(WPOS <= WIN && WIN <= ELEM_WORDS && WOUT <= ELEM_WORDS, "an element is at most ELEM_WORDS dwords in and out");
+    static_assert(WPOS <= WIN && WIN <= CAP && WOUT <= CAP, "an element is at most CAP dwords in and out");
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
     const bool on = i < n;
-    float q[ELEM_WORDS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float q[CAP] = {};
     if (on) {
 #pragma unroll
         for (int k = 0; k < WIN; ++k) q[k] = in[(size_t)WIN * i + k];
     }
-    float r[ELEM_WORDS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float r[CAP] = {};
     bool tame = true;
 #pragma unroll
     for (int k = 0; k < WPOS; ++k) tame = tame && abs_(q[k]) <= 1e4f;                     // a NaN compares false

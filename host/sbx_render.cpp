@@ -62,6 +62,14 @@
 //              [--air-view 0|1] [--air-samples N] [--air-samples-light N] [--air-eye x,y,z] [--air-fov F] [--air-look-at x,y,z]
 //              [--air-hg-g G] [--air-sun x,y,z] [--air-sun-power P] [--air-beta-r r,g,b] [--air-h-r H] [--air-beta-m r,g,b] [--air-h-m H]
 //              [--air-earth-radius R] [--air-atmosphere-radius R]
+//     app "planet_world": src/app_planet.h over the caller's world (SBX_APP_PLANET_WORLD, include/sbx.h).  The block starts as the default of
+//              --time (sbx_planet_world_default) and every flag replaces one field of sbx_aux_planet_world, --world-<field with '-' for '_'>:
+//              [--world-eye x,y,z] [--world-fov F] [--world-look-at x,y,z] [--world-tilt-deg D] [--world-sun-dir x,y,z] [--world-spin-deg D]
+//              [--world-key-color r,g,b] [--world-cloud-spin-deg D] [--world-terrain-offset x,y,z] [--world-max-height V]
+//              [--world-cloud-offset x,y,z] [--world-cld-coverage V] [--world-band a,b,c] [--world-cld-fuzzy V] [--world-c-water r,g,b]
+//              [--world-l-water V] [--world-c-grass r,g,b] [--world-l-shore V] [--world-c-beach r,g,b] [--world-l-grass V]
+//              [--world-c-rock r,g,b] [--world-l-rock V] [--world-c-snow r,g,b] [--world-absorb V] [--world-cloud-light V]
+//              [--world-terr-steps N] [--world-cloud-steps N] [--world-shadow-steps N]
 //     app "2d" / "2d_tex": src/app_2d.h (its alpha is not 1: the .f32 frames carry it; single GPU only), the USE_TEXTURE build
 //              reading hlsltoy's default 128x128 checkerboard at t0
 //     app "func": src/app_func.h, the tiled Worley fBm of its compiled 2D branch (grey, alpha 1; u_time and --mouse do not enter)
@@ -87,13 +95,26 @@
 #include "../include/sbx.h"
 #include "../include/sbx_test.h"      // sbx_math_eval "srgb_pow": --egg-view's linear_to_srgb
 
+// the flags of --app planet_world: one per field of sbx_aux_planet_world, in the block's order (word = its offset in 4-byte words)
+struct WorldFlag { const char* name; int word; char kind; };      // kind: 'v' three floats, 'f' one float, 'i' one int
+static const WorldFlag kWorldFlags[] = {
+    {"--world-eye", 0, 'v'}, {"--world-fov", 3, 'f'}, {"--world-look-at", 4, 'v'}, {"--world-tilt-deg", 7, 'f'},
+    {"--world-sun-dir", 8, 'v'}, {"--world-spin-deg", 11, 'f'}, {"--world-key-color", 12, 'v'}, {"--world-cloud-spin-deg", 15, 'f'},
+    {"--world-terrain-offset", 16, 'v'}, {"--world-max-height", 19, 'f'}, {"--world-cloud-offset", 20, 'v'}, {"--world-cld-coverage", 23, 'f'},
+    {"--world-band", 24, 'v'}, {"--world-cld-fuzzy", 27, 'f'}, {"--world-c-water", 28, 'v'}, {"--world-l-water", 31, 'f'},
+    {"--world-c-grass", 32, 'v'}, {"--world-l-shore", 35, 'f'}, {"--world-c-beach", 36, 'v'}, {"--world-l-grass", 39, 'f'},
+    {"--world-c-rock", 40, 'v'}, {"--world-l-rock", 43, 'f'}, {"--world-c-snow", 44, 'v'}, {"--world-absorb", 47, 'f'},
+    {"--world-cloud-light", 48, 'f'}, {"--world-terr-steps", 49, 'i'}, {"--world-cloud-steps", 50, 'i'}, {"--world-shadow-steps", 51, 'i'}};
+constexpr int kWorldFlagCount = (int)(sizeof(kWorldFlags) / sizeof(kWorldFlags[0]));
+static_assert(sizeof(sbx_aux_planet_world) == 56 * 4, "kWorldFlags addresses the block by words");
+
 static int app_from_name(const std::string& s) {
     const char* names[] = {"planet", "clouds", "vinyl", "egg", "raytracer", "atmosphere", "sdf_ao", "clouds_best", "clouds_tex", "clouds_ue4",
                            "clouds_sky", "vinyl_gpu", "planet_atmosphere", "2d", "2d_tex", "func", "atmosphere_ground", "sdf_ao_shadow", "sdf_ao_normals",
                            "egg_straight", "egg_oval", "clouds_height", "clouds_luminance", "raytracer_phong", "raytracer_noshadow", "raytracer_static",
                            "vinyl_closeup", "vinyl_ridges", "vinyl_noshadow", "planet_closeup", "planet_cloudless", "planet_unlit", "raytracer_scene", "sdf_scene", "egg_pose", "vinyl_deck",
-                           "atmosphere_air"};
-    const int n = 37;
+                           "atmosphere_air", "planet_world"};
+    const int n = 38;
     std::string low;
     for (char c : s) low += (char)tolower(c);
     for (int i = 0; i < n; ++i)
@@ -165,6 +186,8 @@ int main(int argc, char** argv) {
     bool deck_has[16] = {};
     sbx_aux_atmosphere_air air_arg{};                // the fields the air flags gave, and which (air_has[0-2]: view and the counts; then the
     bool air_has[15] = {};                           // six rows of a vec3 and a scalar, then the two radii)
+    sbx_aux_planet_world world_arg{};                // the fields the world flags gave, and which (kWorldFlags' order)
+    bool world_has[kWorldFlagCount] = {};
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -205,6 +228,16 @@ int main(int argc, char** argv) {
             for (float& v : pv_eye) v = (float)atof(next());
             for (float& v : pv_look) v = (float)atof(next());
             vinyl_view = true;
+        }
+        else if (a.rfind("--world-", 0) == 0) {
+            int k = 0;
+            while (k < kWorldFlagCount && a != kWorldFlags[k].name) ++k;
+            if (k == kWorldFlagCount) { fprintf(stderr, "unknown world flag %s\n", a.c_str()); return 2; }
+            float* const wf = (float*)&world_arg + kWorldFlags[k].word;
+            if (kWorldFlags[k].kind == 'v') vec3(wf);
+            else if (kWorldFlags[k].kind == 'f') *wf = (float)atof(next());
+            else { const int v = atoi(next()); memcpy(wf, &v, sizeof(v)); }
+            world_has[k] = true;
         }
         else if (a == "--air-view") { air_arg.view = atoi(next()); air_has[0] = true; }
         else if (a == "--air-samples") { air_arg.num_samples = atoi(next()); air_has[1] = true; }
@@ -329,6 +362,20 @@ int main(int argc, char** argv) {
         }
         if (air_has[13]) d.earth_radius = air_arg.earth_radius;
         if (air_has[14]) d.atmosphere_radius = air_arg.atmosphere_radius;
+        return d;
+    };
+    bool world_flags = false;
+    for (bool b : world_has) world_flags = world_flags || b;
+    if (world_flags && id != SBX_APP_PLANET_WORLD) { fprintf(stderr, "the world flags belong to --app planet_world\n"); return 2; }
+    // the world of frame time `time`: sbx_planet_world_default's block with the flags' fields put in
+    auto world_at = [&](float time) {
+        sbx_uniforms du{};
+        du.u_res[0] = (float)W; du.u_res[1] = (float)H; du.u_time = time;
+        sbx_aux_planet_world d;
+        sbx_planet_world_default(&du, &d);
+        for (int k = 0; k < kWorldFlagCount; ++k)
+            if (world_has[k])
+                memcpy((float*)&d + kWorldFlags[k].word, (const float*)&world_arg + kWorldFlags[k].word, (kWorldFlags[k].kind == 'v' ? 3 : 1) * sizeof(float));
         return d;
     };
     for (const std::string* p : {&ppm, &f32})
@@ -463,6 +510,8 @@ int main(int argc, char** argv) {
         if (id == SBX_APP_VINYL_DECK) { frame_deck = deck_at(u.u_time); aux = &frame_deck; }
         sbx_aux_atmosphere_air frame_air;
         if (id == SBX_APP_ATMOSPHERE_AIR) { frame_air = air_at(u.u_time); aux = &frame_air; }
+        sbx_aux_planet_world frame_world;
+        if (id == SBX_APP_PLANET_WORLD) { frame_world = world_at(u.u_time); aux = &frame_world; }
         (void)hipEventRecord(e0, nullptr);
         if (panorama) rc = sbx_clouds_eval(ctx, "render", have_ac ? &ac : nullptr, u.u_time, rays, dev, npx, nullptr);
         else if (planet_view) rc = sbx_planet_eval(ctx, "render", u.u_time, rays, dev, npx, nullptr);

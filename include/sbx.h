@@ -371,7 +371,34 @@ typedef enum sbx_app {
        SBX_PRECISION_1E4 is ignored: the app stays exact.  sbx_set_variant 1 takes the plain statement for every wave (same bits).
        NOT OFFERED: a caller's value for the 1.1, Schlick's phase function, more suns, ozone or other layers, the tolerance tier,
        SBX_APP_PLANET_ATMOSPHERE under a block, and the drop-in header sbx_mainimage.hpp, which has no way to state a block. */
-    SBX_APP_ATMOSPHERE_AIR = 36
+    SBX_APP_ATMOSPHERE_AIR = 36,
+    /* src/app_planet.h as shipped (CLOUDS and LIGHT defined) over the CALLER'S WORLD: every number the header states as a one-line
+       literal taken from the aux block sbx_aux_planet_world (below) — camera and FOV, the tilt and the two spins, the sun and the key
+       light's colour, max_height, both noise offsets (the terrain "seed"), cloud coverage, fuzziness, band and absorption, the five
+       colours and four limits, the cloud's light divisor and the three step counts.  aux == NULL means
+       sbx_planet_world_default(uni, .), and the frame is then SBX_APP_PLANET's in every bit.  u_res is read; u_time and u_mouse are
+       not when a block is passed.  Alpha is 1.
+       SEMANTICS (tests/planet_world_model.py is the definition), all as app_planet.h has them:
+         - what is not in the block stays the reference's: the planet {0, 1}, the fBm scales, lacunarities, gains and octave counts,
+           the terrain smoothstep edges .35 / .6 / 1, TERR_EPS, the .4567, the .001 of the normal, the two fill lights, background(),
+           the .7 / .33 of the ground shadow, rot = rotate_around_x(spin) * rotate_around_y(tilt), linear_to_srgb;
+         - everything derived is binary32 arithmetic on the block's values in the header's order: max_ray_dist = max_height * 4, the
+           atmosphere's radius 1 + max_height, t_step = max_ray_dist / float(cloud_steps) and max_height / float(shadow_steps),
+           c_water / 2, cld_coverage + cld_fuzzy;
+         - sun_dir is used as given, never normalised;
+         - every float bit pattern is data — NaN, inf, a zero sun, max_height <= 0, cld_fuzzy = 0, unordered band edges,
+           eye == look_at, an eye inside the planet — and the result is what the plain statement of the header computes, NaN pixels
+           included.
+       REFUSED (SBX_ERR_ARG, nothing written): terr_steps outside 1 ... 512, cloud_steps outside 1 ... 256, shadow_steps outside
+       1 ... 32, a non-zero reserved word.
+       sbx_set_variant 1 takes the plain statement over the block's numbers for every block (same bits); so does, whatever the variant, a
+       block outside the stated domain of the short forms (csrc/kern_planet_world.hip, csrc/sbx_frames.hip planet_world_tame).  A block that differs
+       from the default in camera, angles and sun only runs SBX_APP_PLANET's own kernels over its frame block.
+       sbx_planet_world_eval (below) evaluates the header's functions over the caller's rays and points under the same block.
+       NOT OFFERED: the CLOSEUP / CLOUDLESS / UNLIT builds or SBX_APP_PLANET_ATMOSPHERE under a world, a world for the literals
+       listed above, a span model for the multi-GPU split (every block's span is the whole row), and the drop-in header
+       sbx_mainimage.hpp, which has no way to state a block. */
+    SBX_APP_PLANET_WORLD = 37
 } sbx_app;
 
 typedef enum sbx_status {
@@ -534,6 +561,31 @@ typedef struct sbx_aux_atmosphere_air {    /* 128 B */
  * block SBX_APP_ATMOSPHERE_AIR renders when aux is NULL (view 0).  eye (0, earth_radius + 1, 0) and look_at (0, earth_radius + 1.5, -1)
  * in both views, fov 1, counts 16 / 8.  A view other than 0 or 1 is written as given (and refused by the app). */
 void sbx_atmosphere_air_default(const sbx_uniforms* uni, int view, sbx_aux_atmosphere_air* out);
+
+/* the world of SBX_APP_PLANET_WORLD: plain data, 224 bytes.  (:N names the line of src/app_planet.h whose literal the field
+ * replaces.) */
+typedef struct sbx_aux_planet_world {      /* 224 B */
+    float eye[3];            float fov;             /* :55;  :369 (main.h's FOV factor, as given) */
+    float look_at[3];        float tilt_deg;        /* :56;  the angle handed to rotate_around_y at :307 (27) */
+    float sun_dir[3];        float spin_deg;        /* the vector :288 multiplies by local_xform, as given, never normalised;  the angle
+                                                       handed to rotate_around_x at :308 (the reference: u_time * -12.) */
+    float key_color[3];      float cloud_spin_deg;  /* c_L of :224;  the angle of :309 (the reference: u_time * 8.) */
+    float terrain_offset[3]; float max_height;      /* the vec3 of :180 and :193 (one field, both lines);  :20 */
+    float cloud_offset[3];   float cld_coverage;    /* the vec3 of :107;  :110 */
+    float band[3];           float cld_fuzzy;       /* the .2, .35, .65 of :114;  :111 */
+    float c_water[3];        float l_water;         /* :258;  :265 */
+    float c_grass[3];        float l_shore;         /* :259;  :266 */
+    float c_beach[3];        float l_grass;         /* :260;  :267 */
+    float c_rock[3];         float l_rock;          /* :261;  :268 */
+    float c_snow[3];         float absorb;          /* :262;  vol_coeff_absorb :68 */
+    float cloud_light;                              /* the .055 of :76 */
+    int terr_steps, cloud_steps, shadow_steps;      /* TERR_STEPS :165 (1 ... 512);  the `steps` of :127 (1 ... 256) and of :148 (1 ... 32) */
+    unsigned reserved[4];                           /* must be 0 */
+} sbx_aux_planet_world;
+/* Host only, no context: the header's numbers — eye (0, 0, -2.5), look_at (0, 0, 2), fov the spec's tan(radians(30)), tilt 27, the sun
+ * the spec's normalize(1, 1, 0), key (7, 5, 3), counts 120 / 75 / 5 — with spin_deg and cloud_spin_deg the binary32 products
+ * u_time * -12.f and u_time * 8.f: the block SBX_APP_PLANET_WORLD renders when aux is NULL. */
+void sbx_planet_world_default(const sbx_uniforms* uni, sbx_aux_planet_world* out);
 
 typedef struct sbx_ctx sbx_ctx;
 
@@ -850,6 +902,12 @@ int sbx_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, flo
  * in sbx_stats.render_launches; sbx_set_precision does not enter; sbx_set_variant 1 selects the plain statement (same bits).  n == 0
  * returns SBX_OK and touches nothing; SBX_ERR_ARG, with nothing written, for a NULL ctx / fn / in / out, an unknown name, n > 2^31. */
 int sbx_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const float* in, float* out, size_t n, void* stream);
+/* sbx_planet_eval under the caller's world: the same eight names, element layouts and contract, with the numbers and the three angles
+ * read from `world` (host memory, read during the call) instead of u_time and the header's literals.  eye, look_at and fov are not
+ * read; the counts and the reserved words are checked as SBX_APP_PLANET_WORLD checks them (SBX_ERR_ARG, nothing written).  Under
+ * sbx_planet_world_default(uni, .) the result is sbx_planet_eval's at uni->u_time in every bit.  "clouds_density" takes
+ * t_step = max_height * 4 / float(cloud_steps).  tests/planet_world_model.py is the definition. */
+int sbx_planet_world_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_planet_world* world, const float* in, float* out, size_t n, void* stream);
 /* The two bone IK solver (src/IK.h) and the egg's field, shadow and trace (src/app_egg.h as shipped) as standalone functions over n
  * elements of the caller's, under the caller's pose: what the reference reaches only through pixels of its one fixed camera — the
  * solver for a host's own rig, the field for collision queries, the trace for another camera or a reflection.  `pose`: HOST memory,

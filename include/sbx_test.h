@@ -56,6 +56,10 @@ extern "C" {
  * element changes a wave's form (csrc/kern_raytracer_eval.hip).
  * SBX_APP_ATMOSPHERE_AIR and sbx_atmosphere_air_eval: 1 = the plain statement for every wave, whatever the block; every other value
  * leaves the tier to the block (csrc/sbx_frames.hip atmosphere_air_tier).
+ * SBX_APP_PLANET_WORLD: 1 = k_planet_world<false>, the plain statement over the block's numbers, for every block, one that differs from the
+ * default in camera, angles and sun only included; every other value leaves the tier to the block (planet_world_tier).
+ * sbx_planet_world_eval: 1 = the plain form for every wave; 0 runs it for the waves whose own operands fail a guard and for every wave
+ * of a block outside planet_world_tame (csrc/kern_planet_eval.hip PeWorld).
  * All variants are specified to produce identical bits (tests/test_gpu_parity.py sweeps them against each other). */
 int sbx_set_variant(sbx_ctx* ctx, int variant);
 
@@ -80,6 +84,12 @@ int sbx_debug_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* au
  * tests/test_gpu_planet_eval.py and tools/time_planet_eval.py. */
 int sbx_debug_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const float* in, float* out, size_t n, unsigned counts_host[2],
                           void* stream);
+
+/* sbx_planet_world_eval (sbx.h) with counts: as sbx_debug_planet_eval — counts_host[0] the waves that ran with every guarded short form
+ * on, counts_host[1] the waves that took the plain form for at least one part: all of them under variant 1 or a block outside
+ * planet_world_tame (csrc/sbx_frames.hip).  It allocates and synchronises, so it is not capturable. */
+int sbx_debug_planet_world_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_planet_world* world, const float* in, float* out, size_t n,
+                                unsigned counts_host[2], void* stream);
 
 /* sbx_egg_eval (sbx.h) with counts: the same launch (the context's variant included) followed by a wait, after which counts_host[0]
  * holds the waves that took the witnessed roots only and counts_host[1] the waves that re-ran with the IEEE roots because a lane
@@ -111,6 +121,11 @@ int sbx_debug_atmosphere_air_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_at
  * kernels over the block's sun), counts[2] those that took the plain kernel (sbx_set_variant 1, or a block that is neither literal nor
  * tame).  The rest took the run-time kernel with its per-wave selection. */
 int sbx_debug_atmosphere_air_launches(sbx_ctx* ctx, uint64_t counts[3]);
+/* SBX_APP_PLANET_WORLD launches of this context so far, by what ran: counts[0] the literal tier with its short forms (k_planet<true>'s
+ * instantiations over the block's camera, angles and sun), counts[1] the run-time kernel k_planet_world<true>, counts[2] a plain
+ * kernel: k_planet_world<false> (sbx_set_variant 1, whatever the block; a block outside planet_world_tame) or k_planet<false> (a
+ * literal-tier block whose camera or angles are outside planet_world_camera_tame; csrc/sbx_frames.hip). */
+int sbx_debug_planet_world_launches(sbx_ctx* ctx, uint64_t counts[3]);
 /* SBX_APP_VINYL_DECK launches of this context so far, and how many of them took the reference form because their deck was outside the
  * domain of the culls (whatever variant was set; a launch under sbx_set_variant 1 with a tame deck is not among the latter). */
 int sbx_debug_vinyl_deck_launches(sbx_ctx* ctx, uint64_t counts[2]);

@@ -17,7 +17,7 @@ from . import shard  # noqa: F401  (pure-python row-block arithmetic, no GPU nee
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsbx.so")
 
-APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW, APP_PLANET_CLOSEUP, APP_PLANET_CLOUDLESS, APP_PLANET_UNLIT, APP_RAYTRACER_SCENE, APP_SDF_SCENE, APP_EGG_POSE, APP_VINYL_DECK, APP_ATMOSPHERE_AIR = range(37)
+APP_PLANET, APP_CLOUDS, APP_VINYL, APP_EGG, APP_RAYTRACER, APP_ATMOSPHERE, APP_SDF_AO, APP_CLOUDS_BEST, APP_CLOUDS_TEX, APP_CLOUDS_UE4, APP_CLOUDS_SKY, APP_VINYL_GPU, APP_PLANET_ATMOSPHERE, APP_2D, APP_2D_TEX, APP_FUNC, APP_ATMOSPHERE_GROUND, APP_SDF_AO_SHADOW, APP_SDF_AO_NORMALS, APP_EGG_STRAIGHT, APP_EGG_OVAL, APP_CLOUDS_HEIGHT, APP_CLOUDS_LUMINANCE, APP_RAYTRACER_PHONG, APP_RAYTRACER_NOSHADOW, APP_RAYTRACER_STATIC, APP_VINYL_CLOSEUP, APP_VINYL_RIDGES, APP_VINYL_NOSHADOW, APP_PLANET_CLOSEUP, APP_PLANET_CLOUDLESS, APP_PLANET_UNLIT, APP_RAYTRACER_SCENE, APP_SDF_SCENE, APP_EGG_POSE, APP_VINYL_DECK, APP_ATMOSPHERE_AIR, APP_PLANET_WORLD = range(38)
 APPS = {"APP_PLANET": APP_PLANET, "APP_CLOUDS": APP_CLOUDS, "APP_VINYL": APP_VINYL, "APP_EGG": APP_EGG,
         "APP_RAYTRACER": APP_RAYTRACER, "APP_ATMOSPHERE": APP_ATMOSPHERE, "APP_SDF_AO": APP_SDF_AO,
         "APP_CLOUDS_BEST": APP_CLOUDS_BEST,    # src/app_clouds_best.h (stand-alone shader, not an APP_* define)
@@ -49,6 +49,7 @@ MORE_APPS = {"APP_EGG_STRAIGHT": APP_EGG_STRAIGHT,  # APP_EGG without `#define B
              "APP_PLANET_UNLIT": APP_PLANET_UNLIT,          # APP_PLANET without the `#define LIGHT` of src/app_planet.h:249: N = w_normal.y, ocean = water
              "APP_RAYTRACER_SCENE": APP_RAYTRACER_SCENE,    # src/app_raytracer.h's render over the caller's scene: aux = a RaytracerScene (cornell_scene, raytracer_scene)
              "APP_ATMOSPHERE_AIR": APP_ATMOSPHERE_AIR,      # src/app_atmosphere.h over the caller's air (coefficients, scale heights, radii, sun, counts, observer; view 0 = the sky dome, 1 = the ground camera): aux = an AtmosphereAir (atmosphere_air_default, atmosphere_air)
+             "APP_PLANET_WORLD": APP_PLANET_WORLD,          # src/app_planet.h as shipped over the caller's world (camera, tilt and spins, sun and key light, max_height, noise offsets, cloud cover, colours, limits, step counts): aux = a PlanetWorld (planet_world_default, planet_world)
              "APP_VINYL_DECK": APP_VINYL_DECK,              # src/app_vinyl.h as shipped over the caller's deck (platter angle, tilts, sun, colours, groove BRDF): aux = a VinylDeck (vinyl_deck_default, vinyl_deck)
              "APP_EGG_POSE": APP_EGG_POSE,                  # src/app_egg.h as shipped with the rider posed by the caller (src/IK.h at work): aux = an EggPose (egg_pose_default, egg_pose)
              "APP_SDF_SCENE": APP_SDF_SCENE}                # src/app_sdf_ao.h's renderer over the caller's field, a program of src/sdf.h's primitives and operators: aux = an SdfScene (sdf_ramp_scene, SdfSceneBuilder)
@@ -145,6 +146,24 @@ class AtmosphereAir(ctypes.Structure):      # sbx_aux_atmosphere_air (the aux bl
                 ("betaM", ctypes.c_float * 3), ("hM", ctypes.c_float),
                 ("earth_radius", ctypes.c_float), ("atmosphere_radius", ctypes.c_float),
                 ("reserved", ctypes.c_float * 6)]
+
+
+class PlanetWorld(ctypes.Structure):        # sbx_aux_planet_world (the aux block of APP_PLANET_WORLD, 224 bytes)
+    _fields_ = [("eye", ctypes.c_float * 3), ("fov", ctypes.c_float),
+                ("look_at", ctypes.c_float * 3), ("tilt_deg", ctypes.c_float),
+                ("sun_dir", ctypes.c_float * 3), ("spin_deg", ctypes.c_float),
+                ("key_color", ctypes.c_float * 3), ("cloud_spin_deg", ctypes.c_float),
+                ("terrain_offset", ctypes.c_float * 3), ("max_height", ctypes.c_float),
+                ("cloud_offset", ctypes.c_float * 3), ("cld_coverage", ctypes.c_float),
+                ("band", ctypes.c_float * 3), ("cld_fuzzy", ctypes.c_float),
+                ("c_water", ctypes.c_float * 3), ("l_water", ctypes.c_float),
+                ("c_grass", ctypes.c_float * 3), ("l_shore", ctypes.c_float),
+                ("c_beach", ctypes.c_float * 3), ("l_grass", ctypes.c_float),
+                ("c_rock", ctypes.c_float * 3), ("l_rock", ctypes.c_float),
+                ("c_snow", ctypes.c_float * 3), ("absorb", ctypes.c_float),
+                ("cloud_light", ctypes.c_float),
+                ("terr_steps", ctypes.c_int), ("cloud_steps", ctypes.c_int), ("shadow_steps", ctypes.c_int),
+                ("reserved", ctypes.c_uint * 4)]
 
 
 class VinylDeck(ctypes.Structure):          # sbx_aux_vinyl_deck (the aux block of APP_VINYL_DECK and the deck of vinyl_eval, 128 bytes)
@@ -391,6 +410,11 @@ def load_library(path=None):
     lib.sbx_atmosphere_air_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(AtmosphereAir), fp, fp, ctypes.c_size_t, vp]
     lib.sbx_debug_atmosphere_air_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(AtmosphereAir), fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
     lib.sbx_debug_atmosphere_air_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    lib.sbx_planet_world_default.argtypes = [ctypes.POINTER(Uniforms), ctypes.POINTER(PlanetWorld)]
+    lib.sbx_planet_world_default.restype = None
+    lib.sbx_debug_planet_world_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    lib.sbx_planet_world_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(PlanetWorld), fp, fp, ctypes.c_size_t, vp]
+    lib.sbx_debug_planet_world_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(PlanetWorld), fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
     lib.sbx_vinyl_deck_default.argtypes = [ctypes.POINTER(Uniforms), ctypes.POINTER(VinylDeck)]
     lib.sbx_vinyl_deck_default.restype = None
     lib.sbx_vinyl_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(VinylDeck), fp, fp, ctypes.c_size_t, vp]
@@ -610,6 +634,34 @@ def atmosphere_air(time=0.0, view=0, lib=None, **fields):
             setattr(a, name, int(value))
         elif isinstance(getattr(a, name), float):
             setattr(a, name, float(value))
+        else:
+            getattr(a, name)[:] = [float(v) for v in value]
+    return a
+
+
+def planet_world_default(time, lib=None):
+    """sbx_planet_world_default (host only, no GPU needed): the PlanetWorld with the numbers of src/app_planet.h and the two spins it
+    makes of `time` — what APP_PLANET_WORLD renders when aux is None, the frame of APP_PLANET."""
+    lib = lib or load_library()
+    u = uniforms(1, 1, time)
+    a = PlanetWorld()
+    lib.sbx_planet_world_default(ctypes.byref(u), ctypes.byref(a))
+    return a
+
+
+def planet_world(time=0.0, lib=None, **fields):
+    """A PlanetWorld: planet_world_default(time) with the named fields of sbx_aux_planet_world replaced, each float rounded to
+    binary32."""
+    a = planet_world_default(time, lib)
+    for name, value in fields.items():
+        if name not in dict(PlanetWorld._fields_):
+            raise SbxError(SBX_ERR_ARG, "sbx_aux_planet_world has no field %r" % (name,))
+        if isinstance(getattr(a, name), int):
+            setattr(a, name, int(value))
+        elif isinstance(getattr(a, name), float):
+            setattr(a, name, float(value))
+        elif name == "reserved":
+            getattr(a, name)[:] = [int(v) for v in value]
         else:
             getattr(a, name)[:] = [float(v) for v in value]
     return a
@@ -1154,6 +1206,8 @@ class Renderer:
         "clouds": {"render": (6, 4), "render_clouds": (6, 4), "render_sky_color": (3, 3), "density_func": (3, 1), "illuminate_volume": (6, 1)},
         "planet": {"render": (6, 4), "terrain_march": (6, 4), "sdf_terrain_map": (3, 2), "sdf_terrain_map_detail": (3, 2),
                    "sdf_terrain_normal": (3, 3), "clouds_density": (4, 1), "illuminate": (4, 3), "background": (3, 3)},
+        "planet_world": {"render": (6, 4), "terrain_march": (6, 4), "sdf_terrain_map": (3, 2), "sdf_terrain_map_detail": (3, 2),
+                         "sdf_terrain_normal": (3, 3), "clouds_density": (4, 1), "illuminate": (4, 3), "background": (3, 3)},
         "egg": {"ik_solver": (8, 3), "sdf": (3, 2), "sdf_normal": (3, 3), "shadowmarch": (6, 1), "render_scene": (6, 4)},
         "vinyl": {"sdf": (3, 2), "sdf_normal": (3, 3), "sdf_shadow": (6, 1), "illuminate": (7, 3), "render": (6, 5)},
         "sdf": {"sdf": (3, 2)},
@@ -1289,6 +1343,24 @@ class Renderer:
         literal tier, those that took the plain kernel)"""
         c = (ctypes.c_uint64 * 3)(0, 0, 0)
         self._check(self.lib.sbx_debug_atmosphere_air_launches(self.ctx, c))
+        return int(c[0]), int(c[1]), int(c[2])
+
+    def planet_world_eval(self, fn, x, world):
+        """planet_eval under a PlanetWorld (include/sbx.h sbx_planet_world_eval): the same eight names and element layouts, with the
+        numbers and the three angles read from `world` (its eye, look_at and fov are not)."""
+        return self._eval("planet_world", fn, x, (self._by_ref(world),))
+
+    def planet_world_eval_counted(self, fn, x, world):
+        """include/sbx_test.h sbx_debug_planet_world_eval: planet_world_eval that waits -> (out, (waves with every guarded short form
+        on, waves that took the plain form for at least one part))"""
+        counts = (ctypes.c_uint * 2)(0, 0)
+        return self._eval("planet_world", fn, x, (self._by_ref(world),), counts), (int(counts[0]), int(counts[1]))
+
+    def planet_world_launches(self):
+        """include/sbx_test.h sbx_debug_planet_world_launches: APP_PLANET_WORLD launches of this context by what ran -> (the literal
+        tier's short-form kernels, the run-time kernel, a plain kernel)"""
+        c = (ctypes.c_uint64 * 3)(0, 0, 0)
+        self._check(self.lib.sbx_debug_planet_world_launches(self.ctx, c))
         return int(c[0]), int(c[1]), int(c[2])
 
     def _clouds_aux(self, aux):

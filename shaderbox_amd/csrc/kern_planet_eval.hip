@@ -61,6 +61,88 @@ __device__ __forceinline__ bool pe_within(v3 v, float b) {           // every co
     return abs_(v.x) <= b && abs_(v.y) <= b && abs_(v.z) <= b;
 }
 
+// Where the numbers come from (sbx_planet.h's policies one level up: these also carry the rotations, the marches' bounds, the shell's
+// |o|^2 interval, illuminate's materials and the two `tame` tests).  PeLit: sbx_planet_eval — a FramePlanet and the header's literals,
+// every expression as it stood in this file before the numbers could be a caller's.  PeWorld: sbx_planet_world_eval — a
+// FramePlanetWorld (sbx_frames.hip build_planet_world).  Its `tame` tests are the host's block test (F.tame, planet_world_tame) joined
+// to wave-wide tests, and for rays they are k_planet_world's, not the 256 / 4 / 18.6 chain: 1 <= |hit_o|^2 <= (2 + max_height)^2 and
+// |rd|^2 <= 1.001 (a direction that is no unit vector takes the plain form), under which kern_planet_world.hip's bounds hold as
+// written.  For points: within 16 per coordinate — the finest lattice coordinate is (27.8 * 1.50987 + 64) * 2.0244^6 < 7300, times 271
+// below 2^21 — and for clouds_density a height that is 0 or of magnitude in [2^-60, 2^100], since a block's band edge may be 0 and the
+// dividend height - edge must not fall below div3_'s 2^-100.
+struct PeLit {
+    const FramePlanet& F;
+    __device__ __forceinline__ const m3& rot() const { return F.rot; }
+    __device__ __forceinline__ const m3& rot_cloud() const { return F.rot_cloud; }
+    __device__ __forceinline__ const m3& rot_t() const { return F.rot_t; }
+    __device__ __forceinline__ v3 L() const { return F.L; }
+    __device__ __forceinline__ PlLit cloud() const { return PlLit(); }
+    __device__ __forceinline__ PlLit terr() const { return PlLit(); }
+    __device__ __forceinline__ float max_height() const { return PL_MAX_HEIGHT; }
+    __device__ __forceinline__ float max_ray_dist() const { return PL_MAX_RAY_DIST; }
+    __device__ __forceinline__ float atm_radius() const { return 1.f + PL_MAX_HEIGHT; }
+    __device__ __forceinline__ int terr_steps() const { return 120; }
+    __device__ __forceinline__ int cloud_steps() const { return 75; }
+    __device__ __forceinline__ int shadow_steps() const { return 5; }
+    __device__ __forceinline__ float t_step_cloud() const { return PL_MAX_RAY_DIST / 75.f; }
+    __device__ __forceinline__ float t_step_shadow() const { return PL_MAX_HEIGHT / 5.f; }
+    // the shell skip of k_planet: o is finite here (SKIP stands under `tame` only)
+    __device__ __forceinline__ bool outside_shell(float d2) const { return d2 > 1.5885f || d2 < 1.166f; }
+    __device__ __forceinline__ v3 c_water() const { return V3(.015f, .110f, .455f); }
+    __device__ __forceinline__ v3 c_water_half() const { return V3(.015f, .110f, .455f) / 2.f; }
+    __device__ __forceinline__ v3 c_grass() const { return V3(.086f, .132f, .018f); }
+    __device__ __forceinline__ v3 c_beach() const { return V3(.153f, .172f, .121f); }
+    __device__ __forceinline__ v3 c_rock() const { return V3(.080f, .050f, .030f); }
+    __device__ __forceinline__ v3 c_snow() const { return V3(.600f, .600f, .600f); }
+    __device__ __forceinline__ float l_water() const { return .05f; }
+    __device__ __forceinline__ float l_shore() const { return .17f; }
+    __device__ __forceinline__ float l_grass() const { return .211f; }
+    __device__ __forceinline__ float l_rock() const { return .351f; }
+    __device__ __forceinline__ v3 key_color() const { return V3(7, 5, 3); }
+    // `tame` (the note at the top): on the wave's own origins, hit origins and directions
+    __device__ __forceinline__ bool ray_tame(v3 ro, bool hit, v3 hit_o, v3 rd) const {
+        return pe_within(ro, 256.f) && (!hit || (pe_within(hit_o, 4.f) && pe_within(rd, 4.f)));
+    }
+    // `tame` for a point: within 16 per coordinate; clouds_density's height within 2^100 (band's two quotients)
+    __device__ __forceinline__ bool point_tame(v3 p, bool clouds, float h) const { return pe_within(p, 16.f) && (!clouds || abs_(h) <= 1.2676506e30f); }
+};
+struct PeWorld {
+    const FramePlanetWorld& F;
+    __device__ __forceinline__ const m3& rot() const { return F.terr.rot; }
+    __device__ __forceinline__ const m3& rot_cloud() const { return F.cloud.rot_cloud; }
+    __device__ __forceinline__ const m3& rot_t() const { return F.shade.rot_t; }
+    __device__ __forceinline__ v3 L() const { return F.shade.L; }
+    __device__ __forceinline__ PlCloudW cloud() const { return PlCloudW{F.cloud}; }
+    __device__ __forceinline__ PlTerrW terr() const { return PlTerrW{F.terr}; }
+    __device__ __forceinline__ float max_height() const { return F.terr.max_height; }
+    __device__ __forceinline__ float max_ray_dist() const { return F.terr.max_ray_dist; }
+    __device__ __forceinline__ float atm_radius() const { return F.atm_radius; }
+    __device__ __forceinline__ int terr_steps() const { return F.terr.terr_steps; }
+    __device__ __forceinline__ int cloud_steps() const { return F.cloud.cloud_steps; }
+    __device__ __forceinline__ int shadow_steps() const { return F.cloud.shadow_steps; }
+    __device__ __forceinline__ float t_step_cloud() const { return F.cloud.t_step_cloud; }
+    __device__ __forceinline__ float t_step_shadow() const { return F.cloud.t_step_shadow; }
+    __device__ __forceinline__ bool outside_shell(float d2) const { return d2 > F.cloud.shell_hi2 || d2 < F.cloud.shell_lo2; }
+    __device__ __forceinline__ v3 c_water() const { return F.shade.c_water; }
+    __device__ __forceinline__ v3 c_water_half() const { return F.shade.c_water_half; }
+    __device__ __forceinline__ v3 c_grass() const { return F.shade.c_grass; }
+    __device__ __forceinline__ v3 c_beach() const { return F.shade.c_beach; }
+    __device__ __forceinline__ v3 c_rock() const { return F.shade.c_rock; }
+    __device__ __forceinline__ v3 c_snow() const { return F.shade.c_snow; }
+    __device__ __forceinline__ float l_water() const { return F.shade.l_water; }
+    __device__ __forceinline__ float l_shore() const { return F.shade.l_shore; }
+    __device__ __forceinline__ float l_grass() const { return F.shade.l_grass; }
+    __device__ __forceinline__ float l_rock() const { return F.shade.l_rock; }
+    __device__ __forceinline__ v3 key_color() const { return F.shade.key_color; }
+    __device__ __forceinline__ bool ray_tame(v3 ro, bool hit, v3 hit_o, v3 rd) const {
+        const float ho2 = dot(hit_o, hit_o), rd2 = dot(rd, rd);
+        return F.tame != 0 && pe_within(ro, 256.f) && (!hit || (ho2 >= 1.f && ho2 <= F.hit2_max && rd2 <= 1.001f));
+    }
+    __device__ __forceinline__ bool point_tame(v3 p, bool clouds, float h) const {
+        return F.tame != 0 && pe_within(p, 16.f) && (!clouds || (abs_(h) <= 1.2676506e30f && (h == 0.f || abs_(h) >= 0x1p-60f)));
+    }
+};
+
 // what the marches leave behind for the shading and for "terrain_march"
 struct PeRay {
     bool hit_atm;           // :319, committing lanes only
@@ -72,11 +154,12 @@ struct PeRay {
 };
 
 // intersect_sphere(eye, atmosphere = {0, 1 + max_height}) on no_hit (intersect.h:7-33), the statement of k_planet with the caller's origin
-__device__ __forceinline__ void pe_intersect(v3 ro, v3 rd, bool on, PeRay& R) {
+template <class E>
+__device__ __forceinline__ void pe_intersect(const E& e, v3 ro, v3 rd, bool on, PeRay& R) {
     R.hit_atm = false;
     R.hit_o = V3(0, 0, 0);
     R.t_hit = (float)(1e8f + 1e1f);
-    const float radius = 1.f + PL_MAX_HEIGHT;
+    const float radius = e.atm_radius();
     const v3 rc = V3(0, 0, 0) - ro;
     const float radius2 = radius * radius;
     const float tca = dot(rc, rd);
@@ -91,26 +174,26 @@ __device__ __forceinline__ void pe_intersect(v3 ro, v3 rd, bool on, PeRay& R) {
         }
     }
     R.t = 0.f; R.t_pos = 0.f;
-    R.df = V2(1, PL_MAX_HEIGHT);
+    R.df = V2(1, e.max_height());
     R.radiance = 0.f; R.alpha = 0.f;
 }
 
 // the terrain march :328-342 and clouds_march :121-141 of k_planet over the wave's rays; RS = false (the note above)
-template <bool SKIP, bool CLD>
-__device__ __forceinline__ void pe_march(const FramePlanet& F, WaveCache& S, v3 rd, PeRay& R, int lane) {
+template <bool SKIP, bool CLD, class E>
+__device__ __forceinline__ void pe_march(const E& e, WaveCache& S, v3 rd, PeRay& R, int lane) {
     const bool hit_atm = R.hit_atm;
     const v3 hit_o = R.hit_o;
     float t = 0.f, t_pos = 0.f;
-    v2 df = V2(1, PL_MAX_HEIGHT);
-    float max_cld = PL_MAX_RAY_DIST;
+    v2 df = V2(1, e.max_height());
+    float max_cld = e.max_ray_dist();
     bool tm = hit_atm;
-    if (SKIP && PL_SPEC) hc_set_direction(S, mul(F.rot, rd), hit_atm, lane);
-    for (int i = 0; i < 120; ++i) {
-        if (tm && t > PL_MAX_RAY_DIST) tm = false;               // `if (t > max_ray_dist) break;`
+    if (SKIP && PL_SPEC) hc_set_direction(S, mul(e.rot(), rd), hit_atm, lane);
+    for (int i = 0; i < e.terr_steps(); ++i) {
+        if (tm && t > e.max_ray_dist()) tm = false;               // `if (t > max_ray_dist) break;`
         if (!wave_any(tm)) break;
         const v3 o = hit_o + t * rd;
-        const v3 p = mul(F.rot, o - V3(0, 0, 0));
-        const v2 d = terrain_map<3, SKIP, false>(S, p, tm, lane);
+        const v3 p = mul(e.rot(), o - V3(0, 0, 0));
+        const v2 d = terrain_map<3, SKIP, false>(S, p, tm, lane, e.terr());
         if (tm) {
             t_pos = t;
             df = d;
@@ -121,24 +204,23 @@ __device__ __forceinline__ void pe_march(const FramePlanet& F, WaveCache& S, v3 
     R.t = t; R.t_pos = t_pos; R.df = df;
     if constexpr (CLD) {
         Vol cloud = make_vol(hit_o);
-        const float t_step = PL_MAX_RAY_DIST / 75.f;
+        const float t_step = e.t_step_cloud();
         float tc = 0.f;
         bool cm = hit_atm;
-        if (SKIP && PL_SPEC) hc_set_direction(S, mul(F.rot_cloud, rd), hit_atm, lane);
-        for (int i = 0; i < 75; ++i) {
+        if (SKIP && PL_SPEC) hc_set_direction(S, mul(e.rot_cloud(), rd), hit_atm, lane);
+        for (int i = 0; i < e.cloud_steps(); ++i) {
             if (cm && (tc > max_cld || cloud.alpha >= 1.f)) cm = false;       // `return` of clouds_march
             if (!wave_any(cm)) break;
             const v3 o = cloud.origin + tc * rd;
             {
-                // the shell skip of k_planet: o is finite here (SKIP stands under `tame` only)
                 const float d2 = dot(o, o);
-                if (SKIP && !wave_any(cm && !(d2 > 1.5885f || d2 < 1.166f))) { tc += t_step; continue; }
+                if (SKIP && !wave_any(cm && !e.outside_shell(d2))) { tc += t_step; continue; }
             }
-            const v3 cp = mul(F.rot_cloud, o - V3(0, 0, 0));
-            const float ch = PL_DIVK(pl_length<false>(cp) - 1.f, PL_MAX_HEIGHT);
+            const v3 cp = mul(e.rot_cloud(), o - V3(0, 0, 0));
+            const float ch = e.cloud().template div_height<SKIP>(pl_length<false>(cp) - 1.f);
             if (cm) { cloud.pos = cp; cloud.height = ch; }
             tc += t_step;
-            clouds_map<SKIP>(S, cloud, t_step, cm, lane);
+            clouds_map<SKIP>(S, cloud, t_step, cm, lane, e.cloud());
         }
         R.radiance = cloud.radiance; R.alpha = cloud.alpha;
     }
@@ -146,21 +228,21 @@ __device__ __forceinline__ void pe_march(const FramePlanet& F, WaveCache& S, v3 
 }
 
 // the three central differences of sdf_terrain_normal :201-212 (before its normalize): pairs behind k_planet's test, else one code copy
-template <bool SKIP>
-__device__ __forceinline__ v3 pe_normal_differences(WaveCache& S, v3 pos, bool on, int lane) {
+template <bool SKIP, class T>
+__device__ __forceinline__ v3 pe_normal_differences(WaveCache& S, v3 pos, bool on, int lane, const T& w) {
     const float e = 0.001f;
     float g[3] = {0.f, 0.f, 0.f};
     // (a zero coordinate: pos.c + 0 and pos.c - 0 then differ in the sign of their zero — the unpaired path)
     const bool pairs = SKIP && PL_PAIRS && !wave_any(on && (pos.x == 0.f || pos.y == 0.f || pos.z == 0.f));
     if (pairs) {
-        g[0] = terrain_detail_difference<0, SKIP, false>(S, pos, e, on, lane);
-        g[1] = terrain_detail_difference<1, SKIP, false>(S, pos, e, on, lane);
-        g[2] = terrain_detail_difference<2, SKIP, false>(S, pos, e, on, lane);
+        g[0] = terrain_detail_difference<0, SKIP, false>(S, pos, e, on, lane, w);
+        g[1] = terrain_detail_difference<1, SKIP, false>(S, pos, e, on, lane, w);
+        g[2] = terrain_detail_difference<2, SKIP, false>(S, pos, e, on, lane, w);
     } else {
 #pragma unroll 1
         for (int ax = 0; ax < 3; ++ax) {
             const v3 d = V3(ax == 0 ? e : 0.f, ax == 1 ? e : 0.f, ax == 2 ? e : 0.f);
-            const float v = terrain_map<7, SKIP, false>(S, pos + d, on, lane).x - terrain_map<7, SKIP, false>(S, pos - d, on, lane).x;
+            const float v = terrain_map<7, SKIP, false>(S, pos + d, on, lane, w).x - terrain_map<7, SKIP, false>(S, pos - d, on, lane, w).x;
             if (ax == 0) g[0] = v; else if (ax == 1) g[1] = v; else g[2] = v;
         }
     }
@@ -168,62 +250,60 @@ __device__ __forceinline__ v3 pe_normal_differences(WaveCache& S, v3 pos, bool o
 }
 
 // illuminate :238-298 with local_xform = rot (F.L = rot * normalize(1, 1, 0))
-template <bool SKIP>
-__device__ __forceinline__ v3 pe_illuminate(const FramePlanet& F, WaveCache& S, v3 pos, float h, bool on, int lane) {
+template <bool SKIP, class E>
+__device__ __forceinline__ v3 pe_illuminate(const E& e, WaveCache& S, v3 pos, float h, bool on, int lane) {
     const v3 w_normal = normalize(pos);
-    const v3 normal = normalize(pe_normal_differences<SKIP>(S, pos, on, lane));
+    const v3 normal = normalize(pe_normal_differences<SKIP>(S, pos, on, lane, e.terr()));
     const float N = dot(normal, w_normal);
-    const v3 c_water = V3(.015f, .110f, .455f), c_grass = V3(.086f, .132f, .018f),
-             c_beach = V3(.153f, .172f, .121f), c_rock = V3(.080f, .050f, .030f),
-             c_snow = V3(.600f, .600f, .600f);
-    const float l_water = .05f, l_shore = .17f, l_grass = .211f, l_rock = .351f;
+    const v3 c_water = e.c_water(), c_grass = e.c_grass(), c_beach = e.c_beach(), c_rock = e.c_rock(), c_snow = e.c_snow();
+    const float l_water = e.l_water(), l_shore = e.l_shore(), l_grass = e.l_grass(), l_rock = e.l_rock();
     const float s = smoothstep_(.4f, 1.f, h);
     const v3 rock = mix3(c_rock, c_snow, smoothstep_(1.f - .3f * s, 1.f - .2f * s, N));
     const v3 grass = mix3(c_grass, rock, smoothstep_(l_grass, l_rock, h));
     v3 shoreline = mix3(c_beach, grass, smoothstep_(l_shore, l_grass, h));
-    const v3 water = mix3(c_water / 2.f, c_water, smoothstep_(0.f, l_water, h));
-    shoreline = shoreline * setup_lights(F.L, normal);
-    const v3 ocean = setup_lights(F.L, w_normal) * water;
+    const v3 water = mix3(e.c_water_half(), c_water, smoothstep_(0.f, l_water, h));
+    shoreline = shoreline * setup_lights(e.L(), normal, e.key_color());
+    const v3 ocean = setup_lights(e.L(), w_normal, e.key_color()) * water;
     return mix3(ocean, shoreline, smoothstep_(l_water, l_shore, h));
 }
 
 // :349-363 for the lanes with a ground hit: illuminate, the cloud shadow on the ground, the composite
-template <bool SKIP>
-__device__ __forceinline__ v3 pe_shade(const FramePlanet& F, WaveCache& S, v3 pos, float h, float c_cld, float alpha, bool hitl, int lane) {
-    const v3 c_terr = pe_illuminate<SKIP>(F, S, pos, h, hitl, lane);
-    const v3 lp = mul(F.rot_t, pos);
+template <bool SKIP, class E>
+__device__ __forceinline__ v3 pe_shade(const E& e, WaveCache& S, v3 pos, float h, float c_cld, float alpha, bool hitl, int lane) {
+    const v3 c_terr = pe_illuminate<SKIP>(e, S, pos, h, hitl, lane);
+    const v3 lp = mul(e.rot_t(), pos);
     Vol sh = make_vol(lp);
     const v3 local_up = normalize(lp);
-    const float t_step = PL_MAX_HEIGHT / 5.f;
+    const float t_step = e.t_step_shadow();
     float ts = 0.f;
-    for (int i = 0; i < 5; ++i) {
+    for (int i = 0; i < e.shadow_steps(); ++i) {
         const v3 o = sh.origin + ts * local_up;
-        sh.pos = mul(F.rot_cloud, o - V3(0, 0, 0));
-        sh.height = PL_DIVK(pl_length<false>(sh.pos) - 1.f, PL_MAX_HEIGHT);
+        sh.pos = mul(e.rot_cloud(), o - V3(0, 0, 0));
+        sh.height = e.cloud().template div_height<SKIP>(pl_length<false>(sh.pos) - 1.f);
         ts += t_step;
-        clouds_map<SKIP>(S, sh, t_step, hitl, lane);
+        clouds_map<SKIP>(S, sh, t_step, hitl, lane, e.cloud());
     }
     const float shadow = mix_(.7f, 1.f, step_(sh.alpha, 0.33f));
     return abs3(mix3(c_terr * shadow, V3s(c_cld), alpha));
 }
 
 // the body of one point function under one form; r = its outputs
-template <int FN, bool SKIP>
-__device__ __forceinline__ void pe_point(const FramePlanet& F, WaveCache& S, const float (&q)[6], bool on, int lane, float (&r)[4]) {
+template <int FN, bool SKIP, class E>
+__device__ __forceinline__ void pe_point(const E& e, WaveCache& S, const float (&q)[6], bool on, int lane, float (&r)[4]) {
     const v3 pos = V3(q[0], q[1], q[2]);
     if (FN == PE_MAP || FN == PE_MAP_DETAIL) {
-        const v2 d = terrain_map<FN == PE_MAP ? 3 : 7, SKIP, false>(S, pos, on, lane);
+        const v2 d = terrain_map<FN == PE_MAP ? 3 : 7, SKIP, false>(S, pos, on, lane, e.terr());
         r[0] = d.x; r[1] = d.y;
     } else if (FN == PE_NORMAL) {
-        const v3 nrm = normalize(pe_normal_differences<SKIP>(S, pos, on, lane));
+        const v3 nrm = normalize(pe_normal_differences<SKIP>(S, pos, on, lane, e.terr()));
         r[0] = nrm.x; r[1] = nrm.y; r[2] = nrm.z;
     } else if (FN == PE_CLOUDS) {
         // false: the density of every committing lane is exactly +0 (the skips of clouds_density, their operands finite under `tame`)
         float dens = 0.f, T_i = 1.f;
-        if (!clouds_density<SKIP>(S, pos, q[3], PL_MAX_RAY_DIST / 75.f, on, lane, dens, T_i)) dens = 0.f;
+        if (!clouds_density<SKIP>(S, pos, q[3], e.t_step_cloud(), on, lane, dens, T_i, e.cloud())) dens = 0.f;
         r[0] = dens;
     } else {
-        const v3 c = pe_illuminate<SKIP>(F, S, pos, q[3], on, lane);
+        const v3 c = pe_illuminate<SKIP>(e, S, pos, q[3], on, lane);
         r[0] = c.x; r[1] = c.y; r[2] = c.z;
     }
 }
@@ -231,9 +311,9 @@ __device__ __forceinline__ void pe_point(const FramePlanet& F, WaveCache& S, con
 constexpr int pe_in_width(int fn) { return fn <= PE_MARCH ? 6 : (fn == PE_CLOUDS || fn == PE_ILLUM) ? 4 : 3; }
 constexpr int pe_out_width(int fn) { return fn <= PE_MARCH ? 4 : fn <= PE_MAP_DETAIL ? 2 : fn == PE_CLOUDS ? 1 : 3; }
 
-template <int FN, bool PLAIN>
-__global__ void __launch_bounds__(64, PE_MIN_WAVES) k_planet_eval(FramePlanet F, const float* __restrict__ in, float* __restrict__ out, size_t n,
-                                                                  unsigned* __restrict__ counts) {
+// one wave of either entry: e = PeLit over k_planet_eval's FramePlanet, PeWorld over k_planet_world_eval's FramePlanetWorld
+template <int FN, bool PLAIN, class E>
+__device__ __forceinline__ void pe_wave(const E& e, const float* __restrict__ in, float* __restrict__ out, size_t n, unsigned* __restrict__ counts) {
     constexpr int WIN = pe_in_width(FN), WOUT = pe_out_width(FN);
     __shared__ WaveCache cache[1];
     const int lane = threadIdx.x & 63;
@@ -254,12 +334,11 @@ __global__ void __launch_bounds__(64, PE_MIN_WAVES) k_planet_eval(FramePlanet F,
     } else if (FN <= PE_MARCH) {
         const v3 ro = V3(q[0], q[1], q[2]), rd = V3(q[3], q[4], q[5]);
         PeRay R;
-        pe_intersect(ro, rd, on, R);
-        // `tame` (the note at the top): on the wave's own origins, hit origins and directions
-        if (!PLAIN) fast = !wave_any(on && !(pe_within(ro, 256.f) && (!R.hit_atm || (pe_within(R.hit_o, 4.f) && pe_within(rd, 4.f)))));
+        pe_intersect(e, ro, rd, on, R);
+        if (!PLAIN) fast = !wave_any(on && !e.ray_tame(ro, R.hit_atm, R.hit_o, rd));
         if (wave_any(R.hit_atm)) {
-            if (fast) pe_march<true, FN == PE_RENDER>(F, S, rd, R, lane);
-            else pe_march<false, FN == PE_RENDER>(F, S, rd, R, lane);
+            if (fast) pe_march<true, FN == PE_RENDER>(e, S, rd, R, lane);
+            else pe_march<false, FN == PE_RENDER>(e, S, rd, R, lane);
         }
         if (FN == PE_MARCH) {
             r[0] = R.t_hit; r[1] = R.t; r[2] = R.df.x; r[3] = R.df.y;
@@ -268,27 +347,38 @@ __global__ void __launch_bounds__(64, PE_MIN_WAVES) k_planet_eval(FramePlanet F,
             v3 col = V3(0, 0, 0);
             if (wave_any(hitl)) {
                 // the point of the last committed step, as the march computed it
-                const v3 pos = mul(F.rot, (R.hit_o + R.t_pos * rd) - V3(0, 0, 0));
-                const v3 lp = mul(F.rot_t, pos);
+                const v3 pos = mul(e.rot(), (R.hit_o + R.t_pos * rd) - V3(0, 0, 0));
+                const v3 lp = mul(e.rot_t(), pos);
                 if (fast && wave_any(hitl && !(dot(lp, lp) >= 1e-20f))) fast = false;      // normalize(lp) of the shadow march
-                if (fast) col = pe_shade<true>(F, S, pos, R.df.y, R.radiance, R.alpha, hitl, lane);
-                else col = pe_shade<false>(F, S, pos, R.df.y, R.radiance, R.alpha, hitl, lane);
+                if (fast) col = pe_shade<true>(e, S, pos, R.df.y, R.radiance, R.alpha, hitl, lane);
+                else col = pe_shade<false>(e, S, pos, R.df.y, R.radiance, R.alpha, hitl, lane);
             }
             if (R.hit_atm && !hitl) col = abs3(mix3(planet_background(rd), V3s(R.radiance), R.alpha));   // :364-366
             if (!R.hit_atm) col = planet_background(rd);            // :316-320
             r[0] = col.x; r[1] = col.y; r[2] = col.z; r[3] = R.hit_atm ? R.alpha : 0.f;
         }
     } else {
-        // `tame` for a point: within 16 per coordinate; clouds_density's height within 2^100 (band's two quotients)
-        if (!PLAIN) fast = !wave_any(on && !(pe_within(V3(q[0], q[1], q[2]), 16.f) && (FN != PE_CLOUDS || abs_(q[3]) <= 1.2676506e30f)));
-        if (fast) pe_point<FN, true>(F, S, q, on, lane, r);
-        else pe_point<FN, false>(F, S, q, on, lane, r);
+        if (!PLAIN) fast = !wave_any(on && !e.point_tame(V3(q[0], q[1], q[2]), FN == PE_CLOUDS, q[3]));
+        if (fast) pe_point<FN, true>(e, S, q, on, lane, r);
+        else pe_point<FN, false>(e, S, q, on, lane, r);
     }
     if (on) {
 #pragma unroll
         for (int k = 0; k < WOUT; ++k) out[(size_t)WOUT * i + k] = r[k];
     }
     if (counts && lane == 0) atomicAdd(counts + (fast ? 0 : 1), 1u);
+}
+
+template <int FN, bool PLAIN>
+__global__ void __launch_bounds__(64, PE_MIN_WAVES) k_planet_eval(FramePlanet F, const float* __restrict__ in, float* __restrict__ out, size_t n,
+                                                                  unsigned* __restrict__ counts) {
+    pe_wave<FN, PLAIN>(PeLit{F}, in, out, n, counts);
+}
+// sbx_planet_world_eval: the same wave over the caller's world (the camera of F is not read)
+template <int FN, bool PLAIN>
+__global__ void __launch_bounds__(64, PE_MIN_WAVES) k_planet_world_eval(FramePlanetWorld F, const float* __restrict__ in, float* __restrict__ out, size_t n,
+                                                                        unsigned* __restrict__ counts) {
+    pe_wave<FN, PLAIN>(PeWorld{F}, in, out, n, counts);
 }
 
 template <int FN>
@@ -310,6 +400,28 @@ void launch_planet_eval(int fn, const FramePlanet& F, bool plain, const float* i
     case PE_CLOUDS: pe_launch<PE_CLOUDS>(F, plain, in, out, n, counts, s); break;
     case PE_ILLUM: pe_launch<PE_ILLUM>(F, plain, in, out, n, counts, s); break;
     default: pe_launch<PE_BACKGROUND>(F, plain, in, out, n, counts, s); break;
+    }
+}
+
+template <int FN>
+static void pe_world_launch(const FramePlanetWorld& F, bool plain, const float* in, float* out, size_t n, unsigned* counts, hipStream_t s) {
+    const dim3 grid((unsigned)((n + 63) / 64));
+    if (plain) hipLaunchKernelGGL((k_planet_world_eval<FN, true>), grid, dim3(64), 0, s, F, in, out, n, counts);
+    else hipLaunchKernelGGL((k_planet_world_eval<FN, false>), grid, dim3(64), 0, s, F, in, out, n, counts);
+}
+
+// sbx_planet_world_eval: launch_planet_eval's contract over F = build_planet_world of the caller's block.  plain: sbx_set_variant 1; an
+// untame block (F.tame == 0) sends every wave of the other kernel to its plain form as well.
+void launch_planet_world_eval(int fn, const FramePlanetWorld& F, bool plain, const float* in, float* out, size_t n, unsigned* counts, hipStream_t s) {
+    switch (fn) {
+    case PE_RENDER: pe_world_launch<PE_RENDER>(F, plain, in, out, n, counts, s); break;
+    case PE_MARCH: pe_world_launch<PE_MARCH>(F, plain, in, out, n, counts, s); break;
+    case PE_MAP: pe_world_launch<PE_MAP>(F, plain, in, out, n, counts, s); break;
+    case PE_MAP_DETAIL: pe_world_launch<PE_MAP_DETAIL>(F, plain, in, out, n, counts, s); break;
+    case PE_NORMAL: pe_world_launch<PE_NORMAL>(F, plain, in, out, n, counts, s); break;
+    case PE_CLOUDS: pe_world_launch<PE_CLOUDS>(F, plain, in, out, n, counts, s); break;
+    case PE_ILLUM: pe_world_launch<PE_ILLUM>(F, plain, in, out, n, counts, s); break;
+    default: pe_world_launch<PE_BACKGROUND>(F, plain, in, out, n, counts, s); break;
     }
 }
 

@@ -8,7 +8,7 @@
 
 namespace sbx {
 
-constexpr int SBX_APP_COUNT = SBX_APP_ATMOSPHERE_AIR + 1;
+constexpr int SBX_APP_COUNT = SBX_APP_PLANET_WORLD + 1;
 // (sbx_debug_tile_order, include/sbx_test.h, answers for every app — the builds after SBX_APP_FUNC that have an order grid below
 // included; an app without one never has a table: 0 tables, 0 launches, nothing to copy)
 
@@ -22,7 +22,7 @@ constexpr int SBX_APP_COUNT = SBX_APP_ATMOSPHERE_AIR + 1;
 //                      the table's key — a scene that stands still gets its table, a moving one never does
 enum { TILE_SCENE_FREE = 0, TILE_SCENE_REFRESH = 1, TILE_SCENE_KEYED = 2 };
 
-enum AuxKind { AUX_NONE, AUX_CLOUDS, AUX_SDF_AO, AUX_CLOUDS_UE4, AUX_RT_SCENE, AUX_SDF_SCENE, AUX_EGG_POSE, AUX_VINYL_DECK, AUX_ATM_AIR };   // which block `aux` points to: sbx_aux_clouds, sbx_aux_sdf_ao, sbx_aux_clouds_ue4, sbx_aux_raytracer_scene, sbx_aux_sdf_scene, sbx_aux_egg_pose, sbx_aux_vinyl_deck, sbx_aux_atmosphere_air
+enum AuxKind { AUX_NONE, AUX_CLOUDS, AUX_SDF_AO, AUX_CLOUDS_UE4, AUX_RT_SCENE, AUX_SDF_SCENE, AUX_EGG_POSE, AUX_VINYL_DECK, AUX_ATM_AIR, AUX_PLANET_WORLD };   // which block `aux` points to: sbx_aux_clouds, sbx_aux_sdf_ao, sbx_aux_clouds_ue4, sbx_aux_raytracer_scene, sbx_aux_sdf_scene, sbx_aux_egg_pose, sbx_aux_vinyl_deck, sbx_aux_atmosphere_air, sbx_aux_planet_world
 
 struct AppTraits {
     AuxKind aux;
@@ -71,6 +71,7 @@ constexpr AppTraits kApps[] = {
     /* SBX_APP_EGG_POSE          */ {AUX_EGG_POSE, false, false, egg_grid, TILE_SCENE_KEYED},
     /* SBX_APP_VINYL_DECK        */ {AUX_VINYL_DECK, false, false, vinyl_grid, TILE_SCENE_KEYED},
     /* SBX_APP_ATMOSPHERE_AIR    */ {AUX_ATM_AIR, false, false, nullptr, TILE_SCENE_FREE},
+    /* SBX_APP_PLANET_WORLD      */ {AUX_PLANET_WORLD, false, false, nullptr, TILE_SCENE_FREE},   // (as SBX_APP_PLANET: no order grid, so no table the block could be a key of)
 };
 static_assert(sizeof(kApps) / sizeof(kApps[0]) == SBX_APP_COUNT, "every value of enum sbx_app needs its row in kApps");
 
@@ -87,6 +88,7 @@ inline int app_aux_bytes(int app) {
     case AUX_EGG_POSE: return (int)sizeof(sbx_aux_egg_pose);
     case AUX_VINYL_DECK: return (int)sizeof(sbx_aux_vinyl_deck);
     case AUX_ATM_AIR: return (int)sizeof(sbx_aux_atmosphere_air);
+    case AUX_PLANET_WORLD: return (int)sizeof(sbx_aux_planet_world);
     default: return 0;
     }
 }
@@ -127,6 +129,12 @@ inline sbx_aux_vinyl_deck aux_vinyl_deck(const void* aux, const sbx_uniforms& un
 inline sbx_aux_atmosphere_air aux_atmosphere_air(const void* aux, const sbx_uniforms& uni) {
     sbx_aux_atmosphere_air a;
     if (aux) a = *(const sbx_aux_atmosphere_air*)aux; else sbx_atmosphere_air_default(&uni, 0, &a);
+    return a;
+}
+// SBX_APP_PLANET_WORLD: the caller's world, or app_planet.h's numbers with the spins of these uniforms
+inline sbx_aux_planet_world aux_planet_world(const void* aux, const sbx_uniforms& uni) {
+    sbx_aux_planet_world a;
+    if (aux) a = *(const sbx_aux_planet_world*)aux; else sbx_planet_world_default(&uni, &a);
     return a;
 }
 

@@ -30,7 +30,7 @@ static int bind_fault_word(int device) {
     unsigned* dev = nullptr;
     if (hipHostGetDevicePointer((void**)&dev, g_fault_word[device], 0) != hipSuccess) return SBX_ERR_HIP;
     if (bind_fault_clouds(dev) != hipSuccess || bind_fault_clouds_ue4(dev) != hipSuccess || bind_fault_planet(dev) != hipSuccess ||
-        bind_fault_planet_eval(dev) != hipSuccess)
+        bind_fault_planet_eval(dev) != hipSuccess || bind_fault_planet_world(dev) != hipSuccess)
         return SBX_ERR_HIP;
     return SBX_OK;
 }
@@ -214,6 +214,11 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
         AA = aux_atmosphere_air(aux, *uni);
         if (const char* why = atmosphere_air_check(AA, true)) return fail(ctx, SBX_ERR_ARG, why);
     }
+    sbx_aux_planet_world PW;
+    if (T.aux == AUX_PLANET_WORLD) {
+        PW = aux_planet_world(aux, *uni);
+        if (const char* why = planet_world_check(PW)) return fail(ctx, SBX_ERR_ARG, why);
+    }
     if (T.noise_volumes && !ctx->noise.shape) return fail(ctx, SBX_ERR_ARG, "APP_CLOUDS with USE_NOISE_TEX needs sbx_set_noise_volume first");
     const bool capturing = stream_is_capturing(s);
     TimingPair* tp = nullptr;
@@ -320,6 +325,27 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     case SBX_APP_PLANET_CLOSEUP: launch_planet(build_planet(*uni, false, PLANET_CLOSEUP), M, rgba, s, cull_variant, PLANET_CLOSEUP); break;
     case SBX_APP_PLANET_CLOUDLESS: launch_planet(build_planet(*uni), M, rgba, s, cull_variant, PLANET_CLOUDLESS); break;
     case SBX_APP_PLANET_UNLIT: launch_planet(build_planet(*uni), M, rgba, s, cull_variant, PLANET_UNLIT); break;
+    // app_planet.h over the caller's world (validated above; u_time is not read, so its tameness does not enter: the block's does).
+    // The tier (sbx_frames.hip planet_world_tier, kern_planet_world.hip).  LITERAL: SBX_APP_PLANET's kernels over the block's camera,
+    // angles and sun — the shipped instantiation, short roots and all, only for the shipped camera bit for bit; any other camera takes
+    // PLANET_CLOSEUP's code (the IEEE root: sbx_planet.h PL_SQRT_RS), and a camera or angles outside planet_world_camera_tame's bounds
+    // k_planet<false>.  Otherwise k_planet_world, fast for a tame block; under sbx_set_variant 1 k_planet_world<false> for every block
+    case SBX_APP_PLANET_WORLD: {
+        const int tier = planet_world_tier(PW, ctx->variant);
+        if (tier == PLANET_WORLD_LITERAL) {
+            const FramePlanet F = build_planet_world_literal(*uni, PW);
+            sbx_aux_planet_world D;
+            sbx_planet_world_default(uni, &D);
+            const bool shipped_cam = std::memcmp(PW.eye, D.eye, 4 * sizeof(float)) == 0 && std::memcmp(PW.look_at, D.look_at, 3 * sizeof(float)) == 0;
+            const bool skip = planet_world_camera_tame(PW, F);                  // (the variant is not 1 here: planet_world_tier)
+            (skip ? ctx->stats.planet_world_literal : ctx->stats.planet_world_plain).fetch_add(1, std::memory_order_relaxed);
+            launch_planet(F, M, rgba, s, skip ? ctx->variant : 1, shipped_cam ? PLANET_DEFAULT : PLANET_CLOSEUP);
+        } else {
+            (tier == PLANET_WORLD_RUNTIME ? ctx->stats.planet_world_runtime : ctx->stats.planet_world_plain).fetch_add(1, std::memory_order_relaxed);
+            launch_planet_world(build_planet_world(*uni, PW), tier == PLANET_WORLD_RUNTIME, M, rgba, s);
+        }
+        break;
+    }
     case SBX_APP_VINYL: launch_vinyl(build_vinyl(*uni, 60), M, rgba, s, sdf_variant); break;
     case SBX_APP_VINYL_GPU: launch_vinyl(build_vinyl(*uni, 180), M, rgba, s, sdf_variant); break;
     // the builds of app_vinyl.h's three switches (include/sbx.h), 60 steps each: one frame of its own for the shipped kernels, two kernel
@@ -622,6 +648,14 @@ int sbx_debug_clouds_hashtab_read(sbx_ctx* ctx, size_t first, size_t count, floa
 int sbx_debug_raytracer_scene_launches(sbx_ctx* ctx, uint64_t* launches) {
     if (!ctx || !launches) return SBX_ERR_ARG;
     *launches = ctx->stats.rt_scene_launches.load(std::memory_order_relaxed);
+    return SBX_OK;
+}
+
+int sbx_debug_planet_world_launches(sbx_ctx* ctx, uint64_t counts[3]) {
+    if (!ctx || !counts) return SBX_ERR_ARG;
+    counts[0] = ctx->stats.planet_world_literal.load(std::memory_order_relaxed);
+    counts[1] = ctx->stats.planet_world_runtime.load(std::memory_order_relaxed);
+    counts[2] = ctx->stats.planet_world_plain.load(std::memory_order_relaxed);
     return SBX_OK;
 }
 

@@ -142,7 +142,8 @@ struct Stats {
     std::atomic<uint64_t> launches{0}, frames{0}, points{0};
     std::atomic<uint64_t> rt_scene_launches{0};   // k_raytracer_scene launches (sbx_debug_raytracer_scene_launches; never reset)
     std::atomic<uint64_t> atm_air_launches{0}, atm_air_literal{0}, atm_air_plain{0};   // SBX_APP_ATMOSPHERE_AIR launches, those of the literal tier, those of the plain kernel (sbx_debug_atmosphere_air_launches; never reset)
-    std::atomic<uint64_t> vinyl_deck_launches{0}, vinyl_deck_untame{0};   // SBX_APP_VINYL_DECK launches, and those an untame deck sent to the reference form (sbx_debug_vinyl_deck_launches; never reset)
+    std::atomic<uint64_t> planet_world_literal{0}, planet_world_runtime{0}, planet_world_plain{0};   // SBX_APP_PLANET_WORLD launches by tier; plain counts k_planet<false> and k_planet_world<false> alike (sbx_debug_planet_world_launches; never reset)
+    std::atomic<uint64_t> vinyl_deck_launches{0}, vinyl_deck_untame{0};  // SBX_APP_VINYL_DECK launches, and those an untame deck sent to the reference form (sbx_debug_vinyl_deck_launches; never reset)
     std::atomic<uint64_t> egg_pose_launches{0}, egg_pose_untame{0};       // SBX_APP_EGG_POSE launches, and those an untame pose sent to the reference form (sbx_debug_egg_pose_launches; never reset)
 };
 
@@ -252,6 +253,15 @@ FrameVinyl build_vinyl_deck(const sbx_uniforms& U, const sbx_aux_vinyl_deck& A, 
 VinylShade vinyl_shade_of(const sbx_aux_vinyl_deck& A);
 bool vinyl_deck_tame(const sbx_aux_vinyl_deck& A, const FrameVinyl& F);
 FramePlanet build_planet(const sbx_uniforms& U, bool atm_sky = false, int build = PLANET_DEFAULT);   // build: PLANET_* (sbx_frame.h); PLANET_CLOSEUP is the other camera
+// SBX_APP_PLANET_WORLD (sbx_frames.hip): why a block is refused (nullptr: it is not), the two frame blocks made of it, the tier a launch
+// takes, and the host's two domain tests (kern_planet_world.hip says what each is for)
+enum { PLANET_WORLD_LITERAL = 0, PLANET_WORLD_RUNTIME = 1, PLANET_WORLD_PLAIN = 2 };
+const char* planet_world_check(const sbx_aux_planet_world& W);
+FramePlanet build_planet_world_literal(const sbx_uniforms& U, const sbx_aux_planet_world& W);
+FramePlanetWorld build_planet_world(const sbx_uniforms& U, const sbx_aux_planet_world& W);
+int planet_world_tier(const sbx_aux_planet_world& W, int variant);
+bool planet_world_tame(const sbx_aux_planet_world& W);
+bool planet_world_camera_tame(const sbx_aux_planet_world& W, const FramePlanet& F);
 FrameCloudsBest build_clouds_best(const sbx_uniforms& U);
 FrameCloudsUe4 build_clouds_ue4(const sbx_uniforms& U, const sbx_aux_clouds_ue4& A);
 Frame2d build_2d(const sbx_uniforms& U);

@@ -202,6 +202,9 @@ void launch_assemble_peers(int width, int height, int block_rows, int nranks, in
                            int channels, const float* peers, float* frame, hipStream_t s);
 hipError_t bind_fault_clouds(unsigned* word);
 hipError_t bind_fault_clouds_ue4(unsigned* word);
+// SBX_APP_PLANET_WORLD's run-time tier (kern_planet_world.hip k_planet_world): fast = a tame block under a variant other than 1
+void launch_planet_world(const FramePlanetWorld& F, bool fast, const RowMap& M, float* out, hipStream_t s);
+hipError_t bind_fault_planet_world(unsigned* word);
 hipError_t bind_fault_planet(unsigned* word);
 hipError_t bind_fault_planet_eval(unsigned* word);
 void launch_raise_fault(unsigned code, hipStream_t s);
@@ -244,6 +247,8 @@ void launch_clouds_eval(int fn, const FrameClouds& F, bool plain, const CloudsHa
 // 5 clouds_density / 6 illuminate / 7 background over F = build_planet of u_time (its camera is not read); plain = the SKIP = false
 // statement for every wave; counts = NULL or two zeroed device words (waves with every guarded short form on, waves that fell back)
 void launch_planet_eval(int fn, const FramePlanet& F, bool plain, const float* in, float* out, size_t n, unsigned* counts, hipStream_t s);
+// sbx_planet_world_eval: the same functions over F = build_planet_world of the caller's block (its camera is not read)
+void launch_planet_world_eval(int fn, const FramePlanetWorld& F, bool plain, const float* in, float* out, size_t n, unsigned* counts, hipStream_t s);
 // sbx_egg_eval (kern_egg_eval.hip): fn 0 sdf / 1 sdf_normal / 2 shadowmarch / 3 render_scene over build_egg_pose's frame; variant as
 // launch_egg's (1 = the reference form); counts: NULL, or two zeroed device words (witnessed waves, re-run waves).  launch_ik_eval: "ik_solver"
 void launch_egg_eval(int fn, const FrameEgg& F, int variant, const float* in, float* out, size_t n, unsigned* counts, hipStream_t s);

@@ -136,6 +136,21 @@ auto planet_eval_launch(const sbx_ctx* ctx, int id, float u_time, const float* i
         launch_planet_eval(id, build_planet(frame_1x1(u_time)), plain, in, out, n, counts, s);
     };
 }
+// sbx_planet_world_eval: the same names; the block is checked as SBX_APP_PLANET_WORLD checks it and copied here (host memory, read
+// during the call).  Its eye, look_at and fov land in a camera no kernel of this entry reads.  plain: sbx_set_variant 1; the host's
+// block test travels in the frame block (FramePlanetWorld.tame) and joins the wave-wide tests there (kern_planet_eval.hip PeWorld)
+int planet_world_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_planet_world* world, const float* in, const float* out, size_t n, int& id) {
+    static const char* const names[] = {"render", "terrain_march", "sdf_terrain_map", "sdf_terrain_map_detail", "sdf_terrain_normal",
+                                        "clouds_density", "illuminate", "background"};
+    id = name_id(fn, names);
+    return eval_args(ctx, fn, id, "unknown planet function", !world ? "NULL argument" : planet_world_check(*world), "more than 2^31 elements", in, out, n);
+}
+auto planet_world_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_planet_world* world, const float* in, float* out, size_t n) {
+    const sbx_aux_planet_world W = *world;
+    return [=](unsigned* counts, hipStream_t s) {
+        launch_planet_world_eval(id, build_planet_world(frame_1x1(0.f), W), ctx->variant == 1, in, out, n, counts, s);
+    };
+}
 
 // id 0 = "ik_solver", else 1 + launch_egg_eval's fn; every function but ik_solver needs a pose, whatever n is
 int egg_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, const float* in, const float* out, size_t n, int& id) {
@@ -319,6 +334,21 @@ int sbx_debug_planet_eval(sbx_ctx* ctx, const char* fn, float u_time, const floa
     const int rc = planet_eval_args(ctx, fn, in, out, n, id);
     if (rc != SBX_OK) return rc;
     return counted_launch<unsigned, 2>(ctx, "planet_eval (counted)", n, counts_host, stream, planet_eval_launch(ctx, id, u_time, in, out, n));
+}
+
+int sbx_planet_world_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_planet_world* world, const float* in, float* out, size_t n, void* stream) {
+    int id = -1;
+    const int rc = planet_world_eval_args(ctx, fn, world, in, out, n, id);
+    if (rc != SBX_OK || n == 0) return rc;
+    return plain_launch(ctx, "planet_world_eval launch", stream, planet_world_eval_launch(ctx, id, world, in, out, n));
+}
+
+int sbx_debug_planet_world_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_planet_world* world, const float* in, float* out, size_t n,
+                                unsigned counts_host[2], void* stream) {
+    int id = -1;
+    const int rc = planet_world_eval_args(ctx, fn, world, in, out, n, id);
+    if (rc != SBX_OK) return rc;
+    return counted_launch<unsigned, 2>(ctx, "planet_world_eval (counted)", n, counts_host, stream, planet_world_eval_launch(ctx, id, world, in, out, n));
 }
 
 int sbx_egg_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_egg_pose* pose, const float* in, float* out, size_t n, void* stream) {

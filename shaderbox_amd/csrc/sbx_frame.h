@@ -280,6 +280,48 @@ struct FramePlanet {
 // parameters (kern_planet.hip); CLOSEUP is also another camera in the frame block (build_planet).  FramePlanet is the same type in
 // all four; none of the three is combined with atm_sky.
 enum { PLANET_DEFAULT = 0, PLANET_CLOUDLESS = 1, PLANET_UNLIT = 2, PLANET_CLOSEUP = 3 };
+// SBX_APP_PLANET_WORLD's run-time tier (kern_planet_world.hip k_planet_world): FramePlanet's fields built from the caller's block
+// (include/sbx.h sbx_aux_planet_world) plus the numbers k_planet has as literals, and what the host derives from them in the header's
+// binary32 order (sbx_frames.hip build_planet_world).  The (d, r) pairs are a divisor and RN(1 / d) for div3_ of sbx_math.h.
+// what only the shading of a ground hit reads: the kernel fetches it from its argument block there, not at its start, so that these 37
+// words hold no SGPRs across the marches (kern_planet_world.hip pw_late)
+struct PlanetWorldShade {
+    m3 rot_t;                               // transpose(rot) :356
+    v3 L;                                   // rot * sun_dir, the sun as given
+    v3 key_color;
+    v3 c_water, c_water_half, c_grass, c_beach, c_rock, c_snow;    // c_water_half: c_water / 2. (:284)
+    float l_water, l_shore, l_grass, l_rock;
+};
+// what the terrain march and the detail maps read, and what the two cloud marches read: fetched where each begins, as `shade` is
+struct PlanetWorldTerrain {
+    m3 rot;                                 // :308
+    v3 terrain_offset;
+    float max_height, max_height_r;         // :20 and RN(1 / it)
+    float max_ray_dist;                     // max_height * 4 (:21)
+    int terr_steps;
+};
+struct PlanetWorldCloud {
+    m3 rot_cloud;                           // :309
+    v3 cloud_offset;
+    float max_height, max_height_r;
+    float band0, band1, band2;              // :114
+    float band_d01, band_r01, band_d12, band_r12;   // band1 - band0, band2 - band1
+    float cov, cov_hi, cov_d, cov_r;        // cld_coverage, cld_coverage + cld_fuzzy (:112), their difference
+    float neg_absorb;                       // -vol_coeff_absorb (:87)
+    float cloud_light, cloud_light_r;       // :76
+    float t_step_cloud, t_step_shadow;      // max_ray_dist / float(cloud_steps) (:128); max_height / float(shadow_steps) (:149)
+    float shell_lo2, shell_hi2;             // a cloud-march sample with |o|^2 below / above lies outside the band's shell (0 / inf: no such claim)
+    int cloud_steps, shadow_steps;
+};
+struct FramePlanetWorld {
+    Camera cam;
+    float atm_radius;                       // 1 + max_height (:311-312)
+    float hit2_max;                         // (atm_radius + 1)^2: the wave-wide test on |hit_o|^2
+    int tame;                               // planet_world_tame: the block lies in the domain of the short forms (kern_planet_world.hip)
+    PlanetWorldTerrain terr;
+    PlanetWorldCloud cloud;
+    PlanetWorldShade shade;
+};
 
 // ---- "clouds_best" (src/app_clouds_best.h, the stand-alone cloud shader) ------
 // The march runs along projection = dir / dir.y, whose y component is exactly 1, from origin.y = eye.y + 100:

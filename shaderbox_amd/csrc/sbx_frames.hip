@@ -5,6 +5,7 @@
 // is compiled with the library's flags, -ffp-contract=off among them, because they are part of that spec.
 #include "sbx_ctx.h"
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 using namespace sbx;
@@ -673,6 +674,155 @@ FramePlanet build_planet(const sbx_uniforms& U, bool atm_sky, int build) {
     return F;
 }
 
+// ---- SBX_APP_PLANET_WORLD (include/sbx.h sbx_aux_planet_world; the tiers and their domains: kern_planet_world.hip) ----------------
+// the header's numbers (app_planet.h:20,55-56,68,76,107-114,127,148,165,180,224,258-268,288,307-309,369) with the two spins of u_time
+static void planet_default_world(const sbx_uniforms& U, sbx_aux_planet_world& W) {
+    auto put = [](float* d, v3 v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; };
+    std::memset(&W, 0, sizeof(W));
+    put(W.eye, V3(0, 0, -2.5f)); W.fov = tan_(radians_(30.f));
+    put(W.look_at, V3(0, 0, 2)); W.tilt_deg = 27.f;
+    put(W.sun_dir, normalize(V3(1, 1, 0))); W.spin_deg = U.u_time * -12.f;
+    put(W.key_color, V3(7, 5, 3)); W.cloud_spin_deg = U.u_time * 8.f;
+    put(W.terrain_offset, V3(1.9489f, 2.435f, .5483f)); W.max_height = .4f;
+    put(W.cloud_offset, V3(.35f, 13.35f, 2.67f)); W.cld_coverage = .29475675f;
+    put(W.band, V3(.2f, .35f, .65f)); W.cld_fuzzy = .0335f;
+    put(W.c_water, V3(.015f, .110f, .455f)); W.l_water = .05f;
+    put(W.c_grass, V3(.086f, .132f, .018f)); W.l_shore = .17f;
+    put(W.c_beach, V3(.153f, .172f, .121f)); W.l_grass = .211f;
+    put(W.c_rock, V3(.080f, .050f, .030f)); W.l_rock = .351f;
+    put(W.c_snow, V3(.600f, .600f, .600f)); W.absorb = 30.034f;
+    W.cloud_light = .055f;
+    W.terr_steps = 120; W.cloud_steps = 75; W.shadow_steps = 5;
+}
+const char* planet_world_check(const sbx_aux_planet_world& W) {
+    static_assert(sizeof(sbx_aux_planet_world) == 224, "sbx_aux_planet_world is 224 bytes (include/sbx.h)");
+    if (W.terr_steps < 1 || W.terr_steps > 512) return "planet world: terr_steps must lie in 1..512";
+    if (W.cloud_steps < 1 || W.cloud_steps > 256) return "planet world: cloud_steps must lie in 1..256";
+    if (W.shadow_steps < 1 || W.shadow_steps > 32) return "planet world: shadow_steps must lie in 1..32";
+    if ((W.reserved[0] | W.reserved[1] | W.reserved[2] | W.reserved[3]) != 0u) return "planet world: the reserved words must be 0";
+    return nullptr;
+}
+// FramePlanet from the block: what build_planet makes of the header's literals, made of the caller's (the literal tier's frame)
+FramePlanet build_planet_world_literal(const sbx_uniforms& U, const sbx_aux_planet_world& W) {
+    FramePlanet F;
+    F.atm_sky = 0;
+    F.atm_sun = V3(0, 0, 0);                                           // (read with atm_sky only)
+    F.cam = make_camera(U.u_res[0], U.u_res[1], W.fov, V3(W.eye[0], W.eye[1], W.eye[2]), V3(W.look_at[0], W.look_at[1], W.look_at[2]));
+    const m3 rot_y = rotate_around_y(W.tilt_deg);                      // :307
+    F.rot = mul(rotate_around_x(W.spin_deg), rot_y);                   // :308
+    F.rot_cloud = mul(rotate_around_x(W.cloud_spin_deg), rot_y);       // :309
+    F.rot_t = transpose(F.rot);                                        // :356
+    F.L = mul(F.rot, V3(W.sun_dir[0], W.sun_dir[1], W.sun_dir[2]));    // :288, the sun as given
+    return F;
+}
+static bool pw_in(float v, float lo, float hi) { return v >= lo && v <= hi; }                    // (a NaN is in no interval)
+static bool pw_zero_or_mag(float v, float lo, float hi) { return v == 0.f || pw_in(std::fabs(v), lo, hi); }
+// columns of length 1 and at right angles to 1e-5 (a NaN or inf entry fails)
+static bool pw_orthonormal(const m3& m) {
+    const v3 c[3] = {m.c0, m.c1, m.c2};
+    for (int i = 0; i < 3; ++i)
+        for (int j = i; j < 3; ++j) {
+            const double d = (double)c[i].x * c[j].x + (double)c[i].y * c[j].y + (double)c[i].z * c[j].z;
+            if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-5)) return false;
+        }
+    return true;
+}
+// the angles and matrices of a frame: what tame_time (sbx_capi.hip) proves of u_time for SBX_APP_PLANET — the spec's sin / cos reduce
+// their argument accurately below 2^30 rad; 1e9 degrees are 1.75e7 rad — and, checked rather than argued, the products orthonormal
+static bool pw_rotations_tame(const sbx_aux_planet_world& W, const FramePlanet& F) {
+    return pw_in(std::fabs(W.tilt_deg), 0.f, 1e9f) && pw_in(std::fabs(W.spin_deg), 0.f, 1e9f) && pw_in(std::fabs(W.cloud_spin_deg), 0.f, 1e9f) &&
+           pw_orthonormal(F.rot) && pw_orthonormal(F.rot_cloud);
+}
+// The literal tier's SKIP kernel (k_planet<true, false, PLANET_CLOSEUP>, or the shipped instantiation for the shipped camera): its
+// short forms want every march position finite and small (sbx_planet.h PL_MED3, PL_EXP4K; kern_planet_eval.hip's 256 / 4 / 18.6
+// chain).  eye and look_at within 256 per coordinate, |fov| <= 16 and a camera whose fwd, up, right came out finite with |fwd| = 1 to
+// 1e-5 (eye == look_at gives NaN and fails): rd = normalize(fwd + up y + right x) is then a unit vector for every finite point_cam,
+// fwd being at right angles to both; hit_o = eye + rd t0 lies on the atmosphere sphere of radius 1.4 up to the cancellation in
+// d2 = |rc|^2 - tca^2 (|rc|^2 <= 2e5, half an ulp .008: thc off by at most sqrt(.02), hit_o within .2 of the sphere or of the closest
+// approach) — within 4 per coordinate, rd within 1, which is the chain's premise: |p| <= 18.6 at every sample.
+bool planet_world_camera_tame(const sbx_aux_planet_world& W, const FramePlanet& F) {
+    for (int k = 0; k < 3; ++k) if (!pw_in(std::fabs(W.eye[k]), 0.f, 256.f) || !pw_in(std::fabs(W.look_at[k]), 0.f, 256.f)) return false;
+    if (!pw_in(std::fabs(W.fov), 0.f, 16.f)) return false;
+    const v3 v[3] = {F.cam.fwd, F.cam.up, F.cam.right};
+    for (int k = 0; k < 3; ++k) if (!std::isfinite(v[k].x) || !std::isfinite(v[k].y) || !std::isfinite(v[k].z)) return false;
+    const double ff = (double)v[0].x * v[0].x + (double)v[0].y * v[0].y + (double)v[0].z * v[0].z;
+    return std::fabs(ff - 1.0) <= 1e-5 && pw_rotations_tame(W, F);
+}
+FramePlanetWorld build_planet_world(const sbx_uniforms& U, const sbx_aux_planet_world& W) {
+    auto get = [](const float* s) { return V3(s[0], s[1], s[2]); };
+    const FramePlanet P = build_planet_world_literal(U, W);
+    FramePlanetWorld F;
+    F.cam = P.cam;
+    PlanetWorldTerrain& T = F.terr;
+    PlanetWorldCloud& C = F.cloud;
+    PlanetWorldShade& S = F.shade;
+    T.rot = P.rot; C.rot_cloud = P.rot_cloud; S.rot_t = P.rot_t; S.L = P.L;
+    S.key_color = get(W.key_color);
+    T.terrain_offset = get(W.terrain_offset); C.cloud_offset = get(W.cloud_offset);
+    S.c_water = get(W.c_water); S.c_grass = get(W.c_grass); S.c_beach = get(W.c_beach); S.c_rock = get(W.c_rock); S.c_snow = get(W.c_snow);
+    S.c_water_half = S.c_water / 2.f;                                  // :284
+    S.l_water = W.l_water; S.l_shore = W.l_shore; S.l_grass = W.l_grass; S.l_rock = W.l_rock;
+    T.max_height = C.max_height = W.max_height; T.max_height_r = C.max_height_r = 1.0f / W.max_height;
+    T.max_ray_dist = W.max_height * 4.f;                               // :21
+    F.atm_radius = 1.f + W.max_height;                                 // :311-312
+    C.band0 = W.band[0]; C.band1 = W.band[1]; C.band2 = W.band[2];
+    C.band_d01 = C.band1 - C.band0; C.band_r01 = 1.0f / C.band_d01;
+    C.band_d12 = C.band2 - C.band1; C.band_r12 = 1.0f / C.band_d12;
+    C.cov = W.cld_coverage; C.cov_hi = W.cld_coverage + W.cld_fuzzy;   // :112
+    C.cov_d = C.cov_hi - C.cov; C.cov_r = 1.0f / C.cov_d;
+    C.neg_absorb = -W.absorb;                                          // :87
+    C.cloud_light = W.cloud_light; C.cloud_light_r = 1.0f / W.cloud_light;
+    C.t_step_cloud = T.max_ray_dist / float(W.cloud_steps);            // :128
+    C.t_step_shadow = W.max_height / float(W.shadow_steps);            // :149
+    T.terr_steps = W.terr_steps; C.cloud_steps = W.cloud_steps; C.shadow_steps = W.shadow_steps;
+    // the shell of band(): 1 + band0 mh < |p| < 1 + band2 mh, squared and moved out by 1e-3 (the argument: kern_planet_world.hip);
+    // no claim for unordered or non-finite edges, for mh <= 0 or for an edge radius below .05
+    C.shell_lo2 = 0.f; C.shell_hi2 = INFINITY;
+    if (W.band[0] < W.band[1] && W.band[1] < W.band[2] && std::isfinite(W.band[0]) && std::isfinite(W.band[2]) && W.max_height > 0.f &&
+        std::isfinite(W.max_height)) {
+        const double lo = 1.0 + (double)W.band[0] * (double)W.max_height, hi = 1.0 + (double)W.band[2] * (double)W.max_height;
+        if (lo >= .05) C.shell_lo2 = std::nextafter((float)(lo * lo * (1.0 - 1e-3)), 0.f);
+        if (hi >= .05 && hi * hi * (1.0 + 1e-3) < 1e30) C.shell_hi2 = std::nextafter((float)(hi * hi * (1.0 + 1e-3)), INFINITY);
+    }
+    const double rmax = (double)F.atm_radius + 1.0;
+    F.hit2_max = (float)(rmax * rmax);
+    F.tame = planet_world_tame(W) ? 1 : 0;
+    return F;
+}
+// the domain of k_planet_world<true>'s guarded forms, bound by bound as kern_planet_world.hip states and uses them
+bool planet_world_tame(const sbx_aux_planet_world& W) {
+    const float e20 = 0x1p-20f;
+    if (!pw_in(W.max_height, .02f, 2.f)) return false;
+    for (int k = 0; k < 3; ++k) {
+        if (!pw_in(std::fabs(W.terrain_offset[k]), 0.f, 64.f) || !pw_in(std::fabs(W.cloud_offset[k]), 0.f, 64.f)) return false;
+        if (!pw_zero_or_mag(W.band[k], e20, 4.f)) return false;
+    }
+    if (!pw_in(W.band[1] - W.band[0], e20, 8.f) || !pw_in(W.band[2] - W.band[1], e20, 8.f)) return false;
+    if (!pw_zero_or_mag(W.cld_coverage, e20, 4.f)) return false;
+    const float hi = W.cld_coverage + W.cld_fuzzy;
+    if (!pw_in(hi - W.cld_coverage, 0x1p-30f, 8.f)) return false;
+    const float mrd = W.max_height * 4.f;
+    const float ts = std::fmax(mrd / float(W.cloud_steps), W.max_height / float(W.shadow_steps));
+    if (!pw_in(std::fabs(W.absorb) * ts, 0.f, 80.f)) return false;
+    if (!pw_in(std::fabs(W.cloud_light), e20, 0x1p20f)) return false;
+    sbx_uniforms u{};
+    u.u_res[0] = 64.f; u.u_res[1] = 36.f;                              // (the rotations do not read them)
+    return pw_rotations_tame(W, build_planet_world_literal(u, W));
+}
+// sbx_set_variant 1: k_planet_world<false> for EVERY block, a literal-tier one included.  Otherwise PLANET_WORLD_LITERAL where every
+// field but the camera, the three angles and the sun is the default's bit for bit — SBX_APP_PLANET's own kernels over
+// build_planet_world_literal's block (sbx_capi.hip picks the instantiation) — and else the run-time kernel, fast for a tame block.
+int planet_world_tier(const sbx_aux_planet_world& W, int variant) {
+    if (variant == 1) return PLANET_WORLD_PLAIN;
+    sbx_aux_planet_world D;
+    planet_default_world(sbx_uniforms{}, D);
+    const size_t mid = offsetof(sbx_aux_planet_world, cloud_spin_deg);
+    const bool numbers = std::memcmp(W.key_color, D.key_color, sizeof(W.key_color)) == 0 &&
+                         std::memcmp((const char*)&W + mid + sizeof(float), (const char*)&D + mid + sizeof(float), sizeof(W) - mid - sizeof(float)) == 0;
+    if (numbers) return PLANET_WORLD_LITERAL;
+    return planet_world_tame(W) ? PLANET_WORLD_RUNTIME : PLANET_WORLD_PLAIN;
+}
+
 FrameCloudsBest build_clouds_best(const sbx_uniforms& U) {
     FrameCloudsBest F;
     F.cam = make_camera(U.u_res[0], U.u_res[1], 1.f, V3(0, 1.f, 0), V3(0, 1.6f, -1));   // app_clouds_best.h:635-641,663
@@ -753,6 +903,11 @@ void sbx_raytracer_scene_cornell(const sbx_uniforms* uni, int at_rest, sbx_aux_r
 void sbx_atmosphere_air_default(const sbx_uniforms* uni, int view, sbx_aux_atmosphere_air* out) {
     if (!uni || !out) return;
     atmosphere_default_air(*uni, view, *out);
+}
+
+void sbx_planet_world_default(const sbx_uniforms* uni, sbx_aux_planet_world* out) {
+    if (!uni || !out) return;
+    planet_default_world(*uni, *out);
 }
 
 void sbx_vinyl_deck_default(const sbx_uniforms* uni, sbx_aux_vinyl_deck* out) {

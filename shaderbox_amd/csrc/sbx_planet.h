@@ -46,10 +46,59 @@ __device__ __forceinline__ Vol make_vol(v3 o) { return Vol{o, o, 0.f, 1.f, 0.f, 
 #define SMOOTHSTEP_K(e0, e1, x) ((SKIP && PL_DIV3 && PL_MED3) ? smoothstep_d3_med3((e0), (e1) - (e0), 1.0f / ((e1) - (e0)), (x)) \
                                  : (SKIP && PL_DIV3) ? smoothstep_d3((e0), (e1) - (e0), 1.0f / ((e1) - (e0)), (x)) \
                                                    : smoothstep_rd((e0), 1.0 / (double)((e1) - (e0)), (x)))
+// ---- where the header's numbers come from ----------------------------------------------------------------------------------------
+// clouds_density, clouds_map, terrain_map and terrain_detail_difference below read every number that src/app_planet.h states as a
+// one-line literal from a POLICY, their last template parameter and last argument.  PlLit (the default: callers that name no policy
+// are k_planet and k_planet_eval as they always were) holds the literals as literals, with the exact-reciprocal multiplies and the
+// literal div3_ pairs of PL_DIVK / SMOOTHSTEP_K; PlCloudW and PlTerrW read the parts of a FramePlanetWorld (sbx_frame.h: the caller's
+// block of SBX_APP_PLANET_WORLD and sbx_planet_world_eval), dividing by a block's value with div3_ and the host's RN(1 / d) under
+// SKIP and with the IEEE division otherwise.  The domains under which SKIP may be taken with a caller's numbers are argued in
+// kern_planet_world.hip.  What is NOT a policy's business stays written once, here: the fBm scales, lacunarities, gains and octave
+// staging, the terrain edges .35 / .6 / 1 and the TAIL bounds, the .1876 / .06255 of the coverage early-outs, the PL_TB2 tables.
+struct PlLit {
+    template <bool SKIP> __device__ __forceinline__ float band(float t) const {     // band(.2, .35, .65, t)  util.h:103-112
+        return SMOOTHSTEP_K(.2f, .35f, t) * (1.f - SMOOTHSTEP_K(.35f, .65f, t));
+    }
+    __device__ __forceinline__ v3 cloud_offset() const { return V3(.35f, 13.35f, 2.67f); }          // :107
+    __device__ __forceinline__ float cov() const { return .29475675f; }                              // :110
+    template <bool SKIP> __device__ __forceinline__ float cov_smoothstep(float dens) const {        // :112
+        const float cov = .29475675f, fuzzy = .0335f;
+        return SMOOTHSTEP_K(cov, cov + fuzzy, dens);
+    }
+    __device__ __forceinline__ float absorb_arg(float dens, float t_step) const { return -30.034f * dens * t_step; }   // :87
+    template <bool SKIP> __device__ __forceinline__ float light_div(float e) const { return PL_DIVK(e, .055f); }       // :76
+    __device__ __forceinline__ v3 terrain_offset() const { return V3(1.9489f, 2.435f, .5483f); }    // :180, :193
+    __device__ __forceinline__ float max_height() const { return PL_MAX_HEIGHT; }
+    template <bool SKIP> __device__ __forceinline__ float div_height(float a) const { return PL_DIVK(a, PL_MAX_HEIGHT); }
+};
 template <bool SKIP>
-__device__ __forceinline__ float band(float t) {                     // band(.2, .35, .65, t)  util.h:103-112
-    return SMOOTHSTEP_K(.2f, .35f, t) * (1.f - SMOOTHSTEP_K(.35f, .65f, t));
+__device__ __forceinline__ float pw_div(float a, float d, float r) { return (SKIP && PL_DIV3) ? div3_(a, d, r) : a / d; }
+// smoothstep(e0, e1, x) with d = e1 - e0 and r = RN(1 / d) from the host
+template <bool SKIP>
+__device__ __forceinline__ float pw_smoothstep(float e0, float e1, float d, float r, float x) {
+    return (SKIP && PL_DIV3 && PL_MED3) ? smoothstep_d3_med3(e0, d, r, x) : (SKIP && PL_DIV3) ? smoothstep_d3(e0, d, r, x) : smoothstep_(e0, e1, x);
 }
+struct PlCloudW {
+    const PlanetWorldCloud& c;
+    template <bool SKIP> __device__ __forceinline__ float band(float t) const {
+        return pw_smoothstep<SKIP>(c.band0, c.band1, c.band_d01, c.band_r01, t) * (1.f - pw_smoothstep<SKIP>(c.band1, c.band2, c.band_d12, c.band_r12, t));
+    }
+    __device__ __forceinline__ v3 cloud_offset() const { return c.cloud_offset; }
+    __device__ __forceinline__ float cov() const { return c.cov; }
+    template <bool SKIP> __device__ __forceinline__ float cov_smoothstep(float dens) const { return pw_smoothstep<SKIP>(c.cov, c.cov_hi, c.cov_d, c.cov_r, dens); }
+    __device__ __forceinline__ float absorb_arg(float dens, float t_step) const { return c.neg_absorb * dens * t_step; }
+    template <bool SKIP> __device__ __forceinline__ float light_div(float e) const { return pw_div<SKIP>(e, c.cloud_light, c.cloud_light_r); }
+    __device__ __forceinline__ float max_height() const { return c.max_height; }
+    template <bool SKIP> __device__ __forceinline__ float div_height(float a) const { return pw_div<SKIP>(a, c.max_height, c.max_height_r); }
+};
+struct PlTerrW {
+    const PlanetWorldTerrain& t;
+    __device__ __forceinline__ v3 terrain_offset() const { return t.terrain_offset; }
+    __device__ __forceinline__ float max_height() const { return t.max_height; }
+    template <bool SKIP> __device__ __forceinline__ float div_height(float a) const { return pw_div<SKIP>(a, t.max_height, t.max_height_r); }
+};
+template <bool SKIP>
+__device__ __forceinline__ float band(float t) { return PlLit().band<SKIP>(t); }
 
 // DECL_FBM_FUNC(name, OCT, basis(noise_iq(p)))  fbm.h:6 — the OCT noise values come from one cooperative batch
 // MODE 0: noise(p)   1: anoise = |2 noise - 1| (:65)   2: rnoise = 1 - |2 noise - 1| (:167)
@@ -184,20 +233,21 @@ __device__ __forceinline__ float pl_length(v3 v) {
 // SKIP = false (sbx_set_variant 1) evaluates everything: the reference form, kept for the parity sweeps
 // The density part of clouds_map: false = nothing would change for any committing lane of the wave (see below), else
 // dens and T_i = exp(-30.034 dens t_step) of every lane are set.
-template <bool SKIP>
+template <bool SKIP, class P = PlLit>
 __device__ __forceinline__ bool clouds_density(WaveCache& S, v3 pos, float height, float t_step, bool on, int lane, float& dens_out,
-                                               float& T_i_out) {
+                                               float& T_i_out, const P& w = P()) {
     // The cloud shell is the height band (.2, .65): outside it band() is exactly +0, so dens = fbm * 0 = +0,
     // T_i = exp(-0) = 1, and the three updates below are `*= 1`, `+= 0`, `+= 0 * (1 - alpha)`: nothing changes.
     // When that holds for every committing lane of the wave the noise is not evaluated at all (most steps of the
     // 75-step march and 2-3 of the 5 shadow steps).  A NaN height compares unequal and takes the full path.
-    const float bd = band<SKIP>(height);
+    const float bd = w.template band<SKIP>(height);
     if (SKIP && !wave_any(on && bd != 0.f)) return false;
     // fbm of |2 noise - 1| in [0, 1], gains .5 .25 .125 .0625: evaluated in stages {0,1}, {2}, {3}; once the part so far
     // plus the largest possible rest is below the coverage edge for every committing lane, smoothstep(cov, ..) is
     // exactly 0, the density +0, and nothing below would change anything.
-    const float cov = .29475675f, fuzzy = .0335f;
-    v3 q = pos * 3.2343f + V3(.35f, 13.35f, 2.67f);
+    // (with a caller's numbers the two early-outs below also need cld_fuzzy > 0 and a finite coverage: kern_planet_world.hip)
+    const float cov = w.cov();
+    v3 q = pos * 3.2343f + w.cloud_offset();
     float H = .5f, dens = 0.f;
     // (SKIP kernels run only for tame frames — sbx_capi.hip tame_time — where every lattice coordinate is a small integer: XI)
     coop_fbm_range<2, 1, 0, SKIP>(S, q, 2.0276f, H, .5f, dens, on, lane);
@@ -205,36 +255,36 @@ __device__ __forceinline__ bool clouds_density(WaveCache& S, v3 pos, float heigh
     coop_fbm_range<3, 1, 2, SKIP>(S, q, 2.0276f, H, .5f, dens, on, lane);
     if (SKIP && !wave_any(on && !(dens + .06255f < cov))) return false;
     coop_fbm_range<4, 1, 3, SKIP>(S, q, 2.0276f, H, .5f, dens, on, lane);
-    dens *= SMOOTHSTEP_K(cov, cov + fuzzy, dens);
+    dens *= w.template cov_smoothstep<SKIP>(dens);
     dens *= bd;
     // dens is exactly +0 below the coverage edge as well (smoothstep = 0): same identities, skip the two exp
     if (SKIP && !wave_any(on && dens != 0.f)) return false;
     dens_out = dens;
-    T_i_out = PL_EXP(-30.034f * dens * t_step);
+    T_i_out = PL_EXP(w.absorb_arg(dens, t_step));
     return true;
 }
 // clouds_map :102-119 + integrate_volume :79-100; `on` = lanes that commit
 // SKIP = false (sbx_set_variant 1) evaluates everything: the reference form, kept for the parity sweeps
-template <bool SKIP>
-__device__ __forceinline__ void clouds_map(WaveCache& S, Vol& c, float t_step, bool on, int lane) {
+template <bool SKIP, class P = PlLit>
+__device__ __forceinline__ void clouds_map(WaveCache& S, Vol& c, float t_step, bool on, int lane, const P& w = P()) {
     float dens = 0.f, T_i = 1.f;
-    if (!clouds_density<SKIP>(S, c.pos, c.height, t_step, on, lane, dens, T_i)) return;
+    if (!clouds_density<SKIP, P>(S, c.pos, c.height, t_step, on, lane, dens, T_i, w)) return;
     if (on) {
         c.transmittance *= T_i;
-        c.radiance += dens * PL_DIVK(PL_EXP(c.height), .055f) * c.transmittance * t_step;
+        c.radiance += dens * w.template light_div<SKIP>(PL_EXP(c.height)) * c.transmittance * t_step;
         c.alpha += (1.f - T_i) * (1.f - c.alpha);
     }
 }
 
 // sdf_terrain_map / sdf_terrain_map_detail :175-199
-template <int OCT, bool SKIP, bool RS = SKIP>
-__device__ __forceinline__ v2 terrain_map(WaveCache& S, v3 pos, bool on, int lane) {
+template <int OCT, bool SKIP, bool RS = SKIP, class P = PlLit>
+__device__ __forceinline__ v2 terrain_map(WaveCache& S, v3 pos, bool on, int lane, const P& w = P()) {
     const float h0 = coop_fbm<OCT, 0, SKIP>(S, pos * 2.0987f, 2.0244f, .454f, .454f, on, lane);
     const float n0 = SMOOTHSTEP_K(.35f, 1.f, h0);
     // Second fBm (ridged basis, values in [0, 1]): n1 = smoothstep(.6, 1, h1) is exactly +0 whenever h1 < .6.
     // After the first octave, h1 <= t + (.454^2 + ... + .454^OCT); when that bound is below .6 for every
     // committing lane of the wave the remaining octaves cannot change n1 = +0 and are not evaluated.
-    v3 q = pos * 1.50987f + V3(1.9489f, 2.435f, .5483f);
+    v3 q = pos * 1.50987f + w.terrain_offset();
     float H = .454f, h1 = 0.f;
     coop_fbm_range<1, 2, 0, SKIP, PL_TB2>(S, q, 2.0244f, H, .454f, h1, on, lane);
     constexpr float TAIL = (OCT == 3) ? .2998f : .3745f;       // sum of .454^k, k = 2..OCT, rounded up (OCT = 3 or 7)
@@ -245,7 +295,7 @@ __device__ __forceinline__ v2 terrain_map(WaveCache& S, v3 pos, bool on, int lan
         n1 = SMOOTHSTEP_K(.6f, 1.f, h1);
     }
     const float n = n0 + n1;
-    return V2(pl_length<RS>(pos) - 1.f - n * PL_MAX_HEIGHT, PL_DIVK(n, PL_MAX_HEIGHT));
+    return V2(pl_length<RS>(pos) - 1.f - n * w.max_height(), w.template div_height<SKIP>(n));
 }
 
 
@@ -331,8 +381,8 @@ __device__ __forceinline__ void pl_fbm_pair(WaveCache& S, v3& qa, float& qb_ax, 
     }
 }
 // sdf_terrain_map_detail(pos + d).x - sdf_terrain_map_detail(pos - d).x with d = e along axis AX   (:188-199, :201-212)
-template <int AX, bool SKIP, bool RS = SKIP>
-__device__ __forceinline__ float terrain_detail_difference(WaveCache& S, v3 pos, float e, bool on, int lane) {
+template <int AX, bool SKIP, bool RS = SKIP, class P = PlLit>
+__device__ __forceinline__ float terrain_detail_difference(WaveCache& S, v3 pos, float e, bool on, int lane, const P& w = P()) {
     // the two points: pos.c + e and pos.c - e on axis AX; pos.c + 0 = pos.c - 0 = pos.c on the others (no zero coordinates here)
     const float ca = (AX == 0 ? pos.x : AX == 1 ? pos.y : pos.z) + e, cb = (AX == 0 ? pos.x : AX == 1 ? pos.y : pos.z) - e;
     const v3 pa = V3(AX == 0 ? ca : pos.x, AX == 1 ? ca : pos.y, AX == 2 ? ca : pos.z);
@@ -344,7 +394,7 @@ __device__ __forceinline__ float terrain_detail_difference(WaveCache& S, v3 pos,
     pl_fbm_pair<7, 0, 0, AX, SKIP, 0>(S, q, qb, 2.0244f, H, .454f, h0a, h0b, on, lane);
     const float n0a = SMOOTHSTEP_K(.35f, 1.f, h0a), n0b = SMOOTHSTEP_K(.35f, 1.f, h0b);
     // second fBm (ridged): pos * 1.50987 + (1.9489, 2.435, .5483); the tail bound of terrain_map for both points
-    const v3 off = V3(1.9489f, 2.435f, .5483f);
+    const v3 off = w.terrain_offset();
     q = pa * 1.50987f + off;
     qb = cb * 1.50987f + (AX == 0 ? off.x : AX == 1 ? off.y : off.z);
     H = .454f;
@@ -356,14 +406,14 @@ __device__ __forceinline__ float terrain_detail_difference(WaveCache& S, v3 pos,
         n1a = SMOOTHSTEP_K(.6f, 1.f, h1a);
         n1b = SMOOTHSTEP_K(.6f, 1.f, h1b);
     }
-    const float va = pl_length<RS>(pa) - 1.f - (n0a + n1a) * PL_MAX_HEIGHT;
-    const float vb = pl_length<RS>(pb) - 1.f - (n0b + n1b) * PL_MAX_HEIGHT;
+    const float va = pl_length<RS>(pa) - 1.f - (n0a + n1a) * w.max_height();
+    const float vb = pl_length<RS>(pb) - 1.f - (n0b + n1b) * w.max_height();
     return va - vb;
 }
 
-__device__ __forceinline__ v3 setup_lights(v3 L, v3 normal) {                          // :217-236
+__device__ __forceinline__ v3 setup_lights(v3 L, v3 normal, v3 c_L = V3(7, 5, 3)) {    // :217-236; c_L: the key light's colour (:224)
     v3 diffuse = V3(0, 0, 0);
-    diffuse = diffuse + fmax_(0.f, dot(L, normal)) * V3(7, 5, 3);
+    diffuse = diffuse + fmax_(0.f, dot(L, normal)) * c_L;
     const float hemi = clamp_(.25f + .5f * normal.y, .0f, 1.f);
     diffuse = diffuse + hemi * V3(.4f, .6f, .8f) * .2f;
     const float amb = clamp_(.12f + .8f * fmax_(0.f, dot(-L, normal)), 0.f, 1.f);

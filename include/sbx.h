@@ -860,6 +860,35 @@ int sbx_atmosphere_air_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_atmosphe
  * select the IEEE roots as for the app.  n == 0 returns SBX_OK and touches nothing; SBX_ERR_ARG also for a NULL ctx / scene / xyz /
  * out and n > 2^31. */
 int sbx_sdf_eval(sbx_ctx* ctx, const sbx_aux_sdf_scene* scene, const float* xyz, float* out, size_t n, void* stream);
+/* SBX_APP_SDF_SCENE's renderer (src/app_sdf_ao.h, with sdf(pos) the block's program) as standalone functions over n elements of the
+ * caller's, under the caller's block: what the app reaches only through its pinhole camera and into sRGB pixels — normals for a
+ * mesher's vertices, an AO or soft-shadow bake at surface samples, hit points and materials for picking rays, the trace for another
+ * lens, a probe grid or a reflection ray of a host's own integrator.  `scene`: HOST memory, read during the call, required and
+ * validated as SBX_APP_SDF_SCENE validates it (the app's texts) whatever n is; its eye, look_at and fov are not read.  `in`, `out`:
+ * device memory, not overlapping, 4-byte alignment suffices.  Per element:
+ *   "sdf"                       in 3: pos.  out 2: the distance, then the material id as a float: the same bits as sbx_sdf_eval.
+ *   "sdf_normal" (:152-163)     in 3: p.  out 3.
+ *   "sdf_ao" (:165-181)         in 6: hit.origin xyz, hit.normal xyz.  out 1: the `c` of :179.
+ *   "sdf_shadow" (:183-207)     in 6: ray origin xyz, direction xyz — the element's own direction, not the block's sun_dir: the
+ *                               function takes any ray.  out 1.  It runs whatever the block's `shadow` says (the switch is
+ *                               "render_impl"'s).
+ *   "illuminate" (:211-243)     in 9: hit.origin xyz, hit.normal xyz, the material id as a float, ao, sh.  out 3.  int() of the id is
+ *                               taken as for sbx_vinyl_eval — toward zero, saturating at the ends of int, 0 for a NaN.  An id outside
+ *                               0..7 gives the zero colour: the port's choice, the reference's get_material leaves its result unset
+ *                               there.  The checker test is int(id) == checker_material, as written.  Under view == 1 the result is
+ *                               hit.normal (:217-219 compiled in).  The reference's `eye` argument enters only V (:220), which nothing
+ *                               reads: it has no slot.
+ *   "render_impl" (:245-285)    in 6: ray origin xyz, direction xyz.  out 5: rgb and t of the vec4 it returns, then the hit's material
+ *                               id as a float, or -1 where :284 returned the background.  It runs under the block's march_steps,
+ *                               march_end, shadow, view, background and materials.
+ *   "render" (:287-311)         in 6: as above.  out 4: the LINEAR rgb after the fog and the `abs` (no sRGB, no alpha), then orig.w.
+ *                               The fog's ray.origin.y and ray.direction.y are the element's.
+ * Directions and normals are used as given, never normalised; sun_dir is used as given.  Every bit pattern is data, NaN results
+ * included.  Asynchronous on `stream` and capturable (one kernel launch and nothing else); not counted in sbx_stats.render_launches;
+ * sbx_set_variant 1 / 3 select the IEEE roots as for the app (same bits).  n == 0 returns SBX_OK with `in` and `out` not looked at;
+ * SBX_ERR_ARG, with nothing written, for a NULL ctx / fn / scene / in / out, a block the app refuses (at n == 0 too), an unknown
+ * name, n > 2^31.  tests/sdf_scene_eval_model.py is the definition. */
+int sbx_sdf_scene_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_sdf_scene* scene, const float* in, float* out, size_t n, void* stream);
 /* The volumetric clouds and their sky (src/app_clouds.h, the procedural build as shipped: SKY_SPHERE and USE_NOISE_TEX undefined, both
  * `#if 0` of illuminate_volume off) as standalone functions over n elements of the caller's: what the reference reaches only through
  * pixels of the one camera setup_camera fixes at (0, -.5, 0) — sky panoramas and cube faces, the sky a reflective surface of another

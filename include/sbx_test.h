@@ -54,6 +54,8 @@ extern "C" {
  * (csrc/kern_vinyl_eval.hip).
  * sbx_raytracer_eval: 1 and 3 = the IEEE roots for every wave, 2 = the witness's test edge, 0 the witnessed roots; no block and no
  * element changes a wave's form (csrc/kern_raytracer_eval.hip).
+ * sbx_sdf_scene_eval: 1 and 3 = the IEEE roots for every wave, 2 = the witness's test edge, 0 the witnessed roots; no block and no
+ * element changes a wave's form (csrc/kern_sdf_scene_eval.hip).
  * SBX_APP_ATMOSPHERE_AIR and sbx_atmosphere_air_eval: 1 = the plain statement for every wave, whatever the block; every other value
  * leaves the tier to the block (csrc/sbx_frames.hip atmosphere_air_tier).
  * SBX_APP_PLANET_WORLD: 1 = k_planet_world<false>, the plain statement over the block's numbers, for every block, one that differs from the
@@ -111,6 +113,14 @@ int sbx_debug_vinyl_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_vinyl_deck*
  * variants 0 and 2 the two add up to the waves of the launch; under 1 and 3 (the IEEE roots) both are 0.  It allocates and synchronises,
  * so it is not capturable.  For tests/test_gpu_raytracer_eval.py and tools/time_raytracer_eval.py. */
 int sbx_debug_raytracer_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_raytracer_scene* scene, const float* in, float* out, size_t n,
+                             unsigned counts_host[2], void* stream);
+/* sbx_sdf_scene_eval (sbx.h) with counts: the same launch (the context's variant included) followed by a wait, after which
+ * counts_host[0] holds the waves that took the witnessed roots only and counts_host[1] the waves that re-ran with the IEEE roots because
+ * a lane recorded an argument outside the witness's interval.  No wave's form depends on its elements or on the block, so under
+ * variants 0 and 2 the two add up to the waves of the launch ("illuminate" takes no root: all of its waves are in the first); under 1
+ * and 3 (the IEEE roots) both are 0.  It allocates and synchronises, so it is not capturable: a capturing stream is refused with the
+ * capture intact, a NULL counts_host too.  For tests/test_gpu_sdf_scene_eval.py and tools/time_sdf_scene_eval.py. */
+int sbx_debug_sdf_scene_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_sdf_scene* scene, const float* in, float* out, size_t n,
                              unsigned counts_host[2], void* stream);
 /* sbx_atmosphere_air_eval (sbx.h) with a count: the same launch (the context's variant included) followed by a wait, after which
  * *fast_waves_host holds the waves that took the fast body (csrc/sbx_atmosphere.h "CALLER'S AIR"): 0 under an untame block or

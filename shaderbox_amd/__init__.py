@@ -401,6 +401,8 @@ def load_library(path=None):
     lib.sbx_sdf_scene_ramp.argtypes = [ctypes.POINTER(Uniforms), ctypes.POINTER(SdfScene)]
     lib.sbx_sdf_scene_ramp.restype = None
     lib.sbx_sdf_eval.argtypes = [vp, ctypes.POINTER(SdfScene), fp, fp, ctypes.c_size_t, vp]
+    lib.sbx_sdf_scene_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(SdfScene), fp, fp, ctypes.c_size_t, vp]
+    lib.sbx_debug_sdf_scene_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(SdfScene), fp, fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), vp]
     lib.sbx_egg_pose_default.argtypes = [ctypes.POINTER(Uniforms), ctypes.POINTER(EggPose)]
     lib.sbx_egg_pose_default.restype = None
     lib.sbx_egg_eval.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(EggPose), fp, fp, ctypes.c_size_t, vp]
@@ -1212,6 +1214,8 @@ class Renderer:
         "vinyl": {"sdf": (3, 2), "sdf_normal": (3, 3), "sdf_shadow": (6, 1), "illuminate": (7, 3), "render": (6, 5)},
         "sdf": {"sdf": (3, 2)},
         "raytracer": {"raytrace_iteration": (7, 8), "illuminate": (10, 3), "shadow": (3, 2), "render": (6, 4)},
+        "sdf_scene": {"sdf": (3, 2), "sdf_normal": (3, 3), "sdf_ao": (6, 1), "sdf_shadow": (6, 1), "illuminate": (9, 3), "render_impl": (6, 5),
+                      "render": (6, 4)},
     }
     CLOUDS_EVAL_WIDTHS, PLANET_EVAL_WIDTHS = EVAL_WIDTHS["clouds"], EVAL_WIDTHS["planet"]
     EGG_EVAL_WIDTHS, VINYL_EVAL_WIDTHS = EVAL_WIDTHS["egg"], EVAL_WIDTHS["vinyl"]
@@ -1332,6 +1336,21 @@ class Renderer:
         waves that re-ran with the IEEE roots))"""
         counts = (ctypes.c_uint * 2)(0, 0)
         return self._eval("raytracer", fn, x, (self._by_ref(scene),), counts), (int(counts[0]), int(counts[1]))
+
+    def sdf_scene_eval(self, fn, x, scene):
+        """APP_SDF_SCENE's field, normal, ambient occlusion, soft shadow, shading, trace and fogged render over the caller's elements under
+        an SdfScene (include/sbx.h sbx_sdf_scene_eval): fn 'sdf' over points x[n, 3] -> [n, 2] (distance, material id); 'sdf_normal'
+        x[n, 3] -> [n, 3]; 'sdf_ao' over x[n, 6] (hit.origin xyz, hit.normal xyz) -> [n, 1]; 'sdf_shadow' over rays x[n, 6] (origin
+        xyz, direction xyz) -> [n, 1]; 'illuminate' over x[n, 9] (hit.origin xyz, hit.normal xyz, material id, ao, sh) -> [n, 3];
+        'render_impl' over rays x[n, 6] -> [n, 5] (rgb, t, material id or -1); 'render' over rays x[n, 6] -> [n, 4] (linear rgb after
+        the fog, t).  The scene's eye, look_at and fov are not read."""
+        return self._eval("sdf_scene", fn, x, (self._by_ref(scene),))
+
+    def sdf_scene_eval_counted(self, fn, x, scene):
+        """include/sbx_test.h sbx_debug_sdf_scene_eval: sdf_scene_eval that waits -> (out, (waves that took the witnessed roots only,
+        waves that re-ran with the IEEE roots))"""
+        counts = (ctypes.c_uint * 2)(0, 0)
+        return self._eval("sdf_scene", fn, x, (self._by_ref(scene),), counts), (int(counts[0]), int(counts[1]))
 
     def sdf_eval(self, scene, xyz):
         """sdf(pos) of an SdfScene's program over points xyz[n, 3] (include/sbx.h sbx_sdf_eval) -> [n, 2]: the distance and the

@@ -21,7 +21,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
          "-fno-slp-vectorize",
          "-fno-gpu-flush-denormals-to-zero", "-fhip-fp32-correctly-rounded-divide-sqrt", "-mfma",
          "-Wall", "-Wno-unused-function"]
-SOURCES = ["kern_clouds.hip", "kern_clouds_eval.hip", "kern_clouds_tex.hip", "kern_egg.hip", "kern_egg_eval.hip", "kern_raytracer.hip", "kern_raytracer_eval.hip", "kern_atmosphere.hip", "kern_atmosphere_air.hip", "kern_sdf_ao.hip", "kern_sdf_scene.hip",
+SOURCES = ["kern_clouds.hip", "kern_clouds_eval.hip", "kern_clouds_tex.hip", "kern_egg.hip", "kern_egg_eval.hip", "kern_raytracer.hip", "kern_raytracer_eval.hip", "kern_atmosphere.hip", "kern_atmosphere_air.hip", "kern_sdf_ao.hip", "kern_sdf_scene.hip", "kern_sdf_scene_eval.hip",
            "kern_planet.hip", "kern_planet_eval.hip", "kern_planet_world.hip", "kern_vinyl.hip", "kern_vinyl_eval.hip", "kern_clouds_best.hip", "kern_clouds_ue4.hip", "kern_2d.hip", "kern_func.hip", "kern_util.hip", "kern_noise.hip",
            "sbx_capi.hip", "sbx_frames.hip", "sbx_ytab.hip", "sbx_main_image.hip", "sbx_split.hip", "sbx_eval.hip", "sbx_multi.hip", "sbx_shared.hip"]
 # -fno-slp-vectorize: measured on MI355X, the SLP vectoriser's v_pk_{mul,add}_f32 are a net loss for every

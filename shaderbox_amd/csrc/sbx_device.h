@@ -192,6 +192,8 @@ void launch_atmosphere_air(const FrameAtmosphere& F, const AtmAir& K, int view, 
 void launch_sdf_ao(const FrameSdfAo& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = 0);   // build: 1 / 2 = the shadow / normals builds (kern_sdf_ao.hip)
 void launch_sdf_scene(const FrameSdfScene& F, const RowMap& M, float* out, hipStream_t s, int variant);   // SBX_APP_SDF_SCENE (kern_sdf_scene.hip)
 void launch_sdf_scene_eval(const FrameSdfScene& F, const float* xyz, float* out, size_t n, hipStream_t s, int variant);   // sbx_sdf_eval
+// sbx_sdf_scene_eval (kern_sdf_scene_eval.hip): fn = the index among its names; counts NULL or two zeroed words (witnessed / re-run waves)
+void launch_sdf_scene_eval_fn(int fn, const FrameSdfScene& F, int variant, const float* in, float* out, size_t n, unsigned* counts, hipStream_t s);
 void launch_vinyl(const FrameVinyl& F, const RowMap& M, float* out, hipStream_t s, int variant, int build = VINYL_DEFAULT);   // build: VINYL_* (sbx_frame.h)
 void launch_clouds_best(const FrameCloudsBest& F, const RowMap& M, float* out, hipStream_t s);
 void launch_clouds_ue4(const FrameCloudsUe4& F, const RowMap& M, float* out, hipStream_t s);

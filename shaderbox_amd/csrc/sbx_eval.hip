@@ -1,6 +1,7 @@
 // shaderbox_amd/csrc/sbx_eval.hip — the hooks that evaluate one piece of the math spec or of a kernel on the device for the tests
 // (include/sbx_test.h), the eval entries ("a function of an app over the caller's elements": sbx_atmosphere_eval, sbx_atmosphere_air_eval,
-// sbx_sdf_eval, sbx_clouds_eval, sbx_planet_eval, sbx_egg_eval, sbx_vinyl_eval, sbx_raytracer_eval of include/sbx.h, seven of them with a counted twin in
+// sbx_sdf_eval, sbx_sdf_scene_eval, sbx_clouds_eval, sbx_planet_eval, sbx_egg_eval, sbx_vinyl_eval, sbx_raytracer_eval of include/sbx.h, all but
+// sbx_sdf_eval with a counted twin in
 // include/sbx_test.h), and the binding of what the textured apps sample: t0 of APP_2D_TEX, the noise volumes of APP_CLOUDS_TEX.
 // The eval entries share one argument check (eval_args), one plain launch and one counted launch; a new one brings its name list, its
 // `*_eval_args` with whatever check is its own, and its `*_eval_launch` closure, all in the section below.
@@ -207,6 +208,23 @@ auto raytracer_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_raytracer_s
     };
 }
 
+// id = launch_sdf_scene_eval_fn's fn; the block is required and checked as SBX_APP_SDF_SCENE checks it (the app's texts) whatever n is
+int sdf_scene_eval_args(sbx_ctx* ctx, const char* fn, const sbx_aux_sdf_scene* scene, const float* in, const float* out, size_t n, int& id) {
+    static const char* const names[] = {"sdf", "sdf_normal", "sdf_ao", "sdf_shadow", "illuminate", "render_impl", "render"};
+    id = name_id(fn, names);
+    return eval_args(ctx, fn, id, "unknown sdf scene function", !scene ? "NULL argument" : sdf_scene_check(*scene, false), "more than 2^31 elements", in,
+                     out, n);
+}
+// the frame of the block with the ramp block's camera in place of the block's (the kernel reads no camera).  No host judgement of the
+// block: no shortcut of the kernel has a domain (kern_sdf_scene_eval.hip, at the top), so the variant is the context's own
+auto sdf_scene_eval_launch(const sbx_ctx* ctx, int id, const sbx_aux_sdf_scene* scene, const float* in, float* out, size_t n) {
+    return [=](unsigned* counts, hipStream_t s) {
+        sbx_aux_sdf_scene A = *scene;
+        A.eye[0] = 0.f; A.eye[1] = 3.f; A.eye[2] = 5.f; A.look_at[0] = 0.f; A.look_at[1] = 0.f; A.look_at[2] = 0.f; A.fov = 1.f;
+        launch_sdf_scene_eval_fn(id, build_sdf_scene(frame_1x1(0.f), A), witness_variant(ctx), in, out, n, counts, s);
+    };
+}
+
 }  // namespace
 
 extern "C" {
@@ -301,6 +319,21 @@ int sbx_sdf_eval(sbx_ctx* ctx, const sbx_aux_sdf_scene* scene, const float* xyz,
         std::memcpy(A.program, scene->program, sizeof(A.program));
         launch_sdf_scene_eval(build_sdf_scene(U, A), xyz, out, n, s, witness_variant(ctx));
     });
+}
+
+int sbx_sdf_scene_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_sdf_scene* scene, const float* in, float* out, size_t n, void* stream) {
+    int id = -1;
+    const int rc = sdf_scene_eval_args(ctx, fn, scene, in, out, n, id);
+    if (rc != SBX_OK || n == 0) return rc;
+    return plain_launch(ctx, "sdf_scene_eval launch", stream, sdf_scene_eval_launch(ctx, id, scene, in, out, n));
+}
+
+int sbx_debug_sdf_scene_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_sdf_scene* scene, const float* in, float* out, size_t n,
+                             unsigned counts_host[2], void* stream) {
+    int id = -1;
+    const int rc = sdf_scene_eval_args(ctx, fn, scene, in, out, n, id);
+    if (rc != SBX_OK) return rc;
+    return counted_launch<unsigned, 2>(ctx, "sdf_scene_eval (counted)", n, counts_host, stream, sdf_scene_eval_launch(ctx, id, scene, in, out, n));
 }
 
 int sbx_clouds_eval(sbx_ctx* ctx, const char* fn, const sbx_aux_clouds* aux, float u_time, const float* in, float* out, size_t n,

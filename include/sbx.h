@@ -600,7 +600,17 @@ void sbx_aux_sdf_ao_defaults(sbx_aux_sdf_ao* aux);
  * hashes its frames index: 2 MB for frames whose noise lattice indices stay below 2^18 (the default frame: 6.4e4), a larger one —
  * the next power of two — when a frame's bound outgrows it, at most 32 MB (indices below 2^22; frames beyond that keep the kernels
  * that hash per wave).  Tables are never rebuilt; all of them together stay below 64 MB and are freed by sbx_destroy.  Nothing is
- * allocated inside a stream capture. */
+ * allocated inside a stream capture.
+ * THE VIEW TABLE.  The same apps also keep, per camera, what a pixel computes outside its march — sky colour, phase value, horizon
+ * weight — for every pixel of the full frame: 20 bytes per frame pixel per key, two keys per context (166 MB for one 3840 x 2160
+ * camera, 332 MB if a second camera of that size alternates with it).  The key is the camera, the sun (sun_dir, sun_color) and u_res;
+ * u_time, the wind and the cloud parameters are no part of it.  A table is built on the stream of the third consecutive eager launch
+ * of a key (counted over the launches that may read one), so a camera that moves every frame never builds one; a slot is given to another key only after the launches that read it
+ * have completed; only one-rank frame and row-range launches under a sun on the z axis (sun_dir.x = sun_dir.y = 0, the default; the
+ * HEIGHT build under any sun) read one — never a point list, a span or a multi-rank strip, nor SBX_APP_CLOUDS_SKY.  A frame whose table would exceed SBX_CLOUDS_VIEWTAB_DEFAULT_BYTES (7680 x 4320: 664 MB) gets none and
+ * renders with the kernels that compute these values per pixel: the pixels are the same bits either way.  The environment variable
+ * SBX_CLOUDS_VIEWTAB=0 (read once per process) switches the tables off.  Freed by sbx_destroy. */
+#define SBX_CLOUDS_VIEWTAB_DEFAULT_BYTES ((size_t)256 << 20)
 int sbx_create(int device, sbx_ctx** out);
 void sbx_destroy(sbx_ctx* ctx);
 

@@ -230,7 +230,7 @@ typedef struct sbx_clouds_selection {
     int light;          /* the form of sun_dir * dt: 1 z-only (x == 0 and y == 0), 2 y-z (x == 0), 0 general (NaN included) */
     int need_range;     /* clouds_hashtab_range: the hash-table range the frame needs, 0: it takes no table kernel */
     int table_range;    /* the range of the ready table the launch was given, 0: none */
-    int reserved;
+    int vt;             /* 1: k_clouds<..., VT = true>, the instantiation that reads the context's view table (gt != 0 only) */
     uint64_t launches;  /* launches of these apps by the context so far, this one included (sbx_debug_clouds_select: 0) */
 } sbx_clouds_selection;
 
@@ -244,6 +244,35 @@ int sbx_debug_clouds_last_selection(sbx_ctx* ctx, sbx_clouds_selection* out);
  * SBX_OK, or SBX_ERR_ARG for another app, a NULL pointer or negative march steps. */
 int sbx_debug_clouds_select(int app, const sbx_uniforms* uni, const void* aux, int variant, int ytab_rows, int table_range, int point_list,
                             sbx_clouds_selection* out);
+
+/* APP_CLOUDS' view tables (include/sbx.h "THE VIEW TABLE"; csrc/sbx_ctx.h ViewTables): the entries (frame pixels) of the table built or
+ * used last, 0 before the first one; how many tables this context has built; whether its last launch of APP_CLOUDS or of its HEIGHT /
+ * LUMINANCE builds took a view-table kernel (`vt` of sbx_debug_clouds_last_selection's record); and, where it did not, why
+ * (SBX_VIEWTAB_*).  Any pointer may be NULL. */
+enum {
+    SBX_VIEWTAB_USED = 0,        /* the launch read a table */
+    SBX_VIEWTAB_OFF = 1,         /* SBX_CLOUDS_VIEWTAB=0 */
+    SBX_VIEWTAB_INELIGIBLE = 2,  /* not a launch that may read one: a point list, a span, a multi-rank strip, SKY_SPHERE, the per-lane kernel, a sun
+                                    off the z axis (the y-z and the general light march), or a frame that takes no hash-table kernel */
+    SBX_VIEWTAB_NEW_KEY = 3,     /* the key has not been seen on the two eager launches before this one */
+    SBX_VIEWTAB_CAP = 4,         /* the table would exceed the byte cap */
+    SBX_VIEWTAB_NO_SLOT = 5,     /* both slots hold other keys that are still read (or pinned by a capture) */
+    SBX_VIEWTAB_CAPTURE = 6,     /* a stream capture, and no table of the key that the host has seen complete */
+    SBX_VIEWTAB_ALLOC = 7        /* the allocation or an event failed (the error is dropped) */
+};
+int sbx_debug_clouds_viewtab(sbx_ctx* ctx, size_t* entries, int* tables_built, int* last_launch_used_table, int* last_refusal);
+
+/* The byte cap of one view table (default SBX_CLOUDS_VIEWTAB_DEFAULT_BYTES), so that tests reach the refusal at small shapes. */
+int sbx_debug_set_clouds_viewtab_cap(sbx_ctx* ctx, size_t bytes);
+
+/* The key of the view table a launch of `app` (SBX_APP_CLOUDS or its HEIGHT / LUMINANCE builds) under these uniforms and this aux block
+ * would ask for: `words` (28) 32-bit words.  Host only, no context.  SBX_ERR_ARG as sbx_debug_clouds_select. */
+int sbx_debug_clouds_viewtab_key(int app, const sbx_uniforms* uni, const void* aux, unsigned* key, int words);
+
+/* sbx_debug_clouds_select with the further input "a ready view table of the frame's camera is at hand" (view_table != 0), for a
+ * full-frame one-rank launch (or a point list): `vt` of the record. */
+int sbx_debug_clouds_select_vt(int app, const sbx_uniforms* uni, const void* aux, int variant, int ytab_rows, int table_range, int point_list,
+                               int view_table, sbx_clouds_selection* out);
 
 #ifdef __cplusplus
 }

@@ -83,11 +83,13 @@ class AuxClouds(ctypes.Structure):          # sbx_aux_clouds (cbuffer b1, APP_CL
 
 class CloudsSelection(ctypes.Structure):    # sbx_clouds_selection (include/sbx_test.h): the kernel a launch of APP_CLOUDS took
     _fields_ = [(n, ctypes.c_int) for n in ("build", "perlane", "ytab_used", "reg", "lm", "sm", "gt", "ytab", "sky", "regular", "exp_small",
-                                            "index_domain", "div3_domain", "lip_ok", "light", "need_range", "table_range", "reserved")] + \
+                                            "index_domain", "div3_domain", "lip_ok", "light", "need_range", "table_range", "vt")] + \
                [("launches", ctypes.c_uint64)]
 
     def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+        # (`vt`, the view-table instantiation, is reported by Renderer.clouds_viewtab and clouds_select(view_table=True): the records
+        #  the selection cases compare are these fields)
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "vt"}
 
 
 class AuxCloudsUe4(ctypes.Structure):       # sbx_aux_clouds_ue4
@@ -511,6 +513,10 @@ def load_library(path=None):
     lib.sbx_debug_clouds_hashtab_read.argtypes = [vp, ctypes.c_size_t, ctypes.c_size_t, vp]
     lib.sbx_debug_clouds_last_selection.argtypes = [vp, ctypes.POINTER(CloudsSelection)]
     lib.sbx_debug_clouds_select.argtypes = [ci, ctypes.POINTER(Uniforms), vp, ci, ci, ci, ci, ctypes.POINTER(CloudsSelection)]
+    lib.sbx_debug_clouds_select_vt.argtypes = [ci, ctypes.POINTER(Uniforms), vp, ci, ci, ci, ci, ci, ctypes.POINTER(CloudsSelection)]
+    lib.sbx_debug_clouds_viewtab.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t)] + [ctypes.POINTER(ctypes.c_int)] * 3
+    lib.sbx_debug_set_clouds_viewtab_cap.argtypes = [vp, ctypes.c_size_t]
+    lib.sbx_debug_clouds_viewtab_key.argtypes = [ci, ctypes.POINTER(Uniforms), vp, vp, ci]
     lib.sbx_shared_bytes.argtypes = [vp]
     lib.sbx_shared_bytes.restype = ctypes.c_size_t
     lib.sbx_shared_frame_begin.argtypes = [vp, ci, vp]
@@ -725,6 +731,37 @@ def clouds_select(app, width, height, time, mouse=(0.0, 0.0), aux=None, variant=
     if rc < 0:
         raise SbxError(rc, "sbx_debug_clouds_select: bad arguments")
     return out.as_dict()
+
+
+def clouds_select_vt(app, width, height, time, mouse=(0.0, 0.0), aux=None, variant=0, ytab_rows=4096, table_range=0, point_list=False,
+                     view_table=True, lib=None):
+    """include/sbx_test.h sbx_debug_clouds_select_vt: clouds_select for a full-frame launch with "a ready view table of the frame's
+    camera is at hand" as a further input; the dict has the record's `vt` as well"""
+    lib = lib or load_library()
+    u = uniforms(width, height, time, mouse)
+    auxp = ctypes.cast(ctypes.byref(aux), ctypes.c_void_p) if aux is not None else None
+    out = CloudsSelection()
+    rc = lib.sbx_debug_clouds_select_vt(app_id(app), ctypes.byref(u), auxp, int(variant), int(ytab_rows), int(table_range),
+                                        1 if point_list else 0, 1 if view_table else 0, ctypes.byref(out))
+    if rc < 0:
+        raise SbxError(rc, "sbx_debug_clouds_select_vt: bad arguments")
+    return dict(out.as_dict(), vt=int(out.vt))
+
+
+VIEWTAB_KEY_WORDS = 28
+
+
+def clouds_viewtab_key(app, u, aux=None, lib=None):
+    """include/sbx_test.h sbx_debug_clouds_viewtab_key (host only): the view-table key of a launch under the Uniforms `u` and the
+    AuxClouds block `aux`, a numpy array of 28 uint32 words"""
+    import numpy as np
+    lib = lib or load_library()
+    auxp = ctypes.cast(ctypes.byref(aux), ctypes.c_void_p) if aux is not None else None
+    key = np.zeros(VIEWTAB_KEY_WORDS, dtype=np.uint32)
+    rc = lib.sbx_debug_clouds_viewtab_key(app_id(app), ctypes.byref(u), auxp, ctypes.c_void_p(key.ctypes.data), VIEWTAB_KEY_WORDS)
+    if rc < 0:
+        raise SbxError(rc, "sbx_debug_clouds_viewtab_key: bad arguments")
+    return key
 
 
 def span_table(app, width, height, time, block_rows, nranks, root_rounds=1, rounds=1, mouse=(0.0, 0.0), aux=None, lib=None):
@@ -1155,6 +1192,18 @@ class Renderer:
         v = [ctypes.c_int() for _ in range(4)]
         self._check(self.lib.sbx_debug_clouds_hashtab(self.ctx, *[ctypes.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+    def clouds_viewtab(self):
+        """include/sbx_test.h sbx_debug_clouds_viewtab: entries of the view table built or used last, tables built so far, whether
+        the last APP_CLOUDS launch took a view-table kernel, and the reason where it did not (SBX_VIEWTAB_*)"""
+        n = ctypes.c_size_t()
+        v = [ctypes.c_int() for _ in range(3)]
+        self._check(self.lib.sbx_debug_clouds_viewtab(self.ctx, ctypes.byref(n), *[ctypes.byref(x) for x in v]))
+        return (int(n.value),) + tuple(x.value for x in v)
+
+    def set_clouds_viewtab_cap(self, nbytes):
+        """include/sbx_test.h sbx_debug_set_clouds_viewtab_cap: the byte cap of one view table"""
+        self._check(self.lib.sbx_debug_set_clouds_viewtab_cap(self.ctx, int(nbytes)))
 
     def clouds_last_selection(self):
         """include/sbx_test.h sbx_debug_clouds_last_selection: the kernel the context's last launch of APP_CLOUDS, of its HEIGHT /

@@ -85,6 +85,9 @@
                            // the ones that miss, read the table: 3840x2160 2.22 -> 1.96 ms.  0 (no cache in the kernel at all: 58 VGPRs, 3 KB of
                            // LDS, 8 waves): 2.23 ms, the L1's return path is the limit.  3: 2.03 ms.  (profiles/clouds_gtab_timing.txt)
 #endif
+#ifndef CL_VT_PIXEL_PLAIN
+#define CL_VT_PIXEL_PLAIN 1    // 1: the view-table kernels map threads to pixels with pixel_of_plain (no row_to_y divisions); 0: with pixel_of (A/B)
+#endif
 #ifndef CL_MIN_WAVES_GTAB
 #define CL_MIN_WAVES_GTAB 6    // waves per SIMD the hash-table instantiations with the z-only light march are held to: 78 VGPRs, no scratch, 5.4 KB
 #endif                         // of LDS as the cache kernels (7: 2.04 ms against 1.96; 5: 1.96; profiles/clouds_gtab_resources.txt)
@@ -832,6 +835,64 @@ __device__ __forceinline__ v3 clouds_sky(const FrameClouds& F, v3 dir) {
     return abs3(sky);
 }
 
+// ---- the context's view table (VT; host side: sbx_ytab.hip clouds_view_table) ------------------------------------------------
+// Outside the march a pixel of k_clouds evaluates only functions of its view direction, the sun and the camera: the sky colour, the
+// phase value and the horizon weight of :215.  None depends on u_time, the wind or a cloud parameter, so a camera that stands has them
+// the same in every frame.  The context keeps them per camera, over the pixels of the FULL frame (index x + y * width), in two planes:
+//     sky_phase[i] = {clouds_sky(F, dir).xyz, hg_phase(clamp_(dot(F.sun_dir, dir), 0, 1), .2f)}      (float4, W * H entries)
+//     cut[i]       = smoothstep_(.0f, .2f, dot(dir, V3(0, 1, 0)))                                   (float, behind the first plane)
+// filled by k_clouds_viewtab with dir = primary_dir(point_cam(pixel centre)) — the device functions k_clouds calls, on the operands it
+// gives them, under the same compiler flags: the bits a lane would compute (the argument k_clouds_hashtab rests on).  The VT kernels
+// read the phase in the prologue and the other four words in the epilogue; they take the table only on plain one-rank frame launches
+// (clouds_viewtab_eligible), where a pixel's global (x, y) is its place in the table.
+__device__ __forceinline__ const float* vt_cut(const float4* vt, const RowMap& M) { return reinterpret_cast<const float*>(vt + (size_t)M.width * (size_t)M.height); }
+__device__ __forceinline__ bool vt_row(const RowMap& M, const Pixel& px) { return px.valid && (unsigned)px.y < (unsigned)M.height; }   // (always, on an eligible launch)
+__device__ __forceinline__ size_t vt_index(const RowMap& M, const Pixel& px) { return (size_t)px.y * (size_t)M.width + (size_t)px.x; }
+__global__ void __launch_bounds__(256) k_clouds_viewtab(FrameClouds F, int width, int height, float4* __restrict__ sky_phase, float* __restrict__ cut) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= width || y >= height) return;
+    const v2 pc = point_cam(F.cam, (float)x + .5f, (float)y + .5f);     // pixel_of's fragCoord
+    const v3 dir = primary_dir(F.cam, pc);
+    const v3 sky = clouds_sky(F, dir);
+    const size_t i = (size_t)y * (size_t)width + (size_t)x;
+    sky_phase[i] = make_float4(sky.x, sky.y, sky.z, hg_phase(clamp_(dot(F.sun_dir, dir), 0.f, 1.f), .2f));
+    cut[i] = smoothstep_(.0f, .2f, dot(dir, V3(0, 1, 0)));
+}
+void launch_clouds_viewtab(const FrameClouds& F, int width, int height, float4* tab, hipStream_t s) {
+    hipLaunchKernelGGL(k_clouds_viewtab, dim3((unsigned)((width + 63) / 64), (unsigned)((height + 3) / 4)), dim3(256), 0, s, F, width, height, tab,
+                       reinterpret_cast<float*>(tab + (size_t)width * (size_t)height));
+}
+// pixel_of on an eligible launch (one rank, one block per round, no point list, no spans): row_to_y is then y0 + r0 + r — with
+// nranks = rank + 1 = root_rounds = rounds = 1 its cycle is one block, so cycle = blk, round = 0 and gblk = blk — and the two integer
+// divisions by block_rows and by the blocks per cycle (~60 VALU instructions, a third of them quarter-rate multiplies, twice per
+// pixel) are not needed.  The same x, y, idx, valid and fragCoord as pixel_of's.
+template <int TW, int TX, bool TOP_FIRST>
+__device__ __forceinline__ Pixel pixel_of_plain(const RowMap& M, int tid, int bx, int by_in, int grid_y) {
+    constexpr int TH = 64 / TW;
+    const int lane = tid & 63, wave = tid >> 6;
+    ordered_tile(M, bx, by_in);
+    Pixel p;
+    p.x = bx * (TW * TX) + wave * TW + (lane % TW);
+    const int by = TOP_FIRST ? (grid_y - 1 - by_in) : by_in;
+    const int r = by * TH + (lane / TW);
+    p.valid = (p.x < M.width) && (r < M.nrows);
+    p.y = M.y0 + (r + M.r0);
+    p.idx = (size_t)(M.in_place ? p.y : r) * M.width + p.x;
+    p.fx = (float)p.x + .5f;
+    p.fy = (float)p.y + .5f;
+    return p;
+}
+// The launches that may read a view table: one rank's rows of a frame at its full width — whole frames, row ranges, in-place rows —
+// of the camera's own resolution — with the z-only light march (or the HEIGHT build, which has none): the y-z forms, at 96 VGPRs and
+// 16-32 bytes of scratch, were 0.5-0.9 % SLOWER with the table's loads (profiles/clouds_viewtab_timing.txt) and keep their kernels.
+// Never a point list, a span launch, a strip of a multi-rank split or SKY_SPHERE.
+bool clouds_viewtab_eligible(const FrameClouds& F, const RowMap& M, int build) {
+    const v3 lstep = F.sun_dir * F.dt;                          // the kernel's own expression (clouds_select)
+    if (build != CLOUDS_HEIGHT && !(lstep.x == 0.f && lstep.y == 0.f)) return false;
+    return !F.sky && !M.frag && M.span_mode == 0 && M.nranks == 1 && M.rank == 0 && M.width > 0 && M.height > 0 &&
+           (float)M.width == F.cam.res_x && (float)M.height == F.cam.res_y && M.y0 >= 0 && M.r0 >= 0 && M.root_rounds == 1 && M.rounds == 1;
+}
+
 // Waves per workgroup. Waves never talk to each other (one LDS cache per wave), so the workgroup is only a
 // scheduling unit: measured at 4K, 1 wave/WG 5.26 ms, 2 5.57 ms, 4 5.48 ms per launch (profiles/r01_tile_shapes.txt);
 // single-wave workgroups also drain best at the end of a launch (8-rank strips 0.63 vs 0.71 ms/frame pipelined).
@@ -851,12 +912,12 @@ __device__ __forceinline__ v3 clouds_sky(const FrameClouds& F, v3 dir) {
 // with SGPRs spilled to VGPR lanes.  ClArgs mirrors the kernel's argument list: the kernarg segment lays the arguments out in
 // order at their natural alignment, exactly like this struct.  (Passing ONE struct argument instead made every use in the
 // march a scalar load: 3.5 -> 4.0 ms.)
-struct ClArgs { FrameClouds F; RowMap M; float* out; const YRow* ytab; const float* htab; unsigned hbias4; };
+struct ClArgs { FrameClouds F; RowMap M; float* out; const YRow* ytab; const float* htab; unsigned hbias4; const float4* vtab; };
 // offset of argument I in the kernarg segment of a kernel with the parameter types A...
 template <size_t I, class... A>
 constexpr size_t kernarg_off(void (*)(A...)) {
     constexpr size_t sz[] = {sizeof(A)...}, al[] = {alignof(A)...};
-    static_assert(sizeof...(A) == 6, "ClArgs mirrors six kernel arguments");
+    static_assert(sizeof...(A) == 7, "ClArgs mirrors seven kernel arguments");
     size_t o = 0;
     for (size_t i = 0; i <= I; ++i) {
         o = (o + al[i] - 1) / al[i] * al[i];
@@ -875,9 +936,12 @@ constexpr size_t kernarg_off(void (*)(A...)) {
 // GT (CL_GTAB; YTAB && REG && LM != 0 only; 1 + CL_GTAB_OCT): the lattice hashes of octaves GT - 1 ... 3 come from the context's table
 // `htab` (GTab above), in the main sample and in the light march; the lower octaves keep the per-wave cache (GT = 1: the kernel has no
 // cache in LDS and no cross-lane step).  Lanes that do not march are given the straight-up ray, whose indices are in the table.
-template <bool YTAB, bool REG, int LM, bool SM = false, int BUILD = CLOUDS_DEFAULT, int GT = 0>   // SM: exp_small_ (launch_clouds: the frame's exp arguments lie in its domain)
+// VT (GT != 0 only): the pixel's sky colour, phase value and horizon weight come from the context's view table `vtab` ("the context's view table" above)
+template <bool YTAB, bool REG, int LM, bool SM = false, int BUILD = CLOUDS_DEFAULT, int GT = 0, bool VT = false>   // SM: exp_small_ (launch_clouds: the frame's exp arguments lie in its domain)
 __global__ void __launch_bounds__(64 * CL_TX, BUILD == CLOUDS_HEIGHT ? (YTAB ? CL_MIN_WAVES_HEIGHT : CL_MIN_WAVES_HEIGHT_NOTAB) : GT != 0 ? (LM == 2 ? CL_MIN_WAVES_GTAB_YZ : CL_MIN_WAVES_GTAB) : (LM == 1 && (YTAB || !CL_NOTAB_GEN)) ? CL_MIN_WAVES : (LM == 2 ? CL_MIN_WAVES_YZ : CL_MIN_WAVES_GEN)) k_clouds(FrameClouds F, RowMap M, float* __restrict__ out_arg,
-                                                          const YRow* __restrict__ ytab, const float* __restrict__ htab, unsigned hbias4) {
+                                                          const YRow* __restrict__ ytab, const float* __restrict__ htab, unsigned hbias4,
+                                                          const float4* __restrict__ vtab) {
+    static_assert(!VT || (GT != 0 && LM == 1), "the view-table kernels are hash-table kernels with the z-only light march");
     static_assert(GT == 0 || GT == 1 || GT == 3 || GT == 4, "a stage of the main sample reads all its octaves from one place: the table starts at octave 0, 2 or 3");
     static_assert(!GT || (YTAB && REG && LM != 0), "the hash-table kernels are the y-table REG kernels with the z-only or the y-z light march");
     const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();        // (for the dispatch order's cost table, RowMap.cost)
@@ -924,7 +988,8 @@ __global__ void __launch_bounds__(64 * CL_TX, BUILD == CLOUDS_HEIGHT ? (YTAB ? C
         // Only what the march needs stays live across it (origin, projection, phase): the view direction
         // and the sky colour are recomputed in the epilogue from the pixel coordinates — same operations,
         // same bits — which keeps the register budget of the march at 4 waves per SIMD without spills.
-        const Pixel px = pixel_of_thread<CL_TW, CL_TX, CL_TOP_FIRST>(M);
+        const Pixel px = (VT && CL_VT_PIXEL_PLAIN) ? pixel_of_plain<CL_TW, CL_TX, CL_TOP_FIRST>(M, (int)threadIdx.x, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y)
+                            : pixel_of_thread<CL_TW, CL_TX, CL_TOP_FIRST>(M);
         const v2 pc = point_cam(F.cam, px.fx, px.fy);
         const v3 dir = primary_dir(F.cam, pc);
         const float cutoff = dot(dir, V3(0, 1, 0));
@@ -956,6 +1021,10 @@ __global__ void __launch_bounds__(64 * CL_TX, BUILD == CLOUDS_HEIGHT ? (YTAB ? C
                 }
             }
 #if CL_PARK
+            if constexpr (VT) {
+                // the table's entry of the pixel (k_clouds_viewtab: hg_phase of the same direction); one load, long before a lit step reads it
+                if (BUILD != CLOUDS_LUMINANCE) pk[(8 - PARK_0) * 64] = vt_row(M, px) ? vtab[vt_index(M, px)].w : 0.f;
+            } else
             if (BUILD != CLOUDS_LUMINANCE) pk[(8 - PARK_0) * 64] = hg_phase(clamp_(dot(F.sun_dir, dir), 0.f, 1.f), .2f);
 #else
             float phase = 0.f;
@@ -1080,30 +1149,47 @@ __global__ void __launch_bounds__(64 * CL_TX, BUILD == CLOUDS_HEIGHT ? (YTAB ? C
     const FrameClouds& FE = kg->F;
     const RowMap& ME = kg->M;
     float* const out = kg->out;
+    const float4* const vtab_e = kg->vtab;
 #else
     const FrameClouds& FE = F;
     const RowMap& ME = M;
     float* const out = out_arg;
+    const float4* const vtab_e = vtab;
 #endif
+    (void)vtab_e;
 #if CL_EPILOGUE_RELOAD
     // the thread's coordinates as values of unknown origin too: otherwise the pixel arithmetic of the prologue is kept
     // alive (spilled to scratch: 20 B per lane written and read back through HBM) for the whole march
     int tid = (int)threadIdx.x, bx = (int)blockIdx.x, by = (int)blockIdx.y;
     asm volatile("" : "+v"(tid), "+s"(bx), "+s"(by));
-    const Pixel px = pixel_of<CL_TW, CL_TX, CL_TOP_FIRST>(ME, tid, bx, by, (int)gridDim.y);
+    const Pixel px = (VT && CL_VT_PIXEL_PLAIN) ? pixel_of_plain<CL_TW, CL_TX, CL_TOP_FIRST>(ME, tid, bx, by, (int)gridDim.y) : pixel_of<CL_TW, CL_TX, CL_TOP_FIRST>(ME, tid, bx, by, (int)gridDim.y);
 #else
-    const Pixel px = pixel_of_thread<CL_TW, CL_TX, CL_TOP_FIRST>(ME);
+    const Pixel px = (VT && CL_VT_PIXEL_PLAIN) ? pixel_of_plain<CL_TW, CL_TX, CL_TOP_FIRST>(ME, (int)threadIdx.x, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y)
+                        : pixel_of_thread<CL_TW, CL_TX, CL_TOP_FIRST>(ME);
 #endif
     if (!px.valid) return;
-    const v2 pc = point_cam(FE.cam, px.fx, px.fy);
-    const v3 dir = primary_dir(FE.cam, pc);
-    const v3 sky = clouds_sky(FE, dir);
+    v3 sky;
+    float cut = 0.f;
+    if constexpr (VT) {
+        // the two planes of the view table at the pixel's place in the frame: what the lines of the other branch give for it
+        const float4* const vt = vtab_e;
+        const bool row = vt_row(ME, px);
+        const size_t gp = vt_index(ME, px);
+        const float4 sp = row ? vt[gp] : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (marches && row) cut = vt_cut(vt, ME)[gp];
+        sky = V3(sp.x, sp.y, sp.z);
+    } else {
+        const v2 pc = point_cam(FE.cam, px.fx, px.fy);
+        const v3 dir = primary_dir(FE.cam, pc);
+        sky = clouds_sky(FE, dir);
+        if (marches) cut = smoothstep_(.0f, .2f, dot(dir, V3(0, 1, 0)));
+    }
     v3 col = sky;
     if (marches) {
 #if CL_PARK
         const float radiance = pk[(6 - PARK_0) * 64], alpha = pk[(7 - PARK_0) * 64];
 #endif
-        const float a = alpha * smoothstep_(.0f, .2f, dot(dir, V3(0, 1, 0)));
+        const float a = alpha * cut;
         col = abs3(mix3(sky, V3s(radiance), a));               // :215-217
     }
     tile_cost_store(ME, tl_t0);
@@ -1216,7 +1302,7 @@ static bool clouds_exp_small(const FrameClouds& F) {
 // rules for every build (REG / SM / y table / light-march form / hash table), over the build's own instantiations.  The HEIGHT build has
 // no light march, so the form of L * dt selects nothing there (its instantiations carry LM = 1 for the one thing LM decides outside the
 // light march: the SM kernels' div3_ smoothstep in the main sample).  A pure function of its arguments: no device, no context.
-sbx_clouds_selection clouds_select(const FrameClouds& F, const RowMap& M, int variant, int build, int ytab_rows, int table_range) {
+sbx_clouds_selection clouds_select(const FrameClouds& F, const RowMap& M, int variant, int build, int ytab_rows, int table_range, bool view_table) {
     const bool HT = build == CLOUDS_HEIGHT;
     sbx_clouds_selection S{};
     S.build = build;
@@ -1244,6 +1330,8 @@ sbx_clouds_selection clouds_select(const FrameClouds& F, const RowMap& M, int va
         // a regular frame, the z-only or the y-z march among them)
         if (CL_GTAB && S.table_range > 0 && S.need_range > 0 && S.need_range <= S.table_range) {
             S.reg = 1; S.lm = zl ? 1 : 2; S.sm = (zl ? sm : sm && CL_YZ_SM) ? 1 : 0; S.gt = CL_GTAB_OCT + 1;
+            // the view-table kernels: iff a ready view table of the frame's camera is at hand as well, on a launch that may read one
+            S.vt = (view_table && zl && clouds_viewtab_eligible(F, M, build)) ? 1 : 0;
         } else if (zl) { S.reg = reg; S.lm = 1; S.sm = reg && sm; }
         else if (reg && yz) { S.reg = 1; S.lm = 2; S.sm = sm && CL_YZ_SM; }
         else if (reg) { S.reg = 1; S.lm = 0; S.sm = sm; }
@@ -1257,28 +1345,29 @@ sbx_clouds_selection clouds_select(const FrameClouds& F, const RowMap& M, int va
 
 // THE LAUNCHER: every launch of k_clouds and of k_clouds_perlane goes through here, and the record's kernel fields are written from the
 // template arguments of the kernel that is launched — the record cannot name another kernel than the one that ran.
-struct ClLaunch { dim3 grid, block; unsigned lds; hipStream_t s; const FrameClouds* F; const RowMap* M; float* out; const YRow* ct; const float* htab; unsigned hb4; };
-template <bool YTAB, bool REG, int LM, bool SM, int BUILD, int GT>
+struct ClLaunch { dim3 grid, block; unsigned lds; hipStream_t s; const FrameClouds* F; const RowMap* M; float* out; const YRow* ct; const float* htab; unsigned hb4; const float4* vtab; };
+template <bool YTAB, bool REG, int LM, bool SM, int BUILD, int GT, bool VT = false>
 static void launch_form(sbx_clouds_selection& R, const ClLaunch& L) {
-    R.build = BUILD; R.perlane = 0; R.ytab_used = YTAB; R.reg = REG; R.lm = LM; R.sm = SM; R.gt = GT;
-    hipLaunchKernelGGL((k_clouds<YTAB, REG, LM, SM, BUILD, GT>), L.grid, L.block, L.lds, L.s, *L.F, *L.M, L.out, L.ct, L.htab, L.hb4);
+    R.build = BUILD; R.perlane = 0; R.ytab_used = YTAB; R.reg = REG; R.lm = LM; R.sm = SM; R.gt = GT; R.vt = VT;
+    hipLaunchKernelGGL((k_clouds<YTAB, REG, LM, SM, BUILD, GT, VT>), L.grid, L.block, L.lds, L.s, *L.F, *L.M, L.out, L.ct, L.htab, L.hb4, L.vtab);
 }
 template <int BUILD>
 static void launch_perlane(sbx_clouds_selection& R, const ClLaunch& L) {
-    R.build = BUILD; R.perlane = 1; R.ytab_used = 0; R.reg = 0; R.lm = 0; R.sm = 0; R.gt = 0;
+    R.build = BUILD; R.perlane = 1; R.ytab_used = 0; R.reg = 0; R.lm = 0; R.sm = 0; R.gt = 0; R.vt = 0;
     hipLaunchKernelGGL(k_clouds_perlane<BUILD>, grid_for<32>(*L.M), dim3(WG_THREADS), 0, L.s, *L.F, *L.M, L.out);
 }
 
 // One build's launch: the selection above, mapped onto the build's instantiations — 19 for the shipped build and for LUMINANCE (4 with
-// the hash table, 9 with the y table and the LDS cache, 6 table-less), 8 for HEIGHT (LM = 1 only: 2 + 3 + 3), and the per-lane kernel.
+// the hash table, 9 with the y table and the LDS cache, 6 table-less), 8 for HEIGHT (LM = 1 only: 2 + 3 + 3), and the per-lane kernel;
+// and the VT twins of the hash-table forms with LM = 1 (2 per build), taken where a ready view table is at hand.
 // A selection outside the list would be a bug of clouds_select: nothing is launched and the record says perlane = -1.
 template <int BUILD>
 static bool launch_clouds_build(const FrameClouds& F_in, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
-                                bool build_table, const CloudsHashTab* ht, sbx_clouds_selection& R, int ytab_kind) {
+                                bool build_table, const CloudsHashTab* ht, sbx_clouds_selection& R, int ytab_kind, const float4* vtab) {
     constexpr bool HT = BUILD == CLOUDS_HEIGHT;
     constexpr int G = CL_GTAB_OCT + 1;
     const int table_range = (CL_GTAB && ht && ht->tab) ? ht->range : 0;
-    const sbx_clouds_selection S = clouds_select(F_in, M, variant, BUILD, ytab ? ytab_rows : 0, table_range);
+    const sbx_clouds_selection S = clouds_select(F_in, M, variant, BUILD, ytab ? ytab_rows : 0, table_range, vtab != nullptr);
     const uint64_t launches = R.launches;
     R = S;
     R.launches = launches;
@@ -1294,7 +1383,7 @@ static bool launch_clouds_build(const FrameClouds& F_in, const RowMap& M, float*
 #else
     const unsigned pad = 0;
 #endif
-    ClLaunch L{grid_for<CL_TW, CL_TX>(M), dim3(64 * CL_TX), 0u, s, &F, &M, out, nullptr, nullptr, 0u};
+    ClLaunch L{grid_for<CL_TW, CL_TX>(M), dim3(64 * CL_TX), 0u, s, &F, &M, out, nullptr, nullptr, 0u, nullptr};
     if (S.perlane) { launch_perlane<BUILD>(R, L); return false; }
     if (S.ytab_used) {
         YRow* tab = reinterpret_cast<YRow*>(ytab);
@@ -1303,13 +1392,16 @@ static bool launch_clouds_build(const FrameClouds& F_in, const RowMap& M, float*
         if (build_table && HT) hipLaunchKernelGGL(k_clouds_lumtab, dim3((F.steps + 63) / 64), dim3(64), 0, s, F.steps, const_cast<float*>(lum_of(tab, F.steps)));
         L.ct = tab;
         R.ytab = ytab_kind;
-        if (S.gt) { L.htab = ht->tab; L.hb4 = 4u * (unsigned)ht->bias; }
+        if (S.gt) { L.htab = ht->tab; L.hb4 = 4u * (unsigned)ht->bias; if (S.vt) L.vtab = vtab; }
         else if (S.reg && S.lm == 1) L.lds = pad;
     }
-    const int key = S.ytab_used << 12 | S.reg << 8 | S.lm << 4 | S.sm << 1 | (S.gt ? 1 : 0);
-#define CL_FORM(Y, RG, LMV, SMV, GTV) \
-    if (key == ((Y) << 12 | (RG) << 8 | (LMV) << 4 | (SMV) << 1 | ((GTV) ? 1 : 0))) { \
-        if constexpr ((LMV) == 1 || !HT) { launch_form<(Y) != 0, (RG) != 0, (LMV), (SMV) != 0, BUILD, (GTV)>(R, L); return (GTV) != 0; } }
+    const int key = (S.vt ? 1 : 0) << 16 | S.ytab_used << 12 | S.reg << 8 | S.lm << 4 | S.sm << 1 | (S.gt ? 1 : 0);
+#define CL_FORM_VT(Y, RG, LMV, SMV, GTV, VTV) \
+    if (key == ((VTV) << 16 | (Y) << 12 | (RG) << 8 | (LMV) << 4 | (SMV) << 1 | ((GTV) ? 1 : 0))) { \
+        if constexpr ((LMV) == 1 || !HT) { launch_form<(Y) != 0, (RG) != 0, (LMV), (SMV) != 0, BUILD, (GTV), (VTV) != 0>(R, L); return (GTV) != 0; } }
+#define CL_FORM(Y, RG, LMV, SMV, GTV) CL_FORM_VT(Y, RG, LMV, SMV, GTV, 0)
+    // the hash-table kernels that read the view table as well
+    CL_FORM_VT(1, 1, 1, 1, G, 1) CL_FORM_VT(1, 1, 1, 0, G, 1)
     // the y-table kernels that read the lattice-hash table
     CL_FORM(1, 1, 1, 1, G) CL_FORM(1, 1, 1, 0, G) CL_FORM(1, 1, 2, 1, G) CL_FORM(1, 1, 2, 0, G)
     // the y-table kernels with the per-wave LDS cache
@@ -1319,6 +1411,7 @@ static bool launch_clouds_build(const FrameClouds& F_in, const RowMap& M, float*
     CL_FORM(0, 1, 1, 1, 0) CL_FORM(0, 1, 1, 0, 0) CL_FORM(0, 0, 1, 0, 0)
     CL_FORM(0, 1, 0, 1, 0) CL_FORM(0, 1, 0, 0, 0) CL_FORM(0, 0, 0, 0, 0)
 #undef CL_FORM
+#undef CL_FORM_VT
     R.perlane = -1;                                              // unreachable: clouds_select names listed forms only
     return false;
 }
@@ -1327,18 +1420,18 @@ static bool launch_clouds_build(const FrameClouds& F_in, const RowMap& M, float*
 typedef decltype(&k_clouds<true, true, 1>) KCloudsFn;
 static_assert(kernarg_off<0>(KCloudsFn(nullptr)) == offsetof(ClArgs, F) && kernarg_off<1>(KCloudsFn(nullptr)) == offsetof(ClArgs, M) &&
               kernarg_off<2>(KCloudsFn(nullptr)) == offsetof(ClArgs, out) && kernarg_off<3>(KCloudsFn(nullptr)) == offsetof(ClArgs, ytab) &&
-              kernarg_off<4>(KCloudsFn(nullptr)) == offsetof(ClArgs, htab) && kernarg_off<5>(KCloudsFn(nullptr)) == offsetof(ClArgs, hbias4) &&
-              offsetof(ClArgs, hbias4) + sizeof(unsigned) <= sizeof(ClArgs) && sizeof(ClArgs) < offsetof(ClArgs, hbias4) + sizeof(unsigned) + alignof(ClArgs),
+              kernarg_off<4>(KCloudsFn(nullptr)) == offsetof(ClArgs, htab) && kernarg_off<5>(KCloudsFn(nullptr)) == offsetof(ClArgs, hbias4) && kernarg_off<6>(KCloudsFn(nullptr)) == offsetof(ClArgs, vtab) &&
+              offsetof(ClArgs, vtab) + sizeof(void*) <= sizeof(ClArgs) && sizeof(ClArgs) < offsetof(ClArgs, vtab) + sizeof(void*) + alignof(ClArgs),
               "ClArgs must mirror k_clouds' argument list, argument for argument");
 
 bool launch_clouds(const FrameClouds& F, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
-                   bool build_table, int build, const CloudsHashTab* ht, sbx_clouds_selection* rec, int ytab_kind) {
+                   bool build_table, int build, const CloudsHashTab* ht, sbx_clouds_selection* rec, int ytab_kind, const float4* vtab) {
     sbx_clouds_selection local{};
     sbx_clouds_selection& R = rec ? *rec : local;
     R.launches += 1;
-    if (build == CLOUDS_HEIGHT) return launch_clouds_build<CLOUDS_HEIGHT>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht, R, ytab_kind);
-    if (build == CLOUDS_LUMINANCE) return launch_clouds_build<CLOUDS_LUMINANCE>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht, R, ytab_kind);
-    return launch_clouds_build<CLOUDS_DEFAULT>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht, R, ytab_kind);
+    if (build == CLOUDS_HEIGHT) return launch_clouds_build<CLOUDS_HEIGHT>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht, R, ytab_kind, vtab);
+    if (build == CLOUDS_LUMINANCE) return launch_clouds_build<CLOUDS_LUMINANCE>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht, R, ytab_kind, vtab);
+    return launch_clouds_build<CLOUDS_DEFAULT>(F, M, out, s, variant, ytab, ytab_rows, build_table, ht, R, ytab_kind, vtab);
 }
 
 hipError_t bind_fault_clouds(unsigned* word) { return hc_bind_fault_word(word); }

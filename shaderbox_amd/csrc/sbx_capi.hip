@@ -91,6 +91,7 @@ static void destroy_ctx(sbx_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     release(ctx->ytab);
     release(ctx->hashtab);
+    release(ctx->viewtab, ctx->event_pool);
     release(ctx->mi);
     tile_order_destroy(ctx->tile_orders);
     release(ctx->hs);
@@ -267,6 +268,7 @@ int sbx::render_mapped(sbx_ctx* ctx, int app, const sbx_uniforms* uni, const voi
     case SBX_APP_CLOUDS_LUMINANCE: rc = render_clouds(ctx, build_clouds(*uni, AC), M, rgba, s, capturing, CLOUDS_LUMINANCE); break;
     case SBX_APP_CLOUDS_SKY:
         ctx->hashtab.last_used = 0;
+        ctx->viewtab.last_used = 0; ctx->viewtab.last_refusal = SBX_VIEWTAB_INELIGIBLE;
         launch_clouds(build_clouds(*uni, AC, true), M, rgba, s, ctx->variant, nullptr, 0, false, CLOUDS_DEFAULT, nullptr, &ctx->hashtab.last_selection);
         break;
     case SBX_APP_CLOUDS_TEX: launch_clouds_tex(build_clouds(*uni, AC), M, rgba, s, ctx->noise.shape, ctx->noise.shape_size, ctx->noise.detail, ctx->noise.detail_size,
@@ -629,6 +631,51 @@ int sbx_debug_clouds_select(int app, const sbx_uniforms* uni, const void* aux, i
     RowMap M{};                                                        // (the choice reads `frag` alone: a point list or not)
     if (point_list) { M.frag = one_point; M.npoints = 1; }
     *out = clouds_select(build_clouds(*uni, AC, sky), M, variant, build, sky ? 0 : ytab_rows, sky ? 0 : table_range);
+    return SBX_OK;
+}
+
+int sbx_debug_clouds_select_vt(int app, const sbx_uniforms* uni, const void* aux, int variant, int ytab_rows, int table_range, int point_list,
+                               int view_table, sbx_clouds_selection* out) {
+    if (!uni || !out) return SBX_ERR_ARG;
+    int build = CLOUDS_DEFAULT;
+    if (app == SBX_APP_CLOUDS_HEIGHT) build = CLOUDS_HEIGHT;
+    else if (app == SBX_APP_CLOUDS_LUMINANCE) build = CLOUDS_LUMINANCE;
+    else if (app != SBX_APP_CLOUDS && app != SBX_APP_CLOUDS_SKY) return SBX_ERR_ARG;
+    const sbx_aux_clouds AC = aux_clouds(aux);
+    if (AC.cld_march_steps < 0 || AC.illum_march_steps < 0) return SBX_ERR_ARG;
+    const bool sky = app == SBX_APP_CLOUDS_SKY;
+    static const float one_point[2] = {.5f, .5f};
+    const int W = (int)uni->u_res[0], H = (int)uni->u_res[1];
+    RowMap M{W, H, 0, H > 0 ? H : 1, 1, 0, H, 0, 1, 1, 0, 0};          // render_rows' map of the whole frame
+    if (point_list) { M.frag = one_point; M.npoints = 1; }
+    *out = clouds_select(build_clouds(*uni, AC, sky), M, variant, build, sky ? 0 : ytab_rows, sky ? 0 : table_range, view_table != 0);
+    return SBX_OK;
+}
+
+int sbx_debug_clouds_viewtab_key(int app, const sbx_uniforms* uni, const void* aux, unsigned* key, int words) {
+    if (!uni || !key || words != ViewTables::KEY_WORDS) return SBX_ERR_ARG;
+    if (app != SBX_APP_CLOUDS && app != SBX_APP_CLOUDS_HEIGHT && app != SBX_APP_CLOUDS_LUMINANCE) return SBX_ERR_ARG;
+    const sbx_aux_clouds AC = aux_clouds(aux);
+    if (AC.cld_march_steps < 0 || AC.illum_march_steps < 0) return SBX_ERR_ARG;
+    uint32_t k[ViewTables::KEY_WORDS];
+    clouds_viewtab_key(build_clouds(*uni, AC), (int)uni->u_res[0], (int)uni->u_res[1], k);
+    std::memcpy(key, k, sizeof(k));
+    return SBX_OK;
+}
+
+int sbx_debug_clouds_viewtab(sbx_ctx* ctx, size_t* entries, int* tables_built, int* last_launch_used_table, int* last_refusal) {
+    if (!ctx) return SBX_ERR_ARG;
+    const ViewTables& V = ctx->viewtab;
+    if (entries) *entries = V.last_entries;
+    if (tables_built) *tables_built = V.built;
+    if (last_launch_used_table) *last_launch_used_table = V.last_used;
+    if (last_refusal) *last_refusal = V.last_used ? SBX_VIEWTAB_USED : V.last_refusal;
+    return SBX_OK;
+}
+
+int sbx_debug_set_clouds_viewtab_cap(sbx_ctx* ctx, size_t bytes) {
+    if (!ctx) return SBX_ERR_ARG;
+    ctx->viewtab.cap_bytes = bytes;
     return SBX_OK;
 }
 

@@ -77,6 +77,39 @@ struct HashTables {
                                            // (sbx_debug_clouds_last_selection; written by the launcher, kern_clouds.hip launch_form)
 };
 
+// APP_CLOUDS view tables (sbx_ytab.hip clouds_view_table; kern_clouds.hip "the context's view table"): per camera, the sky colour, the
+// phase value and the horizon weight of every pixel of a full frame, 20 bytes per pixel.  Two slots, one key each — the meaningful
+// words of the camera, the sun and the frame size (clouds_viewtab_key), never a pad, u_time, the wind or a cloud parameter.
+// A table is built in line on the stream of the eager launch that is due, once the two eligible eager launches before it had the same
+// key (launches that may read no table — point lists, spans, other suns, the per-lane kernel — neither count nor break the run);
+// it never changes while it is valid.  Ordering as the hash tables': one `ready` event, waited for until the host has once seen it
+// complete.  A slot is given another key (least recently used first) only after it has DRAINED: when it is chosen, an event is
+// recorded on every stream that launched a reader of it, and the slot is free once the host has seen all of them complete — a launch
+// that finds no free slot takes the table-less instantiation.  A table that a stream capture took is pinned: a graph holds its address.
+// INVARIANT: `valid` means the build kernel is ENQUEUED and `ready` recorded behind it; a slot is either valid, draining or free.
+struct ViewTables {
+    static constexpr int KEY_WORDS = 28;
+    struct Tab {
+        float4* dev = nullptr;
+        size_t cap_pixels = 0;             // of the allocation
+        size_t pixels = 0;                 // width * height of the key
+        uint32_t key[KEY_WORDS] = {};
+        bool valid = false, draining = false, pinned = false, seen_complete = false;
+        hipEvent_t ready{};
+        bool have_ready = false;
+        uint64_t last_use = 0;
+        std::vector<std::pair<hipStream_t, hipEvent_t>> users;   // streams that launched readers, each with the event a drain records on it
+    };
+    Tab tabs[2];
+    uint32_t last_key[KEY_WORDS] = {};     // of the context's last eligible eager launch, and how many in a row had it
+    int streak = 0;
+    uint64_t clock = 0;
+    size_t cap_bytes = SBX_CLOUDS_VIEWTAB_DEFAULT_BYTES;   // sbx_debug_set_clouds_viewtab_cap
+    int built = 0;                         // tables built so far
+    int last_used = 0, last_refusal = 0;   // of the context's last launch of k_clouds (SBX_VIEWTAB_* of sbx_test.h)
+    size_t last_entries = 0;               // pixels of the table built or used last
+};
+
 // per-stream timing events (sbx_set_timing): a pair brackets the last launch on its stream
 struct Timers {
     bool enabled = false;
@@ -177,6 +210,7 @@ struct sbx_ctx {
     int sdf_roots = 0;                     // sbx_set_variant 2 / 3: the SDF kernels' square-root witness test build / IEEE roots
     YTables ytab;
     HashTables hashtab;
+    ViewTables viewtab;
     Timers timers;
     NoiseVolumes noise;
     Texture2d tex2d;
@@ -273,6 +307,9 @@ int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rg
 sbx::CloudsHashTab clouds_hash_table_any(sbx_ctx* ctx, hipStream_t s, bool capturing);
 void release(YTables& Y);
 void release(HashTables& H);
+void release(ViewTables& V, std::vector<hipEvent_t>& pool);
+// the key of a launch's view table (ViewTables::KEY_WORDS words): the camera, the sun and the frame size, field by field
+void clouds_viewtab_key(const FrameClouds& F, int width, int height, uint32_t* key);
 
 // ---- sbx_main_image.hip
 void mi_invalidate(sbx_ctx* ctx);          // forget the cached frames (something they were rendered with changed)

@@ -155,13 +155,20 @@ int clouds_hashtab_range(const FrameClouds& F, const RowMap& M, int build);   //
 void launch_clouds_hashtab(float* tab, int entries, int bias, hipStream_t s);
 // The kernel a launch takes, as a pure function of the frame (kern_clouds.hip): "a y table of ytab_rows rows is at hand" (0: none),
 // "a ready hash table of range table_range is at hand" (0: none).  No device, no context; launch_clouds launches what this returns.
-sbx_clouds_selection clouds_select(const FrameClouds& F, const RowMap& M, int variant, int build, int ytab_rows, int table_range);
+// view_table: "a ready view table of the frame's camera is at hand" (kern_clouds.hip "the context's view table"): taken only by a hash-table kernel
+sbx_clouds_selection clouds_select(const FrameClouds& F, const RowMap& M, int variant, int build, int ytab_rows, int table_range,
+                                   bool view_table = false);
 // returns whether the launch took a hash-table kernel (only with `ht`: a READY table; taken iff it covers the frame's index bound).
 // rec: the record of what was launched (sbx_test.h), written by the launcher itself; its `ytab` is ytab_kind where a y table was read
 bool launch_clouds(const FrameClouds& F, const RowMap& M, float* out, hipStream_t s, int variant, void* ytab, int ytab_rows,
                    bool build_table, int build = CLOUDS_DEFAULT,    // build: CLOUDS_* (sbx_frame.h); build_table with CLOUDS_HEIGHT also
                    const CloudsHashTab* ht = nullptr,               // writes the steps' luminances behind the y rows
-                   sbx_clouds_selection* rec = nullptr, int ytab_kind = 0);
+                   sbx_clouds_selection* rec = nullptr, int ytab_kind = 0,
+                   const float4* vtab = nullptr);                   // vtab: a view table of F's camera that is READY on `s`, or NULL
+// APP_CLOUDS' view table (kern_clouds.hip "the context's view table"; owned by the context, sbx_ytab.hip): 20 bytes per frame pixel
+constexpr size_t CLOUDS_VIEWTAB_PIXEL_BYTES = 20;
+void launch_clouds_viewtab(const FrameClouds& F, int width, int height, float4* tab, hipStream_t s);
+bool clouds_viewtab_eligible(const FrameClouds& F, const RowMap& M, int build);   // the launch may read a view table (never: points, spans, ranks' strips, SKY_SPHERE, the y-z light march)
 constexpr int CLOUDS_YTAB_ROWS = 4096;      // march steps covered by a y table of the ring (208 KB per table; beyond it the one big
                                             // table below, or in a capture the table-less kernels: 1100 steps at 4K took 48 ms without a table)
 constexpr int CLOUDS_YTAB_STEP_BYTES = 48 + 4;   // per march step: its YRow and, behind the frame's rows, the HEIGHT build's luminance

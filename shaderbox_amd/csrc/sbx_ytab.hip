@@ -1,6 +1,8 @@
 // shaderbox_amd/csrc/sbx_ytab.hip — APP_CLOUDS' y tables (YTables, sbx_ctx.h): which table a launch of k_clouds reads, when one
-// is rebuilt, and who has to wait for whom; and its lattice-hash tables (HashTables), which are built once and never rebuilt.
+// is rebuilt, and who has to wait for whom; its lattice-hash tables (HashTables), which are built once and never rebuilt; and its view
+// tables (ViewTables), one per camera.
 #include "sbx_ctx.h"
+#include <cstdlib>
 #include <cstring>
 
 namespace sbx {
@@ -69,8 +71,135 @@ CloudsHashTab clouds_hash_table_any(sbx_ctx* ctx, hipStream_t s, bool capturing)
     return clouds_hash_table_range(ctx, CLOUDS_HASHTAB_MIN_RANGE, true, s, capturing);
 }
 
+// ---- the view tables (ViewTables, sbx_ctx.h) ----------------------------------------------------------------------------------
+void clouds_viewtab_key(const FrameClouds& F, int width, int height, uint32_t* key) {
+    const Camera& c = F.cam;
+    const float f[22] = {c.res_x, c.res_y, c.aspect_x, c.fov, c.eye.x, c.eye.y, c.eye.z, c.fwd.x, c.fwd.y, c.fwd.z, c.up.x, c.up.y, c.up.z,
+                         c.right.x, c.right.y, c.right.z, F.sun_dir.x, F.sun_dir.y, F.sun_dir.z, F.sun_color.x, F.sun_color.y, F.sun_color.z};
+    const double d[2] = {c.rres_x, c.rres_y};
+    const int wh[2] = {width, height};
+    static_assert(sizeof(f) + sizeof(d) + sizeof(wh) == ViewTables::KEY_WORDS * sizeof(uint32_t), "the key is these fields, word for word");
+    std::memcpy(key, f, sizeof(f));
+    std::memcpy(key + 22, d, sizeof(d));
+    std::memcpy(key + 26, wh, sizeof(wh));
+}
+static bool viewtab_enabled() {
+    static const bool on = [] { const char* v = std::getenv("SBX_CLOUDS_VIEWTAB"); return !(v && v[0] == '0' && v[1] == 0); }();
+    return on;
+}
+// has every reader of a draining slot completed?  (events recorded when the slot was chosen; queried, never waited for)
+static bool viewtab_drained(ViewTables::Tab& t, std::vector<hipEvent_t>& pool) {
+    for (auto& u : t.users) {
+        if (hipEventQuery(u.second) != hipSuccess) { (void)hipGetLastError(); return false; }
+    }
+    for (auto& u : t.users) pool.push_back(u.second);
+    t.users.clear();
+    t.draining = false;
+    return true;
+}
+// The view table of a launch that takes a hash-table kernel, made ready for stream `s`, or nullptr with the reason in V.last_refusal.
+static const float4* clouds_view_table(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, hipStream_t s, bool capturing, int build) {
+    ViewTables& V = ctx->viewtab;
+    auto refuse = [&V](int why) -> const float4* { V.last_refusal = why; return nullptr; };
+    if (!viewtab_enabled()) return refuse(SBX_VIEWTAB_OFF);
+    if (!clouds_viewtab_eligible(F, M, build)) return refuse(SBX_VIEWTAB_INELIGIBLE);
+    uint32_t key[ViewTables::KEY_WORDS];
+    clouds_viewtab_key(F, M.width, M.height, key);
+    int seen_before = 0;                               // eager launches in a row, just before this one, that had this key
+    if (!capturing) {
+        const bool same = V.streak > 0 && std::memcmp(key, V.last_key, sizeof(key)) == 0;
+        seen_before = same ? V.streak : 0;
+        V.streak = seen_before + 1;
+        std::memcpy(V.last_key, key, sizeof(key));
+    }
+    ViewTables::Tab* t = nullptr;
+    for (auto& c : V.tabs) if (c.valid && std::memcmp(key, c.key, sizeof(key)) == 0) t = &c;
+    if (t) {
+        if (!t->seen_complete) {
+            if (capturing) return refuse(SBX_VIEWTAB_CAPTURE);
+            if (hipEventQuery(t->ready) == hipSuccess) t->seen_complete = true;
+            else {
+                (void)hipGetLastError();                                     // (hipErrorNotReady)
+                if (hipStreamWaitEvent(s, t->ready, 0) != hipSuccess) { (void)hipGetLastError(); return refuse(SBX_VIEWTAB_ALLOC); }
+            }
+        }
+        if (capturing) t->pinned = true;               // the graph holds the table's address: the slot keeps its key for good
+    } else {
+        if (capturing) return refuse(SBX_VIEWTAB_CAPTURE);
+        if (seen_before < 2) return refuse(SBX_VIEWTAB_NEW_KEY);
+        const size_t pixels = (size_t)M.width * (size_t)M.height;
+        if (pixels * CLOUDS_VIEWTAB_PIXEL_BYTES > V.cap_bytes) return refuse(SBX_VIEWTAB_CAP);
+        // a free slot; else the least recently used one that no capture holds starts to drain
+        for (auto& c : V.tabs) if (!c.valid && !c.draining) { t = &c; break; }
+        if (!t) {
+            for (auto& c : V.tabs) if (c.draining && viewtab_drained(c, ctx->event_pool)) { t = &c; break; }
+        }
+        // (while a slot drains no other is chosen: a due key that finds the drain unfinished waits for it, launch after launch, and
+        //  never sends the other table after the first)
+        bool draining = false;
+        for (auto& c : V.tabs) draining = draining || c.draining;
+        if (!t && !draining) {
+            ViewTables::Tab* lru = nullptr;
+            for (auto& c : V.tabs) if (c.valid && !c.pinned && (!lru || c.last_use < lru->last_use)) lru = &c;
+            if (lru) {
+                bool ok = true;
+                for (auto& u : lru->users)
+                    ok = ok && !stream_is_capturing(u.first) && hipEventRecord(u.second, u.first) == hipSuccess;
+                if (!ok) { (void)hipGetLastError(); (void)hipDeviceSynchronize(); (void)hipGetLastError(); }   // (a stream that is gone: everything has run)
+                lru->valid = false;
+                if (!ok) { for (auto& u : lru->users) ctx->event_pool.push_back(u.second); lru->users.clear(); t = lru; }
+                else { lru->draining = true; if (viewtab_drained(*lru, ctx->event_pool)) t = lru; }
+            }
+        }
+        if (!t) return refuse(SBX_VIEWTAB_NO_SLOT);
+        if (t->cap_pixels < pixels) {
+            if (t->dev) (void)hipFree(t->dev);
+            t->dev = nullptr; t->cap_pixels = 0;
+            if (hipMalloc((void**)&t->dev, pixels * CLOUDS_VIEWTAB_PIXEL_BYTES) != hipSuccess) { (void)hipGetLastError(); t->dev = nullptr; return refuse(SBX_VIEWTAB_ALLOC); }
+            t->cap_pixels = pixels;
+        }
+        if (!t->have_ready) {
+            if (hipEventCreateWithFlags(&t->ready, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return refuse(SBX_VIEWTAB_ALLOC); }
+            t->have_ready = true;
+        }
+        launch_clouds_viewtab(F, M.width, M.height, t->dev, s);
+        if (hipGetLastError() != hipSuccess || hipEventRecord(t->ready, s) != hipSuccess) { (void)hipGetLastError(); return refuse(SBX_VIEWTAB_ALLOC); }
+        std::memcpy(t->key, key, sizeof(key));
+        t->pixels = pixels;
+        t->valid = true; t->seen_complete = false; t->pinned = false;
+        V.built += 1;
+    }
+    if (!capturing) {                                  // this stream reads the slot: remembered, nothing recorded (as the y tables do)
+        bool found = false;
+        for (auto& u : t->users) if (u.first == s) { found = true; break; }
+        if (!found) {
+            hipEvent_t ev{};
+            if (!ctx->event_pool.empty()) { ev = ctx->event_pool.back(); ctx->event_pool.pop_back(); }
+            else if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return refuse(SBX_VIEWTAB_ALLOC); }
+            t->users.emplace_back(s, ev);
+        }
+    }
+    t->last_use = ++V.clock;
+    V.last_entries = t->pixels;
+    V.last_refusal = SBX_VIEWTAB_USED;
+    return t->dev;
+}
+// after the launch: what the launcher took is what the hook reports (a table handed to a launch whose selection then takes no VT kernel
+// — a build with CL_GTAB off — counts as not eligible)
+static void viewtab_launched(ViewTables& V, int vt) {
+    V.last_used = vt;
+    if (!vt && V.last_refusal == SBX_VIEWTAB_USED) V.last_refusal = SBX_VIEWTAB_INELIGIBLE;
+}
+// (what every launch of render_clouds does with it: only a launch that was given a hash table asks for a view table)
+static const float4* clouds_view_table_for(sbx_ctx* ctx, const CloudsHashTab& ht, const FrameClouds& F, const RowMap& M, hipStream_t s, bool capturing, int build) {
+    if (!ht.tab) { ctx->viewtab.last_refusal = viewtab_enabled() ? SBX_VIEWTAB_INELIGIBLE : SBX_VIEWTAB_OFF; return nullptr; }
+    return clouds_view_table(ctx, F, M, s, capturing, build);
+}
+
 int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rgba, hipStream_t s, bool capturing, int build) {
     ctx->hashtab.last_used = 0;
+    ctx->viewtab.last_used = 0;
+    ctx->viewtab.last_refusal = viewtab_enabled() ? SBX_VIEWTAB_INELIGIBLE : SBX_VIEWTAB_OFF;
     sbx_clouds_selection* const rec = &ctx->hashtab.last_selection;       // (sbx_debug_clouds_last_selection; launch_clouds counts)
     const bool need_lum = build == CLOUDS_HEIGHT;
     const bool uses_table = ctx->variant == 0 && F.steps > 0 && F.steps <= CLOUDS_YTAB_ROWS;
@@ -100,7 +229,8 @@ int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rg
             (void)hipStreamWaitEvent(s, ctx->ytab.big_ready, 0);
         }
         const CloudsHashTab ht = clouds_hash_table(ctx, F, M, s, capturing, build);
-        ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, ctx->ytab.big, ctx->ytab.big_rows, rebuild, build, &ht, rec, 2) ? 1 : 0;
+        ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, ctx->ytab.big, ctx->ytab.big_rows, rebuild, build, &ht, rec, 2, clouds_view_table_for(ctx, ht, F, M, s, capturing, build)) ? 1 : 0;
+        viewtab_launched(ctx->viewtab, rec->vt);
         if (rebuild) {
             (void)hipEventRecord(ctx->ytab.big_ready, s);
             std::memcpy(ctx->ytab.big_key, key, sizeof(key));
@@ -117,7 +247,8 @@ int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rg
     if (capturing) {
         char* tab = ctx->ytab.ring + (size_t)(CLOUDS_YTAB_RING + (ctx->ytab.cap_next++ % CLOUDS_YTAB_CAPTURE)) * CLOUDS_YTAB_BYTES;
         const CloudsHashTab ht = clouds_hash_table(ctx, F, M, s, capturing, build);
-        ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, true, build, &ht, rec, 3) ? 1 : 0;
+        ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, true, build, &ht, rec, 3, clouds_view_table_for(ctx, ht, F, M, s, capturing, build)) ? 1 : 0;
+        viewtab_launched(ctx->viewtab, rec->vt);
         return SBX_OK;
     }
     const float key[3] = {F.cam.eye.y, F.wind_off.y, F.dt};
@@ -151,7 +282,8 @@ int render_clouds(sbx_ctx* ctx, const FrameClouds& F, const RowMap& M, float* rg
     }
     char* tab = ctx->ytab.ring + (size_t)slot * CLOUDS_YTAB_BYTES;
     const CloudsHashTab ht = clouds_hash_table(ctx, F, M, s, capturing, build);
-    ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, rebuild, build, &ht, rec, 1) ? 1 : 0;
+    ctx->hashtab.last_used = launch_clouds(F, M, rgba, s, 0, tab, CLOUDS_YTAB_ROWS, rebuild, build, &ht, rec, 1, clouds_view_table_for(ctx, ht, F, M, s, capturing, build)) ? 1 : 0;
+    viewtab_launched(ctx->viewtab, rec->vt);
     if (rebuild) {
         (void)hipEventRecord(ctx->ytab.ready, s);                  // the build is enqueued: now the cache state is true
         std::memcpy(ctx->ytab.key, key, sizeof(key));
@@ -180,6 +312,15 @@ void release(YTables& Y) {
     if (Y.have_ready) (void)hipEventDestroy(Y.ready);
     for (auto& sl : Y.slots) for (auto& u : sl.users) (void)hipEventDestroy(u.second);
     Y = YTables();
+}
+
+void release(ViewTables& V, std::vector<hipEvent_t>& pool) {
+    for (auto& t : V.tabs) {
+        if (t.dev) (void)hipFree(t.dev);
+        if (t.have_ready) (void)hipEventDestroy(t.ready);
+        for (auto& u : t.users) pool.push_back(u.second);            // (destroyed with the pool, after this: sbx_capi.hip destroy_ctx)
+    }
+    V = ViewTables();
 }
 
 void release(HashTables& H) {

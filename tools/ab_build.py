@@ -24,7 +24,7 @@ CLOUDS_VARIANTS = [("CL_PARK", 0), ("CL_LIPSKIP", 0), ("CL_LIPSKIP2", 0), ("CL_E
                    ("CL_NO_REG", 1), ("CL_EXP_LDS", 0), ("CL_NOTAB_GEN", 0), ("CL_MIN_WAVES_GEN", 4), ("CL_MAX3", 0),
                    ("CL_MIN_WAVES_YZ", 4), ("CL_YZ_MARCH", 0), ("CL_MIN_WAVES", 5), ("CL_EXP64", 0), ("CL_EXP_SMALL", 0),
                    ("CL_EXP_SMALL_ASM", 0), ("CL_YZ_SM", 0), ("CL_DIV3", 0), ("CL_EXP4K", 0), ("CL_TOP_FIRST", "true"),
-                   ("CL_PRESCALE", 0), ("CL_GTAB", 0), ("CL_GTAB_OCT", 0), ("CL_GTAB_OCT", 3)]
+                   ("CL_PRESCALE", 0), ("CL_GTAB", 0), ("CL_GTAB_OCT", 0), ("CL_GTAB_OCT", 3), ("CL_VT_PIXEL_PLAIN", 0)]
 
 
 # kern_planet.hip / sbx_planet.h / sbx_hashcache.h as k_planet uses it.  Not listed: PL_MIN_WAVES, PL_TW, PL_BATCH* (shapes and sizes).
